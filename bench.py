@@ -11,10 +11,14 @@ every 3rd frame). Inputs (frames, windows) are resident in HBM before the timed 
 N GPUs run N x the sequences with no data-path collective (weak scaling).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Besides the contract line's `roofline` (window kernel; `roofline.frontend` = the front-end step against HBM) and `cpu_baseline`, rank 0
-at N = 1 runs secondary measurements (bounded, ~2 minutes in total; `--quick` skips them): `end_to_end` (the estimator path: host
+A plain run sets up, warms up, times the steps and prints the contract line: `value`, `ms_per_step`, per-kernel times of the timed
+steps and the `roofline` (window kernel; `roofline.frontend` = the front-end step against HBM) computed from them. `--dump-outputs DIR`
+also writes what the last timed step hands its caller as DIR/<name>.npy (dump_outputs). Everything else runs only with `--full`: the
+measured LK iterations of the front-end roofline, `cpu_baseline`, at N > 1 the configs[3] literal batch and the replica cross-check
+(`multi_gpu`), and at N = 1 the secondary measurements (bounded, ~2 minutes in total; `--quick` skips them): `end_to_end` (the estimator path: host
 observations in, host states out), `end_to_end_full` (frames in, states out), `ate` (closed-loop position error against the truth
 and against the CPU path on the same data), `large_windows` (kernel time of configs[2] and configs[4]), `configs2` / `configs4`
 (those configs end to end, at 64 and at 256 sequences), `loop_closure` (pose graph solve and descriptor matching, SURVEY 8f rank
@@ -77,15 +81,17 @@ def pmc_traffic(kernel_key, workload_key):
 
 
 def steady_state_windows(cfg, pkg, pre, seeds, n_features=150, with_loop=0, imu_per_frame=10):
-    """configs[1] windows as solve_ceres sees them in steady state: window A of a sequence is solved with MARGIN_OLD on
-    the device and the prior it leaves is carried by window B, one frame later on the same trajectory (how
-    tests/golden/make_golden.py builds win_chain_b_prior; SURVEY §8d C5 'a prior produced by a preceding MARGIN_OLD step')."""
-    synth, backend = pkg.synth, pkg.backend
-    first = [synth.make_window(cfg, pre, seed=1000 + s, traj_seed=s, frame_offset=0, n_features=n_features,
-                               imu_per_frame=imu_per_frame) for s in seeds]
-    solver = backend.WindowSolver(cfg, max_batch=len(first))
-    solver.solve(first)
-    solver.close()
+    """configs[1] windows as solve_ceres sees them in steady state: window A of a sequence is solved with MARGIN_OLD and the
+    prior it leaves is carried by window B, one frame later on the same trajectory (how tests/golden/make_golden.py builds
+    win_chain_b_prior; SURVEY §8d C5 'a prior produced by a preceding MARGIN_OLD step'). Window A is solved by the CPU
+    restatement (oracle/libvio_oracle.so): one thread in a fixed order, so the benchmark's inputs are the same bits in every run
+    and for every build of the product (the device solve sums with LDS atomics in no fixed order)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import helpers as H
+    synth = pkg.synth
+    osolve, _ = H.oracle_backend()
+    first = [H.solve_with(osolve, cfg, synth.make_window(cfg, pre, seed=1000 + s, traj_seed=s, frame_offset=0, n_features=n_features,
+                                                         imu_per_frame=imu_per_frame))[0] for s in seeds]
     out = []
     for s, a in zip(seeds, first):
         b = synth.make_window(cfg, pre, seed=2000 + s, traj_seed=s, frame_offset=1, n_features=n_features,
@@ -104,8 +110,13 @@ def main():
     ap.add_argument("--sequences", type=int, default=512,
                     help="independent sequences resident per GPU (512 = two windows per CU: the window kernel keeps two "
                          "256-thread workgroups resident per CU; `resident_256` reports the one-window-per-CU batch too)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="contract line only (no secondary measurements)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: LK iteration counts, CPU baseline, secondary measurements (N = 1) or the "
+                         "configs[3] literal batch and replica cross-check (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (tracker states, solved windows) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="no CPU baseline (with --full or --leg)")
+    ap.add_argument("--quick", action="store_true", help="with --full: no LK iteration counts, no secondary measurements")
     ap.add_argument("--no-prior", action="store_true", help="aid: first-solve windows without a marginalization prior")
     ap.add_argument("--streams", type=int, choices=[1, 2], default=1,
                     help="1: tracker and solver kernels in order on one HIP stream; 2: each on its own stream")
@@ -162,9 +173,10 @@ def main():
     windows = [uniq_w[s % len(uniq_w)].copy() for s in range(S)]
     n_prior = int(np.mean([w.prior.n if w.prior is not None else 0 for w in uniq_w]))
 
-    def run_resident(S_, steps, warmup, timed_barrier, detect_always=True):
+    def run_resident(S_, steps, warmup, timed_barrier, detect_always=True, dump_dir=None):
         """One resident batch of S_ sequences per GPU through `steps` timed steps: (seconds, front-end ms, solver ms, stats).
-        detect_always: goodFeaturesToTrack runs on every published frame of every sequence (DETECT_NOTE)."""
+        detect_always: goodFeaturesToTrack runs on every published frame of every sequence (DETECT_NOTE). dump_dir: the
+        last step's outputs go there (dump_outputs)."""
         fr = frames[:, :S_] if S_ <= S else None
         ws = windows[:S_]
         with detect_every_frame(detect_always):
@@ -204,27 +216,30 @@ def main():
         fe_ms_, _ = fe.kernel_ms()
         be_ms_, _ = be.kernel_ms()
         stats_ = be.download(ws)
-        if args.only != "backend" and S_ == S and not lk_stats and not args.quick:  # (--quick: profiling runs keep their kernel trace clean)
+        if dump_dir:
+            dump_outputs(dump_dir, fe, ws, stats_)
+        if args.full and args.only != "backend" and S_ == S and not lk_stats and not args.quick:  # (--quick: profiling runs keep their kernel trace clean)
             lk_stats.extend(measured_lk_iterations(fe, lambda k: fe.step(pingpong[(warmup + steps + k) % len(pingpong)], publish=True, stream=one)))
         fe.close(), be.close()
         return dt_, max(fe_ms_, 1e-9), max(be_ms_, 1e-9), stats_
 
     lk_stats = []  # (mean LK iterations per (feature, level) visit, per level) of the headline batch, measured once
 
-    dt, fe_ms, be_ms, stats = run_resident(S, args.steps, args.warmup, True)
+    dt, fe_ms, be_ms, stats = run_resident(S, args.steps, args.warmup, True, dump_dir=args.dump_outputs if rank == 0 else None)
     replicas = None
     if dist:
-        # one launch of the job answers for both batch sizes: the headline (S sequences per GPU) and BASELINE.json's configs[3]
-        # read literally (64 sequences over 8 GPUs = 8 per GPU); every rank's own step time rides along
+        # with --full one launch of the job answers for both batch sizes: the headline (S sequences per GPU) and BASELINE.json's
+        # configs[3] read literally (64 sequences over 8 GPUs = 8 per GPU); every rank's own step time rides along
         replicas = {"headline": pkg.multi.replica_report(dist, S, args.steps, dt, device="cuda")}
-        dt8 = run_resident(8, args.steps, args.warmup, True)[0]
-        replicas["configs3_literal"] = pkg.multi.replica_report(dist, 8, args.steps, dt8, device="cuda")
+        if args.full:
+            dt8 = run_resident(8, args.steps, args.warmup, True)[0]
+            replicas["configs3_literal"] = pkg.multi.replica_report(dist, 8, args.steps, dt8, device="cuda")
         dt = pkg.multi.max_over_ranks(dist, dt, device="cuda")
     iters = float(np.mean([s["iterations"] - 1 for s in stats]))
     M = float(np.mean([w.n_factors for w in windows]))
 
     multi_gpu = None
-    if dist:
+    if dist and args.full:
         multi_gpu = multi_gpu_proof(pkg, dist, cfg, uniq_w[0], my_ids, pre, rank, local_rank, world)
 
     if rank == 0:
@@ -265,11 +280,10 @@ def main():
                                   "lk_mean_iterations_per_level": lk_stats[1] if lk_stats else None,
                                   "frac_at_measured_lk_iterations": (algorithmic_bytes_per_tracked_frame(rows, cols, 150, mean_iters=lk_stats[0]) * S / (fe_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if lk_stats and lk_stats[0] else None,
                                   "traffic_unit": "bytes per step; " + (fe_src or "no PMC summary for this workload under profiles/")}
-        if multi_gpu is not None:
-            multi_gpu["replicas"] = replicas
-            out["multi_gpu"] = multi_gpu
-        extras = world == 1 and args.only == "both" and not args.quick
-        if world == 1 and not args.no_cpu_baseline:
+        if dist:
+            out["multi_gpu"] = dict(multi_gpu or {}, replicas=replicas)
+        extras = args.full and world == 1 and args.only == "both" and not args.quick
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base = CpuBaseline(cfg, abi, uniq_frames, uniq_w)
             out["cpu_baseline"] = base.one_core(warmup_frames=20, frames=200)
         if extras:
@@ -340,6 +354,43 @@ class detect_every_frame:
             os.environ.pop("VIO_AMD_DETECT_ALWAYS", None)
         else:
             os.environ["VIO_AMD_DETECT_ALWAYS"] = self.old
+
+
+def dump_outputs(out_dir, fe, windows, stats, n_prior_sample=32):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy (float32 / float64, ~3 MB at 512 sequences):
+    every sequence's tracker state (vio_frontend_get_state: pixel positions, feature ids, track counts; rows past a sequence's
+    feature count are NaN / -1 / 0) and solved window (poses, speed / bias, inverse depths, solver statistics), and the
+    marginalization prior left for the next solve of a fixed, seeded sample of sequences, as that solve consumes it: H = J^T J and
+    b = J^T r with the blocks sorted by (kind, index) (abi.Prior.canonical; J itself is defined up to rotations in the eigenspaces
+    of H, which the device's summation order moves)."""
+    os.makedirs(out_dir, exist_ok=True)
+    S, cap = len(windows), fe.cfg.max_corners
+    out = {"track_pts": np.full((S, cap, 2), np.nan, np.float32), "track_ids": np.full((S, cap), -1.0),
+           "track_cnt": np.zeros((S, cap)), "track_n": np.zeros(S)}
+    for s in range(S):
+        pts, ids, cnt = fe.state(s)
+        n = len(ids)
+        out["track_pts"][s, :n], out["track_ids"][s, :n], out["track_cnt"][s, :n], out["track_n"][s] = pts, ids, cnt, n
+    out["pose"] = np.stack([w.pose for w in windows])
+    out["speed_bias"] = np.stack([w.speed_bias for w in windows])
+    depths = max(len(w.inv_depth) for w in windows)
+    out["inv_depth"] = np.full((S, depths), np.nan)
+    for s, w in enumerate(windows):
+        out["inv_depth"][s, :len(w.inv_depth)] = w.inv_depth
+    for key in ("iterations", "initial_cost", "final_cost", "termination"):
+        out["solve_" + key] = np.array([st[key] for st in stats], np.float64)
+    out["prior_rows"] = np.array([w.next_prior.n for w in windows], np.float64)
+    sample = np.sort(np.random.default_rng(0).choice(S, min(n_prior_sample, S), replace=False))
+    rows = max(int(out["prior_rows"][sample].max()), 1)
+    out["prior_sample"] = sample.astype(np.float64)
+    out["prior_hessian"] = np.full((len(sample), rows, rows), np.nan)
+    out["prior_gradient"] = np.full((len(sample), rows), np.nan)
+    for k, s in enumerate(sample):
+        p = windows[s].next_prior
+        if p.n > 0:
+            out["prior_hessian"][k, :p.n, :p.n], out["prior_gradient"][k, :p.n], _ = p.canonical()
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def guarded(fn):

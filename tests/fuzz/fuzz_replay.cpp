@@ -3,26 +3,32 @@
 // must come back as an error code, never as a memory error. Seeds are PNGs written by the library itself; mutations flip
 // bytes / bits, truncate and overwrite header fields, and three times out of four the chunk CRCs are recomputed so that
 // the mutated data reaches inflate, the filters and the colour conversion.
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <string>
+#include <sys/stat.h>
 #include <vector>
 #include <zlib.h>
 #include "vio_amd.h"
 static void fix_crcs(std::vector<uint8_t>&b){ size_t pos=8; while(pos+12<=b.size()){ unsigned len=(b[pos]<<24)|(b[pos+1]<<16)|(b[pos+2]<<8)|b[pos+3]; if(pos+12+(size_t)len>b.size()) break; unsigned long c=crc32(crc32(0L,Z_NULL,0),&b[pos+4],len+4); b[pos+8+len]=c>>24; b[pos+9+len]=c>>16; b[pos+10+len]=c>>8; b[pos+11+len]=c; pos+=12+len; } }
 static unsigned long long st = 88172645463325252ULL;
 static unsigned rnd() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return (unsigned)(st >> 11); }
+// usage: fuzz_replay [iterations] [work directory, default .]: the seed PNGs and the IMU files are written there
 int main(int argc, char **argv) {
   const int iters = argc > 1 ? atoi(argv[1]) : 100000;
+  const std::string work = argc > 2 ? argv[2] : ".", seed_dir = work + "/vio_fuzz_d", imu_path = work + "/vio_fuzz_imu";
+  if (mkdir(seed_dir.c_str(), 0755) != 0 && errno != EEXIST) return 1;
   // seeds: a few valid PNGs written by the library itself
   std::vector<std::vector<uint8_t>> seeds;
   for (int ch : {1, 3, 4}) {
     int rows = 23, cols = 31;
     std::vector<uint8_t> px((size_t)rows * cols * ch);
     for (auto &p : px) p = rnd();
-    if (system("rm -rf /tmp/vio_fuzz_d && mkdir -p /tmp/vio_fuzz_d") != 0) return 1;
-    vio_replay_write_image("/tmp/vio_fuzz_d", 0, px.data(), rows, cols, ch);
-    FILE *f = fopen("/tmp/vio_fuzz_d/0", "rb");
+    if (vio_replay_write_image(seed_dir.c_str(), 0, px.data(), rows, cols, ch) != VIO_OK) return 1;
+    FILE *f = fopen((seed_dir + "/0").c_str(), "rb");
+    if (!f) return 1;
     std::vector<uint8_t> b(1 << 16);
     size_t n = fread(b.data(), 1, b.size(), f);
     fclose(f);
@@ -51,9 +57,9 @@ int main(int argc, char **argv) {
   for (int it = 0; it < 2000; it++) {
     std::vector<uint8_t> b(1 + rnd() % 400);
     for (auto &p : b) p = rnd();
-    FILE *f = fopen("/tmp/vio_fuzz_imu", "wb"); fwrite(b.data(), 1, b.size(), f); fclose(f);
+    FILE *f = fopen(imu_path.c_str(), "wb"); fwrite(b.data(), 1, b.size(), f); fclose(f);
     VioImuMsg m[16]; int32_t n = 0;
-    vio_replay_read_imu("/tmp/vio_fuzz_imu", m, 16, &n);
+    vio_replay_read_imu(imu_path.c_str(), m, 16, &n);
   }
   printf("imu fuzz done\n");
   return 0;

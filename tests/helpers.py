@@ -1,5 +1,5 @@
 """Shared test plumbing: loads the CHECKERS (oracle/) and golden fixtures. Only tests/, smoke() and bench.py's
-cpu_baseline leg may touch oracle/ — the product library never does."""
+cpu_baseline leg and input set-up may touch oracle/ — the product library never does."""
 import ctypes as C
 import glob
 import importlib

@@ -154,10 +154,9 @@ def test_pattern_loader_reads_block_and_flow_sequences(tmp_path):
     got = loop.load_pattern(f)
     for a, b in zip(got, (x1, y1, x2, y2)):
         assert np.array_equal(a, b)
-    ref = "/root/reference/Resources/brief_pattern.yml"
-    if os.path.exists(ref):  # the fixture IS the app's pattern file
-        for a, b in zip(loop.load_pattern(ref), (x1, y1, x2, y2)):
-            assert np.array_equal(a, b)
+    # the fixture IS the app's pattern file (Resources/brief_pattern.yml, kept under tests/golden/)
+    for a, b in zip(loop.load_pattern(os.path.join(H.ROOT, "tests", "golden", "brief_pattern.yml")), (x1, y1, x2, y2)):
+        assert np.array_equal(a, b)
     with pytest.raises(RuntimeError):
         loop.load_pattern(tmp_path / "missing.yml")
 

@@ -194,7 +194,7 @@ def test_file_readers_survive_mutated_input_under_sanitizers(tmp_path):
     src = [os.path.join(H.ROOT, "tests", "fuzz", "fuzz_replay.cpp"), os.path.join(H.ROOT, "vins-mobile_amd", "csrc", "vio_replay.cpp")]
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-I" + os.path.join(H.ROOT, "include")] + src + ["-lz", "-o", exe])
-    r = subprocess.run([exe, "100000"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([exe, "100000", str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
     assert "fuzz done" in r.stdout and "imu fuzz done" in r.stdout
     decoded = int(r.stdout.split("fuzz done:")[1].split("decoded")[0])

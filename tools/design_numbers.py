@@ -87,7 +87,7 @@ def main():
     if b:
         km = b["config"].get("kernel_ms", {})
         r = b["roofline"]
-        out.append("**Bench line** (`profiles/%s_bench.json`, `python bench.py`, %s sequences per GPU, %d steps): **%.1f k frames/s**, "
+        out.append("**Bench line** (`profiles/%s_bench.json`, `python bench.py --full`, %s sequences per GPU, %d steps): **%.1f k frames/s**, "
                    "%.3f ms per step = %.3f ms front-end + %.3f ms window kernel; `roofline.frac` **%.4f** (%.2f TFLOP/s of %.1f fp64), "
                    "`roofline.traffic` %.2f GB per launch; `roofline.frontend.frac` %.3f by SURVEY 8(d)'s formula, **%.3f at the measured %.2f LK "
                    "iterations**; `cpu_baseline` %.1f frames/s on %d core (%s)." % (

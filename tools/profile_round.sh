@@ -58,6 +58,6 @@ VIO_AMD_PROF_TID=64 python tools/time_backend.py 1 2>&1 | grep "stage cycles" | 
 $R/tools/microbench/bin/band_bench > $O/microbench.txt 2>&1
 $R/tools/microbench/bin/mfma_share >> $O/microbench.txt 2>&1
 python tools/time_large.py > $O/large_windows.txt 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
+python bench.py --gpus 1 --steps 20 --warmup 3 --full > $O/bench.json 2> $O/bench.err
 rm -rf $O/sq3b $O/sq4b $O/kt_configs2 $O/kt_configs4 $O/ic $O/kt $O/fetch $O/write $O/calib_fetch $O/calib_write $O/sq1 $O/sq2 $O/sq3 $O/sq4 $O/sq5 $O/tcc $O/kt_res
 ls -la $O
