@@ -3,6 +3,7 @@ reference calls readImage on the camera-callback thread and solve_ceres on the m
 VINS_ios/ViewController.mm:458 vs :688-724). HIP's current device is per thread, default 0: without the binding a
 context created on GPU k > 0 would talk to GPU 0 from every other thread."""
 import ctypes as C
+import os
 import threading
 
 import numpy as np
@@ -118,7 +119,6 @@ def test_two_contexts_two_threads_concurrently():
 
 def test_loop_closure_contexts_created_on_one_thread_run_on_another():
     """The pose-graph, descriptor-extraction and matcher contexts carry the same device binding."""
-    import os
     import torch
     torch.cuda.set_device(torch.cuda.device_count() - 1)
     pg, loop, synth = pkg.posegraph, pkg.loop, pkg.synth
@@ -150,3 +150,89 @@ def test_loop_closure_contexts_created_on_one_thread_run_on_another():
     assert np.abs(g.t - here.t).max() < 1e-9
     assert np.array_equal(kp, kp_here) and np.array_equal(desc, desc_here)
     assert np.array_equal(idx, np.arange(50)) and np.all(dist == 0)
+
+
+def test_contexts_return_their_device_memory():
+    """Every context type, created, made to grow its lazily allocated buffers through one real call each, and destroyed,
+    ten times over (plus creates that fail after allocating): free device memory comes back to where it was. One
+    round holds well over a gigabyte, so a context that kept even part of a round's memory would show."""
+    import torch
+    from test_dbow import make_vocabulary
+    from test_pnp import CASES, make_window
+    torch.cuda.set_device(0)
+    lib = abi.load_product()
+    pg, loop = pkg.posegraph, pkg.loop
+    tolerance = 256 << 20  # bytes of device memory the runtime may keep or give back between rounds
+    rows, cols, n_seq = 480, 640, 256
+    fcfg = abi.default_config(image_rows=rows, image_cols=cols)
+    frames = np.random.default_rng(3).integers(0, 256, (2, n_seq, rows, cols), dtype=np.uint8)
+    bcfg, w, _ = H.load_golden_window("win_c2_easy")
+    pcfg = abi.default_config()
+    pnp_ws = [make_window(pcfg, *c) for c in CASES]
+    blob, desc = make_vocabulary(10, 4, seed=5)
+    kf = np.stack([desc[i] for i in list(desc)[-200:]])
+    graph = pg.Graph.from_npz_dict(np.load(os.path.join(H.ROOT, "tests", "golden", "posegraph.npz")), "lap80_in_")
+    pat = np.load(os.path.join(H.ROOT, "tests", "golden", "brief_pattern.npz"))
+    img = np.ascontiguousarray(pkg.synth.make_texture(np.random.default_rng(1), rows, cols), np.uint8)
+    # vio_backend_resident_reserve (vio_resident.h: the estimator's internal C++ entry, not part of the C ABI)
+    reserve = getattr(lib, "_Z28vio_backend_resident_reserveP11vio_backendiiiPKdS2_S2_")
+    ex = np.array([0, 0, 0, 0, 0, 0, 1.0])
+    tic, ric = np.zeros(3), np.eye(3).ravel()
+
+    def one_round():
+        trk = pkg.frontend.FeatureTracker(fcfg, n_seq=n_seq)
+        trk.lk_iterations(enable=True)
+        trk.submit(frames[0], True)
+        trk.collect()
+        trk.lk_iterations(enable=False)
+        trk.upload_frames(frames)
+        trk.step(1, True)
+        trk.sync()
+        trk.kernel_ms()
+        trk.close()
+        pts = np.array([[100, 100], [300, 200]], np.float32)
+        pkg.frontend.klt_track(fcfg, img, img, pts)
+        pkg.frontend.good_features(fcfg, img, None, 50)
+        solver = pkg.backend.WindowSolver(bcfg, max_batch=256)
+        solver.solve([w.copy() for _ in range(64)])
+        solver.kernel_ms()
+        assert reserve(solver._h, 256, 1024, 256, *(a.ctypes.data_as(C.POINTER(C.c_double)) for a in (ex, tic, ric))) == abi.VIO_OK
+        solver.close()
+        pnp = pkg.pnp.PnpSolver(pcfg, max_batch=len(pnp_ws))
+        pnp.solve([p.copy() for p in pnp_ws])
+        pnp.close()
+        opt = pg.PoseGraphOptimizer(max_nodes=700, max_edges=1024, n_graphs=4)
+        opt.optimize([graph.copy()])
+        opt.close()
+        voc = loop.BowVocabulary(blob=blob)
+        db = loop.BowDatabase(voc, max_entries=4096, max_total_words=1 << 24)
+        (_, _, bw, bv), = voc.transform([kf])
+        db.add(bw, bv)
+        db.query([(bw, bv)], [1])
+        db.close(), voc.close()
+        m = loop.Matcher()
+        d = kf[:100].astype(np.uint64)
+        m.search_by_des([d], [d])
+        m.close()
+        br = loop.BriefExtractor(rows, cols, (pat["x1"], pat["y1"], pat["x2"], pat["y2"]), max_frames=64, max_keypoints=4096)
+        br.extract(img[None], [np.zeros((0, 2), np.float32)], allow_cut=True)
+        br.close()
+        pre = pkg.frontend.Preprocessor(rows, cols, max_frames=64)
+        pre.run(np.repeat(img[None], 64, axis=0))
+        pre.close()
+        # creates that fail: the pose graph's vectors exceed the LDS (VIO_ECAP); a pre-step whose frame is too short for
+        # the reference's CLAHE grid fails (VIO_EINVAL) after its device buffers exist
+        h = C.c_void_p()
+        assert lib.vio_posegraph_create(1000, 1024, 1, C.byref(h)) == abi.VIO_ECAP
+        assert lib.vio_preprocess_create(128, 16, 8192, C.byref(h)) == abi.VIO_EINVAL
+
+    torch.cuda.synchronize()
+    for _ in range(2):  # warm-up: code objects and what the runtime keeps per hardware queue (~270 MiB, taken in the second round)
+        one_round()
+    base = torch.cuda.mem_get_info()[0]
+    lost = []
+    for _ in range(10):
+        one_round()
+        torch.cuda.synchronize()
+        lost.append((base - torch.cuda.mem_get_info()[0]) / 2 ** 20)
+    assert lost[-1] * 2 ** 20 < tolerance, "device memory not returned (MiB after each round): %s" % lost

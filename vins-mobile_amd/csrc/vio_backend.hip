@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include <chrono>
@@ -42,37 +43,6 @@ __global__ __launch_bounds__(1024) void poison_lds_kernel(int n_doubles) {
   if (poison_smem[(threadIdx.x * 7) % n_doubles] == 1.0) poison_smem[0] = 2.0;  // keep the stores alive
 }
 
-#define HIP_OK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      fprintf(stderr, "vio_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return VIO_ENODEV;                                                                   \
-    }                                                                                      \
-  } while (0)
-
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n && p) return VIO_OK;
-    {
-      static const bool log = getenv("VIO_AMD_HOST_TIMING") && getenv("VIO_AMD_HOST_TIMING")[0] == '1';
-      if (log) fprintf(stderr, "vio_amd: device buffer grows %zu -> %zu elements of %zu bytes\n", n, count, sizeof(T));
-    }
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-    if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return VIO_ENOMEM;
-    n = count;
-    return VIO_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-  }
-};
-
 }  // namespace
 
 // The instantiations of the window kernel, one translation unit each (vio_wk_unit.hip, csrc/Makefile).
@@ -95,17 +65,15 @@ static bool host_timing() {
 }
 
 struct vio_resident;
-static void resident_destroy(vio_resident *r);
 
 struct vio_backend {
   VioConfig cfg;
-  vio_resident *res = nullptr;  // device-resident path (vio_resident.h), null until reserved
+  std::unique_ptr<vio_resident> res;  // device-resident path (vio_resident.h), null until reserved
   int peers = 2;  // contexts whose window kernels share the device at the same time (vio_backend_set_peers)
   int device = -1;  // HIP device the context lives on (current device at create)
   int max_batch = 0;
   hipStream_t stream = nullptr;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  size_t events_used = 0;
+  LaunchTimer timer;
   // current batch
   int n = 0;
   bool uploaded = false;
@@ -147,6 +115,7 @@ struct vio_backend {
   HostVec<double> h_out_pose, h_out_sb, h_out_feat, h_raw_pose, h_raw_sb, h_raw_feat, h_out_loop, h_stats_d, h_m_x0,
       h_m_J, h_m_r;
   HostVec<int> h_stats_i, h_m_ints;
+  ~vio_backend();  // (after vio_resident: vio_backend_resident.inc)
 };
 
 extern "C" {
@@ -184,12 +153,7 @@ int32_t vio_prior_capacity(int32_t window_size) { return 15 * (window_size + 1) 
 
 int vio_backend_create(const VioConfig *cfg, int32_t max_batch, vio_backend_t **out) {
   if (!cfg || !out || max_batch < 1) return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "vio_amd: no HIP device visible; the back-end has no CPU fallback\n");
-    return VIO_ENODEV;
-  }
-  if (!vio::single_hip_runtime()) return VIO_ENODEV;
+  if (!vio::device_ready("the back-end")) return VIO_ENODEV;
   vio_backend *be = new (std::nothrow) vio_backend();
   if (!be) return VIO_ENOMEM;
   be->cfg = *cfg;
@@ -225,20 +189,6 @@ int vio_backend_get_device(const vio_backend_t *be, int32_t *device) {
 void vio_backend_destroy(vio_backend_t *be) {
   if (!be) return;
   vio::DeviceScope scope(be->device);
-  (void)hipStreamSynchronize(be->stream);
-  for (auto &e : be->events) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
-  if (be->upload_done) (void)hipEventDestroy(be->upload_done);
-  be->d_in.release(), be->d_stats_i.release(), be->d_m_ints.release();
-  DevBuf<double> *db[] = {&be->d_scratch, &be->d_hm,
-                          &be->d_out_pose, &be->d_out_sb, &be->d_out_feat, &be->d_raw_pose, &be->d_raw_sb,
-                          &be->d_raw_feat, &be->d_out_loop, &be->d_stats_d, &be->d_m_x0, &be->d_m_J, &be->d_m_r,
-                          &be->d_m_scratch};
-  for (auto *b : db) b->release();
-  be->d_prof.release();
-  for (int k = 0; k < 2; k++) be->d_st_x0[k].release(), be->d_st_J[k].release(), be->d_st_r[k].release();
-  be->d_ptab.release();
-  resident_destroy(be->res);
-  (void)hipStreamDestroy(be->stream);
   delete be;
 }
 
@@ -595,17 +545,6 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
   hipStream_t st = stream ? (hipStream_t)stream : be->stream;
   if (st != be->stream && be->upload_done) HIP_OK(hipStreamWaitEvent(st, be->upload_done, 0));
   be->last_stream = st;
-  if (be->events_used == be->events.size()) {
-    if (be->events.size() >= 4096) {  // recycle: fold what is pending into nothing (caller did not ask for it)
-      be->events_used = 0;
-    } else {
-      hipEvent_t a, b;
-      HIP_OK(hipEventCreate(&a));
-      HIP_OK(hipEventCreate(&b));
-      be->events.push_back({a, b});
-    }
-  }
-  auto &ev = be->events[be->events_used++];
   static const bool poison = getenv("VIO_AMD_POISON") && getenv("VIO_AMD_POISON")[0] == '1';
   if (poison) {
     HIP_OK(hipMemsetAsync(be->d_scratch.p, 0xff, be->d_scratch.n * sizeof(double), st));
@@ -615,7 +554,10 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
     HIP_OK(hipFuncSetAttribute((const void *)poison_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
     hipLaunchKernelGGL(poison_lds_kernel, dim3(2048), dim3(1024), kLdsLimit, st, (int)(kLdsLimit / sizeof(double)));
   }
-  HIP_OK(hipEventRecord(ev.first, st));
+  {
+    const int rct = be->timer.begin(st);
+    if (rct != VIO_OK) return rct;
+  }
   if (be->n_lds > 0) {
     BatchPtrs Bl = be->B;
     Bl.d = be->d_lds, Bl.order = be->d_order.p;
@@ -665,8 +607,7 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
     vio_wk::variant(3, be->MP.prof != nullptr).launch(grid, be->lds_bytes_glb, st, Bg, be->MP);
   }
   HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(ev.second, st));
-  return VIO_OK;
+  return be->timer.end(st);
 }
 
 int vio_backend_sync(vio_backend_t *be) {
@@ -680,16 +621,7 @@ int vio_backend_kernel_ms(vio_backend_t *be, double *ms_avg, int32_t *launches) 
   if (!be || !ms_avg || !launches) return VIO_EINVAL;
   VIO_ON_DEVICE_OF(be);
   HIP_OK(hipDeviceSynchronize());
-  double sum = 0;
-  for (size_t i = 0; i < be->events_used; i++) {
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, be->events[i].first, be->events[i].second));
-    sum += ms;
-  }
-  *launches = (int32_t)be->events_used;
-  *ms_avg = be->events_used ? sum / be->events_used : 0.0;
-  be->events_used = 0;
-  return VIO_OK;
+  return be->timer.drain(ms_avg, launches);
 }
 
 int vio_backend_set_profile(vio_backend_t *be, int32_t enable) {
@@ -809,3 +741,10 @@ int vio_backend_solve_windows(vio_backend_t *be, VioWindow *windows, int32_t n, 
 }  // extern "C"
 
 #include "vio_backend_resident.inc"
+
+vio_backend::~vio_backend() {
+  if (!stream) return;
+  (void)hipStreamSynchronize(stream);
+  if (upload_done) (void)hipEventDestroy(upload_done);
+  (void)hipStreamDestroy(stream);
+}

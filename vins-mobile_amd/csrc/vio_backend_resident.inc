@@ -47,24 +47,14 @@ struct vio_resident {
   std::vector<int> active_list;  // slots whose window was solved in this frame
   std::vector<char> solved;
   int phase = 0;  // 0 idle / collected, 1 begun, 2 ingested, 3 launched
-  ~vio_resident() {
-    DevBuf<int> *ib[] = {&fid, &start, &nobs, &flag, &ctl, &b_fhost, &b_ftarget, &b_ffeat, &b_fslot, &b_fstart, &b_pair_h, &b_pair_t, &b_pair_s0, &b_pair_s1};
-    for (auto *b : ib) b->release();
-    DevBuf<double> *db[] = {&depth, &obs, &ctld, &preint, &consts, &b_feat, &b_pts_i, &b_pts_j, &b_dummy, &pre_side};
-    for (auto *b : db) b->release();
-    d_in.release();
-    prof.release();
-  }
   template <class T>
   T *hp(size_t off) { return reinterpret_cast<T *>(h_in.data() + off); }
   template <class T>
   T *dp(size_t off) { return reinterpret_cast<T *>(d_in.p + off); }
 };
 
-static void resident_destroy(vio_resident *r) { delete r; }
-
 static vio::StoreDev resident_store_dev(vio_backend *be) {
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   vio::StoreDev S;
   S.d = r->sd, S.n_slots = r->n_slots;
   S.fid = r->fid.p, S.start = r->start.p, S.nobs = r->nobs.p, S.flag = r->flag.p, S.depth = r->depth.p, S.obs = r->obs.p;
@@ -105,9 +95,8 @@ int vio_backend_resident_reserve(vio_backend_t *be, int32_t n_slots, int32_t lis
   } else if (be->st_n < n_slots) {
     return VIO_EINVAL;
   }
-  resident_destroy(be->res);
-  be->res = nullptr;
-  vio_resident *r = new (std::nothrow) vio_resident();
+  be->res.reset();
+  std::unique_ptr<vio_resident> r(new (std::nothrow) vio_resident());
   if (!r) return VIO_ENOMEM;
   try {
     r->n_slots = n_slots, r->W = W, r->P = P;
@@ -125,10 +114,7 @@ int vio_backend_resident_reserve(vio_backend_t *be, int32_t n_slots, int32_t lis
     if (rc == VIO_OK) rc = r->consts.ensure(19 + 18);
     if (rc == VIO_OK) rc = r->pre_side.ensure(N * W * vio::preint::kSide);
     if (rc == VIO_OK) rc = r->b_dummy.ensure(16);
-    if (rc != VIO_OK) {
-      delete r;
-      return rc;
-    }
+    if (rc != VIO_OK) return rc;
     HIP_OK(hipMemset(r->ctl.p, 0, N * vio::store::C_COUNT * sizeof(int)));
     HIP_OK(hipMemset(r->preint.p, 0, N * W * kPreintDoubles * sizeof(double)));
     double c[19 + 18];
@@ -166,19 +152,15 @@ int vio_backend_resident_reserve(vio_backend_t *be, int32_t n_slots, int32_t lis
     r->total_bytes = o;
     r->h_in.assign(o, 0);
     rc = r->d_in.ensure(o);
-    if (rc != VIO_OK) {
-      delete r;
-      return rc;
-    }
+    if (rc != VIO_OK) return rc;
     HIP_OK(hipMemset(r->d_in.p, 0, o));
     for (size_t b = 0; b < N; b++) memcpy(r->hp<double>(r->o_ex) + 7 * b, ex_pose, 56);
     r->h_ctl.assign(N * vio::store::C_COUNT, 0);
     r->solved.assign(N, 0);
   } catch (const std::bad_alloc &) {
-    delete r;
     return VIO_ENOMEM;
   }
-  be->res = r;
+  be->res = std::move(r);
   be->uploaded = false;
   return VIO_OK;
 }
@@ -203,7 +185,7 @@ int vio_backend_resident_load_batch(vio_backend_t *be, int32_t n, const int32_t 
                                     const int32_t *counts, const double *const *points, const double *last_P /* [n][3] */,
                                     const double *last_R /* [n][9] */) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (n < 0 || (n > 0 && (!slots || !infos || !counts || !points || !last_P || !last_R))) return VIO_EINVAL;
   if (n == 0) return VIO_OK;
   if (r->phase != 0) return VIO_ESTATE;
@@ -273,7 +255,7 @@ int vio_backend_resident_load(vio_backend_t *be, int32_t slot, const VioFeatureI
 int vio_backend_resident_fetch(vio_backend_t *be, int32_t slot, VioFeatureInfo *info, int32_t cap, int32_t *n, double *points,
                                int32_t cap_points, int32_t *n_points) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (slot < 0 || slot >= r->n_slots || !n || cap < 0 || (cap > 0 && !info)) return VIO_EINVAL;
   if (r->phase != 0) return VIO_ESTATE;
   VIO_ON_DEVICE_OF(be);
@@ -318,7 +300,7 @@ int vio_backend_resident_fetch(vio_backend_t *be, int32_t slot, VioFeatureInfo *
 
 int vio_backend_resident_begin(vio_backend_t *be) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (r->phase != 0) return VIO_ESTATE;
   VIO_ON_DEVICE_OF(be);
   // the previous frame's copy out of the arena, and whatever the host-window path left running on this context
@@ -338,7 +320,7 @@ int vio_backend_resident_stage(vio_backend_t *be, int32_t slot, const VioObs *ob
                                const double *pose, const double *speed_bias, const VioPrior *prior, int32_t loop_frame,
                                const int32_t *loop_ids, const double *loop_xy, int32_t n_loop) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (r->phase != 1) return VIO_ESTATE;
   if (slot < 0 || slot >= r->n_slots || n_obs < 0 || (n_obs > 0 && !obs) || !Ps || !Rs || !pose || !speed_bias) return VIO_EINVAL;
   if (n_obs > r->sd.Ocap) return VIO_ECAP;
@@ -387,7 +369,7 @@ int vio_backend_resident_stage(vio_backend_t *be, int32_t slot, const VioObs *ob
 int vio_backend_resident_stage_preint(vio_backend_t *be, int32_t slot, int32_t interval, const VioPreintegration *block,
                                       const double last_acc[3], const double last_gyr[3]) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (r->phase != 1) return VIO_ESTATE;
   if (slot < 0 || slot >= r->n_slots || interval < 0 || interval >= r->W || !block || !last_acc || !last_gyr) return VIO_EINVAL;
   const int k = r->n_pre.fetch_add(1);
@@ -406,7 +388,7 @@ int vio_backend_resident_stage_imu(vio_backend_t *be, int32_t slot, int32_t inte
                                    const double gyr_0[3], const double ba[3], const double bg[3], int32_t n, const double *dt,
                                    const double *acc, const double *gyr) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (r->phase != 1) return VIO_ESTATE;
   if (slot < 0 || slot >= r->n_slots || interval < 0 || interval >= r->W || n < 0 || (n > 0 && (!dt || !acc || !gyr))) return VIO_EINVAL;
   if (fresh && (!acc_0 || !gyr_0 || !ba || !bg)) return VIO_EINVAL;
@@ -427,7 +409,7 @@ int vio_backend_resident_stage_imu(vio_backend_t *be, int32_t slot, int32_t inte
 
 int vio_backend_resident_ingest(vio_backend_t *be) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (r->phase != 1) return VIO_ESTATE;
   VIO_ON_DEVICE_OF(be);
   hipStream_t st = be->stream;
@@ -481,7 +463,7 @@ int vio_backend_resident_ingest(vio_backend_t *be) {
 
 int vio_backend_resident_launch(vio_backend_t *be) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (r->phase != 2) return VIO_ESTATE;
   VIO_ON_DEVICE_OF(be);
   hipStream_t st = be->stream;
@@ -598,7 +580,7 @@ int vio_backend_resident_launch(vio_backend_t *be) {
 
 int vio_backend_resident_collect(vio_backend_t *be) {
   if (!be || !be->res) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (r->phase != 2 && r->phase != 3) return VIO_ESTATE;
   VIO_ON_DEVICE_OF(be);
   const double t0 = now_ms();
@@ -641,7 +623,7 @@ do {                                                                            
 
 int vio_backend_resident_result(vio_backend_t *be, int32_t slot, VioResidentResult *out, VioPrior *next_prior_header) {
   if (!be || !be->res || !out) return VIO_ESTATE;
-  vio_resident *r = be->res;
+  vio_resident *r = be->res.get();
   if (slot < 0 || slot >= r->n_slots) return VIO_EINVAL;
   if (r->phase != 0) return VIO_ESTATE;
   const int *c = r->h_ctl.data() + (size_t)slot * vio::store::C_COUNT;

@@ -38,34 +38,7 @@
 
 namespace {
 
-#define HIP_OK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      fprintf(stderr, "vio_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return VIO_ENODEV;                                                                   \
-    }                                                                                      \
-  } while (0)
-
 constexpr int kMaxBowFeatures = 8192;  // descriptors per keyframe the BowVector kernel sorts in LDS
-
-template <class T>
-struct Buf {
-  T *p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n && p) return VIO_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-    if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return VIO_ENOMEM;
-    n = count;
-    return VIO_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-  }
-};
 
 // 16 lanes per descriptor, 4 descriptors per wave
 __global__ __launch_bounds__(256) void bow_lookup_kernel(const unsigned long long *node_desc, const double *node_weight, const int *node_word,
@@ -296,18 +269,23 @@ __global__ __launch_bounds__(256) void bow_score_kernel(const int *db_off, const
 
 }  // namespace
 
+using vio::DevBuf;
+
 struct vio_vocabulary {
   int device = -1;
   int32_t k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0;  // n_nodes incl. the root
   int height = 0;  // levels below the root: bounds the descent of bow_lookup_kernel
   hipStream_t stream = nullptr;
-  Buf<unsigned long long> d_desc;
-  Buf<double> d_weight, d_wweight;  // per node; per word
-  Buf<int> d_word, d_child_off, d_child;
+  DevBuf<unsigned long long> d_desc;
+  DevBuf<double> d_weight, d_wweight;  // per node; per word
+  DevBuf<int> d_word, d_child_off, d_child;
   // transform scratch
-  Buf<unsigned long long> t_desc;
-  Buf<int> t_word, t_off, t_bcount, t_bword;
-  Buf<double> t_weight, t_bvalue;
+  DevBuf<unsigned long long> t_desc;
+  DevBuf<int> t_word, t_off, t_bcount, t_bword;
+  DevBuf<double> t_weight, t_bvalue;
+  ~vio_vocabulary() {
+    if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+  }
 };
 
 // (A database takes the word count from its vocabulary at create and owns its stream: it keeps working, and can be
@@ -319,23 +297,22 @@ struct vio_bow_database {
   int max_entries = 0, n_entries = 0;
   size_t max_words = 0, n_words = 0;
   std::vector<int> h_off;  // [n_entries + 1]
-  Buf<int> d_off, d_word, q_count, q_word, q_max;  // d_off / d_word / d_value: the direct file (every entry's BowVector)
-  Buf<double> d_value, q_value;
-  Buf<unsigned long long> inv[2];  // the inverted file: postings sorted by (word, entry); inv[cur] is the live copy
+  DevBuf<int> d_off, d_word, q_count, q_word, q_max;  // d_off / d_word / d_value: the direct file (every entry's BowVector)
+  DevBuf<double> d_value, q_value;
+  DevBuf<unsigned long long> inv[2];  // the inverted file: postings sorted by (word, entry); inv[cur] is the live copy
   int cur = 0;
-  Buf<int> flag, n_cand, cand;  // query scratch: [n_queries][n_entries] marks, [n_queries], [n_queries][n_entries]
-  Buf<double> cscore;           // [n_queries][n_entries] raw score of candidate c
+  DevBuf<int> flag, n_cand, cand;  // query scratch: [n_queries][n_entries] marks, [n_queries], [n_queries][n_entries]
+  DevBuf<double> cscore;           // [n_queries][n_entries] raw score of candidate c
+  ~vio_bow_database() {
+    if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+  }
 };
 
 extern "C" {
 
 int vio_vocabulary_create(const void *blob, size_t bytes, vio_vocabulary_t **out) {
   if (!blob || !out) return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "vio_amd: no HIP device visible; the bag-of-words query has no CPU fallback\n");
-    return VIO_ENODEV;
-  }
+  if (!vio::device_ready("the bag-of-words query")) return VIO_ENODEV;
   const unsigned char *p = (const unsigned char *)blob;
   if (bytes < 24) return VIO_EINVAL;
   int32_t hdr[6];
@@ -398,17 +375,16 @@ int vio_vocabulary_create(const void *blob, size_t bytes, vio_vocabulary_t **out
     v->device = vio::current_device();
     v->k = hdr[0], v->L = hdr[1], v->scoring = hdr[2], v->weighting = hdr[3], v->n_nodes = (int32_t)N, v->n_words = nWords;
     v->height = height;
-    bool ok = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && v->d_desc.ensure(4 * N) == VIO_OK && v->d_weight.ensure(N) == VIO_OK && v->d_word.ensure(N) == VIO_OK &&
-         v->d_child_off.ensure(N + 1) == VIO_OK && v->d_child.ensure(nNodes) == VIO_OK && v->d_wweight.ensure(nWords) == VIO_OK;
-    ok = ok && hipMemcpy(v->d_desc.p, desc.data(), 32 * N, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(v->d_weight.p, weight.data(), 8 * N, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(v->d_word.p, word.data(), 4 * N, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(v->d_wweight.p, wweight.data(), 8 * (size_t)nWords, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(v->d_child_off.p, cnt.data(), 4 * (N + 1), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(v->d_child.p, child.data(), 4 * (size_t)nNodes, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-      vio_vocabulary_destroy(v);
+    if (hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess || v->d_desc.ensure(4 * N) != VIO_OK ||
+        v->d_weight.ensure(N) != VIO_OK || v->d_word.ensure(N) != VIO_OK || v->d_child_off.ensure(N + 1) != VIO_OK ||
+        v->d_child.ensure(nNodes) != VIO_OK || v->d_wweight.ensure(nWords) != VIO_OK ||
+        hipMemcpy(v->d_desc.p, desc.data(), 32 * N, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->d_weight.p, weight.data(), 8 * N, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->d_word.p, word.data(), 4 * N, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->d_wweight.p, wweight.data(), 8 * (size_t)nWords, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->d_child_off.p, cnt.data(), 4 * (N + 1), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(v->d_child.p, child.data(), 4 * (size_t)nNodes, hipMemcpyHostToDevice) != hipSuccess) {
+      delete v;
       return VIO_ENOMEM;
     }
     *out = v;
@@ -445,10 +421,6 @@ int vio_vocabulary_load(const char *path, vio_vocabulary_t **out) {
 void vio_vocabulary_destroy(vio_vocabulary_t *v) {
   if (!v) return;
   vio::DeviceScope scope(v->device);
-  if (v->stream) (void)hipStreamSynchronize(v->stream), (void)hipStreamDestroy(v->stream);
-  v->d_desc.release(), v->d_weight.release(), v->d_wweight.release(), v->d_word.release(), v->d_child_off.release(), v->d_child.release();
-  v->t_desc.release(), v->t_word.release(), v->t_off.release(), v->t_bcount.release(), v->t_bword.release();
-  v->t_weight.release(), v->t_bvalue.release();
   delete v;
 }
 
@@ -524,7 +496,7 @@ int vio_bow_database_create(vio_vocabulary_t *v, int32_t max_entries, int32_t ma
   }
   if (d->d_off.ensure((size_t)max_entries + 1) != VIO_OK || d->d_word.ensure(d->max_words) != VIO_OK || d->d_value.ensure(d->max_words) != VIO_OK ||
       d->inv[0].ensure(d->max_words) != VIO_OK || d->inv[1].ensure(d->max_words) != VIO_OK) {
-    vio_bow_database_destroy(d);
+    delete d;
     return VIO_ENOMEM;
   }
   *out = d;
@@ -534,9 +506,6 @@ int vio_bow_database_create(vio_vocabulary_t *v, int32_t max_entries, int32_t ma
 void vio_bow_database_destroy(vio_bow_database_t *d) {
   if (!d) return;
   vio::DeviceScope scope(d->device);
-  if (d->stream) (void)hipStreamSynchronize(d->stream), (void)hipStreamDestroy(d->stream);
-  d->d_off.release(), d->d_word.release(), d->d_value.release(), d->q_count.release(), d->q_word.release(), d->q_max.release();
-  d->q_value.release(), d->inv[0].release(), d->inv[1].release(), d->flag.release(), d->n_cand.release(), d->cand.release(), d->cscore.release();
   delete d;
 }
 

@@ -27,15 +27,6 @@
 
 namespace {
 
-#define HIP_OK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      fprintf(stderr, "vio_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return VIO_ENODEV;                                                                   \
-    }                                                                                      \
-  } while (0)
-
 struct Taps9 {
   int t[9];
 };
@@ -235,10 +226,13 @@ struct vio_brief {
   int rows = 0, cols = 0, max_frames = 0, cap = 0, n_bits = 0;
   Taps9 taps;
   hipStream_t stream = nullptr;
-  uint8_t *d_img = nullptr, *d_blur = nullptr, *d_score = nullptr;
-  float *d_kp = nullptr, *d_wpts = nullptr;
-  unsigned long long *d_desc = nullptr;
-  int *d_nw = nullptr, *d_nfast = nullptr, *d_nkp = nullptr, *d_pat = nullptr;
+  vio::DevBuf<uint8_t> d_img, d_blur, d_score;
+  vio::DevBuf<float> d_kp, d_wpts;
+  vio::DevBuf<unsigned long long> d_desc;
+  vio::DevBuf<int> d_nw, d_nfast, d_nkp, d_pat;
+  ~vio_brief() {
+    if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+  }
 };
 
 extern "C" {
@@ -296,11 +290,7 @@ int vio_brief_create(int32_t rows, int32_t cols, int32_t max_frames, int32_t max
   if (!out || rows < 7 || cols < 7 || cols > kBriefMaxCols || max_frames < 1 || max_keypoints < 1 || !x1 || !y1 || !x2 || !y2 || n_bits < 1 ||
       n_bits > 256)
     return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "vio_amd: no HIP device visible; the descriptor extraction has no CPU fallback\n");
-    return VIO_ENODEV;
-  }
+  if (!vio::device_ready("the descriptor extraction")) return VIO_ENODEV;
   vio_brief *b = new (std::nothrow) vio_brief();
   if (!b) return VIO_ENOMEM;
   b->device = vio::current_device();
@@ -314,21 +304,16 @@ int vio_brief_create(int32_t rows, int32_t cols, int32_t max_frames, int32_t max
     for (int i = 0; i < 9; i++) cf[i] = (float)(cf[i] * sum), b->taps.t[i] = (int)lrint((double)cf[i] * 256.0);
   }
   const size_t px = (size_t)max_frames * rows * cols, kp = (size_t)max_frames * max_keypoints;
-  bool ok = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_img, px) == hipSuccess && hipMalloc(&b->d_blur, px) == hipSuccess && hipMalloc(&b->d_score, px) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_kp, kp * 2 * sizeof(float)) == hipSuccess && hipMalloc(&b->d_wpts, kp * 2 * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_desc, kp * 4 * sizeof(unsigned long long)) == hipSuccess;
-  ok = ok && hipMalloc(&b->d_nw, max_frames * sizeof(int)) == hipSuccess && hipMalloc(&b->d_nfast, max_frames * sizeof(int)) == hipSuccess &&
-       hipMalloc(&b->d_nkp, max_frames * sizeof(int)) == hipSuccess && hipMalloc(&b->d_pat, 4 * 256 * sizeof(int)) == hipSuccess;
-  if (ok) {
-    int pat[4 * 256];
-    memset(pat, 0, sizeof(pat));
-    memcpy(pat, x1, n_bits * sizeof(int)), memcpy(pat + 256, y1, n_bits * sizeof(int));
-    memcpy(pat + 512, x2, n_bits * sizeof(int)), memcpy(pat + 768, y2, n_bits * sizeof(int));
-    ok = hipMemcpy(b->d_pat, pat, sizeof(pat), hipMemcpyHostToDevice) == hipSuccess;
-  }
-  if (!ok) {
-    vio_brief_destroy(b);
+  int pat[4 * 256];
+  memset(pat, 0, sizeof(pat));
+  memcpy(pat, x1, n_bits * sizeof(int)), memcpy(pat + 256, y1, n_bits * sizeof(int));
+  memcpy(pat + 512, x2, n_bits * sizeof(int)), memcpy(pat + 768, y2, n_bits * sizeof(int));
+  if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess || b->d_img.ensure(px) != VIO_OK ||
+      b->d_blur.ensure(px) != VIO_OK || b->d_score.ensure(px) != VIO_OK || b->d_kp.ensure(kp * 2) != VIO_OK ||
+      b->d_wpts.ensure(kp * 2) != VIO_OK || b->d_desc.ensure(kp * 4) != VIO_OK || b->d_nw.ensure(max_frames) != VIO_OK ||
+      b->d_nfast.ensure(max_frames) != VIO_OK || b->d_nkp.ensure(max_frames) != VIO_OK || b->d_pat.ensure(4 * 256) != VIO_OK ||
+      hipMemcpy(b->d_pat.p, pat, sizeof(pat), hipMemcpyHostToDevice) != hipSuccess) {
+    delete b;
     return VIO_ENOMEM;
   }
   *out = b;
@@ -344,10 +329,6 @@ int vio_brief_get_device(const vio_brief_t *b, int32_t *device) {
 void vio_brief_destroy(vio_brief_t *b) {
   if (!b) return;
   vio::DeviceScope scope(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream), (void)hipStreamDestroy(b->stream);
-  void *ptrs[] = {b->d_img, b->d_blur, b->d_score, b->d_kp, b->d_wpts, b->d_desc, b->d_nw, b->d_nfast, b->d_nkp, b->d_pat};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
   delete b;
 }
 
@@ -368,25 +349,25 @@ int vio_brief_extract(vio_brief_t *b, const uint8_t *gray, int32_t n_frames, con
   hipStream_t st = b->stream;
   const int rows = b->rows, cols = b->cols, cap = b->cap;
   const size_t px = (size_t)rows * cols;
-  HIP_OK(hipMemcpyAsync(b->d_img, gray, px * n_frames, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(b->d_nw, n_window, n_frames * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(b->d_img.p, gray, px * n_frames, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(b->d_nw.p, n_window, n_frames * sizeof(int), hipMemcpyHostToDevice, st));
   if (max_w > 0) {
-    HIP_OK(hipMemcpyAsync(b->d_wpts, window_pts, (size_t)n_frames * window_stride * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(b->d_wpts.p, window_pts, (size_t)n_frames * window_stride * 2 * sizeof(float), hipMemcpyHostToDevice, st));
   }
   const int thr = fast_threshold < 0 ? 0 : (fast_threshold > 255 ? 255 : fast_threshold);
-  hipLaunchKernelGGL(blur9_kernel, dim3((cols + kBlW - 1) / kBlW, (rows + kBlH - 1) / kBlH, n_frames), dim3(256), 0, st, b->d_img, b->d_blur,
+  hipLaunchKernelGGL(blur9_kernel, dim3((cols + kBlW - 1) / kBlW, (rows + kBlH - 1) / kBlH, n_frames), dim3(256), 0, st, b->d_img.p, b->d_blur.p,
                      rows, cols, b->taps);
-  hipLaunchKernelGGL(fast_score_kernel, dim3((cols + 63) / 64, (rows + 3) / 4, n_frames), dim3(256), 0, st, b->d_img, b->d_score, rows, cols, thr);
-  hipLaunchKernelGGL(fast_collect_kernel, dim3(n_frames), dim3(kColThreads), 0, st, b->d_score, rows, cols, b->d_wpts, b->d_nw,
-                     window_stride, cap, b->d_kp, b->d_nfast, b->d_nkp);
-  Pattern P = {b->d_pat, b->d_pat + 256, b->d_pat + 512, b->d_pat + 768, b->n_bits};
-  hipLaunchKernelGGL(brief_kernel, dim3((cap + 3) / 4, n_frames), dim3(256), 0, st, b->d_blur, rows, cols, b->d_kp, b->d_nkp, cap, P,
-                     b->d_desc);
+  hipLaunchKernelGGL(fast_score_kernel, dim3((cols + 63) / 64, (rows + 3) / 4, n_frames), dim3(256), 0, st, b->d_img.p, b->d_score.p, rows, cols, thr);
+  hipLaunchKernelGGL(fast_collect_kernel, dim3(n_frames), dim3(kColThreads), 0, st, b->d_score.p, rows, cols, b->d_wpts.p, b->d_nw.p,
+                     window_stride, cap, b->d_kp.p, b->d_nfast.p, b->d_nkp.p);
+  Pattern P = {b->d_pat.p, b->d_pat.p + 256, b->d_pat.p + 512, b->d_pat.p + 768, b->n_bits};
+  hipLaunchKernelGGL(brief_kernel, dim3((cap + 3) / 4, n_frames), dim3(256), 0, st, b->d_blur.p, rows, cols, b->d_kp.p, b->d_nkp.p, cap, P,
+                     b->d_desc.p);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(n_fast, b->d_nfast, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(n_keypoints, b->d_nkp, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(keypoints, b->d_kp, (size_t)n_frames * cap * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(descriptors, b->d_desc, (size_t)n_frames * cap * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(n_fast, b->d_nfast.p, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(n_keypoints, b->d_nkp.p, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(keypoints, b->d_kp.p, (size_t)n_frames * cap * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(descriptors, b->d_desc.p, (size_t)n_frames * cap * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   for (int f = 0; f < n_frames; f++)
     if (n_fast[f] > cap - n_window[f]) return VIO_ECAP;  // (what fitted is valid; the FAST list is cut at the capacity)

@@ -10,8 +10,22 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
+
+#include "vio_amd.h"
+
+// A failed HIP call ends the ABI entry with VIO_ENODEV (and says which call on stderr).
+#define HIP_OK(expr)                                                                       \
+  do {                                                                                     \
+    hipError_t e_ = (expr);                                                                \
+    if (e_ != hipSuccess) {                                                                \
+      fprintf(stderr, "vio_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return VIO_ENODEV;                                                                   \
+    }                                                                                      \
+  } while (0)
 
 namespace vio {
 
@@ -69,6 +83,103 @@ inline bool single_hip_runtime() {
   }();
   return n <= 1 && host_isa_ok();
 }
+
+// The preamble of every *_create: a device is visible, one HIP runtime is mapped, the host CPU runs the host code.
+inline bool device_ready(const char *what) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    fprintf(stderr, "vio_amd: no HIP device visible; %s has no CPU fallback\n", what);
+    return false;
+  }
+  return single_hip_runtime();
+}
+
+// Owning device (DevBuf) / page-locked host (PinnedBuf) arrays. ensure() grows only -- the old contents are not kept --
+// and allocates at least one element; the memory goes back at release() or destruction. A context that holds these
+// frees them after its destructor body has synchronized its stream. Never give one static storage duration: its
+// destructor would run after the HIP runtime has gone at exit.
+template <class T, hipError_t (*Alloc)(void **, size_t), hipError_t (*Free)(void *)>
+struct OwnedBuf {
+  T *p = nullptr;
+  size_t n = 0;
+  OwnedBuf() = default;
+  OwnedBuf(const OwnedBuf &) = delete;
+  OwnedBuf &operator=(const OwnedBuf &) = delete;
+  ~OwnedBuf() { release(); }
+  int ensure(size_t count) {
+    if (count <= n && p) return VIO_OK;
+    {
+      static const bool log = getenv("VIO_AMD_HOST_TIMING") && getenv("VIO_AMD_HOST_TIMING")[0] == '1';
+      if (log) fprintf(stderr, "vio_amd: device buffer grows %zu -> %zu elements of %zu bytes\n", n, count, sizeof(T));
+    }
+    release();
+    if (Alloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
+      p = nullptr;
+      return VIO_ENOMEM;
+    }
+    n = count;
+    return VIO_OK;
+  }
+  void release() {
+    if (p) (void)Free(p);
+    p = nullptr, n = 0;
+  }
+};
+inline hipError_t dev_malloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+inline hipError_t dev_free(void *p) { return hipFree(p); }
+inline hipError_t pinned_malloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+inline hipError_t pinned_free(void *p) { return hipHostFree(p); }
+template <class T>
+using DevBuf = OwnedBuf<T, dev_malloc, dev_free>;
+template <class T>
+using PinnedBuf = OwnedBuf<T, pinned_malloc, pinned_free>;
+
+// Device time of a context's launches (*_kernel_ms): an event pair around each, up to 4096 pairs kept; drain() sums
+// what was recorded since the last drain.
+class LaunchTimer {
+ public:
+  LaunchTimer() = default;
+  LaunchTimer(const LaunchTimer &) = delete;
+  LaunchTimer &operator=(const LaunchTimer &) = delete;
+  ~LaunchTimer() {
+    for (auto &e : ev_) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
+  }
+  int begin(hipStream_t st) {
+    if (used_ == ev_.size()) {
+      if (ev_.size() >= 4096) {  // recycle: fold what is pending into nothing (the caller did not ask for it)
+        used_ = 0;
+      } else {
+        hipEvent_t a, b;
+        HIP_OK(hipEventCreate(&a));
+        HIP_OK(hipEventCreate(&b));
+        ev_.push_back({a, b});
+      }
+    }
+    HIP_OK(hipEventRecord(ev_[used_++].first, st));
+    return VIO_OK;
+  }
+  int end(hipStream_t st) {
+    HIP_OK(hipEventRecord(ev_[used_ - 1].second, st));
+    return VIO_OK;
+  }
+  // average ms over the launches recorded since the last drain (the events must have completed)
+  int drain(double *ms_avg, int32_t *launches) {
+    double sum = 0;
+    for (size_t i = 0; i < used_; i++) {
+      float ms = 0;
+      HIP_OK(hipEventElapsedTime(&ms, ev_[i].first, ev_[i].second));
+      sum += ms;
+    }
+    *launches = (int32_t)used_;
+    *ms_avg = used_ ? sum / used_ : 0.0;
+    used_ = 0;
+    return VIO_OK;
+  }
+
+ private:
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_;
+  size_t used_ = 0;
+};
 
 inline int current_device() {
   int d = 0;

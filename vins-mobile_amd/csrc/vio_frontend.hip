@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -44,15 +45,6 @@ constexpr int kMaxRadius = 128;  // largest MIN_DIST (setMask circle radius) the
 #define VIO_LK_FPW 1
 #endif
 constexpr int kLkFpw = VIO_LK_FPW;  // features per wave of lk_track_kernel (1 or 2)
-
-#define HIP_OK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      fprintf(stderr, "vio_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return VIO_ENODEV;                                                                   \
-    }                                                                                      \
-  } while (0)
 
 struct LevelDims {
   int rows[kMaxLevels], cols[kMaxLevels];
@@ -1830,12 +1822,10 @@ void circle_halfwidths(int radius, std::vector<int> &hw) {  // cv::circle filled
   }
 }
 
-template <class T>
-int dev_alloc(T **p, size_t count) {
-  return hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)) == hipSuccess ? VIO_OK : VIO_ENOMEM;
-}
-
 }  // namespace
+
+using vio::DevBuf;
+using vio::PinnedBuf;
 
 struct vio_frontend {
   int device = -1;  // HIP device the context lives on (current device at create)
@@ -1844,37 +1834,36 @@ struct vio_frontend {
   LevelDims ld;
   hipStream_t stream = nullptr;
   // device state
-  uint8_t *pyr[2] = {nullptr, nullptr};  // [n_seq][pyr_bytes]; cur = pyr[cur_idx], forw = pyr[1 - cur_idx]
+  DevBuf<uint8_t> pyr[2];  // [n_seq][pyr_bytes]; cur = pyr[cur_idx], forw = pyr[1 - cur_idx]
   int cur_idx = 0;
   bool have_img = false;
   // level 0 of pyr[k] when it is NOT the pyramid's own copy: the frame inside the resident ring (vio_frontend_upload_frames) the
   // pyramid was built from -- the ring belongs to the context and outlives the two steps that read the frame
   const uint8_t *lvl0[2] = {nullptr, nullptr};
-  uint8_t *mask = nullptr;      // [rows*cols], only the stand-alone vio_good_features uses a mask image
-  unsigned *max_bits = nullptr;
-  unsigned long long *cand = nullptr;
+  DevBuf<uint8_t> mask;  // [rows*cols], only the stand-alone vio_good_features uses a mask image
+  DevBuf<unsigned> max_bits;
+  DevBuf<unsigned long long> cand;
   int nseg = 0, seg_cap = 0;  // candidate list: one segment per strip of kDetR rows
-  int *n_cand = nullptr;
-  float *cur_pts = nullptr, *pre_pts = nullptr, *forw_pts = nullptr, *lk_err = nullptr;
-  unsigned long long *lk_stats = nullptr;  // [64][16] iteration counters of lk_track_kernel (vio_frontend_lk_iterations)
+  DevBuf<int> n_cand;
+  DevBuf<float> cur_pts, pre_pts, forw_pts, lk_err;
+  DevBuf<unsigned long long> lk_stats;  // [64][16] iteration counters of lk_track_kernel (vio_frontend_lk_iterations)
   bool lk_stats_on = false;
-  int *ids = nullptr, *track_cnt = nullptr, *n_pts = nullptr, *n_forw = nullptr, *n_id = nullptr, *kept_xy = nullptr,
-      *n_kept = nullptr, *hw = nullptr, *n_obs = nullptr, *pnp_ids = nullptr, *n_pnp = nullptr;
-  float *pnp_pts = nullptr;
-  uint8_t *lk_status = nullptr;
-  VioObs *obs = nullptr;
+  DevBuf<int> ids, track_cnt, n_pts, n_forw, n_id, kept_xy, n_kept, hw, n_obs, pnp_ids, n_pnp;
+  DevBuf<float> pnp_pts;
+  DevBuf<uint8_t> lk_status;
+  DevBuf<VioObs> obs;
+  DevBuf<long long> d_prof;  // stage clock of track_update_kernel (VIO_AMD_TU_PROF=1)
   bool attr_set = false;
   bool detect_always = false;  // VIO_AMD_DETECT_ALWAYS=1 (measurement aid): detect_kernel also runs for sequences that need no new corner
   // resident frames (throughput runs)
-  uint8_t *frames = nullptr;
+  DevBuf<uint8_t> frames;
   int n_frames = 0;
-  // timing
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  size_t events_used = 0;
+  vio::LaunchTimer timer;  // vio_frontend_step_resident -> vio_frontend_kernel_ms
   // host-buffer path (vio_frontend_read_images): device staging for the frames, pinned memory for the observations
-  uint8_t *d_stage = nullptr;
-  VioObs *p_obs = nullptr;
-  uint8_t *p_frames = nullptr;  // page-locked gathering buffer of read_images
+  DevBuf<uint8_t> d_stage;
+  PinnedBuf<VioObs> p_obs;
+  PinnedBuf<int> p_nobs;
+  PinnedBuf<uint8_t> p_frames;  // page-locked gathering buffer of read_images
   bool pending = false, pending_publish = false;  // a submitted frame waits for vio_frontend_collect
   bool pending_async = false;                     // ... and it was queued by vio_frontend_submit_images_async (Async::rc is its status)
   // vio_frontend_submit_images_async: the submit itself (gather + transfers + launches) runs on this context's own host
@@ -1887,10 +1876,22 @@ struct vio_frontend {
     const uint8_t *gray = nullptr;
     int rows = 0, cols = 0, stride = 0, publish = 0, rc = VIO_OK;
   } *async = nullptr;
-  int *p_nobs = nullptr;
   // host staging
   std::vector<VioObs> h_obs;
   std::vector<int> h_nobs;
+  ~vio_frontend() {
+    if (async) {
+      {
+        std::lock_guard<std::mutex> lk(async->m);
+        async->quit = true;
+      }
+      async->cv.notify_all();
+      if (async->th.joinable()) async->th.join();
+      delete async;
+    }
+    (void)hipDeviceSynchronize();
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
@@ -2033,15 +2034,14 @@ __global__ __launch_bounds__(256) void copy_frames_kernel(const uint8_t *src, si
 int launch_track_update(vio_frontend *fe, int publish, hipStream_t st) {
   TrackerArrays A;
   A.cap = fe->cap, A.rows = fe->cfg.image_rows, A.cols = fe->cfg.image_cols;
-  A.cur_pts = fe->cur_pts, A.pre_pts = fe->pre_pts, A.forw_pts = fe->forw_pts, A.ids = fe->ids, A.track_cnt = fe->track_cnt;
-  A.n_pts = fe->n_pts, A.n_forw = fe->n_forw, A.n_id = fe->n_id, A.lk_status = fe->lk_status, A.kept_xy = fe->kept_xy;
-  A.n_kept = fe->n_kept, A.hw = fe->hw, A.radius = fe->cfg.min_dist, A.f_thresh = (float)fe->cfg.f_threshold;
-  A.pnp_pts = fe->pnp_pts, A.pnp_ids = fe->pnp_ids, A.n_pnp = fe->n_pnp;
+  A.cur_pts = fe->cur_pts.p, A.pre_pts = fe->pre_pts.p, A.forw_pts = fe->forw_pts.p, A.ids = fe->ids.p, A.track_cnt = fe->track_cnt.p;
+  A.n_pts = fe->n_pts.p, A.n_forw = fe->n_forw.p, A.n_id = fe->n_id.p, A.lk_status = fe->lk_status.p, A.kept_xy = fe->kept_xy.p;
+  A.n_kept = fe->n_kept.p, A.hw = fe->hw.p, A.radius = fe->cfg.min_dist, A.f_thresh = (float)fe->cfg.f_threshold;
+  A.pnp_pts = fe->pnp_pts.p, A.pnp_ids = fe->pnp_ids.p, A.n_pnp = fe->n_pnp.p;
   A.f_conf = fe->cfg.f_confidence;
   static const bool tu_prof = getenv("VIO_AMD_TU_PROF") && getenv("VIO_AMD_TU_PROF")[0] == '1';
-  static long long *d_prof = nullptr;
-  if (tu_prof && !d_prof) (void)hipMalloc(&d_prof, 32 * sizeof(long long));
-  A.prof = tu_prof ? d_prof : nullptr;
+  if (tu_prof) (void)fe->d_prof.ensure(32);
+  A.prof = tu_prof ? fe->d_prof.p : nullptr;
   // the smallest LDS layout that holds this tracker's feature slots (fe->cap <= kMaxCap is checked at create)
   const bool small = fe->cap <= 256;
   const size_t shm = ((small ? sizeof(TrackShared<256>) : sizeof(TrackShared<kMaxCap>)) + 15 & ~(size_t)15) + sizeof(RansacShared);
@@ -2050,12 +2050,12 @@ int launch_track_update(vio_frontend *fe, int publish, hipStream_t st) {
     HIP_OK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     fe->attr_set = true;
   }
-  if (A.prof) (void)hipMemsetAsync(d_prof, 0, 32 * sizeof(long long), st);
+  if (A.prof) (void)hipMemsetAsync(A.prof, 0, 32 * sizeof(long long), st);
   if (small) hipLaunchKernelGGL(track_update_kernel<256>, dim3(fe->n_seq), dim3(256), shm, st, A, publish);
   else hipLaunchKernelGGL(track_update_kernel<kMaxCap>, dim3(fe->n_seq), dim3(256), shm, st, A, publish);
   if (A.prof) {  // (debug only: synchronises)
     long long h[32];
-    if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
+    if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h, A.prof, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
       static const char *name[11] = {"load", "compact", "ransac(cur,forw)", "compact", "pnp list", "ransac(pre,forw)", "compact", "counts+rank",
                                      "inside bits", "greedy", "outputs"};
       fprintf(stderr, "track_update cycles (sequence 0, publish %d):", publish);
@@ -2077,7 +2077,7 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
   const size_t img_bytes = (size_t)rows * cols;
   // forw_img = _img : level 0 of the forw pyramid
   const int fidx = fe->have_img ? 1 - fe->cur_idx : fe->cur_idx;
-  uint8_t *forw = fe->pyr[fidx];
+  uint8_t *forw = fe->pyr[fidx].p;
   // level 0 and level 1 from ONE read of the frame when the rows of both are whole dwords (640x480, 720p, 1080p)
   const bool fused0 = fe->ld.levels >= 2 && cols % 4 == 0 && fe->ld.cols[1] % 4 == 0 && cols >= 8 && fe->ld.pyr_bytes % 4 == 0 &&
                       img_bytes % 4 == 0 && (uintptr_t)d_frames % 4 == 0 && (uintptr_t)forw % 4 == 0 && fe->ld.off[1] % 4 == 0 &&
@@ -2128,26 +2128,26 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
     dim3 grd((cap + 4 * kLkFpw - 1) / (4 * kLkFpw), S);
     // (the counting variant is a kernel of its own: STATS = [2 * levels] iterations run / (feature, level) visits of this launch,
     // vio_frontend_lk_iterations; the product kernel sits at 80 registers for six waves per SIMD and has none to spare)
-    if (fe->lk_stats_on && fe->lk_stats)
-      hipLaunchKernelGGL((lk_track_kernel<kLkFpw, true>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx], forw, P, fe->n_pts, fe->cur_pts,
-                         fe->forw_pts, fe->lk_status, fe->lk_err, fe->lk_stats);
+    if (fe->lk_stats_on && fe->lk_stats.p)
+      hipLaunchKernelGGL((lk_track_kernel<kLkFpw, true>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
+                         fe->forw_pts.p, fe->lk_status.p, fe->lk_err.p, fe->lk_stats.p);
     else
-      hipLaunchKernelGGL((lk_track_kernel<kLkFpw, false>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx], forw, P, fe->n_pts, fe->cur_pts,
-                         fe->forw_pts, fe->lk_status, fe->lk_err, (unsigned long long *)nullptr);
+      hipLaunchKernelGGL((lk_track_kernel<kLkFpw, false>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
+                         fe->forw_pts.p, fe->lk_status.p, fe->lk_err.p, (unsigned long long *)nullptr);
   }
   int rcu = launch_track_update(fe, publish, st);
   if (rcu != VIO_OK) return rcu;
   if (publish) {
     dim3 tb(256), tg((cols + kDetWaves * kDetW - 1) / (kDetWaves * kDetW), fe->nseg, S);
     hipLaunchKernelGGL(detect_kernel<false>, tg, tb, 0, st, alias0 ? d_frames : forw, alias0 ? img_bytes : fe->ld.pyr_bytes, (const uint8_t *)nullptr, (size_t)0,
-                       fe->kept_xy, fe->n_kept, cap, fe->hw, fe->cfg.min_dist, fe->max_bits, rows, cols, fe->cand,
-                       fe->seg_cap, fe->n_cand, fe->detect_always ? (const int *)nullptr : fe->n_forw, fe->cfg.max_corners);
+                       fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist, fe->max_bits.p, rows, cols, fe->cand.p,
+                       fe->seg_cap, fe->n_cand.p, fe->detect_always ? (const int *)nullptr : fe->n_forw.p, fe->cfg.max_corners);
     SelectParams SP;
     SP.cap = cap, SP.rows = rows, SP.cols = cols, SP.max_corners = fe->cfg.max_corners, SP.min_dist = (float)fe->cfg.min_dist;
     SP.fx = fe->cfg.fx, SP.fy = fe->cfg.fy, SP.cx = fe->cfg.cx, SP.cy = fe->cfg.cy;
-    hipLaunchKernelGGL(corner_select_kernel, dim3(S), dim3(kSelThreads), 0, st, fe->cand, fe->seg_cap, fe->nseg, fe->n_cand,
-                       fe->max_bits, fe->cfg.quality_level, SP, fe->forw_pts, fe->cur_pts, fe->pre_pts, fe->ids,
-                       fe->track_cnt, fe->n_forw, fe->n_pts, fe->n_id, fe->obs, fe->n_obs);
+    hipLaunchKernelGGL(corner_select_kernel, dim3(S), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg, fe->n_cand.p,
+                       fe->max_bits.p, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
+                       fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p);
   }
   HIP_OK(hipGetLastError());
   fe->cur_idx = fidx;  // cur_img = forw_img (:284)
@@ -2164,12 +2164,7 @@ int vio_frontend_create(const VioConfig *cfg, int32_t n_seq, vio_frontend_t **ou
       cfg->max_corners > kMaxCap || cfg->image_rows < 32 || cfg->image_cols < 32 || cfg->min_dist < 0 || cfg->min_dist > kMaxRadius ||
       cfg->image_rows > 32767 || cfg->image_cols > 65535)  // (corner candidates carry their position as y << 16 | x)
     return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "vio_amd: no HIP device visible; the front-end has no CPU fallback\n");
-    return VIO_ENODEV;
-  }
-  if (!vio::single_hip_runtime()) return VIO_ENODEV;
+  if (!vio::device_ready("the front-end")) return VIO_ENODEV;
   vio_frontend *fe = new vio_frontend();
   fe->device = vio::current_device();
   fe->cfg = *cfg, fe->n_seq = n_seq, fe->cap = cfg->max_corners;
@@ -2191,51 +2186,32 @@ int vio_frontend_create(const VioConfig *cfg, int32_t n_seq, vio_frontend_t **ou
     return VIO_ECAP;
   }
   fe->seg_cap = kDetR * cfg->image_cols / 4;  // a 3x3 local maximum can occupy at most one pixel in four
-  int rc = VIO_OK;
-  if (hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking) != hipSuccess) rc = VIO_ENODEV;
-#define ALLOC(ptr, count) \
-  if (rc == VIO_OK) rc = dev_alloc(&(ptr), (count))
-  ALLOC(fe->pyr[0], S * ld.pyr_bytes);
-  ALLOC(fe->pyr[1], S * ld.pyr_bytes);
-  ALLOC(fe->max_bits, S * fe->nseg);
-  ALLOC(fe->cand, S * fe->nseg * fe->seg_cap);
-  ALLOC(fe->n_cand, S * fe->nseg);
-  ALLOC(fe->cur_pts, S * cap * 2);
-  ALLOC(fe->pre_pts, S * cap * 2);
-  ALLOC(fe->forw_pts, S * cap * 2);
-  ALLOC(fe->lk_err, S * cap);
-  ALLOC(fe->ids, S * cap);
-  ALLOC(fe->track_cnt, S * cap);
-  ALLOC(fe->n_pts, S);
-  ALLOC(fe->n_forw, S);
-  ALLOC(fe->n_id, S);
-  ALLOC(fe->kept_xy, S * cap * 2);
-  ALLOC(fe->n_kept, S);
-  ALLOC(fe->pnp_pts, S * cap * 2);
-  ALLOC(fe->pnp_ids, S * cap);
-  ALLOC(fe->n_pnp, S);
-  ALLOC(fe->n_obs, S);
-  ALLOC(fe->lk_status, S * cap);
-  ALLOC(fe->obs, S * cap);
-  ALLOC(fe->hw, (size_t)2 * cfg->min_dist + 1);
-#undef ALLOC
-  if (rc == VIO_OK) {
-    std::vector<int> hw;
-    circle_halfwidths(cfg->min_dist, hw);
-    bool ok = hipMemcpy(fe->hw, hw.data(), hw.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemset(fe->max_bits, 0, sizeof(unsigned) * S * fe->nseg) == hipSuccess;
-    ok = ok && hipMemset(fe->n_cand, 0, sizeof(int) * S * fe->nseg) == hipSuccess;
-    ok = ok && hipMemset(fe->n_pts, 0, sizeof(int) * S) == hipSuccess;
-    ok = ok && hipMemset(fe->n_forw, 0, sizeof(int) * S) == hipSuccess;
-    ok = ok && hipMemset(fe->n_id, 0, sizeof(int) * S) == hipSuccess;
-    ok = ok && hipMemset(fe->n_kept, 0, sizeof(int) * S) == hipSuccess;
-    ok = ok && hipMemset(fe->n_pnp, 0, sizeof(int) * S) == hipSuccess;
-    ok = ok && hipMemset(fe->n_obs, 0, sizeof(int) * S) == hipSuccess;
-    if (!ok) rc = VIO_ENODEV;
+  if (hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete fe;
+    return VIO_ENODEV;
   }
-  if (rc != VIO_OK) {
-    vio_frontend_destroy(fe);
-    return rc;
+  if (fe->pyr[0].ensure(S * ld.pyr_bytes) != VIO_OK || fe->pyr[1].ensure(S * ld.pyr_bytes) != VIO_OK ||
+      fe->max_bits.ensure(S * fe->nseg) != VIO_OK || fe->cand.ensure(S * fe->nseg * fe->seg_cap) != VIO_OK ||
+      fe->n_cand.ensure(S * fe->nseg) != VIO_OK || fe->cur_pts.ensure(S * cap * 2) != VIO_OK ||
+      fe->pre_pts.ensure(S * cap * 2) != VIO_OK || fe->forw_pts.ensure(S * cap * 2) != VIO_OK || fe->lk_err.ensure(S * cap) != VIO_OK ||
+      fe->ids.ensure(S * cap) != VIO_OK || fe->track_cnt.ensure(S * cap) != VIO_OK || fe->n_pts.ensure(S) != VIO_OK ||
+      fe->n_forw.ensure(S) != VIO_OK || fe->n_id.ensure(S) != VIO_OK || fe->kept_xy.ensure(S * cap * 2) != VIO_OK ||
+      fe->n_kept.ensure(S) != VIO_OK || fe->pnp_pts.ensure(S * cap * 2) != VIO_OK || fe->pnp_ids.ensure(S * cap) != VIO_OK ||
+      fe->n_pnp.ensure(S) != VIO_OK || fe->n_obs.ensure(S) != VIO_OK || fe->lk_status.ensure(S * cap) != VIO_OK ||
+      fe->obs.ensure(S * cap) != VIO_OK || fe->hw.ensure((size_t)2 * cfg->min_dist + 1) != VIO_OK) {
+    delete fe;
+    return VIO_ENOMEM;
+  }
+  std::vector<int> hw;
+  circle_halfwidths(cfg->min_dist, hw);
+  if (hipMemcpy(fe->hw.p, hw.data(), hw.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(fe->max_bits.p, 0, sizeof(unsigned) * S * fe->nseg) != hipSuccess ||
+      hipMemset(fe->n_cand.p, 0, sizeof(int) * S * fe->nseg) != hipSuccess || hipMemset(fe->n_pts.p, 0, sizeof(int) * S) != hipSuccess ||
+      hipMemset(fe->n_forw.p, 0, sizeof(int) * S) != hipSuccess || hipMemset(fe->n_id.p, 0, sizeof(int) * S) != hipSuccess ||
+      hipMemset(fe->n_kept.p, 0, sizeof(int) * S) != hipSuccess || hipMemset(fe->n_pnp.p, 0, sizeof(int) * S) != hipSuccess ||
+      hipMemset(fe->n_obs.p, 0, sizeof(int) * S) != hipSuccess) {
+    delete fe;
+    return VIO_ENODEV;
   }
   *out = fe;
   return VIO_OK;
@@ -2249,28 +2225,7 @@ int vio_frontend_get_device(const vio_frontend_t *fe, int32_t *device) {
 
 void vio_frontend_destroy(vio_frontend_t *fe) {
   if (!fe) return;
-  if (fe->async) {
-    {
-      std::lock_guard<std::mutex> lk(fe->async->m);
-      fe->async->quit = true;
-    }
-    fe->async->cv.notify_all();
-    if (fe->async->th.joinable()) fe->async->th.join();
-    delete fe->async;
-  }
   vio::DeviceScope scope(fe->device);
-  (void)hipDeviceSynchronize();
-  void *ptrs[] = {fe->pyr[0], fe->pyr[1], fe->mask, fe->max_bits, fe->cand, fe->n_cand, fe->cur_pts, fe->pre_pts,
-                  fe->forw_pts, fe->lk_err, fe->ids, fe->track_cnt, fe->n_pts, fe->n_forw, fe->n_id, fe->kept_xy, fe->n_kept,
-                  fe->n_obs, fe->lk_status, fe->obs, fe->hw, fe->frames, fe->pnp_pts, fe->pnp_ids, fe->n_pnp};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  for (auto &e : fe->events) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
-  if (fe->d_stage) (void)hipFree(fe->d_stage);
-  if (fe->lk_stats) (void)hipFree(fe->lk_stats);
-  if (fe->p_obs) (void)hipHostFree(fe->p_obs);
-  if (fe->p_frames) (void)hipHostFree(fe->p_frames);
-  if (fe->stream) (void)hipStreamDestroy(fe->stream);
   delete fe;
 }
 
@@ -2285,38 +2240,28 @@ int vio_frontend_upload_frames(vio_frontend_t *fe, const uint8_t *gray, int32_t 
   HIP_OK(hipDeviceSynchronize());
   for (int k = 0; k < 2; k++) {
     if (fe->lvl0[k])
-      HIP_OK(hipMemcpy2D(fe->pyr[k], fe->ld.pyr_bytes, fe->lvl0[k], px, px, fe->n_seq, hipMemcpyDeviceToDevice));
+      HIP_OK(hipMemcpy2D(fe->pyr[k].p, fe->ld.pyr_bytes, fe->lvl0[k], px, px, fe->n_seq, hipMemcpyDeviceToDevice));
     fe->lvl0[k] = nullptr;
   }
-  if (fe->frames) (void)hipFree(fe->frames), fe->frames = nullptr;
-  if (dev_alloc(&fe->frames, total * px) != VIO_OK) return VIO_ENOMEM;
-  HIP_OK(hipMemcpy2D(fe->frames, cols, gray, stride, cols, total * rows, hipMemcpyHostToDevice));
+  fe->frames.release();  // (exactly the new size)
+  if (fe->frames.ensure(total * px) != VIO_OK) return VIO_ENOMEM;
+  HIP_OK(hipMemcpy2D(fe->frames.p, cols, gray, stride, cols, total * rows, hipMemcpyHostToDevice));
   fe->n_frames = n_frames;
   return VIO_OK;
 }
 
 int vio_frontend_step_resident(vio_frontend_t *fe, int32_t frame_index, int32_t publish, void *stream) {
   if (!fe) return VIO_EINVAL;
-  if (!fe->frames || frame_index < 0 || frame_index >= fe->n_frames) return VIO_ESTATE;
+  if (!fe->frames.p || frame_index < 0 || frame_index >= fe->n_frames) return VIO_ESTATE;
   if (fe->pending) return VIO_ESTATE;  // a submitted frame owns the tracker state and the observation staging until it is collected
   VIO_ON_DEVICE_OF(fe);
   hipStream_t st = stream ? (hipStream_t)stream : fe->stream;
-  if (fe->events_used == fe->events.size()) {
-    if (fe->events.size() >= 4096) fe->events_used = 0;
-    else {
-      hipEvent_t a, b;
-      HIP_OK(hipEventCreate(&a));
-      HIP_OK(hipEventCreate(&b));
-      fe->events.push_back({a, b});
-    }
-  }
-  auto &ev = fe->events[fe->events_used++];
-  HIP_OK(hipEventRecord(ev.first, st));
-  const size_t px = (size_t)fe->cfg.image_rows * fe->cfg.image_cols;
-  int rc = fe_step(fe, fe->frames + (size_t)frame_index * fe->n_seq * px, publish, st, true);
+  int rc = fe->timer.begin(st);
   if (rc != VIO_OK) return rc;
-  HIP_OK(hipEventRecord(ev.second, st));
-  return VIO_OK;
+  const size_t px = (size_t)fe->cfg.image_rows * fe->cfg.image_cols;
+  rc = fe_step(fe, fe->frames.p + (size_t)frame_index * fe->n_seq * px, publish, st, true);
+  if (rc != VIO_OK) return rc;
+  return fe->timer.end(st);
 }
 
 int vio_frontend_sync(vio_frontend_t *fe) {
@@ -2330,16 +2275,7 @@ int vio_frontend_kernel_ms(vio_frontend_t *fe, double *ms_avg, int32_t *launches
   if (!fe || !ms_avg || !launches) return VIO_EINVAL;
   VIO_ON_DEVICE_OF(fe);
   HIP_OK(hipDeviceSynchronize());
-  double sum = 0;
-  for (size_t i = 0; i < fe->events_used; i++) {
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, fe->events[i].first, fe->events[i].second));
-    sum += ms;
-  }
-  *launches = (int32_t)fe->events_used;
-  *ms_avg = fe->events_used ? sum / fe->events_used : 0.0;
-  fe->events_used = 0;
-  return VIO_OK;
+  return fe->timer.drain(ms_avg, launches);
 }
 
 // Host buffers the caller registered (vio_host_register): page-locked in place, so their frames go to the device by DMA straight
@@ -2362,8 +2298,7 @@ bool host_range_registered(const void *ptr, size_t bytes) {
 
 int vio_host_register(void *ptr, size_t bytes) {
   if (!ptr || bytes == 0) return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || !vio::single_hip_runtime()) return VIO_ENODEV;
+  if (!vio::device_ready("host-buffer registration")) return VIO_ENODEV;
   {
     std::lock_guard<std::mutex> lk(g_host_reg_m);
     const uint8_t *b = static_cast<const uint8_t *>(ptr);
@@ -2406,40 +2341,36 @@ static int submit_body(vio_frontend_t *fe, const uint8_t *gray, int32_t rows, in
   const size_t px = (size_t)rows * cols, S = fe->n_seq;
   // host frames land in a device staging buffer kept for the life of the context; observations come back through
   // pinned host memory (no allocation, no pageable bounce on the return path)
-  if (!fe->d_stage && dev_alloc(&fe->d_stage, S * px) != VIO_OK) return VIO_ENOMEM;
-  if (!fe->p_obs) {
-    if (hipHostMalloc((void **)&fe->p_obs, sizeof(VioObs) * S * fe->cap + sizeof(int) * S, hipHostMallocDefault) != hipSuccess)
-      return VIO_ENOMEM;
-    fe->p_nobs = reinterpret_cast<int *>(fe->p_obs + S * fe->cap);
-  }
+  if (fe->d_stage.ensure(S * px) != VIO_OK) return VIO_ENOMEM;
+  if (fe->p_obs.ensure(S * fe->cap) != VIO_OK || fe->p_nobs.ensure(S) != VIO_OK) return VIO_ENOMEM;
   hipStream_t st = fe->stream;
   // The caller's frames are pageable memory: a direct copy bounces through the runtime's staging at ~5 GB/s. They are
   // gathered into page-locked memory by the host pool (one sequence per task, rows packed) in a few chunks, each chunk
   // going to the device as soon as it is complete, so the DMA of one overlaps the gathering of the next.
   if (stride == cols && host_range_registered(gray, S * px)) {
     // frames in a buffer the caller registered: one DMA from where they are
-    HIP_OK(hipMemcpyAsync(fe->d_stage, gray, S * px, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(fe->d_stage.p, gray, S * px, hipMemcpyHostToDevice, st));
   } else {
-    if (!fe->p_frames && hipHostMalloc((void **)&fe->p_frames, S * px, hipHostMallocDefault) != hipSuccess) return VIO_ENOMEM;
+    if (fe->p_frames.ensure(S * px) != VIO_OK) return VIO_ENOMEM;
     const size_t n_chunks = S >= 32 ? 8 : 1, per = (S + n_chunks - 1) / n_chunks;
     for (size_t c0 = 0; c0 < S; c0 += per) {
       const size_t c1 = std::min(S, c0 + per);
       vio::HostPool::get().parallel_for((int)(c1 - c0), [&](int i) {
         const size_t s = c0 + i;
         const uint8_t *src = gray + s * (size_t)rows * stride;
-        uint8_t *dst = fe->p_frames + s * px;
+        uint8_t *dst = fe->p_frames.p + s * px;
         if (stride == cols) memcpy(dst, src, px);
         else
           for (int r = 0; r < rows; r++) memcpy(dst + (size_t)r * cols, src + (size_t)r * stride, cols);
       });
-      HIP_OK(hipMemcpyAsync(fe->d_stage + c0 * px, fe->p_frames + c0 * px, (c1 - c0) * px, hipMemcpyHostToDevice, st));
+      HIP_OK(hipMemcpyAsync(fe->d_stage.p + c0 * px, fe->p_frames.p + c0 * px, (c1 - c0) * px, hipMemcpyHostToDevice, st));
     }
   }
-  int rc = fe_step(fe, fe->d_stage, publish, st);
+  int rc = fe_step(fe, fe->d_stage.p, publish, st);
   if (rc != VIO_OK) return rc;
   if (publish) {
-    HIP_OK(hipMemcpyAsync(fe->p_obs, fe->obs, sizeof(VioObs) * S * fe->cap, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(fe->p_nobs, fe->n_obs, sizeof(int) * S, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(fe->p_obs.p, fe->obs.p, sizeof(VioObs) * S * fe->cap, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(fe->p_nobs.p, fe->n_obs.p, sizeof(int) * S, hipMemcpyDeviceToHost, st));
   }
   return VIO_OK;
 }
@@ -2514,8 +2445,8 @@ int vio_frontend_collect(vio_frontend_t *fe, VioObs *out_obs, int32_t *n_obs) {
   for (size_t s = 0; s < S; s++) n_obs[s] = 0;
   if (fe->pending_publish)
     for (size_t s = 0; s < S; s++) {
-      n_obs[s] = fe->p_nobs[s];
-      memcpy(out_obs + s * fe->cap, fe->p_obs + s * fe->cap, sizeof(VioObs) * fe->p_nobs[s]);
+      n_obs[s] = fe->p_nobs.p[s];
+      memcpy(out_obs + s * fe->cap, fe->p_obs.p + s * fe->cap, sizeof(VioObs) * fe->p_nobs.p[s]);
     }
   return VIO_OK;
 }
@@ -2543,14 +2474,14 @@ int vio_frontend_get_state(vio_frontend_t *fe, int32_t seq, float *cur_pts, int3
   VIO_ON_DEVICE_OF(fe);
   HIP_OK(hipDeviceSynchronize());
   int m = 0;
-  HIP_OK(hipMemcpy(&m, fe->n_pts + seq, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(&m, fe->n_pts.p + seq, sizeof(int), hipMemcpyDeviceToHost));
   *n = m;
   if (m > cap) return VIO_ECAP;
   const size_t base = (size_t)seq * fe->cap;
   if (m > 0) {
-    HIP_OK(hipMemcpy(cur_pts, fe->cur_pts + base * 2, sizeof(float) * 2 * m, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(ids, fe->ids + base, sizeof(int) * m, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(track_cnt, fe->track_cnt + base, sizeof(int) * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(cur_pts, fe->cur_pts.p + base * 2, sizeof(float) * 2 * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(ids, fe->ids.p + base, sizeof(int) * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(track_cnt, fe->track_cnt.p + base, sizeof(int) * m, hipMemcpyDeviceToHost));
   }
   return VIO_OK;
 }
@@ -2563,20 +2494,20 @@ int vio_frontend_lk_iterations(vio_frontend_t *fe, int32_t enable, uint64_t *ite
   if (fe->pending) return VIO_ESTATE;  // (a submitted frame's worker reads lk_stats_on / lk_stats while it queues the step)
   VIO_ON_DEVICE_OF(fe);
   constexpr int kSlots = 16 * 64;  // 64 copies of [iterations (levels) | visits (levels)], summed here
-  if (!fe->lk_stats) {
-    if (dev_alloc(&fe->lk_stats, (size_t)kSlots) != VIO_OK) return VIO_ENOMEM;
-    HIP_OK(hipMemset(fe->lk_stats, 0, sizeof(unsigned long long) * kSlots));
+  if (!fe->lk_stats.p) {
+    if (fe->lk_stats.ensure(kSlots) != VIO_OK) return VIO_ENOMEM;
+    HIP_OK(hipMemset(fe->lk_stats.p, 0, sizeof(unsigned long long) * kSlots));
   }
   HIP_OK(hipStreamSynchronize(fe->stream));
   if (iterations) {
     unsigned long long h[kSlots];
-    HIP_OK(hipMemcpy(h, fe->lk_stats, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(h, fe->lk_stats.p, sizeof(h), hipMemcpyDeviceToHost));
     const int L = fe->ld.levels;
     for (int l = 0; l < levels_cap; l++) {
       iterations[l] = visits[l] = 0;
       for (int c = 0; c < 64 && l < L; c++) iterations[l] += h[16 * c + l], visits[l] += h[16 * c + L + l];
     }
-    HIP_OK(hipMemset(fe->lk_stats, 0, sizeof(h)));
+    HIP_OK(hipMemset(fe->lk_stats.p, 0, sizeof(h)));
   }
   if (enable >= 0) fe->lk_stats_on = enable != 0;
   return VIO_OK;
@@ -2588,14 +2519,14 @@ int vio_frontend_get_pnp_points(vio_frontend_t *fe, int32_t seq, float *forw_pts
   VIO_ON_DEVICE_OF(fe);
   HIP_OK(hipDeviceSynchronize());
   int m = 0;
-  HIP_OK(hipMemcpy(&m, fe->n_pnp + seq, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(&m, fe->n_pnp.p + seq, sizeof(int), hipMemcpyDeviceToHost));
   *n = m;
   if (m > cap) return VIO_ECAP;
   const size_t base = (size_t)seq * fe->cap;
   if (m > 0) {
     if (!forw_pts || !ids) return VIO_EINVAL;
-    HIP_OK(hipMemcpy(forw_pts, fe->pnp_pts + base * 2, sizeof(float) * 2 * m, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(ids, fe->pnp_ids + base, sizeof(int) * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(forw_pts, fe->pnp_pts.p + base * 2, sizeof(float) * 2 * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(ids, fe->pnp_ids.p + base, sizeof(int) * m, hipMemcpyDeviceToHost));
   }
   return VIO_OK;
 }
@@ -2611,14 +2542,14 @@ int vio_frontend_set_tracks(vio_frontend_t *fe, int32_t seq, int32_t n, const fl
   HIP_OK(hipDeviceSynchronize());
   const size_t base = (size_t)seq * fe->cap;
   if (n > 0) {
-    HIP_OK(hipMemcpy(fe->pre_pts + base * 2, pre_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(fe->cur_pts + base * 2, cur_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(fe->forw_pts + base * 2, forw_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(fe->ids + base, ids, sizeof(int) * n, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(fe->track_cnt + base, track_cnt, sizeof(int) * n, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(fe->lk_status + base, lk_status, n, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fe->pre_pts.p + base * 2, pre_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fe->cur_pts.p + base * 2, cur_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fe->forw_pts.p + base * 2, forw_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fe->ids.p + base, ids, sizeof(int) * n, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fe->track_cnt.p + base, track_cnt, sizeof(int) * n, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fe->lk_status.p + base, lk_status, n, hipMemcpyHostToDevice));
   }
-  HIP_OK(hipMemcpy(fe->n_pts + seq, &n, sizeof(int), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(fe->n_pts.p + seq, &n, sizeof(int), hipMemcpyHostToDevice));
   return VIO_OK;
 }
 
@@ -2640,19 +2571,22 @@ int vio_frontend_get_tracks(vio_frontend_t *fe, int32_t seq, float *forw_pts, in
   VIO_ON_DEVICE_OF(fe);
   HIP_OK(hipDeviceSynchronize());
   int m = 0;
-  HIP_OK(hipMemcpy(&m, fe->n_forw + seq, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(&m, fe->n_forw.p + seq, sizeof(int), hipMemcpyDeviceToHost));
   *n = m;
   if (m > cap) return VIO_ECAP;
   const size_t base = (size_t)seq * fe->cap;
   if (m > 0) {
-    HIP_OK(hipMemcpy(forw_pts, fe->forw_pts + base * 2, sizeof(float) * 2 * m, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(ids, fe->ids + base, sizeof(int) * m, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(track_cnt, fe->track_cnt + base, sizeof(int) * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(forw_pts, fe->forw_pts.p + base * 2, sizeof(float) * 2 * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(ids, fe->ids.p + base, sizeof(int) * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(track_cnt, fe->track_cnt.p + base, sizeof(int) * m, hipMemcpyDeviceToHost));
   }
   return VIO_OK;
 }
 
 // ---- stand-alone operators (one reference call site each), for isolated parity tests --------------------------------
+// (each runs on a temporary context, destroyed on every return path)
+using FrontendPtr = std::unique_ptr<vio_frontend, void (*)(vio_frontend_t *)>;
+
 int vio_klt_track(const VioConfig *cfg, const uint8_t *prev, const uint8_t *next, int32_t rows, int32_t cols, int32_t stride,
                   const float *prev_pts, int32_t n, float *next_pts, uint8_t *status, float *err) {
   if (!cfg || !prev || !next || n < 0 || (n > 0 && (!prev_pts || !next_pts || !status || !err))) return VIO_EINVAL;
@@ -2660,44 +2594,39 @@ int vio_klt_track(const VioConfig *cfg, const uint8_t *prev, const uint8_t *next
   VioConfig c = *cfg;
   c.image_rows = rows, c.image_cols = cols, c.max_corners = std::min(std::max(n, 1), kMaxCap);
   if (n > kMaxCap) return VIO_ECAP;
-  vio_frontend *fe = nullptr;
-  int rc = vio_frontend_create(&c, 1, &fe);
+  vio_frontend *raw = nullptr;
+  int rc = vio_frontend_create(&c, 1, &raw);
   if (rc != VIO_OK) return rc;
+  const FrontendPtr fe(raw, vio_frontend_destroy);
   const size_t px = (size_t)rows * cols;
-  uint8_t *d = nullptr;
-  rc = dev_alloc(&d, 2 * px);
-  auto fail = [&](int code) {
-    if (d) (void)hipFree(d);
-    vio_frontend_destroy(fe);
-    return code;
-  };
-  if (rc != VIO_OK) return fail(rc);
-  if (hipMemcpy2D(d, cols, prev, stride, cols, rows, hipMemcpyHostToDevice) != hipSuccess) return fail(VIO_ENODEV);
-  if (hipMemcpy2D(d + px, cols, next, stride, cols, rows, hipMemcpyHostToDevice) != hipSuccess) return fail(VIO_ENODEV);
+  DevBuf<uint8_t> d;  // prev | next
+  if (d.ensure(2 * px) != VIO_OK) return VIO_ENOMEM;
+  if (hipMemcpy2D(d.p, cols, prev, stride, cols, rows, hipMemcpyHostToDevice) != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpy2D(d.p + px, cols, next, stride, cols, rows, hipMemcpyHostToDevice) != hipSuccess) return VIO_ENODEV;
   hipStream_t st = fe->stream;
   for (int k = 0; k < 2; k++) {
-    uint8_t *dst = fe->pyr[k];
-    if (hipMemcpyAsync(dst, d + k * px, px, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(VIO_ENODEV);
+    uint8_t *dst = fe->pyr[k].p;
+    if (hipMemcpyAsync(dst, d.p + k * px, px, hipMemcpyDeviceToDevice, st) != hipSuccess) return VIO_ENODEV;
     for (int l = 1; l < fe->ld.levels; l++) {
       dim3 blk(256), grd((fe->ld.cols[l] + kPdW - 1) / kPdW, (fe->ld.rows[l] + kPdH - 1) / kPdH, 1);
       hipLaunchKernelGGL(pyr_down_kernel, grd, blk, 0, st, dst + fe->ld.off[l - 1], dst + fe->ld.off[l], fe->ld.pyr_bytes,
                          fe->ld.rows[l - 1], fe->ld.cols[l - 1], fe->ld.rows[l], fe->ld.cols[l]);
     }
   }
-  if (hipMemcpyAsync(fe->cur_pts, prev_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st) != hipSuccess) return fail(VIO_ENODEV);
-  if (hipMemcpyAsync(fe->n_pts, &n, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return fail(VIO_ENODEV);
+  if (hipMemcpyAsync(fe->cur_pts.p, prev_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpyAsync(fe->n_pts.p, &n, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV;
   LkParams P;
   P.ld = fe->ld, P.cap = fe->cap, P.max_count = std::min(std::max(c.lk_max_iters, 0), 100);
   double eps = std::min(std::max(c.lk_eps, 0.), 10.);
   P.epsilon_sq = eps * eps, P.epsilon_sq_f = lk_eps_screen(eps * eps), P.min_eig = (float)c.lk_min_eig;
   P.prev0 = P.next0 = nullptr, P.stride0 = 0;
-  hipLaunchKernelGGL((lk_track_kernel<kLkFpw, false>), dim3((fe->cap + 4 * kLkFpw - 1) / (4 * kLkFpw), 1), dim3(256), 0, st, fe->pyr[0], fe->pyr[1], P, fe->n_pts,
-                     fe->cur_pts, fe->forw_pts, fe->lk_status, fe->lk_err, (unsigned long long *)nullptr);
-  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return fail(VIO_ENODEV);
-  if (hipMemcpy(next_pts, fe->forw_pts, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) return fail(VIO_ENODEV);
-  if (hipMemcpy(status, fe->lk_status, n, hipMemcpyDeviceToHost) != hipSuccess) return fail(VIO_ENODEV);
-  if (hipMemcpy(err, fe->lk_err, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess) return fail(VIO_ENODEV);
-  return fail(VIO_OK);
+  hipLaunchKernelGGL((lk_track_kernel<kLkFpw, false>), dim3((fe->cap + 4 * kLkFpw - 1) / (4 * kLkFpw), 1), dim3(256), 0, st, fe->pyr[0].p, fe->pyr[1].p, P, fe->n_pts.p,
+                     fe->cur_pts.p, fe->forw_pts.p, fe->lk_status.p, fe->lk_err.p, (unsigned long long *)nullptr);
+  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpy(next_pts, fe->forw_pts.p, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpy(status, fe->lk_status.p, n, hipMemcpyDeviceToHost) != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpy(err, fe->lk_err.p, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess) return VIO_ENODEV;
+  return VIO_OK;
 }
 
 int vio_good_features(const VioConfig *cfg, const uint8_t *img, const uint8_t *mask, int32_t rows, int32_t cols, int32_t stride,
@@ -2706,40 +2635,37 @@ int vio_good_features(const VioConfig *cfg, const uint8_t *img, const uint8_t *m
   if (max_corners > kMaxCap) return VIO_ECAP;
   VioConfig c = *cfg;
   c.image_rows = rows, c.image_cols = cols, c.max_corners = max_corners;
-  vio_frontend *fe = nullptr;
-  int rc = vio_frontend_create(&c, 1, &fe);
+  vio_frontend *raw = nullptr;
+  int rc = vio_frontend_create(&c, 1, &raw);
   if (rc != VIO_OK) return rc;
-  auto fail = [&](int code) {
-    vio_frontend_destroy(fe);
-    return code;
-  };
+  const FrontendPtr fe(raw, vio_frontend_destroy);
   const size_t px = (size_t)rows * cols;
   hipStream_t st = fe->stream;
-  if (hipMemcpy2D(fe->pyr[0], cols, img, stride, cols, rows, hipMemcpyHostToDevice) != hipSuccess) return fail(VIO_ENODEV);
-  if (dev_alloc(&fe->mask, px) != VIO_OK) return fail(VIO_ENOMEM);
+  if (hipMemcpy2D(fe->pyr[0].p, cols, img, stride, cols, rows, hipMemcpyHostToDevice) != hipSuccess) return VIO_ENODEV;
+  if (fe->mask.ensure(px) != VIO_OK) return VIO_ENOMEM;
   if (mask) {
-    if (hipMemcpy2D(fe->mask, cols, mask, stride, cols, rows, hipMemcpyHostToDevice) != hipSuccess) return fail(VIO_ENODEV);
-  } else if (hipMemset(fe->mask, 255, px) != hipSuccess) {
-    return fail(VIO_ENODEV);
+    if (hipMemcpy2D(fe->mask.p, cols, mask, stride, cols, rows, hipMemcpyHostToDevice) != hipSuccess) return VIO_ENODEV;
+  } else if (hipMemset(fe->mask.p, 255, px) != hipSuccess) {
+    return VIO_ENODEV;
   }
-  if (hipMemset(fe->max_bits, 0, sizeof(unsigned) * fe->nseg) != hipSuccess ||
-      hipMemset(fe->n_cand, 0, sizeof(int) * fe->nseg) != hipSuccess)
-    return fail(VIO_ENODEV);
+  if (hipMemset(fe->max_bits.p, 0, sizeof(unsigned) * fe->nseg) != hipSuccess ||
+      hipMemset(fe->n_cand.p, 0, sizeof(int) * fe->nseg) != hipSuccess)
+    return VIO_ENODEV;
   dim3 tb(256), tg((cols + kDetWaves * kDetW - 1) / (kDetWaves * kDetW), fe->nseg, 1);
-  hipLaunchKernelGGL(detect_kernel<true>, tg, tb, 0, st, fe->pyr[0], fe->ld.pyr_bytes, fe->mask, px, fe->kept_xy, fe->n_kept,
-                     fe->cap, fe->hw, c.min_dist, fe->max_bits, rows, cols, fe->cand, fe->seg_cap, fe->n_cand, (const int *)nullptr, 0);
+  hipLaunchKernelGGL(detect_kernel<true>, tg, tb, 0, st, fe->pyr[0].p, fe->ld.pyr_bytes, fe->mask.p, px, fe->kept_xy.p, fe->n_kept.p,
+                     fe->cap, fe->hw.p, c.min_dist, fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, (const int *)nullptr, 0);
   SelectParams SP;
   SP.cap = fe->cap, SP.rows = rows, SP.cols = cols, SP.max_corners = max_corners, SP.min_dist = (float)c.min_dist;
   SP.fx = c.fx, SP.fy = c.fy, SP.cx = c.cx, SP.cy = c.cy;
-  hipLaunchKernelGGL(corner_select_kernel, dim3(1), dim3(kSelThreads), 0, st, fe->cand, fe->seg_cap, fe->nseg, fe->n_cand, fe->max_bits,
-                     c.quality_level, SP, fe->forw_pts, fe->cur_pts, fe->pre_pts, fe->ids, fe->track_cnt, fe->n_forw, fe->n_pts,
-                     fe->n_id, fe->obs, fe->n_obs);
-  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return fail(VIO_ENODEV);
+  hipLaunchKernelGGL(corner_select_kernel, dim3(1), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg, fe->n_cand.p, fe->max_bits.p,
+                     c.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p, fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p,
+                     fe->n_id.p, fe->obs.p, fe->n_obs.p);
+  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
   int n = 0;
-  if (hipMemcpy(&n, fe->n_pts, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(VIO_ENODEV);
+  if (hipMemcpy(&n, fe->n_pts.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return VIO_ENODEV;
   *n_corners = n;
-  if (n > 0 && hipMemcpy(corners, fe->forw_pts, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) return fail(VIO_ENODEV);
-  return fail(VIO_OK);
+  if (n > 0 && hipMemcpy(corners, fe->forw_pts.p, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) return VIO_ENODEV;
+  return VIO_OK;
 }
 
 __global__ __launch_bounds__(256) void ransac_only_kernel(const float *p1, const float *p2, int n, float thresh, double conf,
@@ -2754,25 +2680,16 @@ int vio_fundamental_ransac(const VioConfig *cfg, const float *pts1, const float 
   if (n == 0) return VIO_OK;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return VIO_ENODEV;
-  float *d1 = nullptr, *d2 = nullptr;
-  uint8_t *dm = nullptr;
-  int rc = dev_alloc(&d1, (size_t)2 * n);
-  if (rc == VIO_OK) rc = dev_alloc(&d2, (size_t)2 * n);
-  if (rc == VIO_OK) rc = dev_alloc(&dm, (size_t)n);
-  auto done = [&](int code) {
-    if (d1) (void)hipFree(d1);
-    if (d2) (void)hipFree(d2);
-    if (dm) (void)hipFree(dm);
-    return code;
-  };
-  if (rc != VIO_OK) return done(rc);
-  if (hipMemcpy(d1, pts1, sizeof(float) * 2 * n, hipMemcpyHostToDevice) != hipSuccess) return done(VIO_ENODEV);
-  if (hipMemcpy(d2, pts2, sizeof(float) * 2 * n, hipMemcpyHostToDevice) != hipSuccess) return done(VIO_ENODEV);
-  hipLaunchKernelGGL(ransac_only_kernel, dim3(1), dim3(256), sizeof(RansacShared), 0, d1, d2, n, (float)cfg->f_threshold,
-                     cfg->f_confidence, dm);
-  if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return done(VIO_ENODEV);
-  if (hipMemcpy(inlier_mask, dm, n, hipMemcpyDeviceToHost) != hipSuccess) return done(VIO_ENODEV);
-  return done(VIO_OK);
+  DevBuf<float> d1, d2;
+  DevBuf<uint8_t> dm;
+  if (d1.ensure((size_t)2 * n) != VIO_OK || d2.ensure((size_t)2 * n) != VIO_OK || dm.ensure((size_t)n) != VIO_OK) return VIO_ENOMEM;
+  if (hipMemcpy(d1.p, pts1, sizeof(float) * 2 * n, hipMemcpyHostToDevice) != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpy(d2.p, pts2, sizeof(float) * 2 * n, hipMemcpyHostToDevice) != hipSuccess) return VIO_ENODEV;
+  hipLaunchKernelGGL(ransac_only_kernel, dim3(1), dim3(256), sizeof(RansacShared), 0, d1.p, d2.p, n, (float)cfg->f_threshold,
+                     cfg->f_confidence, dm.p);
+  if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpy(inlier_mask, dm.p, n, hipMemcpyDeviceToHost) != hipSuccess) return VIO_ENODEV;
+  return VIO_OK;
 }
 
 }  // extern "C"

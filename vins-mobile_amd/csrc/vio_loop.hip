@@ -23,15 +23,6 @@ namespace {
 constexpr int kWavesPerBlock = 4;
 constexpr int kStage = 512;  // old descriptors staged per round: 16 KB of LDS
 
-#define HIP_OK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      fprintf(stderr, "vio_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return VIO_ENODEV;                                                                   \
-    }                                                                                      \
-  } while (0)
-
 // grid (ceil(max_cur / 4), n_pairs); pair p: queries cur[cur_off[p] .. +n_cur[p]), candidates old[old_off[p] .. +n_old[p])
 __global__ __launch_bounds__(64 * kWavesPerBlock) void search_by_des_kernel(const unsigned long long *cur,
                                                                             const unsigned long long *old, const int *n_cur,
@@ -75,42 +66,25 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void search_by_des_kernel(cons
   }
 }
 
-template <class T>
-struct Buf {
-  T *p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n && p) return VIO_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-    if (hipMalloc((void **)&p, (count ? count : 1) * sizeof(T)) != hipSuccess) return VIO_ENOMEM;
-    n = count;
-    return VIO_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-  }
-};
-
 }  // namespace
 
 struct vio_matcher {
   int device = -1;
   hipStream_t stream = nullptr;
-  Buf<unsigned long long> d_cur, d_old;
-  Buf<int> d_meta, d_idx, d_dist;
+  vio::DevBuf<unsigned long long> d_cur, d_old;
+  vio::DevBuf<int> d_meta, d_idx, d_dist;
+  ~vio_matcher() {
+    if (!stream) return;
+    (void)hipStreamSynchronize(stream);
+    (void)hipStreamDestroy(stream);
+  }
 };
 
 extern "C" {
 
 int vio_matcher_create(vio_matcher_t **out) {
   if (!out) return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "vio_amd: no HIP device visible; the descriptor matcher has no CPU fallback\n");
-    return VIO_ENODEV;
-  }
+  if (!vio::device_ready("the descriptor matcher")) return VIO_ENODEV;
   vio_matcher *m = new (std::nothrow) vio_matcher();
   if (!m) return VIO_ENOMEM;
   m->device = vio::current_device();
@@ -125,9 +99,6 @@ int vio_matcher_create(vio_matcher_t **out) {
 void vio_matcher_destroy(vio_matcher_t *m) {
   if (!m) return;
   vio::DeviceScope scope(m->device);
-  (void)hipStreamSynchronize(m->stream);
-  m->d_cur.release(), m->d_old.release(), m->d_meta.release(), m->d_idx.release(), m->d_dist.release();
-  (void)hipStreamDestroy(m->stream);
   delete m;
 }
 

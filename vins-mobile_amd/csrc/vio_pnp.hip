@@ -52,23 +52,6 @@ __global__ __launch_bounds__(kThreads) void pnp_window_kernel(PnpBatch B) {
   pnp::solve(cx, v, w);
 }
 
-template <class T>
-struct Dev {
-  T *p = nullptr;
-  size_t n = 0;
-  bool ensure(size_t count) {
-    if (count <= n && p) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-    if (hipMalloc(&p, (count ? count : 1) * sizeof(T)) != hipSuccess) return false;
-    n = count;
-    return true;
-  }
-  ~Dev() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 
 struct vio_pnp {
@@ -79,26 +62,27 @@ struct vio_pnp {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double ms_sum = 0;
   int launches = 0;
-  Dev<int> d_hdr, d_track, d_stats_i;
-  Dev<double> d_pose, d_speed, d_bias, d_ex, d_preint, d_obs, d_pos, d_out_pose, d_out_speed, d_stats_d, d_U, d_Jraw;
+  vio::DevBuf<int> d_hdr, d_track, d_stats_i;
+  vio::DevBuf<double> d_pose, d_speed, d_bias, d_ex, d_preint, d_obs, d_pos, d_out_pose, d_out_speed, d_stats_d, d_U, d_Jraw;
+  ~vio_pnp() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 extern "C" {
 
 int vio_pnp_create(const VioConfig *cfg, int32_t max_batch, vio_pnp_t **out) {
   if (!cfg || !out || max_batch < 1) return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "vio_amd: no HIP device visible; the PnP window solve has no CPU fallback\n");
-    return VIO_ENODEV;
-  }
+  if (!vio::device_ready("the PnP window solve")) return VIO_ENODEV;
   vio_pnp *p = new (std::nothrow) vio_pnp();
-  if (p) p->device = vio::current_device();
   if (!p) return VIO_ENOMEM;
+  p->device = vio::current_device();
   p->cfg = *cfg, p->max_batch = max_batch;
   if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess ||
       hipEventCreate(&p->ev1) != hipSuccess) {
-    vio_pnp_destroy(p);
+    delete p;
     return VIO_ENODEV;
   }
   *out = p;
@@ -108,9 +92,6 @@ int vio_pnp_create(const VioConfig *cfg, int32_t max_batch, vio_pnp_t **out) {
 void vio_pnp_destroy(vio_pnp_t *p) {
   if (!p) return;
   vio::DeviceScope scope(p->device);
-  if (p->ev0) (void)hipEventDestroy(p->ev0);
-  if (p->ev1) (void)hipEventDestroy(p->ev1);
-  if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }
 
@@ -153,12 +134,13 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
       memcpy(&track[(size_t)b * Mmax], w.track_num, sizeof(int) * M);
     }
   }
-  bool ok = p->d_hdr.ensure(hdr.size()) && p->d_track.ensure(track.size()) && p->d_pose.ensure(pose.size()) &&
-            p->d_speed.ensure(speed.size()) && p->d_bias.ensure(bias.size()) && p->d_ex.ensure(ex.size()) &&
-            p->d_preint.ensure(pre.size()) && p->d_obs.ensure(obs.size()) && p->d_pos.ensure(pos.size()) &&
-            p->d_out_pose.ensure(pose.size()) && p->d_out_speed.ensure(speed.size()) && p->d_stats_d.ensure(N * kStatsD) &&
-            p->d_stats_i.ensure(N * kStatsI) && p->d_U.ensure(N * (F - 1) * 225) && p->d_Jraw.ensure(N * (F - 1) * 450);
-  if (!ok) return VIO_ENOMEM;
+  if (p->d_hdr.ensure(hdr.size()) != VIO_OK || p->d_track.ensure(track.size()) != VIO_OK || p->d_pose.ensure(pose.size()) != VIO_OK ||
+      p->d_speed.ensure(speed.size()) != VIO_OK || p->d_bias.ensure(bias.size()) != VIO_OK || p->d_ex.ensure(ex.size()) != VIO_OK ||
+      p->d_preint.ensure(pre.size()) != VIO_OK || p->d_obs.ensure(obs.size()) != VIO_OK || p->d_pos.ensure(pos.size()) != VIO_OK ||
+      p->d_out_pose.ensure(pose.size()) != VIO_OK || p->d_out_speed.ensure(speed.size()) != VIO_OK ||
+      p->d_stats_d.ensure(N * kStatsD) != VIO_OK || p->d_stats_i.ensure(N * kStatsI) != VIO_OK ||
+      p->d_U.ensure(N * (F - 1) * 225) != VIO_OK || p->d_Jraw.ensure(N * (F - 1) * 450) != VIO_OK)
+    return VIO_ENOMEM;
   hipStream_t st = p->stream;
 #define H2D(d, h) \
   if (hipMemcpyAsync((d).p, (h).data(), (h).size() * sizeof((h)[0]), hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV

@@ -34,15 +34,6 @@ using namespace vio;
 
 namespace {
 
-#define HIP_OK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      fprintf(stderr, "vio_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return VIO_ENODEV;                                                                   \
-    }                                                                                      \
-  } while (0)
-
 constexpr int kPgThreads = 512;
 constexpr int kPgHdr = 4;  // n_nodes, n_edges, N, max_iterations
 
@@ -436,23 +427,12 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgPtrs P) {
   }
 }
 
+// a device array and its page-locked host staging of the same length
 template <class T>
-struct PgBuf {
-  T *d = nullptr, *h = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n) return VIO_OK;
-    release();
-    if (hipMalloc(&d, count * sizeof(T)) != hipSuccess) return VIO_ENOMEM;
-    if (hipHostMalloc(&h, count * sizeof(T), hipHostMallocDefault) != hipSuccess) return VIO_ENOMEM;
-    n = count;
-    return VIO_OK;
-  }
-  void release() {
-    if (d) (void)hipFree(d);
-    if (h) (void)hipHostFree(h);
-    d = nullptr, h = nullptr, n = 0;
-  }
+struct Mirrored {
+  vio::DevBuf<T> d;
+  vio::PinnedBuf<T> h;
+  int ensure(size_t count) { return d.ensure(count) == VIO_OK ? h.ensure(count) : VIO_ENOMEM; }
 };
 
 }  // namespace
@@ -462,20 +442,19 @@ struct vio_posegraph {
   int max_nodes = 0, max_edges = 0, n_graphs = 0, ld = 0;
   size_t lds_bytes = 0;
   hipStream_t stream = nullptr;
-  PgBuf<int> hdr, col, ei, ej, ek, stats_i;
-  PgBuf<double> node0, meas, xout, stats_d;
-  double *H = nullptr, *A = nullptr;
+  Mirrored<int> hdr, col, ei, ej, ek, stats_i;
+  Mirrored<double> node0, meas, xout, stats_d;
+  vio::DevBuf<double> H, A;
+  ~vio_posegraph() {
+    if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+  }
 };
 
 extern "C" {
 
 int vio_posegraph_create(int32_t max_nodes, int32_t max_edges, int32_t n_graphs, vio_posegraph_t **out) {
   if (!out || max_nodes < 2 || max_edges < 1 || n_graphs < 1) return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "vio_amd: no HIP device visible; the pose graph solver has no CPU fallback\n");
-    return VIO_ENODEV;
-  }
+  if (!vio::device_ready("the pose graph solver")) return VIO_ENODEV;
   vio_posegraph *pg = new (std::nothrow) vio_posegraph();
   if (!pg) return VIO_ENOMEM;
   pg->device = vio::current_device();
@@ -487,29 +466,24 @@ int vio_posegraph_create(int32_t max_nodes, int32_t max_edges, int32_t n_graphs,
     return VIO_ECAP;
   }
   const size_t G = n_graphs, mat = (size_t)pg->ld * pg->ld;
-  bool ok = hipStreamCreateWithFlags(&pg->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && pg->hdr.ensure(G * kPgHdr) == VIO_OK && pg->col.ensure(G * max_nodes) == VIO_OK && pg->ei.ensure(G * max_edges) == VIO_OK &&
-       pg->ej.ensure(G * max_edges) == VIO_OK && pg->ek.ensure(G * max_edges) == VIO_OK && pg->stats_i.ensure(G * kStatsInts) == VIO_OK &&
-       pg->node0.ensure(G * max_nodes * 4) == VIO_OK && pg->meas.ensure(G * max_edges * 6) == VIO_OK &&
-       pg->xout.ensure(G * pg->ld) == VIO_OK && pg->stats_d.ensure(G * kStatsDoubles) == VIO_OK;
-  if (!ok) {  // (stream creation is the only non-allocation step above)
-    const bool no_stream = pg->stream == nullptr;
-    vio_posegraph_destroy(pg);
-    return no_stream ? VIO_ENODEV : VIO_ENOMEM;
+  if (hipStreamCreateWithFlags(&pg->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete pg;
+    return VIO_ENODEV;
   }
-  ok = hipMalloc(&pg->H, G * mat * sizeof(double)) == hipSuccess && hipMalloc(&pg->A, G * mat * sizeof(double)) == hipSuccess;
-  if (!ok) {
-    vio_posegraph_destroy(pg);
+  if (pg->hdr.ensure(G * kPgHdr) != VIO_OK || pg->col.ensure(G * max_nodes) != VIO_OK || pg->ei.ensure(G * max_edges) != VIO_OK ||
+      pg->ej.ensure(G * max_edges) != VIO_OK || pg->ek.ensure(G * max_edges) != VIO_OK || pg->stats_i.ensure(G * kStatsInts) != VIO_OK ||
+      pg->node0.ensure(G * max_nodes * 4) != VIO_OK || pg->meas.ensure(G * max_edges * 6) != VIO_OK ||
+      pg->xout.ensure(G * pg->ld) != VIO_OK || pg->stats_d.ensure(G * kStatsDoubles) != VIO_OK || pg->H.ensure(G * mat) != VIO_OK ||
+      pg->A.ensure(G * mat) != VIO_OK) {
+    delete pg;
     return VIO_ENOMEM;
   }
   // the factorization reads whole 16 x 16 tiles, including the rows past N of the last tile row: no uninitialised
   // memory may reach the matrix cores (their rows are independent, but a NaN pattern need not stay that way)
-  ok = hipMemsetAsync(pg->H, 0, G * mat * sizeof(double), pg->stream) == hipSuccess &&
-       hipMemsetAsync(pg->A, 0, G * mat * sizeof(double), pg->stream) == hipSuccess &&
-       hipStreamSynchronize(pg->stream) == hipSuccess &&
-       hipFuncSetAttribute((const void *)posegraph_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vio::kLdsBytes) == hipSuccess;
-  if (!ok) {
-    vio_posegraph_destroy(pg);
+  if (hipMemsetAsync(pg->H.p, 0, G * mat * sizeof(double), pg->stream) != hipSuccess ||
+      hipMemsetAsync(pg->A.p, 0, G * mat * sizeof(double), pg->stream) != hipSuccess || hipStreamSynchronize(pg->stream) != hipSuccess ||
+      hipFuncSetAttribute((const void *)posegraph_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vio::kLdsBytes) != hipSuccess) {
+    delete pg;
     return VIO_ENODEV;
   }
   *out = pg;
@@ -525,11 +499,6 @@ int vio_posegraph_get_device(const vio_posegraph_t *pg, int32_t *device) {
 void vio_posegraph_destroy(vio_posegraph_t *pg) {
   if (!pg) return;
   vio::DeviceScope scope(pg->device);
-  if (pg->stream) (void)hipStreamSynchronize(pg->stream), (void)hipStreamDestroy(pg->stream);
-  pg->hdr.release(), pg->col.release(), pg->ei.release(), pg->ej.release(), pg->ek.release(), pg->stats_i.release();
-  pg->node0.release(), pg->meas.release(), pg->xout.release(), pg->stats_d.release();
-  if (pg->H) (void)hipFree(pg->H);
-  if (pg->A) (void)hipFree(pg->A);
   delete pg;
 }
 
@@ -549,22 +518,22 @@ int vio_posegraph_optimize(vio_posegraph_t *pg, VioPoseGraph *graphs, int32_t n,
         return VIO_EINVAL;
       used[G.edge_i[e]] = used[G.edge_j[e]] = 1;
     }
-    int *col = pg->col.h + (size_t)g * NC;
-    double *node0 = pg->node0.h + (size_t)g * NC * 4;
+    int *col = pg->col.h.p + (size_t)g * NC;
+    double *node0 = pg->node0.h.p + (size_t)g * NC * 4;
     int nv = 0;
     for (int k = 0; k < G.n_nodes; k++) {
       col[k] = (used[k] && k != G.fixed_node) ? 4 * nv++ : -1;
       node0[4 * k] = G.ypr[3 * k], node0[4 * k + 1] = G.t[3 * k], node0[4 * k + 2] = G.t[3 * k + 1], node0[4 * k + 3] = G.t[3 * k + 2];
     }
-    int *hdr = pg->hdr.h + (size_t)g * kPgHdr;
+    int *hdr = pg->hdr.h.p + (size_t)g * kPgHdr;
     hdr[0] = G.n_nodes, hdr[1] = G.n_edges, hdr[2] = 4 * nv, hdr[3] = std::min<int>(max_iterations, kMaxTrace - 1);
     for (int e = 0; e < G.n_edges; e++) {
-      pg->ei.h[(size_t)g * EC + e] = G.edge_i[e], pg->ej.h[(size_t)g * EC + e] = G.edge_j[e], pg->ek.h[(size_t)g * EC + e] = G.edge_kind[e];
-      memcpy(pg->meas.h + ((size_t)g * EC + e) * 6, G.edge_meas + 6 * e, 48);
+      pg->ei.h.p[(size_t)g * EC + e] = G.edge_i[e], pg->ej.h.p[(size_t)g * EC + e] = G.edge_j[e], pg->ek.h.p[(size_t)g * EC + e] = G.edge_kind[e];
+      memcpy(pg->meas.h.p + ((size_t)g * EC + e) * 6, G.edge_meas + 6 * e, 48);
     }
   }
   hipStream_t st = pg->stream;
-#define UP(b, cnt) HIP_OK(hipMemcpyAsync((b).d, (b).h, (size_t)(cnt) * sizeof(*(b).h), hipMemcpyHostToDevice, st))
+#define UP(b, cnt) HIP_OK(hipMemcpyAsync((b).d.p, (b).h.p, (size_t)(cnt) * sizeof(*(b).h.p), hipMemcpyHostToDevice, st))
   UP(pg->hdr, (size_t)n * kPgHdr);
   UP(pg->col, (size_t)n * NC);
   UP(pg->node0, (size_t)n * NC * 4);
@@ -573,29 +542,29 @@ int vio_posegraph_optimize(vio_posegraph_t *pg, VioPoseGraph *graphs, int32_t n,
   UP(pg->ek, (size_t)n * EC);
   UP(pg->meas, (size_t)n * EC * 6);
 #undef UP
-  HIP_OK(hipMemsetAsync(pg->stats_d.d, 0, (size_t)n * kStatsDoubles * sizeof(double), st));
-  HIP_OK(hipMemsetAsync(pg->stats_i.d, 0, (size_t)n * kStatsInts * sizeof(int), st));
+  HIP_OK(hipMemsetAsync(pg->stats_d.d.p, 0, (size_t)n * kStatsDoubles * sizeof(double), st));
+  HIP_OK(hipMemsetAsync(pg->stats_i.d.p, 0, (size_t)n * kStatsInts * sizeof(int), st));
   PgPtrs P;
   P.ld = pg->ld, P.node_cap = NC, P.edge_cap = EC;
-  P.hdr = pg->hdr.d, P.col = pg->col.d, P.node0 = pg->node0.d, P.edge_i = pg->ei.d, P.edge_j = pg->ej.d, P.edge_kind = pg->ek.d;
-  P.meas = pg->meas.d, P.H = pg->H, P.A = pg->A, P.xout = pg->xout.d, P.stats_d = pg->stats_d.d, P.stats_i = pg->stats_i.d;
+  P.hdr = pg->hdr.d.p, P.col = pg->col.d.p, P.node0 = pg->node0.d.p, P.edge_i = pg->ei.d.p, P.edge_j = pg->ej.d.p, P.edge_kind = pg->ek.d.p;
+  P.meas = pg->meas.d.p, P.H = pg->H.p, P.A = pg->A.p, P.xout = pg->xout.d.p, P.stats_d = pg->stats_d.d.p, P.stats_i = pg->stats_i.d.p;
   hipLaunchKernelGGL(posegraph_kernel, dim3(n), dim3(kPgThreads), pg->lds_bytes, st, P);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(pg->xout.h, pg->xout.d, (size_t)n * pg->ld * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(pg->stats_d.h, pg->stats_d.d, (size_t)n * kStatsDoubles * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(pg->stats_i.h, pg->stats_i.d, (size_t)n * kStatsInts * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(pg->xout.h.p, pg->xout.d.p, (size_t)n * pg->ld * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(pg->stats_d.h.p, pg->stats_d.d.p, (size_t)n * kStatsDoubles * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(pg->stats_i.h.p, pg->stats_i.d.p, (size_t)n * kStatsInts * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   for (int g = 0; g < n; g++) {
     VioPoseGraph &G = graphs[g];
-    const int *col = pg->col.h + (size_t)g * NC;
-    const double *x = pg->xout.h + (size_t)g * pg->ld;
+    const int *col = pg->col.h.p + (size_t)g * NC;
+    const double *x = pg->xout.h.p + (size_t)g * pg->ld;
     for (int k = 0; k < G.n_nodes; k++)
       if (col[k] >= 0) G.ypr[3 * k] = x[col[k]], G.t[3 * k] = x[col[k] + 1], G.t[3 * k + 1] = x[col[k] + 2], G.t[3 * k + 2] = x[col[k] + 3];
     if (stats) {
       VioSolveStats &s = stats[g];
       memset(&s, 0, sizeof(s));
-      const double *sd = pg->stats_d.h + (size_t)g * kStatsDoubles;
-      const int *si = pg->stats_i.h + (size_t)g * kStatsInts;
+      const double *sd = pg->stats_d.h.p + (size_t)g * kStatsDoubles;
+      const int *si = pg->stats_i.h.p + (size_t)g * kStatsInts;
       s.initial_cost = sd[0], s.final_cost = sd[1];
       s.iterations = si[0], s.termination = si[1], s.num_successful_steps = si[2], s.num_unsuccessful_steps = si[3];
       for (int i = 0; i < s.iterations && i < VIO_MAX_TRACE && i < kMaxTrace; i++) {

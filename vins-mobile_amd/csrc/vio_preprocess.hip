@@ -186,30 +186,35 @@ struct vio_preprocess {
   int max_frames = 0, rows = 0, cols = 0;
   double clip_limit = 3.0;  // clahe->setClipLimit(3) ViewController.mm:436
   int tiles_x = 8, tiles_y = 8;  // cv::createCLAHE() default tileGridSize
-  uint8_t *d_src = nullptr, *d_gray = nullptr, *d_lut = nullptr, *d_out = nullptr;
-  uint8_t *h_in = nullptr, *h_out = nullptr;  // page-locked staging of the host-buffer entry point
+  vio::DevBuf<uint8_t> d_src, d_gray, d_lut, d_out;
+  vio::PinnedBuf<uint8_t> h_in, h_out;  // page-locked staging of the host-buffer entry point
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double ms_sum = 0;
   int launches = 0;
+  ~vio_preprocess() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
 
-PreGeom geometry(const vio_preprocess *p) {
+PreGeom geometry(int rows, int cols, int tiles_x, int tiles_y, double clip_limit) {
   PreGeom G;
-  G.rows = p->rows, G.cols = p->cols, G.tiles_x = p->tiles_x, G.tiles_y = p->tiles_y;
+  G.rows = rows, G.cols = cols, G.tiles_x = tiles_x, G.tiles_y = tiles_y;
   // an image that is not a multiple of the grid in BOTH directions is extended on the right by tiles_x - cols % tiles_x
   // and at the bottom by tiles_y - rows % tiles_y (a whole extra `tiles` in a direction that did divide: as published)
-  const bool fits = p->cols % p->tiles_x == 0 && p->rows % p->tiles_y == 0;
-  const int ext_c = fits ? p->cols : p->cols + (p->tiles_x - p->cols % p->tiles_x);
-  const int ext_r = fits ? p->rows : p->rows + (p->tiles_y - p->rows % p->tiles_y);
-  G.tw = ext_c / p->tiles_x, G.th = ext_r / p->tiles_y;
+  const bool fits = cols % tiles_x == 0 && rows % tiles_y == 0;
+  const int ext_c = fits ? cols : cols + (tiles_x - cols % tiles_x);
+  const int ext_r = fits ? rows : rows + (tiles_y - rows % tiles_y);
+  G.tw = ext_c / tiles_x, G.th = ext_r / tiles_y;
   const int area = G.tw * G.th;
   G.lut_scale = (float)(256 - 1) / area;
   G.clip = 0;
-  if (p->clip_limit > 0.0) {
-    G.clip = (int)(p->clip_limit * area / 256);
+  if (clip_limit > 0.0) {
+    G.clip = (int)(clip_limit * area / 256);
     if (G.clip < 1) G.clip = 1;
   }
   return G;
@@ -217,20 +222,20 @@ PreGeom geometry(const vio_preprocess *p) {
 
 int launch(vio_preprocess *p, const uint8_t *d_src, int channels, int n_frames, size_t frame_stride, int row_stride,
            uint8_t *d_out, size_t out_frame_stride, int out_row_stride, hipStream_t st) {
-  const PreGeom G = geometry(p);
+  const PreGeom G = geometry(p->rows, p->cols, p->tiles_x, p->tiles_y, p->clip_limit);
   const dim3 g1(G.tiles_x * G.tiles_y, n_frames), g2((G.rows + kBandRows - 1) / kBandRows, n_frames);
   (void)hipEventRecord(p->ev0, st);
   if (channels == 4)
-    hipLaunchKernelGGL(clahe_lut_kernel<4>, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray, p->d_lut, G);
+    hipLaunchKernelGGL(clahe_lut_kernel<4>, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray.p, p->d_lut.p, G);
   else
-    hipLaunchKernelGGL(clahe_lut_kernel<1>, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray, p->d_lut, G);
+    hipLaunchKernelGGL(clahe_lut_kernel<1>, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray.p, p->d_lut.p, G);
   const bool vec4 = G.cols % 4 == 0 && out_row_stride % 4 == 0 && out_frame_stride % 4 == 0 &&
                     (reinterpret_cast<uintptr_t>(d_out) & 3) == 0;
   if (vec4)
-    hipLaunchKernelGGL(clahe_apply_kernel<true>, g2, dim3(kThreads), 0, st, p->d_gray, p->d_lut, d_out, out_frame_stride,
+    hipLaunchKernelGGL(clahe_apply_kernel<true>, g2, dim3(kThreads), 0, st, p->d_gray.p, p->d_lut.p, d_out, out_frame_stride,
                        out_row_stride, G);
   else
-    hipLaunchKernelGGL(clahe_apply_kernel<false>, g2, dim3(kThreads), 0, st, p->d_gray, p->d_lut, d_out, out_frame_stride,
+    hipLaunchKernelGGL(clahe_apply_kernel<false>, g2, dim3(kThreads), 0, st, p->d_gray.p, p->d_lut.p, d_out, out_frame_stride,
                        out_row_stride, G);
   (void)hipEventRecord(p->ev1, st);
   return hipGetLastError() == hipSuccess ? VIO_OK : VIO_ENODEV;
@@ -247,28 +252,21 @@ extern "C" {
 
 int vio_preprocess_create(int32_t max_frames, int32_t rows, int32_t cols, vio_preprocess_t **out) {
   if (!out || max_frames < 1 || rows < 16 || cols < 16 || rows > 16384 || cols > 16384) return VIO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "vio_amd: no HIP device visible; the image pre-step has no CPU fallback\n");
-    return VIO_ENODEV;
-  }
+  if (!vio::device_ready("the image pre-step")) return VIO_ENODEV;
   vio_preprocess *p = new (std::nothrow) vio_preprocess();
-  if (p) p->device = vio::current_device();
   if (!p) return VIO_ENOMEM;
+  p->device = vio::current_device();
   p->max_frames = max_frames, p->rows = rows, p->cols = cols;
   const size_t px = (size_t)rows * cols;
-  bool ok = hipMalloc((void **)&p->d_src, px * 4 * max_frames) == hipSuccess &&
-            hipMalloc((void **)&p->d_gray, px * max_frames) == hipSuccess &&
-            hipMalloc((void **)&p->d_out, px * max_frames) == hipSuccess &&
-            hipMalloc((void **)&p->d_lut, (size_t)kMaxTiles * kMaxTiles * 256 * max_frames) == hipSuccess &&
-            hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreate(&p->ev0) == hipSuccess && hipEventCreate(&p->ev1) == hipSuccess;
-  if (!ok) {
-    vio_preprocess_destroy(p);
+  if (p->d_src.ensure(px * 4 * max_frames) != VIO_OK || p->d_gray.ensure(px * max_frames) != VIO_OK ||
+      p->d_out.ensure(px * max_frames) != VIO_OK || p->d_lut.ensure((size_t)kMaxTiles * kMaxTiles * 256 * max_frames) != VIO_OK ||
+      hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess ||
+      hipEventCreate(&p->ev1) != hipSuccess) {
+    delete p;
     return VIO_ENOMEM;
   }
   if (vio_preprocess_set_clahe(p, 3.0, 8, 8) != VIO_OK) {  // the reference's setting must fit the frame size
-    vio_preprocess_destroy(p);
+    delete p;
     return VIO_EINVAL;
   }
   *out = p;
@@ -278,23 +276,12 @@ int vio_preprocess_create(int32_t max_frames, int32_t rows, int32_t cols, vio_pr
 void vio_preprocess_destroy(vio_preprocess_t *p) {
   if (!p) return;
   vio::DeviceScope scope(p->device);
-  if (p->d_src) (void)hipFree(p->d_src);
-  if (p->d_gray) (void)hipFree(p->d_gray);
-  if (p->d_out) (void)hipFree(p->d_out);
-  if (p->d_lut) (void)hipFree(p->d_lut);
-  if (p->h_in) (void)hipHostFree(p->h_in);
-  if (p->h_out) (void)hipHostFree(p->h_out);
-  if (p->ev0) (void)hipEventDestroy(p->ev0);
-  if (p->ev1) (void)hipEventDestroy(p->ev1);
-  if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }
 
 int vio_preprocess_set_clahe(vio_preprocess_t *p, double clip_limit, int32_t tiles_x, int32_t tiles_y) {
   if (!p || tiles_x < 1 || tiles_y < 1 || tiles_x > kMaxTiles || tiles_y > kMaxTiles) return VIO_EINVAL;
-  vio_preprocess q = *p;
-  q.clip_limit = clip_limit, q.tiles_x = tiles_x, q.tiles_y = tiles_y;
-  const PreGeom G = geometry(&q);
+  const PreGeom G = geometry(p->rows, p->cols, tiles_x, tiles_y, clip_limit);
   // a band of kBandRows rows must not span more than 3 tile rows; the reflected extension must stay inside the image
   if (G.th < kBandRows || G.tw < 1 || G.th * tiles_y - p->rows >= p->rows || G.tw * tiles_x - p->cols >= p->cols) return VIO_EINVAL;
   p->clip_limit = clip_limit, p->tiles_x = tiles_x, p->tiles_y = tiles_y;
@@ -312,30 +299,29 @@ int vio_preprocess_run(vio_preprocess_t *p, const uint8_t *pixels, int32_t chann
   // caller memory is pageable: gather into / scatter from page-locked staging with the host pool, a few frames per chunk,
   // so that the DMA of one chunk overlaps the host copy of the next (a direct pageable copy runs at ~5 GB/s)
   const size_t N = (size_t)n_frames;
-  if (!p->h_in && hipHostMalloc((void **)&p->h_in, (size_t)p->max_frames * px * 4, hipHostMallocDefault) != hipSuccess) return VIO_ENOMEM;
-  if (!p->h_out && hipHostMalloc((void **)&p->h_out, (size_t)p->max_frames * px * 2, hipHostMallocDefault) != hipSuccess) return VIO_ENOMEM;
+  if (p->h_in.ensure((size_t)p->max_frames * px * 4) != VIO_OK || p->h_out.ensure((size_t)p->max_frames * px * 2) != VIO_OK) return VIO_ENOMEM;
   const size_t n_chunks = N >= 16 ? 8 : 1, per = (N + n_chunks - 1) / n_chunks;
   for (size_t c0 = 0; c0 < N; c0 += per) {
     const size_t c1 = std::min(N, c0 + per);
     vio::HostPool::get().parallel_for((int)(c1 - c0), [&](int i) {
       const size_t f = c0 + i;
       const uint8_t *src = pixels + f * (size_t)p->rows * stride;
-      uint8_t *dst = p->h_in + f * fb;
+      uint8_t *dst = p->h_in.p + f * fb;
       if ((size_t)stride == row_bytes) memcpy(dst, src, fb);
       else
         for (int r = 0; r < p->rows; r++) memcpy(dst + (size_t)r * row_bytes, src + (size_t)r * stride, row_bytes);
     });
-    if (hipMemcpyAsync(p->d_src + c0 * fb, p->h_in + c0 * fb, (c1 - c0) * fb, hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV;
+    if (hipMemcpyAsync(p->d_src.p + c0 * fb, p->h_in.p + c0 * fb, (c1 - c0) * fb, hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV;
   }
-  int rc = launch(p, p->d_src, channels, n_frames, fb, (int)row_bytes, p->d_out, px, p->cols, st);
+  int rc = launch(p, p->d_src.p, channels, n_frames, fb, (int)row_bytes, p->d_out.p, px, p->cols, st);
   if (rc != VIO_OK) return rc;
-  if (hipMemcpyAsync(p->h_out, p->d_out, px * N, hipMemcpyDeviceToHost, st) != hipSuccess) return VIO_ENODEV;
-  if (gray_out && hipMemcpyAsync(p->h_out + (size_t)p->max_frames * px, p->d_gray, px * N, hipMemcpyDeviceToHost, st) != hipSuccess)
+  if (hipMemcpyAsync(p->h_out.p, p->d_out.p, px * N, hipMemcpyDeviceToHost, st) != hipSuccess) return VIO_ENODEV;
+  if (gray_out && hipMemcpyAsync(p->h_out.p + (size_t)p->max_frames * px, p->d_gray.p, px * N, hipMemcpyDeviceToHost, st) != hipSuccess)
     return VIO_ENODEV;
   if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
   vio::HostPool::get().parallel_for(n_frames, [&](int f) {
-    memcpy(equalized_out + (size_t)f * px, p->h_out + (size_t)f * px, px);
-    if (gray_out) memcpy(gray_out + (size_t)f * px, p->h_out + ((size_t)p->max_frames + f) * px, px);
+    memcpy(equalized_out + (size_t)f * px, p->h_out.p + (size_t)f * px, px);
+    if (gray_out) memcpy(gray_out + (size_t)f * px, p->h_out.p + ((size_t)p->max_frames + f) * px, px);
   });
   account(p);
   return VIO_OK;

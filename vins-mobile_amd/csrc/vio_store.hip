@@ -1,6 +1,7 @@
 // vio_store.hip — kernels of the device-resident landmark store (store_core.h): one workgroup per sequence slot.
 // Built with -ffp-contract=off: the passes give the bits of the host-side list (vio_window.cpp).
 #include "vio_store.h"
+#include "vio_device.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -168,22 +169,13 @@ static int raise_lds(const void *fn, size_t lds) {
   return VIO_OK;
 }
 
-#define STORE_HIP_OK(expr)                                                                                      \
-  do {                                                                                                          \
-    hipError_t e_ = (expr);                                                                                     \
-    if (e_ != hipSuccess) {                                                                                     \
-      fprintf(stderr, "vio_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
-      return VIO_ENODEV;                                                                                        \
-    }                                                                                                           \
-  } while (0)
-
 int store_launch_imu(const StoreDev &S, hipStream_t stream) {
   if (S.n_imu_jobs <= 0) return VIO_OK;
   const size_t lds = lds_block(4 * preint::kLdsDoubles * sizeof(double));
   const int rc = raise_lds((const void *)preint_jobs_kernel, lds);
   if (rc != VIO_OK) return rc;
   hipLaunchKernelGGL(preint_jobs_kernel, dim3((S.n_imu_jobs + 3) / 4), dim3(256), lds, stream, S);
-  STORE_HIP_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   return VIO_OK;
 }
 
@@ -192,7 +184,7 @@ int store_launch_ingest(const StoreDev &S, hipStream_t stream) {
   const int rc = raise_lds((const void *)store_ingest_kernel, lds);
   if (rc != VIO_OK) return rc;
   hipLaunchKernelGGL(store_ingest_kernel, dim3(S.n_slots), dim3(st::kThreads), lds, stream, S);
-  STORE_HIP_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   return VIO_OK;
 }
 
@@ -201,7 +193,7 @@ int store_launch_pack(const StoreDev &S, const BatchPtrs &B, int chunk, hipStrea
   const int rc = raise_lds((const void *)store_pack_kernel, lds);
   if (rc != VIO_OK) return rc;
   hipLaunchKernelGGL(store_pack_kernel, dim3(S.n_slots), dim3(st::kThreads), lds, stream, S, B, chunk);
-  STORE_HIP_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   return VIO_OK;
 }
 
@@ -210,7 +202,7 @@ int store_launch_finish(const StoreDev &S, const BatchPtrs &B, hipStream_t strea
   const int rc = raise_lds((const void *)store_finish_kernel, lds);
   if (rc != VIO_OK) return rc;
   hipLaunchKernelGGL(store_finish_kernel, dim3(S.n_slots), dim3(st::kThreads), lds, stream, S, B);
-  STORE_HIP_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   return VIO_OK;
 }
 
