@@ -3,5 +3,5 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 for v in "$@"; do
   cp vins-mobile_amd/csrc/$v vins-mobile_amd/csrc/libvio_amd.so
-  echo "== $v: $(python tools/time_backend.py --path=single 1 512 2>&1 | grep "stage\|path=" | tr ',' '\n' | grep "p_gram\|p_fact\|total=\|kernel" | cut -c1-60 | tr '\n' ' ')"
+  echo "== $v: $(python tools/time_backend.py 1 512 2>&1 | grep "stage\|path=" | tr ',' '\n' | grep "p_gram\|p_fact\|total=\|kernel" | cut -c1-60 | tr '\n' ' ')"
 done

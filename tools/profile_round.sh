@@ -53,7 +53,7 @@ python tools/rocpd_timeline.py $(db kt_res) 24 >> $O/kernel_trace_resident_estim
   python tools/estimator_dataset.py /tmp/est.bin 8 60 > /dev/null 2>&1
   for cfg in "256 1" "512 1" "256 2" "512 2"; do set -- $cfg; echo "== estimator_throughput (C++ driver): $1 sequences x $2 estimator objects"; /tmp/estimator_throughput /tmp/est.bin $1 $2 2>&1 | tail -1; done
   for n in 256 512; do echo "== time_pipeline.py $n sequences, asynchronous submit"; python tools/time_pipeline.py $n 30 2 1 2>&1 | tail -1; done ) > $O/estimator_paths.txt 2>&1
-python tools/time_backend.py --path=single 1 256 512 1024 > $O/stage_cycles.txt 2>&1
+python tools/time_backend.py 1 256 512 1024 > $O/stage_cycles.txt 2>&1
 VIO_AMD_PROF_TID=64 python tools/time_backend.py 1 2>&1 | grep "stage cycles" | sed "s/^/clock on a panel wave: /" >> $O/stage_cycles.txt
 $R/tools/microbench/bin/band_bench > $O/microbench.txt 2>&1
 $R/tools/microbench/bin/mfma_share >> $O/microbench.txt 2>&1

@@ -11,5 +11,5 @@ for a in "$@"; do
   fi
   if [ "$a" = "large" ]; then python tools/time_large.py 2>&1 | grep "kernel" ; fi
 done
-python tools/time_backend.py --path=single 1 8 256 512 1024 2>&1 | grep "path=\|stage" > $O/time_single.txt
+python tools/time_backend.py 1 8 256 512 1024 2>&1 | grep "path=\|stage" > $O/time_single.txt
 cat $O/time_single.txt | cut -c1-1200

@@ -14,12 +14,7 @@ abi, synth, backend = pkg.abi, pkg.synth, pkg.backend
 
 
 def main():
-    path = "single"  # (the launch-sequence path of rounds 4-5 left the library in round 6; the flag is still accepted)
-    prof_batches = [1]
-    for a in sys.argv[1:]:
-        if a.startswith("--prof-batch="):  # stage clock of window 0 (and the last one) with that many windows in the launch
-            prof_batches = [int(x) for x in a.split("=")[1].split(",")]
-    args = [a for a in sys.argv[1:] if a != "--no-prior" and not a.startswith("--path=") and not a.startswith("--prof-batch=")]
+    args = [a for a in sys.argv[1:] if a != "--no-prior"]
     batches = [int(x) for x in args] or [1, 64, 256, 512, 1024]
     cfg = abi.default_config()
     pre = lambda *a: backend.preintegrate(cfg, *a)
@@ -29,23 +24,21 @@ def main():
         sys.path.insert(0, ROOT)
         import bench
         uniq = bench.steady_state_windows(cfg, pkg, pre, [42 + i for i in range(8)])
-    solver = backend.WindowSolver(cfg, max_batch=max(batches + prof_batches))
-    for pb in prof_batches:
-        solver.set_profile(True)
-        ws = [uniq[i % len(uniq)].copy() for i in range(pb)]
-        solver.upload(ws)
-        solver.launch()
-        solver.sync()
-        solver.kernel_ms()
-        solver.launch()
-        solver.sync()
-        pms, _ = solver.kernel_ms()
-        print("profiling launch of %d windows: kernel %.3f ms" % (pb, pms))
-        for wi in sorted({0, pb - 1}):
-            cyc = solver.stage_cycles(wi)
-            tot = max(1, cyc["total"])
-            print("stage cycles (window %d of %d): " % (wi, pb) + ", ".join("%s=%d(%.1f%%)" % (k, c, 100.0 * c / tot) for k, c in cyc.items()))
-        solver.set_profile(False)
+    solver = backend.WindowSolver(cfg, max_batch=max(batches + [1]))
+    # stage clock of one window launched alone
+    solver.set_profile(True)
+    solver.upload([uniq[0].copy()])
+    solver.launch()
+    solver.sync()
+    solver.kernel_ms()
+    solver.launch()
+    solver.sync()
+    pms, _ = solver.kernel_ms()
+    print("profiling launch of 1 windows: kernel %.3f ms" % pms)
+    cyc = solver.stage_cycles(0)
+    tot = max(1, cyc["total"])
+    print("stage cycles (window 0 of 1): " + ", ".join("%s=%d(%.1f%%)" % (k, c, 100.0 * c / tot) for k, c in cyc.items()))
+    solver.set_profile(False)
     for B in batches:
         ws = [uniq[i % len(uniq)].copy() for i in range(B)]
         solver.upload(ws)
@@ -60,7 +53,8 @@ def main():
         wall = (time.time() - t0) / reps
         ms, n = solver.kernel_ms()
         st = solver.download(ws)
-        print("path=%s " % path + "B=%5d kernel %.3f ms (wall %.3f ms) -> %.0f solves/s, %.1f us/solve/CU-slot; iters %s final cost %.4f" % (
+        # ("path=single": the label the A/B scripts under tools/ look for)
+        print("path=single B=%5d kernel %.3f ms (wall %.3f ms) -> %.0f solves/s, %.1f us/solve/CU-slot; iters %s final cost %.4f" % (
             B, ms, wall * 1e3, B / (ms * 1e-3), ms * 1e3 / max(1, -(-B // 256)), st[0]["iterations"], st[0]["final_cost"]))
 
 

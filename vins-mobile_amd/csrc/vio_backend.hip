@@ -47,20 +47,20 @@ __global__ __launch_bounds__(1024) void poison_lds_kernel(int n_doubles) {
 
 // The instantiations of the window kernel, one translation unit each (vio_wk_unit.hip, csrc/Makefile).
 #define VIO_WK_DECL(v) vio_wk::VariantFns vio_wk_variant_##v##_0(); vio_wk::VariantFns vio_wk_variant_##v##_1();
-VIO_WK_DECL(0) VIO_WK_DECL(1) VIO_WK_DECL(2) VIO_WK_DECL(3) VIO_WK_DECL(4) VIO_WK_DECL(5)
+VIO_WK_DECL(0) VIO_WK_DECL(1) VIO_WK_DECL(2) VIO_WK_DECL(3) VIO_WK_DECL(4)
 #undef VIO_WK_DECL
 const vio_wk::VariantFns &vio_wk::variant(int v, bool prof) {
   static const VariantFns tab[kVariants][2] = {{vio_wk_variant_0_0(), vio_wk_variant_0_1()}, {vio_wk_variant_1_0(), vio_wk_variant_1_1()},
                                                {vio_wk_variant_2_0(), vio_wk_variant_2_1()}, {vio_wk_variant_3_0(), vio_wk_variant_3_1()},
-                                               {vio_wk_variant_4_0(), vio_wk_variant_4_1()}, {vio_wk_variant_5_0(), vio_wk_variant_5_1()}};
+                                               {vio_wk_variant_4_0(), vio_wk_variant_4_1()}};
   return tab[v][prof ? 1 : 0];
 }
 
 static double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-static bool host_timing() {
-  static const bool on = getenv("VIO_AMD_HOST_TIMING") && getenv("VIO_AMD_HOST_TIMING")[0] == '1';
+static bool poison() {
+  static const bool on = vio::env_flag("VIO_AMD_POISON");
   return on;
 }
 
@@ -89,7 +89,6 @@ struct vio_backend {
   HostVec<int> h_order;
   bool profile = false;
   size_t lds_bytes = 0;
-  int threads_lds = kThreadsLds;
   int n_cus = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   bool static_w = false;  // every window of the LDS launch has W = vio_wk::kStaticW frames and the batch has that window's capacities
   bool coop_ok = false;  // the global-matrix windows of the uploaded batch may run as cooperative windows (host-packed, no bucket across chunks)
@@ -223,20 +222,16 @@ static int plan_layout(vio_backend *be, BatchDims &d, int n, const int *nfeat, i
   // variant in one launch -- with half a CU's LDS per workgroup whenever that is enough, so that two windows share a
   // CU --, everything else the global-matrix variant in a second one. (Decided before packing: the staging chunk the
   // buckets are aligned to depends on the layout.)
-  static const int threads_lds = (getenv("VIO_AMD_WINDOW_THREADS") && atoi(getenv("VIO_AMD_WINDOW_THREADS")) == 512) ? kThreadsGlb : kThreadsLds;
-  be->threads_lds = threads_lds;
   auto need_lds = [&](BatchDims dd, int asp) {
     dd.lds_asp = asp;
     size_t se = 0, tail = 0;
-    const size_t bs = carve_work<ldsd>(dd, true, threads_lds, nullptr, nullptr, nullptr, nullptr, &se, &tail);
+    const size_t bs = carve_work<ldsd>(dd, true, kThreadsLds, nullptr, nullptr, nullptr, nullptr, &se, &tail);
     const size_t bm = (se + tail) * sizeof(double) + carve_marg<ldsd>(dd, true, nullptr, nullptr, nullptr, 0);
     // the marginalization phase additionally wants >= 64 staging slots behind its matrix
     return std::max(bs, bm + 64 * kMargSlot * sizeof(double));
   };
-  // (eligibility: the lean layout, IMU coupling in global memory, inside one CU; the 512-thread build of the LDS variant
-  // -- an experiment switch -- only exists with the coupling in LDS)
-  const int lean_asp = threads_lds == kThreadsLds ? 0 : 1;
-  auto fits_lds = [&](const BatchDims &dd) { return pose_jp(dd) <= 16 * kPanelTiles && need_lds(dd, lean_asp) <= kLdsLimit; };
+  // (eligibility: the lean layout, IMU coupling in global memory, inside one CU)
+  auto fits_lds = [&](const BatchDims &dd) { return pose_jp(dd) <= 16 * kPanelTiles && need_lds(dd, 0) <= kLdsLimit; };
   std::vector<int> cand;
   order.clear();
   if (active) cand = *active;
@@ -259,23 +254,17 @@ static int plan_layout(vio_backend *be, BatchDims &d, int n, const int *nfeat, i
   // Two workgroups per CU (half its LDS each) beat everything else; inside that, the IMU speed-bias x pose coupling is
   // better off in LDS. Windows with many landmarks give its 14 KB up (global scratch, L2-resident) to stay two per CU.
   // The marginalization phase stages Jacobian rows in whatever LDS is left behind its matrix.
-  static const bool one_per_cu = getenv("VIO_AMD_WINDOW_ONE_PER_CU") && getenv("VIO_AMD_WINDOW_ONE_PER_CU")[0] == '1';
-  static const int force_asp = getenv("VIO_AMD_LDS_ASP") ? atoi(getenv("VIO_AMD_LDS_ASP")) : -1;
   be->lds_bytes = kLdsLimit;
   if (n_lds > 0) {
-    const size_t fat = need_lds(dl, 1), lean = need_lds(dl, lean_asp);
+    const size_t fat = need_lds(dl, 1), lean = need_lds(dl, 0);
     // (the lean layout costs a window ~10 % of its latency -- a few more round trips to L2 per Gauss-Newton step --: it only
     // pays when the launch has enough windows to fill the second workgroup slot of the CUs. Measured with closed-loop
     // windows of ~190 landmarks: 2 x 128 windows are faster with the fat layout on whole CUs, 2 x 256 windows take 7.3
     // instead of 9.4 ms per frame with the lean one.)
     const bool crowded = n_lds * std::max(1, be->peers) > be->n_cus;  // (with the other contexts' launches: more windows than CUs)
-    if (!one_per_cu && fat <= kLdsHalf) dl.lds_asp = 1, be->lds_bytes = kLdsHalf;
-    else if (!one_per_cu && crowded && lean <= kLdsHalf) dl.lds_asp = lean_asp, be->lds_bytes = kLdsHalf;
-    else dl.lds_asp = fat <= kLdsLimit ? 1 : lean_asp;
-    if ((force_asp == 0 && lean_asp == 0) || (force_asp == 1 && fat <= kLdsLimit)) {
-      dl.lds_asp = force_asp;
-      be->lds_bytes = (!one_per_cu && need_lds(dl, force_asp) <= kLdsHalf) ? kLdsHalf : kLdsLimit;
-    }
+    if (fat <= kLdsHalf) dl.lds_asp = 1, be->lds_bytes = kLdsHalf;
+    else if (crowded && lean <= kLdsHalf) dl.lds_asp = 0, be->lds_bytes = kLdsHalf;
+    else dl.lds_asp = fat <= kLdsLimit ? 1 : 0;
   }
   be->d_lds = dl;
   if (be->n_glb > 0) {
@@ -296,12 +285,11 @@ static int plan_layout(vio_backend *be, BatchDims &d, int n, const int *nfeat, i
 
 // May the LDS launch of this batch take the instantiations with the window size at compile time (vio_window_variants.h)? Every
 // window has W = kStaticW frames, no window carries a relocalization pose (one more 6-dof block: other strides, another LDS
-// layout) and the prior capacity is what marginalize() can leave at that size. VIO_AMD_STATIC_W=0 keeps the run-time variants (A/B).
-static bool static_launch_ok(const vio_backend *be, const BatchDims &d, bool all_windows_static_w) {
-  static const bool off = getenv("VIO_AMD_STATIC_W") && getenv("VIO_AMD_STATIC_W")[0] == '0';
+// layout) and the prior capacity is what marginalize() can leave at that size.
+static bool static_launch_ok(const BatchDims &d, bool all_windows_static_w) {
   constexpr int W = vio_wk::kStaticW;
-  return !off && all_windows_static_w && be->threads_lds == kThreadsLds && d.Wcap == W && d.Pcap == W + 1 && d.nblk_cap == W + 1 &&
-         d.n6cap == 6 * (W + 2) && d.Ncap == 6 * W + 15 && d.pair_cap == (W + 2) * (W + 3) / 2;
+  return all_windows_static_w && d.Wcap == W && d.Pcap == W + 1 && d.nblk_cap == W + 1 && d.n6cap == 6 * (W + 2) &&
+         d.Ncap == 6 * W + 15 && d.pair_cap == (W + 2) * (W + 3) / 2;
 }
 
 // Work and output buffers of a batch of N windows with dims d (sticky: they only grow).
@@ -348,8 +336,8 @@ static int bind_work_buffers(vio_backend *be, const BatchDims &d, const BatchStr
   MP.s_ints = m_ints, MP.s_x0 = 9 * kMaxPriorBlocks, MP.s_J = (size_t)d.Ncap * d.Ncap, MP.s_r = d.Ncap;
   MP.s_scratch = m_scr;
   MP.prof = nullptr;
-  MP.prof_tid = getenv("VIO_AMD_PROF_TID") ? atoi(getenv("VIO_AMD_PROF_TID")) : 0;
-  MP.wrot = getenv("VIO_AMD_WAVE_ROT") ? atoi(getenv("VIO_AMD_WAVE_ROT")) : -1;
+  MP.prof_tid = vio::env_int("VIO_AMD_PROF_TID", 0);
+  MP.wrot = vio::env_int("VIO_AMD_WAVE_ROT", -1);
   if (be->profile) {
     int rcp = be->d_prof.ensure(N * ST_COUNT);
     if (rcp != VIO_OK) return rcp;
@@ -438,20 +426,18 @@ static int backend_upload_impl(vio_backend_t *be, const VioWindow *windows, int3
   {
     bool all_w = true;
     for (int b = 0; b < n; b++) all_w = all_w && windows[b].window_size == vio_wk::kStaticW;
-    be->static_w = static_launch_ok(be, d, all_w);
+    be->static_w = static_launch_ok(d, all_w);
   }
-  const int threads_lds = be->threads_lds, n_lds = be->n_lds;
+  const int n_lds = be->n_lds;
   const BatchDims dl = be->d_lds;
-  (void)n_lds;
-  static const bool poison_staging = getenv("VIO_AMD_POISON") && getenv("VIO_AMD_POISON")[0] == '1';
   // the previous upload's copy may still be reading the staging arena (uploads do not wait for their own transfer)
   HIP_OK(hipStreamSynchronize(be->stream));
   const double t0 = now_ms();
-  be->hb.resize(d, n, poison_staging);
+  be->hb.resize(d, n, poison());
   {
     std::vector<int> rcs(n, VIO_OK);
     const bool lds_shape = pose_jp(d) <= 16 * kPanelTiles;
-    const int chunk = stage_chunk_slots(dl, lds_shape, lds_shape ? threads_lds : kThreadsGlb);
+    const int chunk = stage_chunk_slots(dl, lds_shape, lds_shape ? kThreadsLds : kThreadsGlb);
     // (windows of the global-matrix launch have their own layout and chunk; a cooperative launch needs every bucket inside a chunk)
     const int chunk_glb = be->n_glb > 0 ? stage_chunk_slots(be->d_glb, false, kThreadsGlb) : 0;
     std::vector<char> glb(n, 0), strad(n, 0);
@@ -545,8 +531,7 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
   hipStream_t st = stream ? (hipStream_t)stream : be->stream;
   if (st != be->stream && be->upload_done) HIP_OK(hipStreamWaitEvent(st, be->upload_done, 0));
   be->last_stream = st;
-  static const bool poison = getenv("VIO_AMD_POISON") && getenv("VIO_AMD_POISON")[0] == '1';
-  if (poison) {
+  if (poison()) {
     HIP_OK(hipMemsetAsync(be->d_scratch.p, 0xff, be->d_scratch.n * sizeof(double), st));
     HIP_OK(hipMemsetAsync(be->d_hm.p, 0xff, be->d_hm.n * sizeof(double), st));
     HIP_OK(hipMemsetAsync(be->d_out_pose.p, 0xff, be->d_out_pose.n * sizeof(double), st));
@@ -561,8 +546,8 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
   if (be->n_lds > 0) {
     BatchPtrs Bl = be->B;
     Bl.d = be->d_lds, Bl.order = be->d_order.p;
-    int variant = be->threads_lds == kThreadsLds ? (be->d_lds.lds_asp ? 0 : 1) : 2;
-    if (variant < 2 && be->static_w) variant += 4;  // (every window of the launch has the compile-time window size: vio_window_variants.h)
+    int variant = be->d_lds.lds_asp ? 0 : 1;
+    if (be->static_w) variant += 3;  // (every window of the launch has the compile-time window size: vio_window_variants.h)
     vio_wk::variant(variant, be->MP.prof != nullptr).launch(be->n_lds, be->lds_bytes, st, Bl, be->MP);
   }
   if (be->n_glb > 0) {
@@ -573,8 +558,7 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
     // forces the width (1: off). The profiling clock follows one workgroup per window: off while it runs.
     int coop = 1;
     if (be->coop_ok && !be->MP.prof && be->lds_bytes_glb > kLdsHalf) {
-      const char *fe_ = getenv("VIO_AMD_COOP");  // (read per launch: tests switch it within one process)
-      const int forced = fe_ ? atoi(fe_) : 0;
+      const int forced = vio::env_int("VIO_AMD_COOP", 0);  // (read per launch: tests switch it within one process)
       const int cus = be->n_cus / std::max(1, be->peers);
       const int groups = (be->n_glb + 7) / 8;  // (grids are padded to whole groups of eight windows: the XCD mapping)
       // (measured, profiles/r05_*_large_windows.txt: four members pay at W = 30 up to a full chip, at W = 20 only while half the
@@ -586,7 +570,7 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
         // every workgroup of the launch has to be resident at once (the members of a window wait for each other): ask the runtime
         // what the device holds of this kernel at this LDS size instead of trusting the arithmetic above alone
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vio_wk::variant(3, false).fn,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vio_wk::variant(2, false).fn,
                                                          kThreadsGlb, be->lds_bytes_glb) != hipSuccess ||
             (long long)per_cu * cus < (long long)groups * 8 * coop)
           coop = 1;
@@ -594,9 +578,9 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
     }
     Bg.coop = coop, Bg.n_launch = be->n_glb;
     {  // test hooks of the timeout path (tests/test_backend_gpu.py): read per launch
-      const char *sp_ = getenv("VIO_AMD_COOP_SPIN"), *ft_ = getenv("VIO_AMD_COOP_FAULT");
-      Bg.coop_spin = sp_ && atoi(sp_) > 0 ? (unsigned)atoi(sp_) : vio::kCoopSpinLimit;
-      Bg.coop_fault = ft_ && ft_[0] == '1' ? 1 : 0;
+      const int spin = vio::env_int("VIO_AMD_COOP_SPIN", 0);
+      Bg.coop_spin = spin > 0 ? (unsigned)spin : vio::kCoopSpinLimit;
+      Bg.coop_fault = vio::env_flag("VIO_AMD_COOP_FAULT") ? 1 : 0;
     }
     int grid = be->n_glb;
     if (coop > 1) {
@@ -604,7 +588,7 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
       // flag words of every window of the batch: command, completions, error (the first 32 bytes of the cooperative area)
       HIP_OK(hipMemset2DAsync(be->d_scratch.p + be->B.s.s_coop, be->B.s.scratch * sizeof(double), 0, 32, (size_t)be->B.n, st));
     }
-    vio_wk::variant(3, be->MP.prof != nullptr).launch(grid, be->lds_bytes_glb, st, Bg, be->MP);
+    vio_wk::variant(2, be->MP.prof != nullptr).launch(grid, be->lds_bytes_glb, st, Bg, be->MP);
   }
   HIP_OK(hipGetLastError());
   return be->timer.end(st);

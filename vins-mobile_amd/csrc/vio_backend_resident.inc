@@ -69,7 +69,7 @@ static vio::StoreDev resident_store_dev(vio_backend *be) {
   S.imu_jobs = r->dp<double>(r->o_jobs), S.imu_samples = r->dp<double>(r->o_samples), S.n_imu_jobs = r->n_jobs.load();
   S.pre_side = r->pre_side.p, S.noise = r->consts.p + 19;
   S.prof = nullptr;
-  static const bool prof = getenv("VIO_AMD_STORE_PROF") && getenv("VIO_AMD_STORE_PROF")[0] == '1';
+  static const bool prof = vio::env_flag("VIO_AMD_STORE_PROF");
   if (prof && r->prof.ensure(32) == VIO_OK) S.prof = r->prof.p;
   return S;
 }
@@ -535,7 +535,7 @@ int vio_backend_resident_launch(vio_backend_t *be) {
     std::vector<int> order;
     int rc = plan_layout(be, d, n, nfeat.data(), Fmax, order, &r->active_list);
     if (rc != VIO_OK) return rc;
-    be->static_w = static_launch_ok(be, d, r->W == vio_wk::kStaticW);  // (every resident window has the store's window size)
+    be->static_w = static_launch_ok(d, r->W == vio_wk::kStaticW);  // (every resident window has the store's window size)
     const BatchDims dl = be->d_lds;
     rc = ensure_work_buffers(be, d, s, n);
     if (rc != VIO_OK) return rc;
@@ -555,7 +555,7 @@ int vio_backend_resident_launch(vio_backend_t *be) {
     rc = bind_work_buffers(be, d, s, n);
     if (rc != VIO_OK) return rc;
     const bool lds_shape = pose_jp(d) <= 16 * kPanelTiles;
-    const int chunk = stage_chunk_slots(dl, lds_shape, lds_shape ? be->threads_lds : kThreadsGlb);
+    const int chunk = stage_chunk_slots(dl, lds_shape, lds_shape ? kThreadsLds : kThreadsGlb);
     const vio::StoreDev S = resident_store_dev(be);
     rc = vio::store_launch_pack(S, B, chunk, st);
     if (rc != VIO_OK) return rc;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "vio_amd.h"
+#include "vio_env.h"
 
 // A failed HIP call ends the ABI entry with VIO_ENODEV (and says which call on stderr).
 #define HIP_OK(expr)                                                                       \
@@ -71,8 +72,7 @@ inline bool host_isa_ok() {
 inline bool single_hip_runtime() {
   static const int n = [] {
     const std::vector<std::string> r = hip_runtimes();
-    const char *allow = getenv("VIO_AMD_ALLOW_TWO_RUNTIMES");
-    if (r.size() > 1 && allow && allow[0] == '1') return 1;  // (the caller knows what it is doing)
+    if (r.size() > 1 && env_flag("VIO_AMD_ALLOW_TWO_RUNTIMES")) return 1;  // (the caller knows what it is doing)
     if (r.size() > 1) {
       fprintf(stderr, "vio_amd: %zu different HIP runtimes are mapped into this process:\n", r.size());
       for (const std::string &p : r) fprintf(stderr, "vio_amd:   %s\n", p.c_str());
@@ -108,10 +108,7 @@ struct OwnedBuf {
   ~OwnedBuf() { release(); }
   int ensure(size_t count) {
     if (count <= n && p) return VIO_OK;
-    {
-      static const bool log = getenv("VIO_AMD_HOST_TIMING") && getenv("VIO_AMD_HOST_TIMING")[0] == '1';
-      if (log) fprintf(stderr, "vio_amd: device buffer grows %zu -> %zu elements of %zu bytes\n", n, count, sizeof(T));
-    }
+    if (host_timing()) fprintf(stderr, "vio_amd: device buffer grows %zu -> %zu elements of %zu bytes\n", n, count, sizeof(T));
     release();
     if (Alloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
       p = nullptr;

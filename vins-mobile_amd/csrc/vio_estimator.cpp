@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "vio_amd.h"
+#include "vio_env.h"
 #include "vio_resident.h"
 #include "vio_math.h"
 #include "vio_initial.h"
@@ -124,15 +125,15 @@ struct vio_estimator {
   bool init_relpose_fit = false;  // relativePose by the all-correspondence fit instead of the reference's five-point RANSAC
   // the marginalization prior of every sequence stays in device memory between launches; only its header comes back
   // (VIO_AMD_HOST_PRIORS=1: carry it through host memory instead, ~45 KB per sequence and direction)
-  bool resident_priors = !(getenv("VIO_AMD_HOST_PRIORS") && getenv("VIO_AMD_HOST_PRIORS")[0] == '1');
+  bool resident_priors = !vio::env_flag("VIO_AMD_HOST_PRIORS");
   // Sequences in the NON_LINEAR state keep their landmark list on the device and have their windows assembled there
   // (on by default; vio_estimator_set_resident / VIO_AMD_RESIDENT=0 turn it off); needs the device-resident priors.
-  bool resident = !(getenv("VIO_AMD_RESIDENT") && getenv("VIO_AMD_RESIDENT")[0] == '0');
+  bool resident = !vio::env_flag("VIO_AMD_RESIDENT", '0');
   int res_list_cap = 0, res_obs_cap = 0;
   // VIO_AMD_RESIDENT_IMU=1: the IMU samples of their intervals travel instead of the integrated blocks and a kernel integrates
   // them (preint_core.h: the host's bits). Off by default: measured at 512 sequences the kernel takes what the host pool saves
   // (124 us against ~120 us of host::propagate on 16 AVX2 threads) and sits on the frame's critical path.
-  bool resident_imu = getenv("VIO_AMD_RESIDENT_IMU") && getenv("VIO_AMD_RESIDENT_IMU")[0] == '1';
+  bool resident_imu = vio::env_flag("VIO_AMD_RESIDENT_IMU");
   std::vector<int> res_rc;  // per sequence: outcome of staging in the current call
   std::vector<int> solving;  // sequences of the current launch
   std::vector<VioWindow> staged;   // per sequence, built in parallel, compacted into `windows`
@@ -686,7 +687,7 @@ void regroup(vio_estimator *e) {
   for (int g = 0; g < vio_estimator::kMaxGroups; g++)
     if (e->be[g]) return;  // (contexts exist: slots and prior stores are bound to the grouping)
   const int n_seq = e->n_seq;
-  {  // VIO_AMD_EST_GROUPS overrides the number of solve groups (1 = one launch for all sequences)
+  {
     // Two groups by default: more groups only pay while every group's stream has a hardware queue of its own (HIP maps
     // streams onto 4 queues by default; in a process that holds other streams — a torch process, say — four groups
     // alias, two of the kernels serialize and the frame gets slower than with one group: 36 k instead of 48 k solves/s).
@@ -695,12 +696,6 @@ void regroup(vio_estimator *e) {
     // Resident sequences leave the host little to overlap with the kernel, and one launch of all windows fills the CUs'
     // second workgroup slots by itself (measured, 512 sequences: 4.9 ms per frame with one group, 6.7 ms with two)
     if (e->resident && e->resident_priors) ng = 1;
-    if (const char *env = getenv("VIO_AMD_EST_GROUPS")) {
-      char *end = nullptr;
-      const long val = strtol(env, &end, 10);
-      if (end == env || *end != '\0' || val < 1) fprintf(stderr, "vio_amd: VIO_AMD_EST_GROUPS=\"%s\" is not a positive number, ignored\n", env);
-      else ng = (int)std::min<long>(val, vio_estimator::kMaxGroups);
-    }
     ng = std::max(1, std::min(std::min(ng, (int)vio_estimator::kMaxGroups), n_seq));
     e->group_size = (n_seq + ng - 1) / ng;
     e->n_groups = (n_seq + e->group_size - 1) / e->group_size;
@@ -1197,12 +1192,7 @@ int vio_estimator_process_images(vio_estimator_t *e, const VioObs *obs, const in
     if (ng == 0 || rc != VIO_OK) continue;
     if (!e->be[g]) {
       rc = vio_backend_create(&e->cfg, e->group_size, &e->be[g]);
-      if (rc == VIO_OK) {
-        // (VIO_AMD_EST_PEERS: how many launches the layout rule should assume on the device, e.g. 2 when a front-end context
-        // runs its kernels under this estimator's and should find half of every CU's LDS free)
-        const char *pe = getenv("VIO_AMD_EST_PEERS");
-        rc = vio_backend_set_peers(e->be[g], pe && atoi(pe) > 0 ? atoi(pe) : e->n_groups);
-      }
+      if (rc == VIO_OK) rc = vio_backend_set_peers(e->be[g], e->n_groups);
       if (rc == VIO_OK && e->resident_priors) rc = vio_backend_reserve_priors(e->be[g], e->group_size);
     }
     if (rc == VIO_OK) rc = vio_backend_upload(e->be[g], e->windows.data() + g0[g], ng);

@@ -41,10 +41,6 @@ constexpr int kMaxCap = 512;    // max tracked features per sequence supported b
 constexpr int kWin = 21;        // LK window (the kernel is specialised for 21x21; cfg->lk_win must match)
 constexpr int kWBits = 14;
 constexpr int kMaxRadius = 128;  // largest MIN_DIST (setMask circle radius) the tracker's LDS tables are sized for
-#ifndef VIO_LK_FPW
-#define VIO_LK_FPW 1
-#endif
-constexpr int kLkFpw = VIO_LK_FPW;  // features per wave of lk_track_kernel (1 or 2)
 
 struct LevelDims {
   int rows[kMaxLevels], cols[kMaxLevels];
@@ -186,28 +182,7 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Sums over the lanes of one feature. FPW = 1: the whole wave (wave_sum_i32). FPW = 2: each half of the wave is a feature;
-// the row-level DPP steps never leave a row of 16 lanes and row_bcast:15 only feeds rows 1 and 3, so the two halves do
-// not mix: the totals land in lanes 31 and 63.
-template <int FPW>
-__device__ __forceinline__ int feat_sum_i32(int v, int sub) {
-  if (FPW == 1) return wave_sum_i32(v);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
-  const int lo = __builtin_amdgcn_readlane(v, 31), hi = __builtin_amdgcn_readlane(v, 63);
-  return sub ? hi : lo;
-}
-template <int FPW>
-__device__ __forceinline__ double feat_sum_exact(int p, int sub) {
-  int lo = p & 0xffff, hi = p >> 16;
-  int slo = feat_sum_i32<FPW>(lo, sub), shi = feat_sum_i32<FPW>(hi, sub);
-  return (double)shi * 65536.0 + (double)slo;
-}
-
-// Two exact sums at once (one feature per wave): the four 32-bit chains advance in lockstep, so that every DPP step finds
+// Two exact sums at once: the four 32-bit chains advance in lockstep, so that every DPP step finds
 // its operand written three instructions earlier (a chain on its own waits two issue slots after every step).
 // (every partial below 2^24 in magnitude -- what a window of ordinary contrast gives: the bounds are 2^28 -- means the 64-lane sums fit
 // 32 bits unsplit: half the chains. The split form stays for the rest; both give the exact integer, rounded once.)
@@ -281,44 +256,34 @@ __device__ __forceinline__ void wave_sum_exact3(int p, int q, int r, float &sp, 
   sp = (float)s[3] * 65536.f + (float)s[0], sq = (float)s[4] * 65536.f + (float)s[1], sr = (float)s[5] * 65536.f + (float)s[2];
 }
 
-// FPW features per wave (64 / FPW lanes each). prev/next pyramids: per sequence `pyr_bytes` apart. pts arrays:
-// [seq][cap][2]. Two features per wave share every wave-uniform instruction (the reductions, the 2x2 solve, the
-// convergence tests, the bilinear weights): the kernel is VALU-issue-bound and those are half of an LK iteration.
+// One feature per wave. prev/next pyramids: per sequence `pyr_bytes` apart. pts arrays: [seq][cap][2].
 // Occupancy: the kernel is latency-bound on its dependent chains (LDS round trips, DPP reductions), not on VALU issue —
-// two features per wave (FPW = 2: half the wave-uniform instructions per feature, but 154 VGPRs = 3 waves per SIMD) is
+// two features per wave (half the wave-uniform instructions per feature, but 154 VGPRs = 3 waves per SIMD) was measured
 // SLOWER (1.36 vs 1.28 ms per front-end step), more resident waves are faster: with the LDS per feature down to 4.3 KB the
 // register count is what limits residency, so the kernel is compiled for 6 waves per SIMD (80 VGPRs, no spills; 95 -> 5
 // waves before): front-end step 1.28 -> 1.17 ms. (8 waves per SIMD = 64 VGPRs spills 17 registers and gains another 0.5 %.)
-template <int FPW, bool STATS = false>
-__global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const uint8_t *prev_pyr, const uint8_t *next_pyr, LkParams P,
+template <bool STATS = false>
+__global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_pyr, const uint8_t *next_pyr, LkParams P,
                                                        const int *n_pts, const float *prev_pts, float *next_pts,
                                                        uint8_t *status, float *err, unsigned long long *stats) {
-  constexpr int LPF = 64 / FPW;  // lanes per feature
-  __shared__ LkWaveLds lds_all[4 * FPW];
+  __shared__ LkWaveLds lds_all[4];
   const int seq = blockIdx.y;
-  const int wave = threadIdx.x >> 6, wlane = threadIdx.x & 63;
-  const int sub = wlane / LPF, lane = wlane & (LPF - 1);  // feature within the wave, lane within the feature
-  const int pt = (blockIdx.x * (blockDim.x >> 6) + wave) * FPW + sub;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int pt = blockIdx.x * (blockDim.x >> 6) + wave;
   if (pt >= n_pts[seq]) return;
-  LkWaveLds &L = lds_all[wave * FPW + sub];
+  LkWaveLds &L = lds_all[wave];
   const uint8_t *pp = prev_pyr + (size_t)seq * P.ld.pyr_bytes, *np = next_pyr + (size_t)seq * P.ld.pyr_bytes;
   const size_t pidx = ((size_t)seq * P.cap + pt) * 2;
   const float ptx = prev_pts[pidx], pty = prev_pts[pidx + 1];
   const float half = (kWin - 1) * 0.5f;
   const float FLT_SCALE = 1.f / (1 << 20);
-  constexpr int NPX = (kWin * kWin + LPF - 1) / LPF;  // window pixels per lane: 7 (14 with two features per wave)
-  // This lane's window pixels. One feature per wave: lane l owns column l % 21 of rows l / 21 + 3 q (q = 0..6; 63 lanes) --
-  // the q-th pixel sits a CONSTANT 3 q rows below the first, so the LDS reads of an iteration share one address register
-  // (+ immediate offsets) instead of one address computation per pixel. Two features per wave: pixel lane + 32 q of the
-  // row-major window. (The sums over the window are exact integers: which lane owns which pixel does not reach the result.)
-  constexpr bool COLS = FPW == 1;
+  constexpr int NPX = (kWin * kWin + 63) / 64;  // window pixels per lane: 7
+  // This lane's window pixels: lane l owns column l % 21 of rows l / 21 + 3 q (q = 0..6; 63 lanes) -- the q-th pixel sits a
+  // CONSTANT 3 q rows below the first, so the LDS reads of an iteration share one address register (+ immediate offsets)
+  // instead of one address computation per pixel. (The sums over the window are exact integers: which lane owns which pixel
+  // does not reach the result.)
   const int wy0 = min(lane / kWin, 2), wx0 = lane % kWin;  // (lane 63 owns nothing: it shadows lane 62's rows, masked below)
-  auto pix_ok = [&](int q) { return COLS ? lane < 3 * kWin : lane + LPF * q < kWin * kWin; };
-  auto pix_y = [&](int q) { return COLS ? wy0 + 3 * q : min(lane + LPF * q, kWin * kWin - 1) / kWin; };  // (always inside the window)
-  auto pix_x = [&](int q) { return COLS ? wx0 : min(lane + LPF * q, kWin * kWin - 1) % kWin; };
-  int joff[COLS ? 1 : NPX];  // element offsets into the staged J region (COLS: of the first pixel)
-#pragma unroll
-  for (int q = 0; q < (COLS ? 1 : NPX); q++) joff[q] = pix_y(q) * kJS + pix_x(q);
+  const int joff = wy0 * kJS + wx0;  // element offset of the first pixel in the staged J region
   bool st = true;
   float er = 0.f;
   float nxx = 0.f, nxy = 0.f;
@@ -348,7 +313,7 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
     // stage I on [ipx-1, ipx+23) x [ipy-1, ipy+23) (BORDER_REFLECT_101), then its Scharr derivatives on
     // [ipx, ipx+22) x [ipy, ipy+22): zero outside the image (copyMakeBorder BORDER_CONSTANT of derivI)
     wave_lds_fence();  // previous level's readers are done
-    if (FPW == 1 && ipx >= 1 && ipx + kIP - 1 <= cols && ipy >= 1 && ipy + kIP - 1 <= rows) {
+    if (ipx >= 1 && ipx + kIP - 1 <= cols && ipy >= 1 && ipy + kIP - 1 <= rows) {
       // the patch lies inside the image (all but the features within a window of the border): FOUR pixels per lane and
       // load, 6 lanes per row, 10 rows per trip -- 3 trips instead of 12 (the kernel is VALU-issue-bound: staging the two
       // patches byte by byte was a quarter of a level's instructions)
@@ -380,21 +345,17 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
       const int x = reflect101(ipx - 1 + min(lx, kIP - 1), cols);
       // (a third of the features take this path at the coarse levels, where the patch is a quarter of the image: all loads
       // of the patch are issued before the first is consumed -- one memory round trip instead of one per trip)
-      constexpr int RPT = LPF / 32, TB = kIP / RPT;
+      constexpr int RPT = 2, TB = kIP / RPT;
       static_assert(kIP % RPT == 0, "whole trips");
       int vs[TB];
 #pragma unroll
       for (int t = 0; t < TB; t++) {
-        if constexpr (FPW == 1) {
-          // (one feature per wave: the patch origin is the same in every lane, so the reflected ROW of a trip is one of two scalars
-          // -- even / odd half of the wave -- and comes off the scalar unit: 2 vector instructions per trip instead of ~16; the
-          // border path is not rare: 58 % of the features take it at level 3, 32 % at level 2)
-          const int s_y0 = __builtin_amdgcn_readfirstlane(ipy) - 1 + RPT * t;
-          const int ro_a = reflect101(s_y0, rows) * cols, ro_b = reflect101(s_y0 + 1, rows) * cols;
-          vs[t] = I[(unsigned)(((lane >> 5) ? ro_b : ro_a) + x)];
-        } else {
-          vs[t] = I[(unsigned)(__mul24(reflect101(ipy - 1 + (lane >> 5) + RPT * t, rows), cols) + x)];
-        }
+        // (the patch origin is the same in every lane, so the reflected ROW of a trip is one of two scalars -- even / odd half
+        // of the wave -- and comes off the scalar unit: 2 vector instructions per trip instead of ~16; the border path is not
+        // rare: 58 % of the features take it at level 3, 32 % at level 2)
+        const int s_y0 = __builtin_amdgcn_readfirstlane(ipy) - 1 + RPT * t;
+        const int ro_a = reflect101(s_y0, rows) * cols, ro_b = reflect101(s_y0 + 1, rows) * cols;
+        vs[t] = I[(unsigned)(((lane >> 5) ? ro_b : ro_a) + x)];
       }
 #pragma unroll
       for (int t = 0; t < TB; t++) {
@@ -404,75 +365,46 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
       }
     }
     wave_lds_fence();
-    if (FPW == 1) {
-      // Scharr derivatives by COLUMN-PAIR WALK on packed 16-bit arithmetic: lanes 0..54 = 11 column pairs x five segments of five
-      // output rows (the last one starts at row 17 and repeats three rows of its neighbour). A staged dword is a pixel pair
-      // (I[x] | I[x+1] << 16), so the three pair words at columns c, c + 1, c + 2 are the left / centre / right taps of the derivative
-      // columns c AND c + 1 at once: per input row h = P2 - P0 and v = 3 (P0 + P2) + 10 P1, per output row dx = 3 (h0 + h2) + 10 h1 and
-      // dy = v2 - v0, each ONE v_pk_* instruction for both columns (|values| <= 16 x 255: exact in 16 bits) -- the same integers as the
-      // 3 x 3 sums of calcSharrDeriv. (The one-column walk on 32-bit values, rounds 4-6: 168 vector instructions per level on 44 lanes,
-      // a seventh of the kernel's; this form: ~75 on 55 lanes.)
-      constexpr int SEG = 5, NSEG = 5, NCP = kDP / 2;
-      static_assert(kDP % 2 == 0 && NCP * NSEG <= 64 && SEG * NSEG >= kDP && kDP >= SEG, "column pairs x segments");
-      const bool inside = ipx >= 0 && ipx + kDP <= cols && ipy >= 0 && ipy + kDP <= rows;  // every derivative position is in the image
-      if (lane < NCP * NSEG) {
-        const int seg = lane / NCP, cp = lane - NCP * seg, c = 2 * cp;
-        const int r0 = seg * SEG < kDP - SEG ? seg * SEG : kDP - SEG;
-        const uint32_t *Ip = &L.I[0][0] + (__mul24(r0, kIS) + c);
-        uint32_t *Dp = reinterpret_cast<uint32_t *>(&L.dI[0][0]) + (__mul24(r0, kDP) + c);
-        const lk_s2 k3 = {3, 3}, k10 = {10, 10};
-        auto walk = [&](auto checked) {  // (checked: the patch leaves the image -- derivI's BORDER_CONSTANT zeros)
-          const unsigned ok0 = (unsigned)(ipx + c) < (unsigned)cols, ok1 = (unsigned)(ipx + c + 1) < (unsigned)cols;
-          lk_s2 P0[SEG + 2], P1[SEG + 2], P2[SEG + 2];  // pair words of input row r0 + r: the staged patch holds reflected values at the image border
+    // Scharr derivatives by COLUMN-PAIR WALK on packed 16-bit arithmetic: lanes 0..54 = 11 column pairs x five segments of five
+    // output rows (the last one starts at row 17 and repeats three rows of its neighbour). A staged dword is a pixel pair
+    // (I[x] | I[x+1] << 16), so the three pair words at columns c, c + 1, c + 2 are the left / centre / right taps of the derivative
+    // columns c AND c + 1 at once: per input row h = P2 - P0 and v = 3 (P0 + P2) + 10 P1, per output row dx = 3 (h0 + h2) + 10 h1 and
+    // dy = v2 - v0, each ONE v_pk_* instruction for both columns (|values| <= 16 x 255: exact in 16 bits) -- the same integers as the
+    // 3 x 3 sums of calcSharrDeriv. (The one-column walk on 32-bit values, rounds 4-6: 168 vector instructions per level on 44 lanes,
+    // a seventh of the kernel's; this form: ~75 on 55 lanes.)
+    constexpr int SEG = 5, NSEG = 5, NCP = kDP / 2;
+    static_assert(kDP % 2 == 0 && NCP * NSEG <= 64 && SEG * NSEG >= kDP && kDP >= SEG, "column pairs x segments");
+    const bool inside = ipx >= 0 && ipx + kDP <= cols && ipy >= 0 && ipy + kDP <= rows;  // every derivative position is in the image
+    if (lane < NCP * NSEG) {
+      const int seg = lane / NCP, cp = lane - NCP * seg, c = 2 * cp;
+      const int r0 = seg * SEG < kDP - SEG ? seg * SEG : kDP - SEG;
+      const uint32_t *Ip = &L.I[0][0] + (__mul24(r0, kIS) + c);
+      uint32_t *Dp = reinterpret_cast<uint32_t *>(&L.dI[0][0]) + (__mul24(r0, kDP) + c);
+      const lk_s2 k3 = {3, 3}, k10 = {10, 10};
+      auto walk = [&](auto checked) {  // (checked: the patch leaves the image -- derivI's BORDER_CONSTANT zeros)
+        const unsigned ok0 = (unsigned)(ipx + c) < (unsigned)cols, ok1 = (unsigned)(ipx + c + 1) < (unsigned)cols;
+        lk_s2 P0[SEG + 2], P1[SEG + 2], P2[SEG + 2];  // pair words of input row r0 + r: the staged patch holds reflected values at the image border
 #pragma unroll
-          for (int r = 0; r < SEG + 2; r++)  // (all reads ahead of the first write: one wait instead of one per row)
-            __builtin_memcpy(&P0[r], Ip + r * kIS, 4), __builtin_memcpy(&P1[r], Ip + r * kIS + 1, 4), __builtin_memcpy(&P2[r], Ip + r * kIS + 2, 4);
-          lk_s2 h[SEG + 2], v[SEG + 2];
+        for (int r = 0; r < SEG + 2; r++)  // (all reads ahead of the first write: one wait instead of one per row)
+          __builtin_memcpy(&P0[r], Ip + r * kIS, 4), __builtin_memcpy(&P1[r], Ip + r * kIS + 1, 4), __builtin_memcpy(&P2[r], Ip + r * kIS + 2, 4);
+        lk_s2 h[SEG + 2], v[SEG + 2];
 #pragma unroll
-          for (int r = 0; r < SEG + 2; r++) h[r] = P2[r] - P0[r], v[r] = (P0[r] + P2[r]) * k3 + P1[r] * k10;
+        for (int r = 0; r < SEG + 2; r++) h[r] = P2[r] - P0[r], v[r] = (P0[r] + P2[r]) * k3 + P1[r] * k10;
 #pragma unroll
-          for (int r = 2; r < SEG + 2; r++) {
-            const lk_s2 dx = (h[r - 2] + h[r]) * k3 + h[r - 1] * k10, dy = v[r] - v[r - 2];
-            uint32_t ux, uy;
-            __builtin_memcpy(&ux, &dx, 4), __builtin_memcpy(&uy, &dy, 4);
-            uint32_t d0 = __builtin_amdgcn_perm(uy, ux, 0x05040100u), d1 = __builtin_amdgcn_perm(uy, ux, 0x07060302u);  // short2 {dx, dy} of columns c, c + 1
-            if (decltype(checked)::value) {
-              const unsigned rok = (unsigned)(ipy + r0 + r - 2) < (unsigned)rows;
-              d0 &= 0u - (ok0 & rok), d1 &= 0u - (ok1 & rok);
-            }
-            Dp[(r - 2) * kDP] = d0, Dp[(r - 2) * kDP + 1] = d1;
+        for (int r = 2; r < SEG + 2; r++) {
+          const lk_s2 dx = (h[r - 2] + h[r]) * k3 + h[r - 1] * k10, dy = v[r] - v[r - 2];
+          uint32_t ux, uy;
+          __builtin_memcpy(&ux, &dx, 4), __builtin_memcpy(&uy, &dy, 4);
+          uint32_t d0 = __builtin_amdgcn_perm(uy, ux, 0x05040100u), d1 = __builtin_amdgcn_perm(uy, ux, 0x07060302u);  // short2 {dx, dy} of columns c, c + 1
+          if (decltype(checked)::value) {
+            const unsigned rok = (unsigned)(ipy + r0 + r - 2) < (unsigned)rows;
+            d0 &= 0u - (ok0 & rok), d1 &= 0u - (ok1 & rok);
           }
-        };
-        if (inside) walk(std::false_type{});
-        else walk(std::true_type{});
-      }
-    } else {
-      {
-        // element e = lane + LPF t of the 22 x 22 derivative patch, (ly, lx) advanced by (LPF / 22, LPF % 22) per trip (an
-        // integer division and the 32-bit multiplies of the Scharr sums are quarter-rate instructions: none are left here)
-        int e = lane, ly = lane / kDP, lx = lane - kDP * ly;
-        const bool inside = ipx >= 0 && ipx + kDP <= cols && ipy >= 0 && ipy + kDP <= rows;  // every derivative position is in the image
-#pragma unroll 1
-        for (int t = 0; t < (kDP * kDP + LPF - 1) / LPF; t++) {
-          if (ly < kDP) {
-            uint32_t d = 0;
-            if (inside || (ipx + lx >= 0 && ipx + lx < cols && ipy + ly >= 0 && ipy + ly < rows)) {
-              // the staged patch holds reflected values, i.e. exactly what calcSharrDeriv reads at the image border
-              const uint32_t *Ip = &L.I[0][0] + (e + __mul24(kIS - kDP, ly));  // = &L.I[ly][lx]
-              const uint32_t a0 = Ip[0], a1 = Ip[1], b0 = Ip[kIS], b1 = Ip[kIS + 1], c0 = Ip[2 * kIS], c1 = Ip[2 * kIS + 1];
-              const int p00 = a0 & 0xffff, p01 = a0 >> 16, p02 = a1 >> 16;
-              const int p10 = b0 & 0xffff, p12 = b1 >> 16;
-              const int p20 = c0 & 0xffff, p21 = c0 >> 16, p22 = c1 >> 16;
-              const int dx = __mul24(3, (p02 - p00) + (p22 - p20)) + __mul24(10, p12 - p10);
-              const int dy = __mul24(3, (p20 - p00) + (p22 - p02)) + __mul24(10, p21 - p01);
-              d = __builtin_amdgcn_perm((uint32_t)dy, (uint32_t)dx, 0x05040100u);  // short2 {dx, dy}
-            }
-            __builtin_memcpy(&L.dI[0][0] + e, &d, 4);  // = L.dI[ly][lx]
-          }
-          e += LPF, lx += LPF % kDP, ly += LPF / kDP;
-          if (lx >= kDP) lx -= kDP, ly++;
+          Dp[(r - 2) * kDP] = d0, Dp[(r - 2) * kDP + 1] = d1;
         }
-      }
+      };
+      if (inside) walk(std::false_type{});
+      else walk(std::true_type{});
     }
     wave_lds_fence();
     // template patch + derivatives for this lane's window pixels, kept in registers across the iterations
@@ -489,7 +421,7 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
     for (int h = 0; h < NPP; h++) IxP[h] = IyP[h] = lk_s2{0, 0};
 #pragma unroll
     for (int q = 0; q < NPX; q++) {
-      const int y = pix_y(q), x = pix_x(q);
+      const int y = wy0 + 3 * q, x = wx0;  // (always inside the window)
       // bilinear taps as dot products of packed pairs (a 32-bit integer multiply is a quarter-rate instruction here; the
       // element-wise form of this block was 12 of them per pixel): the I patch is staged as pairs already; the derivative
       // pairs (d[x], d[x+1]) are cut out of two (dx, dy) words with v_perm_b32. Weights <= 2^14 fit int16, and the SIGNED
@@ -507,15 +439,14 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
       __builtin_memcpy(&sxt, &xt, 4), __builtin_memcpy(&syt, &yt, 4), __builtin_memcpy(&sxb, &xb, 4), __builtin_memcpy(&syb, &yb, 4);
       int ixval = __builtin_amdgcn_sdot2(sxt, sw_top, __builtin_amdgcn_sdot2(sxb, sw_bot, 1 << (kWBits - 1), false), false) >> kWBits;
       int iyval = __builtin_amdgcn_sdot2(syt, sw_top, __builtin_amdgcn_sdot2(syb, sw_bot, 1 << (kWBits - 1), false), false) >> kWBits;
-      if (!pix_ok(q)) ixval = iyval = 0;  // a pixel this lane does not own: weight zero in every sum below
+      if (lane >= 3 * kWin) ixval = iyval = 0;  // a pixel this lane does not own: weight zero in every sum below
       Ic[q] = (1 << (kWBits - 5 - 1)) - (int)((unsigned)ival << (kWBits - 5));
       if (q & 1) IxP[q >> 1].y = (short)ixval, IyP[q >> 1].y = (short)iyval;
       else IxP[q >> 1].x = (short)ixval, IyP[q >> 1].x = (short)iyval;
       p11 += ixval * ixval, p12 += ixval * iyval, p22 += iyval * iyval;
     }
     float f11, f12, f22;  // exact integer sums, rounded once to float
-    if (FPW == 1) wave_sum_exact3(p11, p12, p22, f11, f12, f22);
-    else f11 = (float)feat_sum_exact<FPW>(p11, sub), f12 = (float)feat_sum_exact<FPW>(p12, sub), f22 = (float)feat_sum_exact<FPW>(p22, sub);
+    wave_sum_exact3(p11, p12, p22, f11, f12, f22);
     float A11 = f11 * FLT_SCALE, A12 = f12 * FLT_SCALE, A22 = f22 * FLT_SCALE;
     float D = A11 * A22 - A12 * A12;
     float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (2 * kWin * kWin);
@@ -531,7 +462,7 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
     auto stage_j = [&](int iqx, int iqy) {
       jox = iqx - kJMargin, joy = iqy - kJMargin;
       wave_lds_fence();
-      if (FPW == 1 && jox >= 0 && jox + kJP <= cols && joy >= 0 && joy + kJP <= rows) {
+      if (jox >= 0 && jox + kJP <= cols && joy >= 0 && joy + kJP <= rows) {
         // inside the image: 4 pixels per lane and load, 7 lanes per row, 9 rows per trip -- 4 trips instead of 14
         const int r = lane / 7, d = lane - 7 * r;
         constexpr int TJ = (kJP + 8) / 9;
@@ -558,20 +489,15 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
       } else {  // 32 lanes per row (28 used), two rows per trip; pairs (J[x] | J[x+1] << 16) like the template patch
         const int lx = lane & 31;
         const int x = reflect101(min(max(jox + min(lx, kJP - 1), -cols + 1), 2 * cols - 2), cols);
-        constexpr int RPT = LPF / 32, TB = kJP / RPT;
+        constexpr int RPT = 2, TB = kJP / RPT;
         static_assert(kJP % RPT == 0, "whole trips");
         int vs[TB];
 #pragma unroll
-        for (int t = 0; t < TB; t++) {
-          if constexpr (FPW == 1) {  // (rows on the scalar unit, as in the template patch's border path)
-            const int s_y0 = __builtin_amdgcn_readfirstlane(joy) + RPT * t;
-            const int ro_a = reflect101(min(max(s_y0, -rows + 1), 2 * rows - 2), rows) * cols;
-            const int ro_b = reflect101(min(max(s_y0 + 1, -rows + 1), 2 * rows - 2), rows) * cols;
-            vs[t] = J[(unsigned)(((lane >> 5) ? ro_b : ro_a) + x)];
-          } else {
-            const int y = reflect101(min(max(joy + (lane >> 5) + RPT * t, -rows + 1), 2 * rows - 2), rows);
-            vs[t] = J[(unsigned)(__mul24(y, cols) + x)];
-          }
+        for (int t = 0; t < TB; t++) {  // (rows on the scalar unit, as in the template patch's border path)
+          const int s_y0 = __builtin_amdgcn_readfirstlane(joy) + RPT * t;
+          const int ro_a = reflect101(min(max(s_y0, -rows + 1), 2 * rows - 2), rows) * cols;
+          const int ro_b = reflect101(min(max(s_y0 + 1, -rows + 1), 2 * rows - 2), rows) * cols;
+          vs[t] = J[(unsigned)(((lane >> 5) ? ro_b : ro_a) + x)];
         }
 #pragma unroll
         for (int t = 0; t < TB; t++) {
@@ -589,7 +515,7 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
     auto diff_j = [&](int base, int q, lk_us2 wtop, lk_s2 wbot) {  // bilinear J at this lane's q-th window pixel, minus I there
       lk_us2 top;
       lk_s2 bot;
-      const int o = base + (COLS ? joff[0] + 3 * q * kJS : joff[COLS ? 0 : q]);  // (q is a constant after unrolling)
+      const int o = base + (joff + 3 * q * kJS);  // (q is a constant after unrolling)
       const uint32_t t32 = Jl[o], b32 = Jl[o + kJS];
       __builtin_memcpy(&top, &t32, 4);
       __builtin_memcpy(&bot, &b32, 4);
@@ -619,8 +545,7 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
         pb1 = __builtin_amdgcn_sdot2(dp, IxP[h], pb1, false), pb2 = __builtin_amdgcn_sdot2(dp, IyP[h], pb2, false);
       }
       float fb1, fb2;  // the exact integer sums, rounded once to float (what (float) of the exact double gave)
-      if (FPW == 1) wave_sum_exact2(pb1, pb2, fb1, fb2);
-      else fb1 = (float)feat_sum_exact<FPW>(pb1, sub), fb2 = (float)feat_sum_exact<FPW>(pb2, sub);
+      wave_sum_exact2(pb1, pb2, fb1, fb2);
       float b1 = fb1 * FLT_SCALE, b2 = fb2 * FLT_SCALE;
       float ddx = (A12 * b2 - A22 * b1) * D, ddy = (A12 * b1 - A11 * b2) * D;
       qx += ddx, qy += ddy;
@@ -660,9 +585,9 @@ __global__ __launch_bounds__(256, FPW == 1 ? 6 : 1) void lk_track_kernel(const u
 #pragma unroll
       for (int q = 0; q < NPX; q++) {
         const int d = abs(diff_j(jbase, q, wtop, wbot));
-        pe += pix_ok(q) ? d : 0;
+        pe += lane < 3 * kWin ? d : 0;
       }
-      const int se = feat_sum_i32<FPW>(pe, sub);  // <= 441 * 16320 < 2^23
+      const int se = wave_sum_i32(pe);  // <= 441 * 16320 < 2^23
       er = (float)se * 1.f / (32 * kWin * kWin);
     }
   }
@@ -1908,10 +1833,7 @@ constexpr int kPd4H = 16, kPd4Dw = (2 * kPdW + 8) / 4;  // 34 dwords per staged 
 // A workgroup walks kPd4T tiles down its column of the image: the loads of the NEXT tile's patch are issued (into registers) before
 // the barriers and the arithmetic of this one, so a workgroup always has a patch in flight -- with one tile per workgroup the load
 // phase was a third of a workgroup's life and the kernel ran at a third of the memory system's rate (2.2 TB/s on level 1).
-#ifndef VIO_PD4T
-#define VIO_PD4T 3
-#endif
-constexpr int kPd4T = VIO_PD4T;
+constexpr int kPd4T = 3;
 template <bool COPY>
 __global__ __launch_bounds__(256) void pyr_down4_kernel(const uint8_t *src_base, size_t src_stride, uint8_t *dst_base, size_t seq_stride,
                                                         int srows, int scols, int drows, int dcols, uint8_t *copy_base) {
@@ -2039,7 +1961,7 @@ int launch_track_update(vio_frontend *fe, int publish, hipStream_t st) {
   A.n_kept = fe->n_kept.p, A.hw = fe->hw.p, A.radius = fe->cfg.min_dist, A.f_thresh = (float)fe->cfg.f_threshold;
   A.pnp_pts = fe->pnp_pts.p, A.pnp_ids = fe->pnp_ids.p, A.n_pnp = fe->n_pnp.p;
   A.f_conf = fe->cfg.f_confidence;
-  static const bool tu_prof = getenv("VIO_AMD_TU_PROF") && getenv("VIO_AMD_TU_PROF")[0] == '1';
+  static const bool tu_prof = vio::env_flag("VIO_AMD_TU_PROF");
   if (tu_prof) (void)fe->d_prof.ensure(32);
   A.prof = tu_prof ? fe->d_prof.p : nullptr;
   // the smallest LDS layout that holds this tracker's feature slots (fe->cap <= kMaxCap is checked at create)
@@ -2080,9 +2002,8 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
   uint8_t *forw = fe->pyr[fidx].p;
   // level 0 and level 1 from ONE read of the frame when the rows of both are whole dwords (640x480, 720p, 1080p)
   const bool fused0 = fe->ld.levels >= 2 && cols % 4 == 0 && fe->ld.cols[1] % 4 == 0 && cols >= 8 && fe->ld.pyr_bytes % 4 == 0 &&
-                      img_bytes % 4 == 0 && (uintptr_t)d_frames % 4 == 0 && (uintptr_t)forw % 4 == 0 && fe->ld.off[1] % 4 == 0 &&
-                      !(getenv("VIO_AMD_PYR_UNFUSED") && getenv("VIO_AMD_PYR_UNFUSED")[0] == '1');
-  const bool alias0 = keep_frames && fused0 && !(getenv("VIO_AMD_COPY_LEVEL0") && getenv("VIO_AMD_COPY_LEVEL0")[0] == '1');
+                      img_bytes % 4 == 0 && (uintptr_t)d_frames % 4 == 0 && (uintptr_t)forw % 4 == 0 && fe->ld.off[1] % 4 == 0;
+  const bool alias0 = keep_frames && fused0 && !vio::env_flag("VIO_AMD_COPY_LEVEL0");
   fe->lvl0[fidx] = alias0 ? d_frames : nullptr;
   if (!fused0) {
     const int vec_ok = img_bytes % 16 == 0 && fe->ld.pyr_bytes % 16 == 0 && (uintptr_t)d_frames % 16 == 0 &&
@@ -2125,14 +2046,14 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
     double eps = std::min(std::max(fe->cfg.lk_eps, 0.), 10.);
     P.epsilon_sq = eps * eps, P.epsilon_sq_f = lk_eps_screen(eps * eps), P.min_eig = (float)fe->cfg.lk_min_eig;
     P.prev0 = fe->lvl0[fe->cur_idx], P.next0 = fe->lvl0[fidx], P.stride0 = img_bytes;
-    dim3 grd((cap + 4 * kLkFpw - 1) / (4 * kLkFpw), S);
+    dim3 grd((cap + 3) / 4, S);
     // (the counting variant is a kernel of its own: STATS = [2 * levels] iterations run / (feature, level) visits of this launch,
     // vio_frontend_lk_iterations; the product kernel sits at 80 registers for six waves per SIMD and has none to spare)
     if (fe->lk_stats_on && fe->lk_stats.p)
-      hipLaunchKernelGGL((lk_track_kernel<kLkFpw, true>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
+      hipLaunchKernelGGL((lk_track_kernel<true>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
                          fe->forw_pts.p, fe->lk_status.p, fe->lk_err.p, fe->lk_stats.p);
     else
-      hipLaunchKernelGGL((lk_track_kernel<kLkFpw, false>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
+      hipLaunchKernelGGL((lk_track_kernel<false>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
                          fe->forw_pts.p, fe->lk_status.p, fe->lk_err.p, (unsigned long long *)nullptr);
   }
   int rcu = launch_track_update(fe, publish, st);
@@ -2168,7 +2089,7 @@ int vio_frontend_create(const VioConfig *cfg, int32_t n_seq, vio_frontend_t **ou
   vio_frontend *fe = new vio_frontend();
   fe->device = vio::current_device();
   fe->cfg = *cfg, fe->n_seq = n_seq, fe->cap = cfg->max_corners;
-  fe->detect_always = getenv("VIO_AMD_DETECT_ALWAYS") && getenv("VIO_AMD_DETECT_ALWAYS")[0] == '1';
+  fe->detect_always = vio::env_flag("VIO_AMD_DETECT_ALWAYS");
   // buildOpticalFlowPyramid: levels stop when one would not hold the window
   LevelDims &ld = fe->ld;
   ld.rows[0] = cfg->image_rows, ld.cols[0] = cfg->image_cols, ld.off[0] = 0, ld.levels = 1;
@@ -2620,7 +2541,7 @@ int vio_klt_track(const VioConfig *cfg, const uint8_t *prev, const uint8_t *next
   double eps = std::min(std::max(c.lk_eps, 0.), 10.);
   P.epsilon_sq = eps * eps, P.epsilon_sq_f = lk_eps_screen(eps * eps), P.min_eig = (float)c.lk_min_eig;
   P.prev0 = P.next0 = nullptr, P.stride0 = 0;
-  hipLaunchKernelGGL((lk_track_kernel<kLkFpw, false>), dim3((fe->cap + 4 * kLkFpw - 1) / (4 * kLkFpw), 1), dim3(256), 0, st, fe->pyr[0].p, fe->pyr[1].p, P, fe->n_pts.p,
+  hipLaunchKernelGGL((lk_track_kernel<false>), dim3((fe->cap + 3) / 4, 1), dim3(256), 0, st, fe->pyr[0].p, fe->pyr[1].p, P, fe->n_pts.p,
                      fe->cur_pts.p, fe->forw_pts.p, fe->lk_status.p, fe->lk_err.p, (unsigned long long *)nullptr);
   if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
   if (hipMemcpy(next_pts, fe->forw_pts.p, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) return VIO_ENODEV;

@@ -22,6 +22,8 @@
 #include <thread>
 #include <vector>
 
+#include "vio_env.h"
+
 namespace vio {
 
 class HostPool {
@@ -115,16 +117,14 @@ class HostPool {
     HostPool *p = nullptr;
     Pools() {
       const int hw = (int)std::thread::hardware_concurrency();
-      if (const char *e = getenv("VIO_AMD_HOST_POOLS")) n = atoi(e);
-      else n = hw >= 128 ? 2 : 1;
-      n = std::min(4, std::max(1, n));
+      n = std::min(4, std::max(1, env_int("VIO_AMD_HOST_POOLS", hw >= 128 ? 2 : 1)));
       p = new HostPool[n];
-      const char *numa = getenv("VIO_AMD_HOST_NUMA");
+      const bool numa = !env_flag("VIO_AMD_HOST_NUMA", '0');
       cpu_set_t set;
       int nodes = 0;
       while (nodes < 16 && node_cpus(nodes, &set)) nodes++;
       for (int i = 0; i < n; i++) {
-        const bool bind = nodes > 1 && !(numa && numa[0] == '0') && node_cpus(i % nodes, &set);
+        const bool bind = nodes > 1 && numa && node_cpus(i % nodes, &set);
         p[i].start(bind ? &set : nullptr);
       }
     }
@@ -136,8 +136,7 @@ class HostPool {
   }
   HostPool() {}
   void start(const cpu_set_t *cpus) {
-    int t = 0;
-    if (const char *e = getenv("VIO_AMD_HOST_THREADS")) t = atoi(e);
+    int t = env_int("VIO_AMD_HOST_THREADS", 0);
     if (t <= 0) {
       // width from the CPUs this process may run on (a container often sees all of the host's but is bound to a few).
       // Measured on a 256-thread host, 256 sequences per frame: 4 threads 12.8 ms, 16: 6.4, 32: 5.1, 64: 5.0, 96: 5.3
@@ -155,13 +154,9 @@ class HostPool {
       // Several ranks of one node share the CPUs and the quota (one process per GPU under torchrun / mpirun): every
       // process takes its share, not all of it -- eight ranks of full-width pools bring the throttling stalls back times
       // eight. LOCAL_WORLD_SIZE is what torchrun exports; other launchers set VIO_AMD_HOST_THREADS per rank.
-      int local_world = 1;
-      for (const char *name : {"LOCAL_WORLD_SIZE", "OMPI_COMM_WORLD_LOCAL_SIZE", "MV2_COMM_WORLD_LOCAL_SIZE"})
-        if (const char *e = getenv(name)) {
-          local_world = std::max(1, atoi(e));
-          break;
-        }
-      t = std::max(1, t / local_world);
+      const int local_world =
+          env_int("LOCAL_WORLD_SIZE", env_int("OMPI_COMM_WORLD_LOCAL_SIZE", env_int("MV2_COMM_WORLD_LOCAL_SIZE", 1)));
+      t = std::max(1, t / std::max(1, local_world));
     }
     for (int i = 1; i < t; i++) {
       workers_.emplace_back([this] { loop(); });

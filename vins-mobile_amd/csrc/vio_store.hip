@@ -158,11 +158,7 @@ size_t store_pack_lds_bytes(const store::Dims &d, int Mcap) {
 // of the CU's LDS while a window-kernel workgroup of another context is placed next to it leaves, when it ends, two free
 // pieces neither of which takes the next window-kernel workgroup (half a CU each) -- measured as two contexts' window
 // kernels running one after the other. Blocks of the window kernel's own size keep the halves whole.
-static size_t lds_block(size_t need) {
-  static const bool exact = getenv("VIO_AMD_STORE_LDS_EXACT") && getenv("VIO_AMD_STORE_LDS_EXACT")[0] == '1';
-  if (exact) return need;
-  return need <= kLdsBytes / 2 ? kLdsBytes / 2 : kLdsBytes;
-}
+static size_t lds_block(size_t need) { return need <= kLdsBytes / 2 ? kLdsBytes / 2 : kLdsBytes; }
 static int raise_lds(const void *fn, size_t lds) {
   if (lds > kLdsBytes) return VIO_ECAP;
   if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return VIO_ENODEV;

@@ -1,5 +1,5 @@
 // vio_window_kernel.inc -- the window kernel (one workgroup per window, or several: cooperative windows) and its launch table.
-// Included by vio_backend.hip (PROF = false: the product's launches) and vio_backend_prof.hip (PROF = true: the stage clock).
+// Included by vio_wk_unit.hip, compiled once per (variant, PROF) pair of vio_window_variants.h (PROF = true: the stage clock).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,7 +44,7 @@ __device__ __forceinline__ WinView static_view(WinView v) {
 // PROF: the stage clock (vio_backend_set_profile). The product launches PROF = false: cx.prof is then a compile-time null and every
 // stamp() of the kernel folds away -- with the counters' pointer a run-time value each of the ~100 stamps a wave passes per
 // iteration cost ~18 instructions whether the clock ran or not (the pointer sits in a spilled scalar register), 9 % of the
-// kernel's instructions. The PROF = true instantiations live in a translation unit of their own (vio_backend_prof.hip).
+// kernel's instructions. The PROF = true instantiations are translation units of their own (vio_wk_unit.hip, vio_window_variants.h).
 // WS: 0 = the window size, the batch capacities and with them every stride and the LDS layout are run-time values (any window the
 // layout takes); WS > 0 = a launch whose windows all have W = WS frames, no relocalization pose and the capacities that go with
 // it (static_dims / static_view below: the launcher checks, vio_backend.hip) -- the reference's WINDOW_SIZE is a compile-time 10

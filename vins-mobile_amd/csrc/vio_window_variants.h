@@ -18,18 +18,17 @@ constexpr int kThreadsLds = 256, kThreadsGlb = 512;
 // variant: pose matrix in LDS?, IMU coupling in LDS?, work-items, compile-time window size (0: run-time)
 //   0  LDS, LDS, 256, 0     the fat layout, two windows per CU (F <= 160 at W = 10)
 //   1  LDS, scratch, 256, 0 the lean layout (F <= 310)
-//   2  LDS, LDS, 512, 0     experiment switch VIO_AMD_WINDOW_THREADS=512
-//   3  scratch, scratch, 512, 0   W > 12 (cooperative windows)
-//   4  = 0 with W = 10 at compile time (the reference's WINDOW_SIZE, global_param.hpp:28), no relocalization pose in the batch
-//   5  = 1 with W = 10 at compile time
-constexpr int kVariants = 6;
+//   2  scratch, scratch, 512, 0   W > 12 (cooperative windows)
+//   3  = 0 with W = 10 at compile time (the reference's WINDOW_SIZE, global_param.hpp:28), no relocalization pose in the batch
+//   4  = 1 with W = 10 at compile time
+constexpr int kVariants = 5;
 constexpr int kStaticW = 10;
 struct VariantTraits {
   bool lds_matrix, lds_asp;
   int threads, ws;
 };
-constexpr VariantTraits kTraits[kVariants] = {{true, true, kThreadsLds, 0},  {true, false, kThreadsLds, 0},      {true, true, kThreadsGlb, 0},
-                                              {false, false, kThreadsGlb, 0}, {true, true, kThreadsLds, kStaticW}, {true, false, kThreadsLds, kStaticW}};
+constexpr VariantTraits kTraits[kVariants] = {{true, true, kThreadsLds, 0},        {true, false, kThreadsLds, 0}, {false, false, kThreadsGlb, 0},
+                                              {true, true, kThreadsLds, kStaticW}, {true, false, kThreadsLds, kStaticW}};
 
 struct VariantFns {
   const void *fn;  // the kernel (hipFuncSetAttribute, occupancy queries)
