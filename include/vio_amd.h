@@ -481,6 +481,74 @@ int vio_bow_database_query(vio_bow_database_t *d, int32_t n_queries, const int32
                            const double *bow_value, int32_t bow_stride, const int32_t *max_id, int32_t max_results,
                            int32_t *n_results, int32_t *entry, double *score, int32_t result_stride);
 
+/* The loop detector: TemplatedLoopDetector::detectLoop (VINS_ios/loop/TemplatedLoopDetector.h:668-877), the step of
+ * the app's loop_thread (VINS_ios/ViewController.mm:929-947, LoopClosure::startLoopClosure) that decides whether the
+ * newest keyframe closes a loop and with which old keyframe, for n independent sessions that share one vocabulary:
+ *   transform(features, bowvec, featvec, levelsup)  ThirdParty/DBoW/TemplatedVocabulary.h:1121-1189, :1212-1254
+ *   TemplatedDatabase::query / add / delete_entry   ThirdParty/DBoW/TemplatedDatabase.h:603-720, 439-470, 476-499
+ *   L1Scoring::score (ns_factor)                    ThirdParty/DBoW/ScoringObject.cpp:23-68
+ *   removeLowScores :1228-1246, computeIslands :891-965, updateTemporalWindow :982-1017
+ *   isGeometricallyConsistent_DI :1056-1144, getMatches_neighratio :1164-1223, checkFoundamental :1031-1053
+ *   eraseIndex :1250-1259, clear :882-886
+ * The FeatureVector of a keyframe maps the node met at level L - di_levels of the descent (the root when that level is
+ * <= 0) to the indices of its descriptors. For a descriptor whose descent ends at a leaf above that level the reference
+ * leaves the node unset; here it is the leaf's node id.                                                            */
+typedef struct VioLoopDetectorParams {     /* TemplatedLoopDetector::Parameters, TemplatedLoopDetector.h:94-147      */
+  int32_t use_nss; float alpha; int32_t k;
+  int32_t geom_check;                      /* GeometricalCheck :32-43: 1 GEOM_DI, 3 GEOM_NONE; 0 / 2 are refused     */
+  int32_t di_levels;
+  int32_t dislocal, max_db_results; float min_nss_factor;
+  int32_t min_matches_per_group, max_intragroup_gap, max_distance_between_groups, max_distance_between_queries;
+  int32_t min_Fpoints; double max_neighbor_ratio;
+  double f_threshold, f_confidence; int32_t min_inliers;  /* checkFoundamental's literals :1036-1047: 1.0, 0.99, "> 20" */
+} VioLoopDetectorParams;
+/* What the app constructs: Parameters(height, width) = (frequency 1, nss, alpha 0.3f, k 1, GEOM_DI, di_levels 2)
+ * (:165-167) + set(frequency) (:525-541, products truncated to int).                                              */
+void vio_loop_detector_params_default(VioLoopDetectorParams *p, float frequency);
+
+enum {                                     /* DetectionStatus :46-64                                                 */
+  VIO_LOOP_DETECTED = 0, VIO_LOOP_CLOSE_MATCHES_ONLY = 1, VIO_LOOP_NO_DB_RESULTS = 2, VIO_LOOP_LOW_NSS_FACTOR = 3,
+  VIO_LOOP_LOW_SCORES = 4, VIO_LOOP_NO_GROUPS = 5, VIO_LOOP_NO_TEMPORAL_CONSISTENCY = 6,
+  VIO_LOOP_NO_GEOMETRICAL_CONSISTENCY = 7
+};
+typedef struct VioLoopDetection {          /* DetectionResult :67-84 + what decided it                               */
+  int32_t status;                          /* VIO_LOOP_*                                                             */
+  int32_t query, match;                    /* match = -1 where the reference leaves it unset                         */
+  double  ns_factor;                       /* 1.0 when not computed                                                  */
+  int32_t n_results, n_after_cut;          /* query results; after removeLowScores (0 when the cut was not reached)  */
+  int32_t island_first, island_last, island_best_entry;  /* the chosen island; -1 / 0.0 when there is none           */
+  double island_score, island_best_score;
+  int32_t consistent_entries;              /* m_window.nentries after the call                                       */
+  int32_t n_di_matches, n_inliers;         /* geometric check: pairs of the direct-index matcher; pairs RANSAC kept
+                                            * (0 when it did not run: fewer than max(min_Fpoints, 8) pairs)          */
+} VioLoopDetection;
+
+typedef struct vio_loop_detector vio_loop_detector_t;
+/* A detector for n_sessions sessions of at most max_entries keyframes with at most max_keypoints (<= 4096) descriptors
+ * each. It copies what it needs from the vocabulary and owns its stream and device memory: it stays valid after
+ * vio_vocabulary_destroy. VIO_EINVAL for geom_check other than 1 / 3, di_levels outside 0..L, a vocabulary whose
+ * scoring is not L1.                                                                                               */
+int  vio_loop_detector_create(vio_vocabulary_t *voc, const VioLoopDetectorParams *p, int32_t n_sessions,
+                              int32_t max_entries, int32_t max_keypoints, vio_loop_detector_t **out);
+void vio_loop_detector_destroy(vio_loop_detector_t *d);
+int  vio_loop_detector_get_device(const vio_loop_detector_t *d, int32_t *device);
+/* detectLoop (:668-877) for the newest keyframe of n sessions (each session at most once per call: VIO_EINVAL), one
+ * batch of launches. keys [sum n_keys][2] pixels, desc [sum n_keys][4] words (vio_matcher_* layout). cur_pts / old_pts
+ * [n][pts_stride][2] (optional): the RANSAC-kept pairs of a VIO_LOOP_DETECTED result in the reference's order
+ * (n_inliers each; VIO_EINVAL when pts_stride < max_keypoints). The keyframe's keys, descriptors, BowVector and
+ * FeatureVector stay on the device as entry out[i].query of its session. VIO_ECAP (nothing changed) when a keyframe has
+ * more than max_keypoints descriptors or a session already holds max_entries.                                       */
+int  vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *session, const int32_t *n_keys,
+                              const float *keys, const uint64_t *desc, VioLoopDetection *out,
+                              float *cur_pts, float *old_pts, int32_t pts_stride);
+/* eraseIndex (:1250-1259) -> TemplatedDatabase::delete_entry: the entries' postings leave the inverted file, their
+ * BowVector and FeatureVector are emptied; ids are not reused and vio_loop_detector_size keeps counting. Erasing an
+ * entry twice is a no-op; an id outside [0, size) is VIO_EINVAL (nothing erased).                                   */
+int  vio_loop_detector_erase(vio_loop_detector_t *d, int32_t session, int32_t n, const int32_t *entries);
+int  vio_loop_detector_clear(vio_loop_detector_t *d, int32_t session);   /* clear() :882-886: database + window      */
+int  vio_loop_detector_size(const vio_loop_detector_t *d, int32_t session, int32_t *n_entries);
+int  vio_loop_detector_kernel_ms(vio_loop_detector_t *d, float *ms);     /* device time of the last detect           */
+
 /* Keyframe descriptor extraction: BriefExtractor::operator() (loop/keyframe.cpp:395-409) =
  * cv::FAST(im, keys, 20, true); keys += window_pts; DVision::BRIEF::compute
  * (ThirdParty/DVision/BRIEF.cpp:40-105: GaussianBlur 9x9 sigma 2, then n_bits

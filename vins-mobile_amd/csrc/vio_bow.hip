@@ -15,9 +15,10 @@
 //   bow_lookup_kernel   16 lanes per descriptor: every lane takes children (256-bit XOR + popcount), the key
 //                       distance << 20 | child position is min-reduced inside the 16-lane row; one tree level per
 //                       dependent global fetch, thousands of descriptors in flight
-//   bow_vector_kernel   one workgroup per keyframe: bitonic sort of the word ids in LDS, run heads -> unique words, the
-//                       value of a word by the reference's own sequence of additions, L1 norm summed in ascending word
-//                       order by one lane (the order of std::map iteration: bit-identical values)
+//   bow_vector_kernel   (vio_bow_core.h, shared with the loop detector) one workgroup per keyframe: bitonic sort of the
+//                       word ids in LDS, run heads -> unique words, the value of a word by the reference's own sequence
+//                       of additions, L1 norm summed in ascending word order by one lane (the order of std::map
+//                       iteration: bit-identical values)
 //   bow_insert_kernel / bow_candidates_kernel / bow_score_kernel   the database: an inverted file (sorted postings) finds the
 //                       entries that share a word with a query, one wave per such entry sums |q - d| - |q| - |d| over the
 //                       common words in ascending word order (= the order in which queryL1 meets them: bit-identical sums)
@@ -34,11 +35,10 @@
 #include <vector>
 
 #include "vio_amd.h"
+#include "vio_bow_core.h"
 #include "vio_device.h"
 
 namespace {
-
-constexpr int kMaxBowFeatures = 8192;  // descriptors per keyframe the BowVector kernel sorts in LDS
 
 // 16 lanes per descriptor, 4 descriptors per wave
 __global__ __launch_bounds__(256) void bow_lookup_kernel(const unsigned long long *node_desc, const double *node_weight, const int *node_word,
@@ -69,71 +69,6 @@ __global__ __launch_bounds__(256) void bow_lookup_kernel(const unsigned long lon
   if (have && l == 0) word[g] = node_word[node], weight[g] = node_weight[node];
 }
 
-// one workgroup per keyframe: its descriptors' (word, weight) -> ascending unique words with their L1-normalised values
-__global__ __launch_bounds__(256) void bow_vector_kernel(const int *kf_off, const int *word, const double *weight, const double *word_weight,
-                                                          int accumulate, int *bow_count, int *bow_word, double *bow_value, int stride) {
-  __shared__ int key[kMaxBowFeatures];
-  __shared__ int scan[257];
-  __shared__ double norm_s;
-  const int kf = blockIdx.x, o = kf_off[kf], n = kf_off[kf + 1] - o, tid = threadIdx.x, nt = blockDim.x;
-  int np2 = nt;
-  while (np2 < n) np2 <<= 1;
-  for (int i = tid; i < np2; i += nt) key[i] = (i < n && weight[o + i] > 0.0) ? word[o + i] : 0x7fffffff;  // stopped words drop out
-  __syncthreads();
-  for (int k = 2; k <= np2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < np2; i += nt) {
-        const int p = i ^ j;
-        if (p > i) {
-          const int a = key[i], b = key[p];
-          if (((i & k) == 0) == (a > b)) key[i] = b, key[p] = a;
-        }
-      }
-      __syncthreads();
-    }
-  // heads of runs of equal words: every lane owns a contiguous piece of the sorted list
-  const int chunk = np2 / nt, i0 = tid * chunk;
-  int cnt = 0;
-  for (int i = i0; i < i0 + chunk; i++) cnt += key[i] != 0x7fffffff && (i == 0 || key[i] != key[i - 1]);
-  scan[tid + 1] = cnt;
-  if (tid == 0) scan[0] = 0;
-  __syncthreads();
-  if (tid == 0)
-    for (int t = 0; t < nt; t++) scan[t + 1] += scan[t];
-  __syncthreads();
-  const int u = scan[nt];
-  int *ow = bow_word + (size_t)kf * stride;
-  double *ov = bow_value + (size_t)kf * stride;
-  if (u > stride) {  // caller's capacity too small: report the count, write nothing
-    if (tid == 0) bow_count[kf] = -u;
-    return;
-  }
-  int q = scan[tid];
-  for (int i = i0; i < i0 + chunk; i++) {
-    const int wd = key[i];
-    if (wd == 0x7fffffff || (i > 0 && wd == key[i - 1])) continue;
-    int i1 = i + 1;
-    while (i1 < np2 && key[i1] == wd) i1++;
-    // BowVector::addWeight adds the word's weight once per occurrence (in that order: w + w + ...), addIfNotExist keeps it once
-    const double wv = word_weight[wd];
-    double sv = wv;
-    if (accumulate)
-      for (int r = i + 1; r < i1; r++) sv += wv;
-    ow[q] = wd, ov[q] = sv;
-    q++;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double norm = 0.0;
-    for (int r = 0; r < u; r++) norm += fabs(ov[r]);  // ascending word order, like BowVector::normalize over the std::map
-    norm_s = norm;
-    bow_count[kf] = u;
-  }
-  __syncthreads();
-  const double norm = norm_s;
-  if (norm > 0.0)
-    for (int r = tid; r < u; r += nt) ov[r] /= norm;
-}
 
 // ---- the database: inverted file + direct file ----------------------------------------------------------------------
 // TemplatedDatabase keeps, per word, the list of (entry, value) pairs that hold it (m_ifile, TemplatedDatabase.h:439-470)
@@ -174,16 +109,6 @@ __global__ __launch_bounds__(256) void bow_insert_kernel(const unsigned long lon
   }
 }
 
-__device__ __forceinline__ int posting_lower_bound(const unsigned long long *key, int n, unsigned long long k) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int m = (lo + hi) >> 1;
-    if (key[m] < k) lo = m + 1;
-    else hi = m;
-  }
-  return lo;
-}
-
 // flag [n_queries][n_entries] (zeroed), n_cand [n_queries] (zeroed), cand [n_queries][n_entries]
 __global__ __launch_bounds__(256) void bow_candidates_kernel(const unsigned long long *key, int n_post, int n_entries, const int *q_count,
                                                               const int *q_word, int q_stride, const int *max_id, int *flag, int *n_cand,
@@ -201,12 +126,6 @@ __global__ __launch_bounds__(256) void bow_candidates_kernel(const unsigned long
       if (atomicExch(&flag[(size_t)q * n_entries + e], 1) == 0) cand[(size_t)q * n_entries + atomicAdd(&n_cand[q], 1)] = e;
     }
   }
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), lane);
-  return __longlong_as_double((long long)((unsigned long long)hi << 32 | lo));
 }
 
 constexpr int kBowQueryLds = 8192;  // query words staged in LDS (a BowVector has at most kMaxBowFeatures words)
@@ -270,23 +189,6 @@ __global__ __launch_bounds__(256) void bow_score_kernel(const int *db_off, const
 }  // namespace
 
 using vio::DevBuf;
-
-struct vio_vocabulary {
-  int device = -1;
-  int32_t k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0;  // n_nodes incl. the root
-  int height = 0;  // levels below the root: bounds the descent of bow_lookup_kernel
-  hipStream_t stream = nullptr;
-  DevBuf<unsigned long long> d_desc;
-  DevBuf<double> d_weight, d_wweight;  // per node; per word
-  DevBuf<int> d_word, d_child_off, d_child;
-  // transform scratch
-  DevBuf<unsigned long long> t_desc;
-  DevBuf<int> t_word, t_off, t_bcount, t_bword;
-  DevBuf<double> t_weight, t_bvalue;
-  ~vio_vocabulary() {
-    if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
-  }
-};
 
 // (A database takes the word count from its vocabulary at create and owns its stream: it keeps working, and can be
 // destroyed, after the vocabulary is gone, and two threads may use a vocabulary and its database side by side.)

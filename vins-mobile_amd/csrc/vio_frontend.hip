@@ -2614,3 +2614,26 @@ int vio_fundamental_ransac(const VioConfig *cfg, const float *pts1, const float 
 }
 
 }  // extern "C"
+
+// findFundamentalMat for many independent point sets in one launch (the loop detector's geometric check): problem p =
+// p1 / p2 [p][stride][2] with count[p] pairs, one workgroup each, the same block routine as vio_fundamental_ransac.
+// A problem with fewer than min_count pairs is left alone (its mask is not written).
+__global__ __launch_bounds__(256) void ransac_batch_kernel(const float *p1, const float *p2, const int *count, int stride, int min_count,
+                                                           float thresh, double conf, uint8_t *mask) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  RansacShared &R = *reinterpret_cast<RansacShared *>(smem_raw);
+  const int p = blockIdx.x, n = count[p];
+  if (n < min_count || n > stride) return;  // (uniform per workgroup)
+  fundamental_ransac_block(R, p1 + 2 * (size_t)p * stride, p2 + 2 * (size_t)p * stride, n, thresh, conf, mask + (size_t)p * stride);
+}
+
+namespace vio {
+int fundamental_ransac_batch(hipStream_t st, const float *p1, const float *p2, const int *count, int n_prob, int stride, int min_count,
+                             float thresh, double conf, uint8_t *mask) {
+  if (n_prob < 1) return VIO_OK;
+  hipLaunchKernelGGL(ransac_batch_kernel, dim3(n_prob), dim3(256), sizeof(RansacShared), st, p1, p2, count, stride, min_count, thresh, conf,
+                     mask);
+  HIP_OK(hipGetLastError());
+  return VIO_OK;
+}
+}  // namespace vio

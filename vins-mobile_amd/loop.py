@@ -1,5 +1,7 @@
 """Host-side mirror of the loop-closure producer's descriptor side: KeyFrame::searchByDes / findConnectionWithOldFrame
-(VINS_ios/loop/keyframe.cpp:161-187, 267-273). Plumbing over csrc/vio_loop.hip for tests; no compute here."""
+(VINS_ios/loop/keyframe.cpp:161-187, 267-273), descriptor extraction, the bag-of-words query and the loop detector
+(TemplatedLoopDetector::detectLoop). Plumbing over csrc/vio_loop.hip, vio_brief.hip, vio_bow.hip and vio_loop_detector.hip for
+tests and tools; no compute here."""
 import ctypes as C
 
 import numpy as np
@@ -248,3 +250,130 @@ class BowDatabase:
         if rc != abi.VIO_OK:
             raise RuntimeError("vio_bow_database_query failed rc=%d" % rc)
         return [(ent[q, :nr[q]].copy(), sc[q, :nr[q]].copy()) for q in range(nq)]
+
+
+# ---- the loop detector (DLoopDetector's detectLoop for n sessions: csrc/vio_loop_detector.hip) --------------------------
+class VioLoopDetectorParams(C.Structure):
+    _fields_ = [("use_nss", C.c_int32), ("alpha", C.c_float), ("k", C.c_int32), ("geom_check", C.c_int32), ("di_levels", C.c_int32),
+                ("dislocal", C.c_int32), ("max_db_results", C.c_int32), ("min_nss_factor", C.c_float),
+                ("min_matches_per_group", C.c_int32), ("max_intragroup_gap", C.c_int32), ("max_distance_between_groups", C.c_int32),
+                ("max_distance_between_queries", C.c_int32), ("min_Fpoints", C.c_int32), ("max_neighbor_ratio", C.c_double),
+                ("f_threshold", C.c_double), ("f_confidence", C.c_double), ("min_inliers", C.c_int32)]
+
+
+class VioLoopDetection(C.Structure):
+    _fields_ = [("status", C.c_int32), ("query", C.c_int32), ("match", C.c_int32), ("ns_factor", C.c_double), ("n_results", C.c_int32),
+                ("n_after_cut", C.c_int32), ("island_first", C.c_int32), ("island_last", C.c_int32), ("island_best_entry", C.c_int32),
+                ("island_score", C.c_double), ("island_best_score", C.c_double), ("consistent_entries", C.c_int32),
+                ("n_di_matches", C.c_int32), ("n_inliers", C.c_int32)]
+
+
+LOOP_STATUS = ("LOOP_DETECTED", "CLOSE_MATCHES_ONLY", "NO_DB_RESULTS", "LOW_NSS_FACTOR", "LOW_SCORES", "NO_GROUPS",
+               "NO_TEMPORAL_CONSISTENCY", "NO_GEOMETRICAL_CONSISTENCY")   # DetectionStatus, TemplatedLoopDetector.h:46-64
+
+
+def bind_loop_detector(lib):
+    vp, pp, dp = C.c_void_p, C.POINTER(VioLoopDetectorParams), C.POINTER(VioLoopDetection)
+    lib.vio_loop_detector_params_default.argtypes = [pp, C.c_float]
+    lib.vio_loop_detector_params_default.restype = None
+    lib.vio_loop_detector_create.argtypes = [vp, pp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    lib.vio_loop_detector_destroy.argtypes = [vp]
+    lib.vio_loop_detector_destroy.restype = None
+    lib.vio_loop_detector_get_device.argtypes = [vp, _i32p]
+    lib.vio_loop_detector_detect.argtypes = [vp, C.c_int32, _i32p, _i32p, _fp, _u64p, dp, _fp, _fp, C.c_int32]
+    lib.vio_loop_detector_erase.argtypes = [vp, C.c_int32, C.c_int32, _i32p]
+    lib.vio_loop_detector_clear.argtypes = [vp, C.c_int32]
+    lib.vio_loop_detector_size.argtypes = [vp, C.c_int32, _i32p]
+    lib.vio_loop_detector_kernel_ms.argtypes = [vp, _fp]
+    return lib
+
+
+def loop_detector_params(frequency=1.0, **over):
+    """What the app constructs (Parameters(height, width) + set(frequency)), with fields overridden by keyword."""
+    lib = bind_loop_detector(abi.load_product())
+    p = VioLoopDetectorParams()
+    lib.vio_loop_detector_params_default(C.byref(p), frequency)
+    for k, v in over.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+class LoopDetectorError(RuntimeError):
+    def __init__(self, what, rc):
+        RuntimeError.__init__(self, "%s failed rc=%d" % (what, rc))
+        self.rc = rc
+
+
+class LoopDetector:
+    """TemplatedLoopDetector<FBrief> for n_sessions sessions that share a vocabulary; detect() takes the newest keyframe
+    of any subset of them."""
+
+    def __init__(self, voc, params=None, n_sessions=1, max_entries=256, max_keypoints=1024):
+        self.voc, self.lib = voc, bind_loop_detector(voc.lib)
+        self.params = params if params is not None else loop_detector_params()
+        self.n_sessions, self.max_keypoints = n_sessions, max_keypoints
+        self._h = C.c_void_p()
+        rc = self.lib.vio_loop_detector_create(voc._h, C.byref(self.params), n_sessions, max_entries, max_keypoints, C.byref(self._h))
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_create", rc)
+
+    def close(self):
+        if self._h:
+            self.lib.vio_loop_detector_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def detect(self, sessions, keys_list, desc_list):
+        """sessions: ids; keys_list / desc_list: per keyframe float [m][2] pixels, uint64 [m][4].
+        -> per keyframe (dict of the VioLoopDetection fields, cur_pts [n_inliers][2], old_pts [n_inliers][2])."""
+        n = len(sessions)
+        ses = np.ascontiguousarray(sessions, np.int32)
+        nk = np.array([len(d_) for d_ in desc_list], np.int32)
+        keys = np.ascontiguousarray(np.concatenate([np.asarray(k_, np.float32).reshape(-1, 2) for k_ in keys_list] + [np.zeros((0, 2), np.float32)]))
+        desc = np.ascontiguousarray(np.concatenate([np.asarray(d_, np.uint64).reshape(-1, 4) for d_ in desc_list] + [np.zeros((0, 4), np.uint64)]))
+        assert len(keys) == len(desc)
+        out = (VioLoopDetection * n)()
+        stride = self.max_keypoints
+        cur, old = np.zeros((n, stride, 2), np.float32), np.zeros((n, stride, 2), np.float32)
+        rc = self.lib.vio_loop_detector_detect(self._h, n, ses.ctypes.data_as(_i32p), nk.ctypes.data_as(_i32p), keys.ctypes.data_as(_fp),
+                                               desc.ctypes.data_as(_u64p), out, cur.ctypes.data_as(_fp), old.ctypes.data_as(_fp), stride)
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_detect", rc)
+        res = []
+        for q in range(n):
+            r = {f: getattr(out[q], f) for f, _ in VioLoopDetection._fields_}
+            m = r["n_inliers"] if r["status"] == 0 else 0
+            res.append((r, cur[q, :m].copy(), old[q, :m].copy()))
+        return res
+
+    def erase(self, session, entries):
+        e = np.ascontiguousarray(entries, np.int32)
+        rc = self.lib.vio_loop_detector_erase(self._h, session, len(e), e.ctypes.data_as(_i32p))
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_erase", rc)
+
+    def clear(self, session):
+        rc = self.lib.vio_loop_detector_clear(self._h, session)
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_clear", rc)
+
+    def size(self, session):
+        n = C.c_int32(-1)
+        rc = self.lib.vio_loop_detector_size(self._h, session, C.byref(n))
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_size", rc)
+        return n.value
+
+    def device(self):
+        dev = C.c_int32(-1)
+        rc = self.lib.vio_loop_detector_get_device(self._h, C.byref(dev))
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_get_device", rc)
+        return dev.value
+
+    def kernel_ms(self):
+        ms = C.c_float(0)
+        rc = self.lib.vio_loop_detector_kernel_ms(self._h, C.byref(ms))
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_kernel_ms", rc)
+        return ms.value
