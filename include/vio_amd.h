@@ -177,7 +177,7 @@ typedef struct VioSolveStats {
   double final_cost;     /* summary.final_cost VINS.cpp:660 */
   int32_t iterations;    /* iteration records incl. iteration 0 */
   int32_t termination;   /* 0 NO_CONVERGENCE, 1 CONVERGENCE, 2 FAILURE */
-  int32_t num_successful_steps;
+  int32_t num_successful_steps;   /* vio_pnp_*: both counts -1 for a window of constant frames only (Summary's default) */
   int32_t num_unsuccessful_steps;
   /* per-iteration trace (IterationSummary, CS/include/ceres/iteration_callback.h) */
   double it_cost[VIO_MAX_TRACE];

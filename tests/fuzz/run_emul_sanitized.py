@@ -1,7 +1,8 @@
 """Runs the host builds of both solver kernels (window solver: the device sections on the wave64 SIMT emulator; PnP: the
 one-thread emulation; built with -fsanitize=address,undefined by tests/test_host_sanitizers.py, this process started
-with the sanitizer runtimes preloaded) over the golden windows, the odd-shaped seeded windows and the PnP cases: an
-out-of-range index in the kernel SOURCE shows up as a sanitizer report."""
+with the sanitizer runtimes preloaded) over the golden windows, the odd-shaped seeded windows, the PnP cases and the PnP
+edge windows (rejected steps, 2 and 8 frames, no factor to over 3000): an out-of-range index in the kernel SOURCE shows
+up as a sanitizer report."""
 import sys, ctypes as C, numpy as np
 import os
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,4 +27,6 @@ lp=C.CDLL(sys.argv[2]); lp.emul_pnp_solve.argtypes=None
 cfg=abi.default_config()
 for c in T.CASES:
     w=T.make_window(cfg,*c); pkg.pnp.solve_with(lp.emul_pnp_solve,cfg,w)
-print("pnp emulation under ASan/UBSan:", len(T.CASES), "windows clean")
+for w in T.edge_windows(cfg).values():
+    pkg.pnp.solve_with(lp.emul_pnp_solve,cfg,w)
+print("pnp emulation under ASan/UBSan:", len(T.CASES)+len(T.EDGE_CASES), "windows clean")

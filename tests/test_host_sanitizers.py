@@ -38,7 +38,7 @@ def test_host_code_walk_is_clean_under_asan_ubsan_and_tsan(tmp_path):
 
 def test_kernel_sources_are_clean_under_asan_ubsan(tmp_path):
     """solver_core.h / marg_core.h compiled for the host with -DVIO_SIMT -- the DEVICE sections, one fiber per work-item
-    (tests/emul/simt.h) -- and pnp_core.h with -DVIO_EMUL, both WITH sanitizers, run over 26 + 7 windows
+    (tests/emul/simt.h) -- and pnp_core.h with -DVIO_EMUL, both WITH sanitizers, run over 26 + 26 windows
     (tests/fuzz/run_emul_sanitized.py): index arithmetic of the kernel source against the packed batch arrays, the carved
     LDS (a heap buffer here) and the scratch arrays."""
     import sys
@@ -55,4 +55,5 @@ def test_kernel_sources_are_clean_under_asan_ubsan(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "fuzz", "run_emul_sanitized.py"), so_b, so_p], env=env,
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-4000:]
-    assert "26 windows clean" in r.stdout and "7 windows clean" in r.stdout
+    assert "backend emulation under ASan/UBSan: 26 windows clean" in r.stdout
+    assert "pnp emulation under ASan/UBSan: 26 windows clean" in r.stdout

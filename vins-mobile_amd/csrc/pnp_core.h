@@ -9,11 +9,11 @@
 // weight track_num / 10, CauchyLoss(1)). Options (:317-326): DENSE_SCHUR, DOGLEG, max_num_iterations 5; the 0.01 s
 // wall-clock limit is not reproduced (results would depend on the machine).
 //
-// One workgroup per window. The normal equations have at most 7 x 9 = 63 unknowns: the matrix lives in LDS as one dense
-// block, factors are evaluated by all lanes and accumulated with LDS atomics, the factorization is a right-looking
-// Cholesky with one lane per row. The trust-region loop is the one of the window solver (solver_core.h::minimize, i.e.
-// Ceres' TrustRegionMinimizer + DoglegStrategy, CSI/trust_region_minimizer.cc, CSI/dogleg_strategy.cc) without
-// landmark blocks.
+// One workgroup per window. The normal equations have at most kMaxFrames x 9 = 72 unknowns (VIO_PNP_MAX_FRAMES = 8; the
+// reference's 7 frames give 63): the matrix lives in LDS as one dense block, factors are evaluated by all lanes and
+// accumulated with LDS atomics, the factorization is a right-looking Cholesky with one lane per row. The trust-region
+// loop is the one of the window solver (solver_core.h::minimize, i.e. Ceres' TrustRegionMinimizer + DoglegStrategy,
+// CSI/trust_region_minimizer.cc, CSI/dogleg_strategy.cc) without landmark blocks.
 #pragma once
 #include "solver_core.h"
 
@@ -360,8 +360,8 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
   int it = 0, n_ok = 1, n_bad = 0, invalid_run = 0, termination = 0, recorded = 1;
   double min_rec = x_cost;
   if (cx.tid == 0) sd[0] = x_cost;
-  if (dim == 0) {  // every block constant: Ceres returns before its first iteration record
-    termination = 1, recorded = 0, n_ok = 0;
+  if (dim == 0) {  // every block constant: Ceres returns before its first iteration record, its step counts left at -1
+    termination = 1, recorded = 0, n_ok = -1, n_bad = -1;
   } else {
     double x_norm = -1.0;  // "Invalid value", trust_region_minimizer.cc:168
     VIO_PARFOR(i, dim) w.sc[i] = 1.0 / (1.0 + sqrt(w.H[i * dim + i]));  // Jacobi scaling, :239-254

@@ -40,8 +40,10 @@ class PnpWindow:
 def stats_dict(st):
     n = st.iterations
     return dict(initial_cost=st.initial_cost, final_cost=st.final_cost, iterations=n, termination=st.termination,
+                num_successful_steps=st.num_successful_steps, num_unsuccessful_steps=st.num_unsuccessful_steps,
                 it_cost=np.array(st.it_cost[:n]), it_flags=np.array(st.it_flags[:n]), it_radius=np.array(st.it_radius[:n]),
-                it_step_norm=np.array(st.it_step_norm[:n]), it_gradient_max_norm=np.array(st.it_gradient_max_norm[:n]))
+                it_step_norm=np.array(st.it_step_norm[:n]), it_relative_decrease=np.array(st.it_relative_decrease[:n]),
+                it_gradient_max_norm=np.array(st.it_gradient_max_norm[:n]))
 
 
 def solve_with(fn, cfg, w):
