@@ -18,6 +18,8 @@
 
 #include <type_traits>
 
+#include "vio_exact_math.h"
+
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -599,7 +601,13 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
 }
 
 // ---- findFundamentalMat(FM_RANSAC): device version of calib3d fundam.cpp / ptsetreg.cpp -------------------------
-__device__ int solve_cubic_dev(const double c[4], double r[3]) {
+// (kept out of line: inlined, the double-double code cost the RANSAC path of track_update_kernel its last free registers)
+__device__ __attribute__((noinline)) double exact_fn(int which, double x) {
+  return which == 0 ? vio_xm::acos_cr(x) : which == 1 ? vio_xm::cos_cr(x) : vio_xm::pow_cr(x, 0.333333333333);
+}
+// exact: acos, cos and pow correctly rounded (vio_exact_math.h) instead of the device library's, which agree with the host's
+// only to within an ulp. The LMedS branch asks for it: there the winning model is decided by the roots' last bit.
+__device__ int solve_cubic_dev(const double c[4], double r[3], bool exact) {
   double a0 = c[0], a1 = c[1], a2 = c[2], a3 = c[3];
   double x0 = 0, x1 = 0, x2 = 0;
   int n = 0;
@@ -623,13 +631,16 @@ __device__ int solve_cubic_dev(const double c[4], double r[3]) {
     double Qcubed = Q * Q * Q, d = Qcubed - R * R;
     const double kPi = 3.14159265358979323846;
     if (d >= 0) {
-      double theta = acos(R / sqrt(Qcubed)), sqrtQ = sqrt(Q);
+      const double av = R / sqrt(Qcubed);
+      double theta = exact ? exact_fn(0, av) : acos(av), sqrtQ = sqrt(Q);
       double t0 = -2 * sqrtQ, t1 = theta * (1. / 3), t2 = a1 * (1. / 3);
-      x0 = t0 * cos(t1) - t2, x1 = t0 * cos(t1 + (2. * kPi / 3)) - t2, x2 = t0 * cos(t1 + (4. * kPi / 3)) - t2;
+      const double g0 = t1, g1 = t1 + (2. * kPi / 3), g2 = t1 + (4. * kPi / 3);
+      if (exact) x0 = t0 * exact_fn(1, g0) - t2, x1 = t0 * exact_fn(1, g1) - t2, x2 = t0 * exact_fn(1, g2) - t2;
+      else x0 = t0 * cos(g0) - t2, x1 = t0 * cos(g1) - t2, x2 = t0 * cos(g2) - t2;
       n = 3;
     } else {
       d = sqrt(-d);
-      double e = pow(d + fabs(R), 0.333333333333);
+      double e = exact ? exact_fn(2, d + fabs(R)) : pow(d + fabs(R), 0.333333333333);
       if (R > 0) e = -e;
       x0 = (e + Q / e) - a1 * (1. / 3);
       n = 1;
@@ -656,7 +667,7 @@ struct SevenPointWork {
 // elements, every lane reads its factors and pivot-row entries before anyone writes) run across the lanes; every element
 // sees exactly the operations of the serial restatement (oracle run7point), so the result is bit-identical. The cubic and the model assembly
 // (~300 flops) stay on lane 0. Returns the number of models on every lane of the group.
-__device__ __forceinline__ int run7point_group(const float *ms1, const float *ms2, double *fmatrix, SevenPointWork &wk, int l) {
+__device__ __forceinline__ int run7point_group(const float *ms1, const float *ms2, double *fmatrix, SevenPointWork &wk, int l, bool exact) {
   double *a = wk.a, *f1 = wk.f1, *f2 = wk.f2;
   int *colperm = wk.colperm;
   auto group_sync = [] {
@@ -753,7 +764,7 @@ __device__ __forceinline__ int run7point_group(const float *ms1, const float *ms
            f2[6] * (f1[1] * f1[5] - f1[2] * f1[4]) - f2[7] * (f1[0] * f1[5] - f1[2] * f1[3]) +
            f2[8] * (f1[0] * f1[4] - f1[1] * f1[3]);
     c[0] = f1[0] * t0 - f1[1] * t1 + f1[2] * t2;
-    n = solve_cubic_dev(c, r);
+    n = solve_cubic_dev(c, r, exact);
     if (n >= 1 && n <= 3)
       for (int k = 0; k < n; k++, fmatrix += 9) {
         double lambda = r[k], mu = 1., s = f1[8] * r[k] + f2[8];
@@ -817,12 +828,20 @@ struct RansacShared {
   double med[kHypBatch][3], min_median;  // LMedS (fewer than 15 correspondences)
 };
 
-// Block-cooperative RANSAC over `count` correspondences (m1, m2 in LDS or global). Writes mask[count] (1 = inlier).
+// Block-cooperative RANSAC over `count` correspondences; pts(i) -> (x1, y1, x2, y2) of correspondence i, from LDS
+// (track_update_kernel's packed list) or global memory (GlobalPts). Writes mask[count] (1 = inlier).
 // Exactly reproduces the sequential loop of RANSACPointSetRegistrator::run: subsets are drawn in order from one RNG
 // stream; hypotheses are evaluated a batch at a time and then scanned in order with the adaptive iteration bound.
-template <class MaskT>
-__device__ void fundamental_ransac_block(RansacShared &S, const float *m1, const float *m2, int count, float thresh,
-                                         double confidence, MaskT *mask, long long *prof = nullptr) {
+// Forced inline: the callers' operands keep their address space (LDS arrays are read with LDS instructions, not as flat
+// accesses) and there is no call frame (as a function with two call sites in track_update_kernel it cost 120 loads and 119
+// stores to the private segment per call: the frame plus the spills under the kernel's 256-register cap).
+struct GlobalPts {
+  const float *m1, *m2;
+  __device__ __forceinline__ float4 operator()(int i) const { return make_float4(m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1]); }
+};
+template <class MaskT, class Pts>
+__device__ __forceinline__ void fundamental_ransac_block(RansacShared &S, const Pts pts, int count, float thresh, double confidence,
+                                                         MaskT *mask, long long *prof = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x;
   long long pt = prof ? clock64() : 0;
 #define RS_STAMP(k)                                                    \
@@ -873,8 +892,9 @@ __device__ void fundamental_ransac_block(RansacShared &S, const float *m1, const
               if (idx_i == idx[j]) break;
             if (j == i) break;
           }
-          S.ms1[h][2 * i] = m1[2 * idx_i], S.ms1[h][2 * i + 1] = m1[2 * idx_i + 1];
-          S.ms2[h][2 * i] = m2[2 * idx_i], S.ms2[h][2 * i + 1] = m2[2 * idx_i + 1];
+          const float4 q = pts(idx_i);
+          S.ms1[h][2 * i] = q.x, S.ms1[h][2 * i + 1] = q.y;
+          S.ms2[h][2 * i] = q.z, S.ms2[h][2 * i + 1] = q.w;
           i++;
         }
         if (with_check && i == model_points && (have_collinear_dev(S.ms1[h], i) || have_collinear_dev(S.ms2[h], i))) continue;
@@ -914,9 +934,10 @@ __device__ void fundamental_ransac_block(RansacShared &S, const float *m1, const
     __syncthreads();
     RS_STAMP(0);
     for (int it = tid; it < nb * 7; it += nt) {
-      const int h = it / 7, i = it - 7 * h, id = S.idx[h][i];
-      S.ms1[h][2 * i] = m1[2 * id], S.ms1[h][2 * i + 1] = m1[2 * id + 1];
-      S.ms2[h][2 * i] = m2[2 * id], S.ms2[h][2 * i + 1] = m2[2 * id + 1];
+      const int h = it / 7, i = it - 7 * h;
+      const float4 q = pts(S.idx[h][i]);
+      S.ms1[h][2 * i] = q.x, S.ms1[h][2 * i + 1] = q.y;
+      S.ms2[h][2 * i] = q.z, S.ms2[h][2 * i + 1] = q.w;
     }
     __syncthreads();
     if (tid < nb) S.coll[tid] = (have_collinear_dev(S.ms1[tid], 7) || have_collinear_dev(S.ms2[tid], 7)) ? 1 : 0;
@@ -942,7 +963,7 @@ __device__ void fundamental_ransac_block(RansacShared &S, const float *m1, const
     // ---- phase 2: 7-point models, 16 lanes per hypothesis
     for (int h = tid >> 4; h < nb; h += nt >> 4) {
       int n = 0;
-      if (S.valid[h]) n = run7point_group(S.ms1[h], S.ms2[h], S.F[h], S.work[h], tid & 15);
+      if (S.valid[h]) n = run7point_group(S.ms1[h], S.ms2[h], S.F[h], S.work[h], tid & 15, lmeds);
       if ((tid & 15) == 0) {
         S.nmodels[h] = n < 0 ? 0 : n;
         S.good[h][0] = S.good[h][1] = S.good[h][2] = 0;
@@ -957,7 +978,8 @@ __device__ void fundamental_ransac_block(RansacShared &S, const float *m1, const
         if (k >= S.nmodels[h]) continue;
         int bits[14];  // count <= 14; std::sort on the float bit patterns as ints (ptsetreg.cpp)
         for (int i = 0; i < count; i++) {
-          const int b = __float_as_int(epipolar_error(S.F[h] + 9 * k, m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1]));
+          const float4 q = pts(i);
+          const int b = __float_as_int(epipolar_error(S.F[h] + 9 * k, q.x, q.y, q.z, q.w));
           int j = i;
           for (; j > 0 && bits[j - 1] > b; j--) bits[j] = bits[j - 1];
           bits[j] = b;
@@ -969,8 +991,10 @@ __device__ void fundamental_ransac_block(RansacShared &S, const float *m1, const
     for (int item = tid; item < nb * 3 * count; item += nt) {
       int hk = item / count, i = item - hk * count;
       int h = hk / 3, k = hk - 3 * h;
-      if (k < S.nmodels[h] && epipolar_inlier(S.F[h] + 9 * k, m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1], t))
-        atomicAdd(&S.good[h][k], 1);
+      if (k < S.nmodels[h]) {
+        const float4 q = pts(i);
+        if (epipolar_inlier(S.F[h] + 9 * k, q.x, q.y, q.z, q.w, t)) atomicAdd(&S.good[h][k], 1);
+      }
     }
     __syncthreads();
     RS_STAMP(3);
@@ -1012,11 +1036,15 @@ __device__ void fundamental_ransac_block(RansacShared &S, const float *m1, const
     double sigma = 2.5 * 1.4826 * (1 + 5. / (count - model_points)) * sqrt(S.min_median);
     sigma = fmax(sigma, 0.001);
     const float ts = (float)(sigma * sigma);
-    for (int i = tid; i < count; i += nt)
-      mask[i] = epipolar_inlier(S.bestF, m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1], ts) ? 1 : 0;
+    for (int i = tid; i < count; i += nt) {
+      const float4 q = pts(i);
+      mask[i] = epipolar_inlier(S.bestF, q.x, q.y, q.z, q.w, ts) ? 1 : 0;
+    }
   } else if (!lmeds && S.max_good > 0 && !S.failed_first) {
-    for (int i = tid; i < count; i += nt)
-      mask[i] = epipolar_inlier(S.bestF, m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1], t) ? 1 : 0;
+    for (int i = tid; i < count; i += nt) {
+      const float4 q = pts(i);
+      mask[i] = epipolar_inlier(S.bestF, q.x, q.y, q.z, q.w, t) ? 1 : 0;
+    }
   } else {
     for (int i = tid; i < count; i += nt) mask[i] = 1;
   }
@@ -1046,72 +1074,63 @@ struct TrackerArrays {
   long long *prof;  // null, or cycle stamps of sequence 0's workgroup (VIO_AMD_TU_PROF, tools/tu_prof.sh)
 };
 
-// Stable compaction of the five per-feature arrays by `keep` flags; all arrays staged in LDS.
-// CAP: capacity the LDS arrays are laid out for. The launcher picks the smallest instantiation that holds the tracker's
-// feature slots: with the arrays of the 512-slot layout (95 KB with the RANSAC state) only ONE workgroup fits a CU and the
-// 512 sequences of the bench ran as two rounds; the 256-slot layout is 47 KB.
+// The per-feature arrays are staged in LDS once and never moved: the tracks still alive are a stable list of their slots
+// (idx), which every filter shortens. The launcher picks the smallest instantiation (CAP) that holds the tracker's feature
+// slots: with the 512-slot layout only ONE workgroup fits a CU and the 512 sequences of the bench ran as two rounds.
 template <int CAP>
 struct TrackShared {
-  float pre[CAP][2], cur[CAP][2], forw[CAP][2];
+  float pre[CAP][2], cur[CAP][2], forw[CAP][2];  // by slot, as loaded
   int ids[CAP], cnt[CAP];
-  int keep[CAP];  // (dword flags: sub-dword LDS accesses are slow)
+  int keep[CAP];  // flags of the filter in hand: by slot for the first one, by list position afterwards (dword flags: sub-dword LDS accesses are slow)
+  int idx[CAP];   // the list
   int pos[CAP];
-  float t_pre[CAP][2], t_cur[CAP][2], t_forw[CAP][2];
-  int t_ids[CAP], t_cnt[CAP];
-  int n;
+  float4 pack[CAP];  // (x1, y1, x2, y2) of the list's correspondences, for the F-test in hand
+  int n;             // length of the list
   int order[CAP];
+  int ncnt[CAP];  // publish frames: track_cnt + 1, by list position
   int ixy[CAP][2];
   unsigned long long inside[CAP][CAP / 64];
   int hw[2 * kMaxRadius + 1];  // half-widths of the filled circle (setMask), staged from global memory
 };
 
-template <int CAP>
-__device__ void compact_block(TrackShared<CAP> &T) {
+// Shortens the list to the entries whose keep flag is set, in order: idx[rank of i among the kept] = idx[i] (FIRST: = i, the
+// flags are by slot and the list is all of them). The caller's last barrier lies behind the writes of keep[] and T.n.
+// Exclusive rank: a ballot per wave and chunk of blockDim items, the waves' counts through LDS. In place: a chunk reads its
+// entries before its barrier and writes behind it, to positions no later chunk reads.
+// (This replaces a compaction that also copied the eight arrays to temporaries and back after every filter: six barriers and
+// two passes over the arrays per call, three calls per publish frame.)
+template <int CAP, bool FIRST>
+__device__ __forceinline__ void shorten_list(TrackShared<CAP> &T) {
+  __shared__ int s_wcnt[16];
   const int tid = threadIdx.x, nt = blockDim.x;
+  const int wave = tid >> 6, lane = tid & 63, nwv = nt >> 6;
   const int n = T.n;
-  __syncthreads();  // everyone has read n
-  // exclusive prefix sum of keep (n <= kMaxCap): a ballot per wave and chunk of blockDim items, the waves' counts through LDS
-  // (one work-item walking the flags was a chain of ~n LDS round trips, three times per frame)
-  {
-    __shared__ int s_wcnt[16];
-    const int wave = tid >> 6, lane = tid & 63, nwv = nt >> 6;
-    int running = 0;
-    for (int base = 0; base < n; base += nt) {
-      const int i = base + tid;
-      const bool k = i < n && T.keep[i];
-      const unsigned long long b = __builtin_amdgcn_ballot_w64(k);
-      if (lane == 0) s_wcnt[wave] = __builtin_popcountll(b);
-      __syncthreads();
-      int off = running, total = 0;
-      for (int w = 0; w < nwv; w++) {
-        const int c = s_wcnt[w];
-        if (w < wave) off += c;
-        total += c;
-      }
-      if (i < n) T.pos[i] = off + __builtin_popcountll(b & ((1ull << lane) - 1ull));
-      running += total;
-      __syncthreads();
+  int running = 0;
+  for (int base = 0; base < n; base += nt) {
+    const int i = base + tid;
+    const bool k = i < n && T.keep[i];
+    const int v = FIRST ? i : (i < n ? T.idx[i] : 0);
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(k);
+    if (lane == 0) s_wcnt[wave] = __builtin_popcountll(b);
+    __syncthreads();
+    int off = running, total = 0;
+    for (int w = 0; w < nwv; w++) {
+      const int c = s_wcnt[w];
+      if (w < wave) off += c;
+      total += c;
     }
-    if (tid == 0) T.n = running;
+    if (k) T.idx[off + __builtin_popcountll(b & ((1ull << lane) - 1ull))] = v;
+    running += total;
+    if (base + nt < n) __syncthreads();  // (the next chunk writes the waves' counts again)
   }
-  __syncthreads();
-  for (int i = tid; i < n; i += nt)
-    if (T.keep[i]) {
-      int p = T.pos[i];
-      T.t_pre[p][0] = T.pre[i][0], T.t_pre[p][1] = T.pre[i][1];
-      T.t_cur[p][0] = T.cur[i][0], T.t_cur[p][1] = T.cur[i][1];
-      T.t_forw[p][0] = T.forw[i][0], T.t_forw[p][1] = T.forw[i][1];
-      T.t_ids[p] = T.ids[i], T.t_cnt[p] = T.cnt[i];
-    }
-  __syncthreads();
-  for (int i = tid; i < T.n; i += nt) {
-    T.pre[i][0] = T.t_pre[i][0], T.pre[i][1] = T.t_pre[i][1];
-    T.cur[i][0] = T.t_cur[i][0], T.cur[i][1] = T.t_cur[i][1];
-    T.forw[i][0] = T.t_forw[i][0], T.forw[i][1] = T.t_forw[i][1];
-    T.ids[i] = T.t_ids[i], T.cnt[i] = T.t_cnt[i];
-  }
+  if (tid == 0) T.n = running;  // (everyone read n ahead of the chunk barrier; n == 0 stays 0)
   __syncthreads();
 }
+
+struct PackedPts {
+  const float4 *pack;
+  __device__ __forceinline__ float4 operator()(int i) const { return pack[i]; }
+};
 
 // One workgroup per sequence: everything between the LK call and goodFeaturesToTrack.
 // (two waves per SIMD: left to itself the compiler takes 289 registers per work-item for the double-precision 7-point code --
@@ -1142,47 +1161,60 @@ __global__ __launch_bounds__(256, 2) void track_update_kernel(TrackerArrays A, i
   }
   __syncthreads();
   TU_STAMP(1);
-  if (n0 > 0) {
-    compact_block(T);
-    TU_STAMP(2);
-    if (T.n >= 8) {  // findFundamentalMat(cur_pts, forw_pts, FM_RANSAC, F_THRESHOLD, 0.99) :194-205
-      fundamental_ransac_block(R, &T.cur[0][0], &T.forw[0][0], T.n, A.f_thresh, A.f_conf, T.keep, A.prof && seq == 0 ? A.prof + 16 : nullptr);
-      TU_STAMP(3);
-      compact_block(T);
+  shorten_list<CAP, true>(T);
+  TU_STAMP(2);
+  // The two F-tests share ONE inlined copy of the RANSAC code (the pass loop is kept a loop):
+  //   pass 0  findFundamentalMat(cur_pts, forw_pts, FM_RANSAC, F_THRESHOLD, 0.99) :194-205
+  //   pass 1  rejectWithF: (pre_pts, forw_pts) :89-103, publish frames only
+  // Every condition below is uniform over the workgroup (T.n is read behind a barrier), so every barrier is reached by all.
+  const int npass = publish ? 2 : 1;
+#pragma nounroll
+  for (int pass = 0; pass < npass; pass++) {
+    if (pass) TU_STAMP(5);
+    const int np = T.n;
+    if (np >= 8) {
+      // the list's correspondences side by side: the F-test reads position i with one LDS instruction and no index in between
+      const float(*from)[2] = pass ? T.pre : T.cur;
+      for (int i = tid; i < np; i += nt) {
+        const int o = T.idx[i];
+        T.pack[i] = make_float4(from[o][0], from[o][1], T.forw[o][0], T.forw[o][1]);
+      }
+      __syncthreads();
+      fundamental_ransac_block(R, PackedPts{T.pack}, np, A.f_thresh, A.f_conf, T.keep, A.prof && seq == 0 ? A.prof + 16 + 8 * pass : nullptr);
+      TU_STAMP(pass ? 6 : 3);
+      shorten_list<CAP, false>(T);
+    }
+    if (pass == 0) {
+      TU_STAMP(4);
+      // the point list solveVinsPnP joins with the solved landmarks (:207): behind the first rejection, ahead of the
+      // publish-frame steps (rejectWithF :235, setMask :255) that drop more of it
+      for (int i = tid; i < T.n; i += nt) {
+        const int o = T.idx[i];
+        A.pnp_pts[(base + i) * 2] = T.forw[o][0], A.pnp_pts[(base + i) * 2 + 1] = T.forw[o][1];
+        A.pnp_ids[base + i] = T.ids[o];
+      }
+      if (tid == 0) A.n_pnp[seq] = T.n;
     }
   }
-  TU_STAMP(4);
-  // the point list solveVinsPnP joins with the solved landmarks (:207): behind the first rejection, ahead of the
-  // publish-frame steps (rejectWithF :235, setMask :255) that drop more of it
-  for (int i = tid; i < T.n; i += nt) {
-    A.pnp_pts[(base + i) * 2] = T.forw[i][0], A.pnp_pts[(base + i) * 2 + 1] = T.forw[i][1];
-    A.pnp_ids[base + i] = T.ids[i];
-  }
-  if (tid == 0) A.n_pnp[seq] = T.n;
+  const int n = T.n;
   if (publish) {
-    if (T.n >= 8) {  // rejectWithF: (pre_pts, forw_pts) :89-103
-      TU_STAMP(5);
-      fundamental_ransac_block(R, &T.pre[0][0], &T.forw[0][0], T.n, A.f_thresh, A.f_conf, T.keep, A.prof && seq == 0 ? A.prof + 24 : nullptr);
-      TU_STAMP(6);
-      compact_block(T);
-    }
     TU_STAMP(7);
-    const int n = T.n;
     for (int i = tid; i < n; i += nt) {
-      T.cnt[i] += 1;  // for (auto &n : track_cnt) n++ :252-253
-      T.ixy[i][0] = __float2int_rn(T.forw[i][0]), T.ixy[i][1] = __float2int_rn(T.forw[i][1]);
+      const int o = T.idx[i];
+      T.ncnt[i] = T.cnt[o] + 1;  // for (auto &n : track_cnt) n++ :252-253
+      T.ixy[i][0] = __float2int_rn(T.forw[o][0]), T.ixy[i][1] = __float2int_rn(T.forw[o][1]);
     }
     __syncthreads();
-    // setMask :50-87 — stable order by track_cnt desc
+    // setMask :50-87 — stable order by track_cnt desc (i, j below are list positions)
     for (int i = tid; i < n; i += nt) {
-      int rank = 0, ci = T.cnt[i];
-      for (int j = 0; j < n; j++) rank += (T.cnt[j] > ci || (T.cnt[j] == ci && j < i)) ? 1 : 0;
+      int rank = 0, ci = T.ncnt[i];
+      for (int j = 0; j < n; j++) rank += (T.ncnt[j] > ci || (T.ncnt[j] == ci && j < i)) ? 1 : 0;
       T.order[rank] = i;
     }
     const int words = (n + 63) / 64;
     __syncthreads();
     TU_STAMP(8);
-    // inside[i][w] bit j: pixel of i lies in the filled circle painted at j (i, j in ORIGINAL indices). One word per wave
+    // inside[i][w] bit j: pixel of i lies in the filled circle painted at j (i, j: list positions, not ranks). One word per wave
     // instruction: the wave takes (i, w), lane b tests j = 64 w + b, the ballot IS the word. (The per-thread loop over
     // 64 j with the half-width table read from global memory inside it was 57 k cycles; the table now sits in LDS.)
     for (int q = tid; q < 2 * A.radius + 1; q += nt) T.hw[q] = A.hw[q];
@@ -1256,36 +1288,26 @@ __global__ __launch_bounds__(256, 2) void track_update_kernel(TrackerArrays A, i
     }
     __syncthreads();
     TU_STAMP(10);
+    // the arrays are gathered once, here, straight into the tracker's fields: list position i -> slot idx[i] -> output position pos[i]
+    // (forw_pts.push_back order); pre_pts / cur_pts are overwritten with forw_pts at the end of a publish frame (:274, :285)
     for (int i = tid; i < n; i += nt)
       if (T.keep[i]) {
-        int p = T.pos[i];
-        T.t_forw[p][0] = T.forw[i][0], T.t_forw[p][1] = T.forw[i][1];
-        T.t_ids[p] = T.ids[i], T.t_cnt[p] = T.cnt[i];
+        const int p = T.pos[i], o = T.idx[i];
+        A.forw_pts[(base + p) * 2] = T.forw[o][0], A.forw_pts[(base + p) * 2 + 1] = T.forw[o][1];
+        A.ids[base + p] = T.ids[o], A.track_cnt[base + p] = T.ncnt[i];
         A.kept_xy[(base + p) * 2] = T.ixy[i][0], A.kept_xy[(base + p) * 2 + 1] = T.ixy[i][1];
       }
-    __syncthreads();
-    for (int i = tid; i < T.n; i += nt) {
-      T.forw[i][0] = T.t_forw[i][0], T.forw[i][1] = T.t_forw[i][1];
-      T.ids[i] = T.t_ids[i], T.cnt[i] = T.t_cnt[i];
-      // pre_pts / cur_pts are overwritten with forw_pts at the end of a publish frame (:274, :285)
-    }
-    if (tid == 0) A.n_kept[seq] = T.n;
-    __syncthreads();
-  }
-  // write back
-  const int n = T.n;
-  for (int i = tid; i < n; i += nt) {
-    A.forw_pts[(base + i) * 2] = T.forw[i][0], A.forw_pts[(base + i) * 2 + 1] = T.forw[i][1];
-    A.ids[base + i] = T.ids[i], A.track_cnt[base + i] = T.cnt[i];
-    if (!publish) {
-      A.pre_pts[(base + i) * 2] = T.pre[i][0], A.pre_pts[(base + i) * 2 + 1] = T.pre[i][1];
+    if (tid == 0) A.n_kept[seq] = T.n, A.n_forw[seq] = T.n;
+  } else {
+    for (int i = tid; i < n; i += nt) {
+      const int o = T.idx[i];
+      A.forw_pts[(base + i) * 2] = T.forw[o][0], A.forw_pts[(base + i) * 2 + 1] = T.forw[o][1];
+      A.ids[base + i] = T.ids[o], A.track_cnt[base + i] = T.cnt[o];
+      A.pre_pts[(base + i) * 2] = T.pre[o][0], A.pre_pts[(base + i) * 2 + 1] = T.pre[o][1];
       // cur_pts = forw_pts (:285)
-      A.cur_pts[(base + i) * 2] = T.forw[i][0], A.cur_pts[(base + i) * 2 + 1] = T.forw[i][1];
+      A.cur_pts[(base + i) * 2] = T.forw[o][0], A.cur_pts[(base + i) * 2 + 1] = T.forw[o][1];
     }
-  }
-  if (tid == 0) {
-    A.n_forw[seq] = n;
-    if (!publish) A.n_pts[seq] = n;
+    if (tid == 0) A.n_forw[seq] = n, A.n_pts[seq] = n;
   }
   TU_STAMP(11);
 #undef TU_STAMP
@@ -1558,43 +1580,87 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
                                                                     double quality, SelectParams P, float *forw_pts,
                                                                     float *cur_pts, float *pre_pts, int *ids, int *track_cnt,
                                                                     int *n_forw, int *n_pts, int *n_id, VioObs *obs,
-                                                                    int *n_obs) {
+                                                                    int *n_obs, long long *prof) {
+  // prof: null, or cycle stamps of sequence 0's workgroup (VIO_AMD_CS_PROF, tools/cs_prof.sh)
+#define CS_STAMP(k)                                                  \
+  do {                                                               \
+    if (prof && blockIdx.x == 0 && threadIdx.x == 0) prof[k] = clock64(); \
+  } while (0)
+  CS_STAMP(0);
   __shared__ unsigned long long keys[kSelLds];
-  __shared__ unsigned long long red[kSelThreads / 64];
+  __shared__ unsigned long long red[2][kSelThreads / 64];
   __shared__ int s_n, s_cnt;
+  __shared__ unsigned s_mb;
   __shared__ int s_off[kSelMaxSeg + 1];
+  __shared__ unsigned s_pick[kMaxCap];  // y << 16 | x of the corners taken, by output position
+  __shared__ int s_wnew[kSelThreads / 64];
+  static_assert(kMaxCap <= kSelThreads, "the id pass gives every feature slot its own work-item");
   const int seq = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int lane = tid & 63, wave = tid >> 6;
   unsigned long long *cand = cand_base + (size_t)seq * nseg * seg_cap;  // nseg segments of seg_cap keys
   const size_t base = (size_t)seq * P.cap;
-  int n = n_forw[seq];
+  const int n_old = n_forw[seq];
+  int n = n_old;
   const int want = P.max_corners - n;
   const float md2 = P.min_dist * P.min_dist;
-  unsigned mb = 0;
-  for (int g = 0; g < nseg; g++) mb = max(mb, max_bits[(size_t)seq * nseg + g]);
-  const float thr = mb ? (float)((double)from_ordered_bits(mb) * quality) : 3.4e38f;
-  if (tid == 0) s_n = n, s_cnt = 0;
-  __syncthreads();
+  // what the id and output passes need of the tracks that are already there: asked for now, used behind the selection
+  const int nid0 = n_id[seq];
+  int my_id = -1;
+  float my_x = 0.f, my_y = 0.f;
+  if (tid < n_old) my_id = ids[base + tid], my_x = forw_pts[(base + tid) * 2], my_y = forw_pts[(base + tid) * 2 + 1];
   // threshold(eig, maxVal * qualityLevel, THRESH_TOZERO): keep v > thr. Only the slots the detector really filled are
   // visited (prefix of the per-segment counts), survivors go to LDS and NOTHING is written back to the candidate list:
   // the first version zeroed every rejected and unused slot in HBM (0.6 MB per sequence and publish frame, twice the
   // frame itself) although only the rare in-place path below reads the list again.
-  if (tid == 0) {
-    int o = 0;
-    for (int g = 0; g < nseg; g++) s_off[g] = o, o += min(n_cand[(size_t)seq * nseg + g], seg_cap);
-    s_off[nseg] = o;
+  // The per-segment prefix and the maximum over the segments: one wave, one load of each counter per lane (work-item 0 walking
+  // the counters was a chain of nseg dependent loads).
+  if (wave == 0) {
+    int carry = 0;
+    unsigned mb = 0;
+    for (int g0 = 0; g0 < nseg; g0 += 64) {
+      const int g = g0 + lane;
+      const int c = g < nseg ? min(n_cand[(size_t)seq * nseg + g], seg_cap) : 0;
+      mb = max(mb, g < nseg ? max_bits[(size_t)seq * nseg + g] : 0u);
+      int incl = c;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        incl += lane >= o ? t : 0;
+      }
+      if (g < nseg) s_off[g] = carry + incl - c;
+      carry += __shfl(incl, 63, 64);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, o, 64));
+    if (lane == 0) s_off[nseg] = carry, s_mb = mb, s_n = n, s_cnt = 0;
   }
   __syncthreads();
+  const unsigned mb = s_mb;
+  const float thr = mb ? (float)((double)from_ordered_bits(mb) * quality) : 3.4e38f;
   const int real = s_off[nseg];
-  for (int i = tid; i < real; i += nt) {
-    int g = 0;
-    while (s_off[g + 1] <= i) g++;
-    const unsigned long long k = cand[(size_t)g * seg_cap + (i - s_off[g])];
-    if (k && __uint_as_float((unsigned)(k >> 32)) > thr) {
-      int slot = atomicAdd(&s_cnt, 1);
-      if (slot < kSelLds) keys[slot] = k;
+  // (every lane of a wave runs every trip: the survivors of a trip take their slots with ONE atomic per wave -- ballot and
+  // popcount -- instead of one returning atomic per candidate on one address. The order of keys[] is free: keys are unique and
+  // the rounds below take maxima. A work-item's indices only grow, so its segment search resumes where it stopped.)
+  int sg = 0;
+  for (int i0 = 0; i0 < real; i0 += nt) {
+    const int i = i0 + tid;
+    unsigned long long k = 0;
+    if (i < real) {
+      while (s_off[sg + 1] <= i) sg++;  // (i < s_off[nseg]: stops at a segment < nseg)
+      k = cand[(size_t)sg * seg_cap + (i - s_off[sg])];
+    }
+    const bool ok = k && __uint_as_float((unsigned)(k >> 32)) > thr;
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(ok);
+    if (b) {
+      int slot0 = 0;
+      if (lane == 0) slot0 = atomicAdd(&s_cnt, __builtin_popcountll(b));
+      slot0 = __builtin_amdgcn_readfirstlane(slot0);
+      const int slot = slot0 + __builtin_popcountll(b & ((1ull << lane) - 1ull));
+      if (ok && slot < kSelLds) keys[slot] = k;
     }
   }
   __syncthreads();
+  CS_STAMP(1);
   // this kernel is the only consumer of the per-segment counters: leave them zeroed for the next detection pass
   for (int g = tid; g < nseg; g += nt) n_cand[(size_t)seq * nseg + g] = 0, max_bits[(size_t)seq * nseg + g] = 0;
   if (s_cnt > kSelLds) {
@@ -1656,11 +1722,7 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
       if (best == 0) break;
       const unsigned bidx = 0xffffffffu - (unsigned)(best & 0xffffffffu);
       const int bx = bidx & 0xffffu, by = bidx >> 16;
-      if (tid == 0) {
-        int p = s_n++;
-        forw_pts[(base + p) * 2] = (float)bx, forw_pts[(base + p) * 2 + 1] = (float)by;
-        ids[base + p] = -1, track_cnt[base + p] = 1;  // addPoints :36-48
-      }
+      if (tid == 0) s_pick[s_n++] = bidx;  // addPoints :36-48 (the arrays are written by the output pass)
       const int glo = max(0, (by - reach) / kDetR), ghi = min(nseg - 1, (by + reach) / kDetR);
       for (int g0 = glo; g0 <= ghi; g0 += 4) rescan(g0, min(4, ghi - g0 + 1), bx, by, false);
     }
@@ -1675,20 +1737,19 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
     mine = k > mine ? k : mine;
   }
   for (int round = 0; round < want; round++) {
+    // (the waves' maxima alternate between two rows: a wave writes row r & 1 again only behind the barrier of round r + 1,
+    // which every wave reaches behind its reads of round r -- one barrier per round, not two)
     unsigned long long best = wave_max_u64(mine);
-    if ((tid & 63) == 0) red[tid >> 6] = best;
+    unsigned long long *rd = red[round & 1];
+    if (lane == 0) rd[wave] = best;
     __syncthreads();
-    best = red[0];
-    for (int w = 1; w < nt / 64; w++) best = red[w] > best ? red[w] : best;
-    __syncthreads();
+    best = rd[0];
+#pragma unroll
+    for (int w = 1; w < kSelThreads / 64; w++) best = rd[w] > best ? rd[w] : best;
     if (best == 0) break;
     const unsigned bidx = 0xffffffffu - (unsigned)(best & 0xffffffffu);
     const int bx = bidx & 0xffffu, by = bidx >> 16;
-    if (tid == 0) {
-      int p = s_n++;
-      forw_pts[(base + p) * 2] = (float)bx, forw_pts[(base + p) * 2 + 1] = (float)by;
-      ids[base + p] = -1, track_cnt[base + p] = 1;  // addPoints :36-48
-    }
+    if (tid == 0) s_pick[s_n++] = bidx;  // addPoints :36-48 (the arrays are written by the output pass)
     mine = 0;
     if (P.min_dist >= 1.f) {
       for (int i = tid; i < nc; i += nt) {
@@ -1710,25 +1771,46 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
   }
   }
   __syncthreads();
+  CS_STAMP(2);
   n = s_n;
   // updateID (:311-321), image_msg (:297-306), pre_pts = cur_pts = forw_pts (:274, :285)
-  if (tid == 0) {
-    int nid = n_id[seq];
-    for (int i = 0; i < n; i++)
-      if (ids[base + i] == -1) ids[base + i] = nid++;
-    n_id[seq] = nid;
-    n_forw[seq] = n, n_pts[seq] = n, n_obs[seq] = n;
+  // Work-item i owns feature i (n <= kMaxCap <= kSelThreads): a track that was there keeps the id loaded at the start, a
+  // corner taken above has none (-1). The features without an id are numbered from n_id in index order, like the serial loop
+  // (which was up to n dependent trips to global memory on one lane): rank = exclusive count of the -1 entries before i,
+  // from a ballot per wave and the waves' counts through LDS.
+  const bool is_new = tid >= n_old && tid < n;
+  if (is_new) {
+    const unsigned bidx = s_pick[tid];
+    my_x = (float)(int)(bidx & 0xffffu), my_y = (float)(int)(bidx >> 16);
   }
+  const bool no_id = tid < n && my_id == -1;
+  const unsigned long long nb = __builtin_amdgcn_ballot_w64(no_id);
+  if (lane == 0) s_wnew[wave] = __builtin_popcountll(nb);
   __syncthreads();
-  for (int i = tid; i < n; i += nt) {
-    float x = forw_pts[(base + i) * 2], y = forw_pts[(base + i) * 2 + 1];
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < kSelThreads / 64; w++) {
+    const int c = s_wnew[w];
+    before += w < wave ? c : 0;
+    total += c;
+  }
+  if (no_id) my_id = nid0 + before + __builtin_popcountll(nb & ((1ull << lane) - 1ull));
+  if (tid == 0) n_id[seq] = nid0 + total, n_forw[seq] = n, n_pts[seq] = n, n_obs[seq] = n;
+  CS_STAMP(3);
+  if (tid < n) {
+    const int i = tid;
+    const float x = my_x, y = my_y;
+    if (is_new) forw_pts[(base + i) * 2] = x, forw_pts[(base + i) * 2 + 1] = y, track_cnt[base + i] = 1;
+    if (no_id) ids[base + i] = my_id;
     cur_pts[(base + i) * 2] = x, cur_pts[(base + i) * 2 + 1] = y;
     pre_pts[(base + i) * 2] = x, pre_pts[(base + i) * 2 + 1] = y;
     VioObs o;
-    o.id = ids[base + i];
+    o.id = my_id;
     o.x = ((double)x - P.cx) / P.fx, o.y = ((double)y - P.cy) / P.fy, o.z = 1.0;
     obs[base + i] = o;
   }
+  CS_STAMP(4);
+#undef CS_STAMP
 }
 
 void circle_halfwidths(int radius, std::vector<int> &hw) {  // cv::circle filled midpoint raster (drawing.cpp Circle())
@@ -1778,6 +1860,8 @@ struct vio_frontend {
   DevBuf<uint8_t> lk_status;
   DevBuf<VioObs> obs;
   DevBuf<long long> d_prof;  // stage clock of track_update_kernel (VIO_AMD_TU_PROF=1)
+  DevBuf<long long> d_cs_prof;  // stage clock of corner_select_kernel (VIO_AMD_CS_PROF=1, read at create)
+  bool cs_prof = false;
   bool attr_set = false;
   bool detect_always = false;  // VIO_AMD_DETECT_ALWAYS=1 (measurement aid): detect_kernel also runs for sequences that need no new corner
   // resident frames (throughput runs)
@@ -2068,7 +2152,13 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
     SP.fx = fe->cfg.fx, SP.fy = fe->cfg.fy, SP.cx = fe->cfg.cx, SP.cy = fe->cfg.cy;
     hipLaunchKernelGGL(corner_select_kernel, dim3(S), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg, fe->n_cand.p,
                        fe->max_bits.p, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
-                       fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p);
+                       fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p, fe->cs_prof ? fe->d_cs_prof.p : nullptr);
+    if (fe->cs_prof) {  // (debug only: synchronises)
+      long long h[5];
+      if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h, fe->d_cs_prof.p, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
+        fprintf(stderr, "corner_select cycles (sequence 0): threshold %lld, selection %lld, ids %lld, outputs %lld, total %lld\n", h[1] - h[0],
+                h[2] - h[1], h[3] - h[2], h[4] - h[3], h[4] - h[0]);
+    }
   }
   HIP_OK(hipGetLastError());
   fe->cur_idx = fidx;  // cur_img = forw_img (:284)
@@ -2090,6 +2180,7 @@ int vio_frontend_create(const VioConfig *cfg, int32_t n_seq, vio_frontend_t **ou
   fe->device = vio::current_device();
   fe->cfg = *cfg, fe->n_seq = n_seq, fe->cap = cfg->max_corners;
   fe->detect_always = vio::env_flag("VIO_AMD_DETECT_ALWAYS");
+  fe->cs_prof = vio::env_flag("VIO_AMD_CS_PROF") && fe->d_cs_prof.ensure(8) == VIO_OK;
   // buildOpticalFlowPyramid: levels stop when one would not hold the window
   LevelDims &ld = fe->ld;
   ld.rows[0] = cfg->image_rows, ld.cols[0] = cfg->image_cols, ld.off[0] = 0, ld.levels = 1;
@@ -2580,7 +2671,7 @@ int vio_good_features(const VioConfig *cfg, const uint8_t *img, const uint8_t *m
   SP.fx = c.fx, SP.fy = c.fy, SP.cx = c.cx, SP.cy = c.cy;
   hipLaunchKernelGGL(corner_select_kernel, dim3(1), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg, fe->n_cand.p, fe->max_bits.p,
                      c.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p, fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p,
-                     fe->n_id.p, fe->obs.p, fe->n_obs.p);
+                     fe->n_id.p, fe->obs.p, fe->n_obs.p, (long long *)nullptr);
   if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
   int n = 0;
   if (hipMemcpy(&n, fe->n_pts.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return VIO_ENODEV;
@@ -2593,7 +2684,7 @@ __global__ __launch_bounds__(256) void ransac_only_kernel(const float *p1, const
                                                           uint8_t *mask) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   RansacShared &R = *reinterpret_cast<RansacShared *>(smem_raw);
-  fundamental_ransac_block(R, p1, p2, n, thresh, conf, mask);
+  fundamental_ransac_block(R, GlobalPts{p1, p2}, n, thresh, conf, mask);
 }
 
 int vio_fundamental_ransac(const VioConfig *cfg, const float *pts1, const float *pts2, int32_t n, uint8_t *inlier_mask) {
@@ -2624,7 +2715,7 @@ __global__ __launch_bounds__(256) void ransac_batch_kernel(const float *p1, cons
   RansacShared &R = *reinterpret_cast<RansacShared *>(smem_raw);
   const int p = blockIdx.x, n = count[p];
   if (n < min_count || n > stride) return;  // (uniform per workgroup)
-  fundamental_ransac_block(R, p1 + 2 * (size_t)p * stride, p2 + 2 * (size_t)p * stride, n, thresh, conf, mask + (size_t)p * stride);
+  fundamental_ransac_block(R, GlobalPts{p1 + 2 * (size_t)p * stride, p2 + 2 * (size_t)p * stride}, n, thresh, conf, mask + (size_t)p * stride);
 }
 
 namespace vio {
