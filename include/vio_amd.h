@@ -172,6 +172,8 @@ typedef struct VioWindow {
 } VioWindow;
 
 #define VIO_MAX_TRACE 64
+/* Filled by the solve entries; the it_* slots at index >= iterations are 0 (csrc/solve_trace.h is the one reader of the
+ * device trace).                                                              */
 typedef struct VioSolveStats {
   double initial_cost;
   double final_cost;     /* summary.final_cost VINS.cpp:660 */

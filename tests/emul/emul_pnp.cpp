@@ -15,7 +15,7 @@ extern "C" int emul_pnp_solve(const VioConfig *cfg, VioPnpWindow *win, VioSolveS
   const double kNaN = std::numeric_limits<double>::quiet_NaN();
   std::vector<int> fixed(n), si(kStatsInts, 0);
   for (int k = 0; k < n; k++) fixed[k] = win->fixed[k] ? 1 : 0;
-  std::vector<double> out_pose(7 * n, kNaN), out_speed(3 * n, kNaN), sd(kStatsDoubles, 0.0), U(225 * (n - 1), kNaN), Jraw(450 * (n - 1), kNaN);
+  std::vector<double> out_pose(7 * n, kNaN), out_speed(3 * n, kNaN), sd(kStatsDoubles, 0.0), Jraw(450 * (n - 1), kNaN);
   pnp::View v;
   v.n = n, v.M = M, v.max_iter = 5;
   v.fixed = fixed.data(), v.feat_start = win->feat_start;
@@ -33,15 +33,6 @@ extern "C" int emul_pnp_solve(const VioConfig *cfg, VioPnpWindow *win, VioSolveS
   pnp::solve(cx, v, w);
   for (int i = 0; i < 7 * n; i++) win->pose[i] = out_pose[i];
   for (int i = 0; i < 3 * n; i++) win->speed[i] = out_speed[i];
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
-    stats->initial_cost = sd[0], stats->final_cost = sd[1];
-    stats->iterations = si[0], stats->termination = si[1], stats->num_successful_steps = si[2], stats->num_unsuccessful_steps = si[3];
-    for (int k = 0; k < kMaxTrace && k < VIO_MAX_TRACE; k++) {
-      stats->it_cost[k] = sd[4 + k], stats->it_radius[k] = sd[4 + kMaxTrace + k], stats->it_step_norm[k] = sd[4 + 2 * kMaxTrace + k];
-      stats->it_relative_decrease[k] = sd[4 + 3 * kMaxTrace + k], stats->it_gradient_max_norm[k] = sd[4 + 4 * kMaxTrace + k];
-      stats->it_flags[k] = si[4 + k];
-    }
-  }
+  if (stats) unpack_solve_stats(sd.data(), si.data(), stats);
   return VIO_OK;
 }

@@ -586,19 +586,7 @@ inline void unpack_window(const BatchStrides &s, int b, const double *out_pose, 
   for (int k = 0; k < w.n_factors; k++)
     if (w.factor_target[k] == P) has_loop = true;
   if (has_loop && w.loop_pose) memcpy(w.loop_pose, out_loop + b * s.out_loop, sizeof(double) * 7);
-  if (st) {
-    const double *sd = stats_d + b * s.stats_d;
-    const int *si = stats_i + b * s.stats_i;
-    memset(st, 0, sizeof(*st));
-    st->initial_cost = sd[0], st->final_cost = sd[1];
-    st->iterations = si[0], st->termination = si[1], st->num_successful_steps = si[2];
-    st->num_unsuccessful_steps = si[3];
-    for (int i = 0; i < kMaxTrace && i < VIO_MAX_TRACE; i++) {
-      st->it_cost[i] = sd[4 + i], st->it_radius[i] = sd[4 + kMaxTrace + i];
-      st->it_step_norm[i] = sd[4 + 2 * kMaxTrace + i], st->it_relative_decrease[i] = sd[4 + 3 * kMaxTrace + i];
-      st->it_gradient_max_norm[i] = sd[4 + 4 * kMaxTrace + i], st->it_flags[i] = si[4 + i];
-    }
-  }
+  if (st) unpack_solve_stats(stats_d + b * s.stats_d, stats_i + b * s.stats_i, st);
 }
 
 }  // namespace vio

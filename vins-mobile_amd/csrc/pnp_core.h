@@ -338,15 +338,7 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
     for (int i = 0; i < 450; i++) v.Jraw[(size_t)k * 450 + i] = 0.0;
   }
   VIO_SYNC();
-  double *sd = v.stats_d;
-  int *si = v.stats_i;
-  auto record = [&](int i, double cost, double radius, double step_norm, double rel, double gmax, bool valid, bool ok) {
-    if (cx.tid == 0 && i < kMaxTrace) {
-      sd[4 + i] = cost, sd[4 + kMaxTrace + i] = radius, sd[4 + 2 * kMaxTrace + i] = step_norm;
-      sd[4 + 3 * kMaxTrace + i] = rel, sd[4 + 4 * kMaxTrace + i] = gmax;
-      si[4 + i] = (valid ? 1 : 0) | (ok ? 2 : 0);
-    }
-  };
+  const SolveTrace trace{v.stats_d, v.stats_i};  // (work-item 0 writes it)
   auto grad_max_norm = [&]() {  // |x - Plus(x, -g)|_inf (trust_region_minimizer.cc:270-284)
     VIO_PARFOR(i, dim) w.t2[i] = -w.g[i];
     VIO_SYNC();
@@ -359,7 +351,7 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
   double x_cost = evaluate(cx, v, w, w.xp, w.xs, dim > 0);
   int it = 0, n_ok = 1, n_bad = 0, invalid_run = 0, termination = 0, recorded = 1;
   double min_rec = x_cost;
-  if (cx.tid == 0) sd[0] = x_cost;
+  if (cx.tid == 0) trace.initial(x_cost);
   if (dim == 0) {  // every block constant: Ceres returns before its first iteration record, its step counts left at -1
     termination = 1, recorded = 0, n_ok = -1, n_bad = -1;
   } else {
@@ -371,8 +363,8 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
     const double min_mu = 1e-8, max_mu = 1.0, mu_inc = 10.0;
     bool reuse = false, last_ok = true;
     double dogleg_step_norm = 0, alpha = 0;
-    double ev_min = x_cost, ev_cur = x_cost, ev_ref = x_cost, ev_cand = x_cost, ev_acc_ref = 0, ev_acc_cand = 0;
-    record(0, x_cost, radius, 0, 0, gmax, true, true);
+    StepEvaluator ev = StepEvaluator::at(x_cost);
+    if (cx.tid == 0) trace.record(0, x_cost, radius, 0, 0, gmax, true, true);
     while (true) {
       if (it >= v.max_iter) break;
       if (last_ok && gmax <= 1e-10) { termination = 1; break; }
@@ -419,21 +411,8 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
         VIO_SYNC();
 #endif
         const double gradient_norm = sqrt(a), gauss_newton_norm = sqrt(b), gdot = c;
-        double ca = 0, cb = 0;
-        if (gauss_newton_norm <= radius) {
-          ca = 0, cb = 1, dogleg_step_norm = gauss_newton_norm;
-        } else if (gradient_norm * alpha >= radius) {
-          ca = -(radius / gradient_norm), cb = 0, dogleg_step_norm = radius;
-        } else {
-          const double b_dot_a = -alpha * gdot;
-          const double a_sq = pow(alpha * gradient_norm, 2.0);
-          const double bma_sq = a_sq - 2 * b_dot_a + pow(gauss_newton_norm, 2);
-          const double cc = b_dot_a - a_sq;
-          const double dd = sqrt(cc * cc + bma_sq * (pow(radius, 2.0) - a_sq));
-          const double beta = (cc <= 0) ? (dd - cc) / bma_sq : (radius * radius - a_sq) / (dd + cc);
-          ca = -alpha * (1.0 - beta), cb = beta;
-          dogleg_step_norm = -1;
-        }
+        double ca, cb;
+        dogleg_combination(alpha, gradient_norm, gauss_newton_norm, gdot, radius, &ca, &cb, &dogleg_step_norm);
         double n2 = 0;
         VIO_PARFOR(i, dim) {
           const double s = ca * w.gd[i] + cb * w.gn[i];
@@ -460,7 +439,7 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
         mu *= mu_inc;
         reuse = false, last_ok = false;
         n_bad++;
-        record(it, x_cost, radius, 0, 0, gmax, false, false);
+        if (cx.tid == 0) trace.record(it, x_cost, radius, 0, 0, gmax, false, false);
         recorded = it + 1;
         continue;
       }
@@ -475,9 +454,7 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
       if (step_norm <= 1e-8 * (x_norm + 1e-8)) { termination = 1; break; }       // ParameterToleranceReached
       const double cost_change = x_cost - cand_cost;
       if (fabs(cost_change) <= 1e-6 * x_cost) { termination = 1; break; }          // FunctionToleranceReached
-      const double rel = (ev_cur - cand_cost) / model_cost_change;
-      const double hist = (ev_ref - cand_cost) / (ev_acc_ref + model_cost_change);
-      const double rho = fmax(rel, hist);
+      const double rho = step_quality(ev, cand_cost, model_cost_change);
       if (rho > 1e-3) {
         VIO_SYNC();
         VIO_PARFOR(i, 7 * v.n) w.xp[i] = w.cp[i];
@@ -499,20 +476,17 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
         if (rho > 0.75) radius = fmax(radius, 3.0 * dogleg_step_norm);
         mu = fmax(min_mu, 2.0 * mu / mu_inc);
         reuse = false;
-        ev_cur = cand_cost, ev_acc_cand += model_cost_change, ev_acc_ref += model_cost_change;
-        if (ev_cur < ev_min) ev_min = ev_cur, ev_cand = ev_cur, ev_acc_cand = 0;
-        else if (ev_cur > ev_cand) ev_cand = ev_cur, ev_acc_cand = 0;
-        ev_ref = ev_cand, ev_acc_ref = ev_acc_cand;
+        ev = step_accepted(ev, cand_cost, model_cost_change);
         last_ok = true;
         n_ok++;
-        record(it, x_cost, radius, step_norm, rho, gmax, true, true);
+        if (cx.tid == 0) trace.record(it, x_cost, radius, step_norm, rho, gmax, true, true);
         recorded = it + 1;
         min_rec = fmin(min_rec, x_cost);
       } else {
         radius *= 0.5;  // StepRejected (:631-634)
         reuse = true, last_ok = false;
         n_bad++;
-        record(it, cand_cost, radius, step_norm, rho, 0.0, true, false);
+        if (cx.tid == 0) trace.record(it, cand_cost, radius, step_norm, rho, 0.0, true, false);
         recorded = it + 1;
         min_rec = fmin(min_rec, cand_cost);
       }
@@ -525,10 +499,7 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
     for (int c = 0; c < 3; c++) v.out_pose[7 * k + c] = w.xp[7 * k + c], v.out_speed[3 * k + c] = w.xs[3 * k + c];
     v.out_pose[7 * k + 3] = q.x, v.out_pose[7 * k + 4] = q.y, v.out_pose[7 * k + 5] = q.z, v.out_pose[7 * k + 6] = q.w;
   }
-  if (cx.tid == 0) {
-    sd[1] = min_rec;
-    si[0] = recorded, si[1] = termination, si[2] = n_ok, si[3] = n_bad;
-  }
+  if (cx.tid == 0) trace.finish(recorded, termination, n_ok, n_bad, min_rec);
 }
 
 // LDS / workspace carving: doubles needed for n frames.

@@ -31,6 +31,7 @@
 
 #include <type_traits>
 
+#include "solve_trace.h"
 #include "vio_math.h"
 
 // Three builds of this file:
@@ -136,9 +137,6 @@ constexpr int kSS = kSB * kSB;   // 81
 constexpr int kAW = 18;          // pose columns an IMU chain couples a speed-bias block to: frames k-1, k, k+1
 constexpr int kAS = kSB * kAW;   // 162
 constexpr int kPreintDoubles = 467;
-constexpr int kMaxTrace = 64;
-constexpr int kStatsDoubles = 4 + 5 * kMaxTrace;  // initial, final, (it_cost, radius, step_norm, rel, gmax)[64]
-constexpr int kStatsInts = 4 + kMaxTrace;         // iterations, termination, n_ok, n_bad, flags[64]
 
 // Per-stage cycle counters (the kernel-side counterpart of the reference's TS/TE timers, global_param.hpp:85-92).
 enum Stage {
@@ -3668,16 +3666,7 @@ template <bool REGS, int NW, class WK, class VP, class WP>
 VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fresh, const WP &fresh_work) {
   WK &w = w_whole;
   const int np = v.np, F = v.F;
-  double *sd = v.stats_d;
-  int *si = v.stats_i;
-  auto record = [&](int i, double cost, double radius, double step_norm, double rel, double gmax, bool valid,
-                    bool ok) {
-    if (cx.tid == 0 && i < kMaxTrace) {
-      sd[4 + i] = cost, sd[4 + kMaxTrace + i] = radius, sd[4 + 2 * kMaxTrace + i] = step_norm;
-      sd[4 + 3 * kMaxTrace + i] = rel, sd[4 + 4 * kMaxTrace + i] = gmax;
-      si[4 + i] = (valid ? 1 : 0) | (ok ? 2 : 0);
-    }
-  };
+  const SolveTrace trace{v.stats_d, v.stats_i};  // (work-item 0 writes it)
   auto grad_max_norm = [&]() { return gradient_max_norm(cx, fresh(), w); };
 
   double x_cost = evaluate(cx, fresh(), w, w.xpose, w.xsb, w.xfeat, true, false);
@@ -3690,10 +3679,10 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
   bool reuse = false, last_ok = true, have_factor = false;
   double dogleg_step_norm = 0, alpha = 0;
   int it = 0, n_ok = 1, n_bad = 0, invalid_run = 0, termination = 0, recorded = 1;
-  double ev_min = x_cost, ev_cur = x_cost, ev_ref = x_cost, ev_cand = x_cost, ev_acc_ref = 0, ev_acc_cand = 0;
+  StepEvaluator ev = StepEvaluator::at(x_cost);
   double min_rec = x_cost;
-  record(0, x_cost, radius, 0, 0, gmax, true, true);
-  if (cx.tid == 0) sd[0] = x_cost;
+  if (cx.tid == 0) trace.record(0, x_cost, radius, 0, 0, gmax, true, true);
+  if (cx.tid == 0) trace.initial(x_cost);
   double gd_sq = 0, mu_used = mu, qf_cauchy = 0, qf_part = 0;
   bool qf_pending = false;  // the W part of the Cauchy point's quadratic form is still to be added (first dogleg step after a solve)
   // a linearization at x is due at the head of the next iteration: after a step that was accepted on a cost-only evaluation
@@ -3712,7 +3701,7 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
       evaluate(cx, fresh(), w, w.xpose, w.xsb, w.xfeat, true, true, relin_reuse);
       if (rec_pending) {
         gmax = grad_max_norm();
-        record(rec_it, x_cost, radius, rec_step_norm, rec_rho, gmax, true, true);
+        if (cx.tid == 0) trace.record(rec_it, x_cost, radius, rec_step_norm, rec_rho, gmax, true, true);
         stamp(cx, ST_V_GMAX);
       }
       relin = relin_reuse = rec_pending = false;
@@ -3729,8 +3718,9 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
       // factorization are short of). (w.park: a slot of its own -- an evaluation inside the retry loop uses every other scratch vector.)
       ldsd park = w.park;
       if (cx.tid == 0) {
-        park[0] = x_cost, park[1] = x_norm, park[2] = gmax, park[3] = radius, park[4] = dogleg_step_norm, park[5] = ev_min;
-        park[6] = ev_cur, park[7] = ev_ref, park[8] = ev_cand, park[9] = ev_acc_ref, park[10] = ev_acc_cand, park[11] = min_rec;
+        park[0] = x_cost, park[1] = x_norm, park[2] = gmax, park[3] = radius, park[4] = dogleg_step_norm, park[5] = ev.minimum_cost;
+        park[6] = ev.current_cost, park[7] = ev.reference_cost, park[8] = ev.candidate_cost;
+        park[9] = ev.accumulated_reference_model_cost_change, park[10] = ev.accumulated_candidate_model_cost_change, park[11] = min_rec;
         ldsi pi = reinterpret_cast<ldsi>(park + 12);
         pi[0] = it, pi[1] = n_ok, pi[2] = n_bad, pi[3] = invalid_run, pi[4] = termination, pi[5] = recorded, pi[6] = last_ok ? 1 : 0;
       }
@@ -3812,8 +3802,9 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
       }
       {
         VIO_SYNC();
-        x_cost = park[0], x_norm = park[1], gmax = park[2], radius = park[3], dogleg_step_norm = park[4], ev_min = park[5];
-        ev_cur = park[6], ev_ref = park[7], ev_cand = park[8], ev_acc_ref = park[9], ev_acc_cand = park[10], min_rec = park[11];
+        x_cost = park[0], x_norm = park[1], gmax = park[2], radius = park[3], dogleg_step_norm = park[4], ev.minimum_cost = park[5];
+        ev.current_cost = park[6], ev.reference_cost = park[7], ev.candidate_cost = park[8];
+        ev.accumulated_reference_model_cost_change = park[9], ev.accumulated_candidate_model_cost_change = park[10], min_rec = park[11];
         ldsi pi = reinterpret_cast<ldsi>(park + 12);
         it = pi[0], n_ok = pi[1], n_bad = pi[2], invalid_run = pi[3], termination = pi[4], recorded = pi[5], last_ok = pi[6] != 0;
       }
@@ -3831,7 +3822,7 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
     bool step_valid = false;
     double model_cost_change = 0;
     if (solver_ok) {
-      // ComputeTraditionalDoglegStep (dogleg_strategy.cc:199-255)
+      // ComputeTraditionalDoglegStep (dogleg_strategy.cc:199-255): dogleg_combination of solve_trace.h, kept in line (need_norm as a flag)
       double p1 = 0, p2 = 0, p3 = 0;
       VIO_PARFOR(i, np) p1 += w.gnp[i] * w.gnp[i], p2 += pose_gd(w, i) * w.gnp[i];
       VIO_PARFOR(f, F) {
@@ -3896,7 +3887,7 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
       reuse = false;
       last_ok = false;
       n_bad++;
-      record(it, x_cost, radius, 0, 0, gmax, false, false);
+      if (cx.tid == 0) trace.record(it, x_cost, radius, 0, 0, gmax, false, false);
       recorded = it + 1, min_rec = fmin(min_rec, x_cost);
       relin = true;  // the matrix buffer holds a factorization: H is rebuilt before the next build_reduced_system
       continue;
@@ -3944,9 +3935,7 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
       termination = 1;
       break;
     }
-    double rel = (ev_cur - cand_cost) / model_cost_change;                    // StepQuality
-    double hist = (ev_ref - cand_cost) / (ev_acc_ref + model_cost_change);
-    double rho = fmax(rel, hist);
+    const double rho = step_quality(ev, cand_cost, model_cost_change);
     if (rho > 1e-3) {
       x_norm = cand_norm;
       x_cost = cand_cost;  // (x is the candidate)
@@ -3954,16 +3943,17 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
       if (rho > 0.75) radius = fmax(radius, 3.0 * dogleg_step_norm);
       mu = fmax(min_mu, 2.0 * mu / mu_inc);
       reuse = false;
-      ev_cur = cand_cost, ev_acc_cand += model_cost_change, ev_acc_ref += model_cost_change;
-      if (ev_cur < ev_min) ev_min = ev_cur, ev_cand = ev_cur, ev_acc_cand = 0;
-      else if (ev_cur > ev_cand) ev_cand = ev_cur, ev_acc_cand = 0;
-      ev_ref = ev_cand, ev_acc_ref = ev_acc_cand;
+      // step_accepted of solve_trace.h, kept in line (the call costs one unit of this kernel two register moves)
+      ev.current_cost = cand_cost, ev.accumulated_candidate_model_cost_change += model_cost_change, ev.accumulated_reference_model_cost_change += model_cost_change;
+      if (ev.current_cost < ev.minimum_cost) ev.minimum_cost = ev.current_cost, ev.candidate_cost = ev.current_cost, ev.accumulated_candidate_model_cost_change = 0;
+      else if (ev.current_cost > ev.candidate_cost) ev.candidate_cost = ev.current_cost, ev.accumulated_candidate_model_cost_change = 0;
+      ev.reference_cost = ev.candidate_cost, ev.accumulated_reference_model_cost_change = ev.accumulated_candidate_model_cost_change;
       last_ok = true;
       n_ok++;
       recorded = it + 1, min_rec = fmin(min_rec, x_cost);
       if (speculate) {  // the linearization is in place
         gmax = grad_max_norm();
-        record(it, x_cost, radius, step_norm, rho, gmax, true, true);
+        if (cx.tid == 0) trace.record(it, x_cost, radius, step_norm, rho, gmax, true, true);
         stamp(cx, ST_V_GMAX);
       } else {          // it follows at the head of the next iteration, the record with it
         relin = true, relin_reuse = true, rec_pending = true;
@@ -3974,7 +3964,7 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
       reuse = true;
       last_ok = false;
       n_bad++;
-      record(it, cand_cost, radius, step_norm, rho, 0.0, true, false);
+      if (cx.tid == 0) trace.record(it, cand_cost, radius, step_norm, rho, 0.0, true, false);
       recorded = it + 1, min_rec = fmin(min_rec, cand_cost);
       // back to the iterate and, after a speculative evaluation, to the vectors of ITS linearization: the next dogleg step is
       // formed from them (the matrix buffer then holds the candidate's linearization, which nothing reads: an invalid next
@@ -3988,10 +3978,7 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
       stamp(cx, ST_V_REST);
     }
   }
-  if (cx.tid == 0) {
-    sd[1] = min_rec;
-    si[0] = recorded, si[1] = termination, si[2] = n_ok, si[3] = n_bad;
-  }
+  if (cx.tid == 0) trace.finish(recorded, termination, n_ok, n_bad, min_rec);
   VIO_SYNC();
 }
 

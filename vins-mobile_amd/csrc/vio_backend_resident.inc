@@ -644,18 +644,7 @@ int vio_backend_resident_result(vio_backend_t *be, int32_t slot, VioResidentResu
   }
   out->pose = r->h_out_pose.data() + (size_t)slot * s.out_pose;
   out->speed_bias = r->h_out_sb.data() + (size_t)slot * s.out_sb;
-  {
-    const double *sd = r->h_stats_d.data() + (size_t)slot * s.stats_d;
-    const int *si = r->h_stats_i.data() + (size_t)slot * s.stats_i;
-    VioSolveStats *t = &out->stats;
-    t->initial_cost = sd[0], t->final_cost = sd[1];
-    t->iterations = si[0], t->termination = si[1], t->num_successful_steps = si[2], t->num_unsuccessful_steps = si[3];
-    for (int i = 0; i < kMaxTrace && i < VIO_MAX_TRACE; i++) {
-      t->it_cost[i] = sd[4 + i], t->it_radius[i] = sd[4 + kMaxTrace + i];
-      t->it_step_norm[i] = sd[4 + 2 * kMaxTrace + i], t->it_relative_decrease[i] = sd[4 + 3 * kMaxTrace + i];
-      t->it_gradient_max_norm[i] = sd[4 + 4 * kMaxTrace + i], t->it_flags[i] = si[4 + i];
-    }
-  }
+  unpack_solve_stats(r->h_stats_d.data() + (size_t)slot * s.stats_d, r->h_stats_i.data() + (size_t)slot * s.stats_i, &out->stats);
   if (next_prior_header) {
     MargOut mo;
     int *mi = r->h_m_ints.data() + (size_t)slot * be->MP.s_ints;

@@ -16,14 +16,13 @@ using namespace vio;
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kStatsD = 4 + 5 * kMaxTrace, kStatsI = 4 + kMaxTrace;
 
 struct PnpBatch {  // device pointers, per-window strides in elements
   int n_windows, max_frames, max_factors;
   const int *hdr;  // [N][4 + 2*max_frames + 1]: n, M, max_iter, -, fixed[max_frames], feat_start[max_frames+1]
   const double *pose, *speed, *bias, *ex, *preint, *obs, *pos;
   const int *track;
-  double *out_pose, *out_speed, *stats_d, *U, *Jraw;
+  double *out_pose, *out_speed, *stats_d, *Jraw;
   int *stats_i;
   double s_info, gravity, cauchy_b;
 };
@@ -41,7 +40,7 @@ __global__ __launch_bounds__(kThreads) void pnp_window_kernel(PnpBatch B) {
   v.obs = B.obs + (size_t)b * 2 * B.max_factors, v.pos = B.pos + (size_t)b * 3 * B.max_factors;
   v.track = B.track + (size_t)b * B.max_factors;
   v.out_pose = B.out_pose + (size_t)b * 7 * F, v.out_speed = B.out_speed + (size_t)b * 3 * F;
-  v.stats_d = B.stats_d + (size_t)b * kStatsD, v.stats_i = B.stats_i + (size_t)b * kStatsI;
+  v.stats_d = B.stats_d + (size_t)b * kStatsDoubles, v.stats_i = B.stats_i + (size_t)b * kStatsInts;
   v.Jraw = B.Jraw + (size_t)b * (F - 1) * 450;
   v.s_info = B.s_info, v.gravity = B.gravity, v.cauchy_b = B.cauchy_b;
   Ctx cx;
@@ -59,14 +58,10 @@ struct vio_pnp {
   VioConfig cfg;
   int max_batch = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms_sum = 0;
-  int launches = 0;
+  vio::LaunchTimer timer;
   vio::DevBuf<int> d_hdr, d_track, d_stats_i;
-  vio::DevBuf<double> d_pose, d_speed, d_bias, d_ex, d_preint, d_obs, d_pos, d_out_pose, d_out_speed, d_stats_d, d_U, d_Jraw;
+  vio::DevBuf<double> d_pose, d_speed, d_bias, d_ex, d_preint, d_obs, d_pos, d_out_pose, d_out_speed, d_stats_d, d_Jraw;
   ~vio_pnp() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -80,8 +75,7 @@ int vio_pnp_create(const VioConfig *cfg, int32_t max_batch, vio_pnp_t **out) {
   if (!p) return VIO_ENOMEM;
   p->device = vio::current_device();
   p->cfg = *cfg, p->max_batch = max_batch;
-  if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess ||
-      hipEventCreate(&p->ev1) != hipSuccess) {
+  if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) {
     delete p;
     return VIO_ENODEV;
   }
@@ -138,12 +132,11 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
       p->d_speed.ensure(speed.size()) != VIO_OK || p->d_bias.ensure(bias.size()) != VIO_OK || p->d_ex.ensure(ex.size()) != VIO_OK ||
       p->d_preint.ensure(pre.size()) != VIO_OK || p->d_obs.ensure(obs.size()) != VIO_OK || p->d_pos.ensure(pos.size()) != VIO_OK ||
       p->d_out_pose.ensure(pose.size()) != VIO_OK || p->d_out_speed.ensure(speed.size()) != VIO_OK ||
-      p->d_stats_d.ensure(N * kStatsD) != VIO_OK || p->d_stats_i.ensure(N * kStatsI) != VIO_OK ||
-      p->d_U.ensure(N * (F - 1) * 225) != VIO_OK || p->d_Jraw.ensure(N * (F - 1) * 450) != VIO_OK)
+      p->d_stats_d.ensure(N * kStatsDoubles) != VIO_OK || p->d_stats_i.ensure(N * kStatsInts) != VIO_OK ||
+      p->d_Jraw.ensure(N * (F - 1) * 450) != VIO_OK)
     return VIO_ENOMEM;
   hipStream_t st = p->stream;
-#define H2D(d, h) \
-  if (hipMemcpyAsync((d).p, (h).data(), (h).size() * sizeof((h)[0]), hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV
+#define H2D(d, h) HIP_OK(hipMemcpyAsync((d).p, (h).data(), (h).size() * sizeof((h)[0]), hipMemcpyHostToDevice, st))
   H2D(p->d_hdr, hdr);
   H2D(p->d_track, track);
   H2D(p->d_pose, pose);
@@ -159,43 +152,29 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
   B.hdr = p->d_hdr.p, B.pose = p->d_pose.p, B.speed = p->d_speed.p, B.bias = p->d_bias.p, B.ex = p->d_ex.p;
   B.preint = p->d_preint.p, B.obs = p->d_obs.p, B.pos = p->d_pos.p, B.track = p->d_track.p;
   B.out_pose = p->d_out_pose.p, B.out_speed = p->d_out_speed.p, B.stats_d = p->d_stats_d.p, B.stats_i = p->d_stats_i.p;
-  B.U = p->d_U.p, B.Jraw = p->d_Jraw.p;
+  B.Jraw = p->d_Jraw.p;
   B.s_info = p->cfg.fx / 1.5;  // PerspectiveFactor::sqrt_info = FOCUS_LENGTH_X / 1.5 (vins_pnp.cpp:19)
   B.gravity = p->cfg.gravity, B.cauchy_b = p->cfg.cauchy_a * p->cfg.cauchy_a;
   const size_t lds = pnp::carve<ldsd>(F, kThreads, nullptr, nullptr, nullptr);
-  if (hipFuncSetAttribute((const void *)pnp_window_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return VIO_ENODEV;
-  (void)hipEventRecord(p->ev0, st);
+  HIP_OK(hipFuncSetAttribute((const void *)pnp_window_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc = p->timer.begin(st);
+  if (rc != VIO_OK) return rc;
   hipLaunchKernelGGL(pnp_window_kernel, dim3(n), dim3(kThreads), lds, st, B);
-  (void)hipEventRecord(p->ev1, st);
-  if (hipGetLastError() != hipSuccess) return VIO_ENODEV;
-  std::vector<double> o_pose(pose.size()), o_speed(speed.size()), sd(N * kStatsD);
-  std::vector<int> si(N * kStatsI);
-  if (hipMemcpyAsync(o_pose.data(), p->d_out_pose.p, o_pose.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(o_speed.data(), p->d_out_speed.p, o_speed.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(sd.data(), p->d_stats_d.p, sd.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(si.data(), p->d_stats_i.p, si.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess)
-    return VIO_ENODEV;
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, p->ev0, p->ev1) == hipSuccess) p->ms_sum += ms, p->launches++;
+  if ((rc = p->timer.end(st)) != VIO_OK) return rc;
+  HIP_OK(hipGetLastError());
+  std::vector<double> o_pose(pose.size()), o_speed(speed.size()), sd(N * kStatsDoubles);
+  std::vector<int> si(N * kStatsInts);
+  HIP_OK(hipMemcpyAsync(o_pose.data(), p->d_out_pose.p, o_pose.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(o_speed.data(), p->d_out_speed.p, o_speed.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(sd.data(), p->d_stats_d.p, sd.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(si.data(), p->d_stats_i.p, si.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  HIP_OK(hipGetLastError());
   for (int b = 0; b < n; b++) {
     VioPnpWindow &w = windows[b];
     memcpy(w.pose, &o_pose[(size_t)b * 7 * F], sizeof(double) * 7 * w.n_frames);
     memcpy(w.speed, &o_speed[(size_t)b * 3 * F], sizeof(double) * 3 * w.n_frames);
-    if (stats) {
-      VioSolveStats &s = stats[b];
-      memset(&s, 0, sizeof(s));
-      const double *d = &sd[(size_t)b * kStatsD];
-      const int *i = &si[(size_t)b * kStatsI];
-      s.initial_cost = d[0], s.final_cost = d[1];
-      s.iterations = i[0], s.termination = i[1], s.num_successful_steps = i[2], s.num_unsuccessful_steps = i[3];
-      for (int k = 0; k < kMaxTrace && k < VIO_MAX_TRACE; k++) {
-        s.it_cost[k] = d[4 + k], s.it_radius[k] = d[4 + kMaxTrace + k], s.it_step_norm[k] = d[4 + 2 * kMaxTrace + k];
-        s.it_relative_decrease[k] = d[4 + 3 * kMaxTrace + k], s.it_gradient_max_norm[k] = d[4 + 4 * kMaxTrace + k];
-        s.it_flags[k] = i[4 + k];
-      }
-    }
+    if (stats) unpack_solve_stats(&sd[(size_t)b * kStatsDoubles], &si[(size_t)b * kStatsInts], &stats[b]);
   }
   return VIO_OK;
 }
@@ -203,9 +182,7 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
 int vio_pnp_kernel_ms(vio_pnp_t *p, double *ms_avg, int32_t *launches) {
   if (!p || !ms_avg || !launches) return VIO_EINVAL;
   VIO_ON_DEVICE_OF(p);
-  *launches = p->launches, *ms_avg = p->launches ? p->ms_sum / p->launches : 0.0;
-  p->ms_sum = 0, p->launches = 0;
-  return VIO_OK;
+  return p->timer.drain(ms_avg, launches);  // (every solve waited for its stream: the events have completed)
 }
 
 }  // extern "C"

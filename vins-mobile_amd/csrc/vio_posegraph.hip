@@ -289,8 +289,7 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgPtrs P) {
   ldsi ints = reinterpret_cast<ldsi>(lds + 7 * ld + 6 * (kPgThreads / 64) + 2);
   v.ft = ints, v.list = ints + ld / 16, v.cnt = ints + 2 * (ld / 16);
   const int N = v.N;
-  double *sd = P.stats_d + (size_t)gidx * kStatsDoubles;
-  int *si = P.stats_i + (size_t)gidx * kStatsInts;
+  const SolveTrace trace{P.stats_d + (size_t)gidx * kStatsDoubles, P.stats_i + (size_t)gidx * kStatsInts};  // (work-item 0 writes it)
 
   // envelope at tile granularity: first tile column of every tile row
   VIO_PARFOR(t, v.nt) v.ft[t] = t;
@@ -307,18 +306,8 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgPtrs P) {
   }
   VIO_SYNC();
 
-  int recorded = 0, n_ok = 0, n_bad = 0, termination = 0;
-  double min_recorded = 1.7976931348623157e308;
+  int recorded = 1, n_ok = 1, n_bad = 0, termination = 0;
   double radius = 1e4, decrease_factor = 2.0;
-  auto record = [&](int i, double cost, double step_norm, double rel, double gmax, bool valid, bool ok) {
-    recorded = i + 1;
-    min_recorded = fmin(min_recorded, cost);
-    if (cx.tid == 0 && i < kMaxTrace) {
-      sd[4 + i] = cost, sd[4 + kMaxTrace + i] = radius, sd[4 + 2 * kMaxTrace + i] = step_norm;
-      sd[4 + 3 * kMaxTrace + i] = rel, sd[4 + 4 * kMaxTrace + i] = gmax;
-      si[4 + i] = (valid ? 1 : 0) | (ok ? 2 : 0);
-    }
-  };
   auto grad_max = [&]() {  // |x - Plus(x, -g)|_inf (CSI/trust_region_minimizer.cc:270-284)
     double m = 0.0;
     VIO_PARFOR(c, N) {
@@ -334,10 +323,9 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgPtrs P) {
   VIO_SYNC();
   double gmax = grad_max();
   bool last_ok = true, reuse_diagonal = false;
-  n_ok++;
-  record(0, x_cost, 0, 0, gmax, true, true);
-  if (cx.tid == 0) sd[0] = x_cost;
-  double ev_min = x_cost, ev_cur = x_cost, ev_ref = x_cost, ev_cand = x_cost, ev_acc_ref = 0, ev_acc_cand = 0;
+  double min_rec = x_cost;
+  if (cx.tid == 0) trace.record(0, x_cost, radius, 0, 0, gmax, true, true), trace.initial(x_cost);
+  StepEvaluator ev = StepEvaluator::at(x_cost);
   int it = 0, invalid_run = 0;
   while (N > 0) {
     if (it >= v.max_iter) break;
@@ -371,7 +359,8 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgPtrs P) {
       radius = radius / decrease_factor, decrease_factor *= 2.0, reuse_diagonal = true;  // StepIsInvalid -> StepRejected(0)
       last_ok = false;
       n_bad++;
-      record(it, x_cost, 0, 0, gmax, false, false);
+      if (cx.tid == 0) trace.record(it, x_cost, radius, 0, 0, gmax, false, false);
+      recorded = it + 1, min_rec = fmin(min_rec, x_cost);
       continue;
     }
     invalid_run = 0;
@@ -389,9 +378,7 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgPtrs P) {
     if (step_norm <= 1e-8 * (x_norm + 1e-8)) { termination = 1; break; }
     const double cost_change = x_cost - cand_cost;
     if (fabs(cost_change) <= 1e-6 * x_cost) { termination = 1; break; }
-    const double rel = (ev_cur - cand_cost) / model_cost_change;
-    const double hist = (ev_ref - cand_cost) / (ev_acc_ref + model_cost_change);
-    const double rho = fmax(rel, hist);
+    const double rho = step_quality(ev, cand_cost, model_cost_change);
     if (rho > 1e-3) {
       double xn2 = 0.0;
       VIO_PARFOR(c, N) {
@@ -405,26 +392,22 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgPtrs P) {
       radius = radius / fmax(1.0 / 3.0, 1.0 - q * q * q);  // StepAccepted (:146-153)
       radius = fmin(1e16, radius);
       decrease_factor = 2.0, reuse_diagonal = false;
-      ev_cur = cand_cost, ev_acc_cand += model_cost_change, ev_acc_ref += model_cost_change;
-      if (ev_cur < ev_min) ev_min = ev_cur, ev_cand = ev_cur, ev_acc_cand = 0;
-      else if (ev_cur > ev_cand) ev_cand = ev_cur, ev_acc_cand = 0;
-      ev_ref = ev_cand, ev_acc_ref = ev_acc_cand;
+      ev = step_accepted(ev, cand_cost, model_cost_change);
       last_ok = true;
       n_ok++;
-      record(it, x_cost, step_norm, rho, gmax, true, true);
+      if (cx.tid == 0) trace.record(it, x_cost, radius, step_norm, rho, gmax, true, true);
+      recorded = it + 1, min_rec = fmin(min_rec, x_cost);
     } else {
       radius = radius / decrease_factor, decrease_factor *= 2.0, reuse_diagonal = true;  // StepRejected (:155-159)
       last_ok = false;
       n_bad++;
-      record(it, cand_cost, step_norm, rho, 0.0, true, false);
+      if (cx.tid == 0) trace.record(it, cand_cost, radius, step_norm, rho, 0.0, true, false);
+      recorded = it + 1, min_rec = fmin(min_rec, cand_cost);
     }
   }
   VIO_SYNC();
   VIO_PARFOR(c, N) P.xout[(size_t)gidx * ld + c] = v.x[c];
-  if (cx.tid == 0) {
-    sd[1] = min_recorded;
-    si[0] = recorded, si[1] = termination, si[2] = n_ok, si[3] = n_bad;
-  }
+  if (cx.tid == 0) trace.finish(recorded, termination, n_ok, n_bad, min_rec);
 }
 
 // a device array and its page-locked host staging of the same length
@@ -542,8 +525,6 @@ int vio_posegraph_optimize(vio_posegraph_t *pg, VioPoseGraph *graphs, int32_t n,
   UP(pg->ek, (size_t)n * EC);
   UP(pg->meas, (size_t)n * EC * 6);
 #undef UP
-  HIP_OK(hipMemsetAsync(pg->stats_d.d.p, 0, (size_t)n * kStatsDoubles * sizeof(double), st));
-  HIP_OK(hipMemsetAsync(pg->stats_i.d.p, 0, (size_t)n * kStatsInts * sizeof(int), st));
   PgPtrs P;
   P.ld = pg->ld, P.node_cap = NC, P.edge_cap = EC;
   P.hdr = pg->hdr.d.p, P.col = pg->col.d.p, P.node0 = pg->node0.d.p, P.edge_i = pg->ei.d.p, P.edge_j = pg->ej.d.p, P.edge_kind = pg->ek.d.p;
@@ -560,19 +541,7 @@ int vio_posegraph_optimize(vio_posegraph_t *pg, VioPoseGraph *graphs, int32_t n,
     const double *x = pg->xout.h.p + (size_t)g * pg->ld;
     for (int k = 0; k < G.n_nodes; k++)
       if (col[k] >= 0) G.ypr[3 * k] = x[col[k]], G.t[3 * k] = x[col[k] + 1], G.t[3 * k + 1] = x[col[k] + 2], G.t[3 * k + 2] = x[col[k] + 3];
-    if (stats) {
-      VioSolveStats &s = stats[g];
-      memset(&s, 0, sizeof(s));
-      const double *sd = pg->stats_d.h.p + (size_t)g * kStatsDoubles;
-      const int *si = pg->stats_i.h.p + (size_t)g * kStatsInts;
-      s.initial_cost = sd[0], s.final_cost = sd[1];
-      s.iterations = si[0], s.termination = si[1], s.num_successful_steps = si[2], s.num_unsuccessful_steps = si[3];
-      for (int i = 0; i < s.iterations && i < VIO_MAX_TRACE && i < kMaxTrace; i++) {
-        s.it_cost[i] = sd[4 + i], s.it_radius[i] = sd[4 + kMaxTrace + i], s.it_step_norm[i] = sd[4 + 2 * kMaxTrace + i];
-        s.it_relative_decrease[i] = sd[4 + 3 * kMaxTrace + i], s.it_gradient_max_norm[i] = sd[4 + 4 * kMaxTrace + i];
-        s.it_flags[i] = si[4 + i];
-      }
-    }
+    if (stats) unpack_solve_stats(pg->stats_d.h.p + (size_t)g * kStatsDoubles, pg->stats_i.h.p + (size_t)g * kStatsInts, &stats[g]);
   }
   return VIO_OK;
 }
