@@ -18,6 +18,7 @@
 
 #include <type_traits>
 
+#include "lk_layout.h"
 #include "vio_exact_math.h"
 
 #include <math.h>
@@ -144,19 +145,27 @@ constexpr int kIP = kWin + 3;              // 24: window + 1 (bilinear) + 2 (Sch
 constexpr int kDP = kWin + 1;              // 22: derivative positions
 constexpr int kJMargin = 3;
 constexpr int kJP = kWin + 1 + 2 * kJMargin;  // 28
-constexpr int kJS = 43;  // row stride of the staged J region (dwords): the three lane groups of an iteration read rows 0 / 1 / 2 of 21 columns each -- at 43 (and 2 x 43 = 22 mod 64) their bank ranges [0, 21), [43, 64), [22, 43) do not meet (29: 15 two-way conflicts per read; lk_track 539 -> 532 us)
-constexpr int kIS = kIP + 1;                  // row stride of the staged I patch (dwords)
+// Row strides (dwords) of the staged arrays and the lane -> window pixel ownership come from lk_layout.h, with the model of
+// the LDS banking they are chosen for: 32 dword banks, lanes 0-31 and 32-63 served apart, one extra cycle per further
+// distinct dword on a busy bank. Every window read of the template build and of the iterations is conflict-free under it.
+// (The previous layout -- lane l on column l % 21 of rows l / 21 + 3 q, strides 25 / 22 / 43 -- was laid out for 64 banks across the
+// whole wave: +2 / +1 / +2 cycles on every 2-cycle read, 45 % of the kernel's LDS-array cycles were conflicts.)
+constexpr int kIS = lk_layout::kStrideI, kDS = lk_layout::kStrideDI, kJS = lk_layout::kStrideJ;
+static_assert(lk_layout::kWin == kWin && kIS >= kIP && kDS >= kDP && kJS >= kJP, "strides hold a row");
+static_assert(lk_layout::window_reads_extra_cycles(kIS) == 0 && lk_layout::window_reads_extra_cycles(kDS) == 0 &&
+                  lk_layout::window_reads_extra_cycles(kJS) == 0,
+              "window reads of I, dI and J are free of LDS bank conflicts");
 // Every staged pixel is ONE ALIGNED DWORD holding the pair (v[x] | v[x+1] << 16): sub-dword and unaligned LDS accesses
 // crawl on this hardware (the byte-array version of this kernel spent 40 % of its wave cycles in LDS issue stalls).
 // A pair is also exactly one v_dot2_u32_u16 operand, so a bilinear sample is two reads and two dot instructions
 // (weights < 2^15, products < 2^22).
 // The template patch and its derivatives are consumed (into registers) before the first J region of a level is staged,
-// so the two share their LDS: 4.3 KB per feature instead of 7.6 KB.
+// so the two share their LDS: 5.3 KB per feature (six workgroups per CU: 128 of 160 KB).
 struct LkWaveLds {
   union {
     struct {
       uint32_t I[kIP][kIS];
-      short2 dI[kDP][kDP];
+      uint32_t dI[kDP][kDS];  // short2 {dx, dy}
     };
     uint32_t J[kJP][kJS];
   };
@@ -264,13 +273,17 @@ __device__ __forceinline__ void wave_sum_exact3(int p, int q, int r, float &sp, 
 // SLOWER (1.36 vs 1.28 ms per front-end step), more resident waves are faster: with the LDS per feature down to 4.3 KB the
 // register count is what limits residency, so the kernel is compiled for 6 waves per SIMD (80 VGPRs, no spills; 95 -> 5
 // waves before): front-end step 1.28 -> 1.17 ms. (8 waves per SIMD = 64 VGPRs spills 17 registers and gains another 0.5 %.)
-template <bool STATS = false>
+// ERR: the error output of calcOpticalFlowPyrLK (mean |J - I| over the window at the final position: one more bilinear pass,
+// at times a re-stage of J, and a wave sum per tracked feature). readImage never reads it, so the step path launches
+// ERR = false: no pass and no store to `err`; next_pts and status are the same in both.
+template <bool STATS = false, bool ERR = true>
 __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_pyr, const uint8_t *next_pyr, LkParams P,
                                                        const int *n_pts, const float *prev_pts, float *next_pts,
                                                        uint8_t *status, float *err, unsigned long long *stats) {
   __shared__ LkWaveLds lds_all[4];
   const int seq = blockIdx.y;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // (the wave index off the scalar unit: the feature's slot and its output index stay in scalar registers to the end)
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int pt = blockIdx.x * (blockDim.x >> 6) + wave;
   if (pt >= n_pts[seq]) return;
   LkWaveLds &L = lds_all[wave];
@@ -280,11 +293,13 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
   const float half = (kWin - 1) * 0.5f;
   const float FLT_SCALE = 1.f / (1 << 20);
   constexpr int NPX = (kWin * kWin + 63) / 64;  // window pixels per lane: 7
-  // This lane's window pixels: lane l owns column l % 21 of rows l / 21 + 3 q (q = 0..6; 63 lanes) -- the q-th pixel sits a
-  // CONSTANT 3 q rows below the first, so the LDS reads of an iteration share one address register (+ immediate offsets)
+  // This lane's window pixels (lk_layout.h): seven consecutive rows wy0 + q (q = 0..6) of column wx0 -- the q-th pixel sits a
+  // CONSTANT q rows below the first, so the LDS reads of an iteration share one address register (+ immediate offsets)
   // instead of one address computation per pixel. (The sums over the window are exact integers: which lane owns which pixel
   // does not reach the result.)
-  const int wy0 = min(lane / kWin, 2), wx0 = lane % kWin;  // (lane 63 owns nothing: it shadows lane 62's rows, masked below)
+  static_assert(NPX == lk_layout::kPxPerLane, "pixels per lane");
+  const lk_layout::Px px0 = lk_layout::lane_pixel0(lane);
+  const int wy0 = px0.row, wx0 = px0.col;  // (lane 63 owns nothing: it shadows lane 42's addresses, masked below)
   const int joff = wy0 * kJS + wx0;  // element offset of the first pixel in the staged J region
   bool st = true;
   float er = 0.f;
@@ -381,7 +396,7 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
       const int seg = lane / NCP, cp = lane - NCP * seg, c = 2 * cp;
       const int r0 = seg * SEG < kDP - SEG ? seg * SEG : kDP - SEG;
       const uint32_t *Ip = &L.I[0][0] + (__mul24(r0, kIS) + c);
-      uint32_t *Dp = reinterpret_cast<uint32_t *>(&L.dI[0][0]) + (__mul24(r0, kDP) + c);
+      uint32_t *Dp = reinterpret_cast<uint32_t *>(&L.dI[0][0]) + (__mul24(r0, kDS) + c);
       const lk_s2 k3 = {3, 3}, k10 = {10, 10};
       auto walk = [&](auto checked) {  // (checked: the patch leaves the image -- derivI's BORDER_CONSTANT zeros)
         const unsigned ok0 = (unsigned)(ipx + c) < (unsigned)cols, ok1 = (unsigned)(ipx + c + 1) < (unsigned)cols;
@@ -402,7 +417,7 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
             const unsigned rok = (unsigned)(ipy + r0 + r - 2) < (unsigned)rows;
             d0 &= 0u - (ok0 & rok), d1 &= 0u - (ok1 & rok);
           }
-          Dp[(r - 2) * kDP] = d0, Dp[(r - 2) * kDP + 1] = d1;
+          Dp[(r - 2) * kDS] = d0, Dp[(r - 2) * kDS + 1] = d1;
         }
       };
       if (inside) walk(std::false_type{});
@@ -421,26 +436,30 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
     int p11 = 0, p12 = 0, p22 = 0;  // per-lane partials: <= 14 products of |v| <= 4080^2 fit 32 bits
 #pragma unroll
     for (int h = 0; h < NPP; h++) IxP[h] = IyP[h] = lk_s2{0, 0};
+    // bilinear taps as dot products of packed pairs (a 32-bit integer multiply is a quarter-rate instruction here; the
+    // element-wise form of this block was 12 of them per pixel): the I patch is staged as pairs already; the derivative
+    // pairs (d[x], d[x+1]) are cut out of two (dx, dy) words with v_perm_b32. Weights <= 2^14 fit int16, and the SIGNED
+    // dot keeps iw11 = 2^14 - iw00 - iw01 - iw10 right when the three roundings push it to -1.
+    // The lane's pixels are consecutive rows of one column: the bottom row words of pixel q are the top row words of pixel
+    // q + 1, read (and cut) once -- 8 reads of I and 16 of dI per lane instead of 14 and 28.
+    const uint32_t *Iw = &L.I[wy0 + 1][wx0 + 1], *Dw = &L.dI[wy0][wx0];  // (I[x+1], I[x+2]) of row y + 1; (dx, dy) of [y][x]
+    auto tap_row = [&](int k, lk_s2 &iv, lk_s2 &sx, lk_s2 &sy) {
+      uint32_t d0, d1;
+      __builtin_memcpy(&iv, Iw + k * kIS, 4);
+      __builtin_memcpy(&d0, Dw + k * kDS, 4), __builtin_memcpy(&d1, Dw + k * kDS + 1, 4);
+      const uint32_t xs = __builtin_amdgcn_perm(d1, d0, 0x05040100u), ys = __builtin_amdgcn_perm(d1, d0, 0x07060302u);
+      __builtin_memcpy(&sx, &xs, 4), __builtin_memcpy(&sy, &ys, 4);
+    };
+    lk_s2 it, sxt, syt;
+    tap_row(0, it, sxt, syt);
 #pragma unroll
-    for (int q = 0; q < NPX; q++) {
-      const int y = wy0 + 3 * q, x = wx0;  // (always inside the window)
-      // bilinear taps as dot products of packed pairs (a 32-bit integer multiply is a quarter-rate instruction here; the
-      // element-wise form of this block was 12 of them per pixel): the I patch is staged as pairs already; the derivative
-      // pairs (d[x], d[x+1]) are cut out of two (dx, dy) words with v_perm_b32. Weights <= 2^14 fit int16, and the SIGNED
-      // dot keeps iw11 = 2^14 - iw00 - iw01 - iw10 right when the three roundings push it to -1.
-      lk_s2 it, ib;
-      __builtin_memcpy(&it, &L.I[y + 1][x + 1], 4);  // (I[x+1], I[x+2]) of the two rows
-      __builtin_memcpy(&ib, &L.I[y + 2][x + 1], 4);
+    for (int q = 0; q < NPX; q++) {  // (rows wy0 + q: always inside the window)
+      lk_s2 ib, sxb, syb;
+      tap_row(q + 1, ib, sxb, syb);
       const int ival = __builtin_amdgcn_sdot2(it, sw_top, __builtin_amdgcn_sdot2(ib, sw_bot, 1 << (kWBits - 5 - 1), false), false) >> (kWBits - 5);
-      uint32_t d00, d01, d10, d11;
-      __builtin_memcpy(&d00, &L.dI[y][x], 4), __builtin_memcpy(&d01, &L.dI[y][x + 1], 4);
-      __builtin_memcpy(&d10, &L.dI[y + 1][x], 4), __builtin_memcpy(&d11, &L.dI[y + 1][x + 1], 4);
-      const uint32_t xt = __builtin_amdgcn_perm(d01, d00, 0x05040100u), yt = __builtin_amdgcn_perm(d01, d00, 0x07060302u);
-      const uint32_t xb = __builtin_amdgcn_perm(d11, d10, 0x05040100u), yb = __builtin_amdgcn_perm(d11, d10, 0x07060302u);
-      lk_s2 sxt, syt, sxb, syb;
-      __builtin_memcpy(&sxt, &xt, 4), __builtin_memcpy(&syt, &yt, 4), __builtin_memcpy(&sxb, &xb, 4), __builtin_memcpy(&syb, &yb, 4);
       int ixval = __builtin_amdgcn_sdot2(sxt, sw_top, __builtin_amdgcn_sdot2(sxb, sw_bot, 1 << (kWBits - 1), false), false) >> kWBits;
       int iyval = __builtin_amdgcn_sdot2(syt, sw_top, __builtin_amdgcn_sdot2(syb, sw_bot, 1 << (kWBits - 1), false), false) >> kWBits;
+      it = ib, sxt = sxb, syt = syb;
       if (lane >= 3 * kWin) ixval = iyval = 0;  // a pixel this lane does not own: weight zero in every sum below
       Ic[q] = (1 << (kWBits - 5 - 1)) - (int)((unsigned)ival << (kWBits - 5));
       if (q & 1) IxP[q >> 1].y = (short)ixval, IyP[q >> 1].y = (short)iyval;
@@ -514,13 +533,16 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
     const uint32_t *Jl = &L.J[0][0];
     // (the top-row weights are never negative: their dot is the unsigned three-operand instruction, seeded with Ic without
     // a copy; the bottom row, whose iw11 can be -1, goes through the signed accumulate-in-place one)
-    auto diff_j = [&](int base, int q, lk_us2 wtop, lk_s2 wbot) {  // bilinear J at this lane's q-th window pixel, minus I there
+    // (the pair words of the lane's eight rows, each read once: row q + 1 is the bottom of pixel q and the top of pixel q + 1)
+    auto load_j = [&](int base, uint32_t (&jr)[NPX + 1]) {
+#pragma unroll
+      for (int k = 0; k <= NPX; k++) jr[k] = Jl[base + (joff + k * kJS)];  // (one address register + immediate offsets)
+    };
+    auto diff_j = [&](const uint32_t (&jr)[NPX + 1], int q, lk_us2 wtop, lk_s2 wbot) {  // bilinear J at this lane's q-th window pixel, minus I there
       lk_us2 top;
       lk_s2 bot;
-      const int o = base + (joff + 3 * q * kJS);  // (q is a constant after unrolling)
-      const uint32_t t32 = Jl[o], b32 = Jl[o + kJS];
-      __builtin_memcpy(&top, &t32, 4);
-      __builtin_memcpy(&bot, &b32, 4);
+      __builtin_memcpy(&top, &jr[q], 4);
+      __builtin_memcpy(&bot, &jr[q + 1], 4);
       return __builtin_amdgcn_sdot2(bot, wbot, (int)__builtin_amdgcn_udot2(top, wtop, (unsigned)Ic[q], false), false) >> (kWBits - 5);  // (mod 2^32)
     };
     int nit = 0;  // (STATS only)
@@ -538,9 +560,11 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
       const lk_us2 wtop = {(unsigned short)iw00, (unsigned short)iw01};
       const lk_s2 wbot = {(short)iw10, (short)iw11};
       const int jbase = __mul24(iqy - joy, kJS) + (iqx - jox);
+      uint32_t jr[NPX + 1];
+      load_j(jbase, jr);
 #pragma unroll
       for (int h = 0; h < NPP; h++) {  // (a pixel the lane does not own has Ix = Iy = 0)
-        const int d0 = diff_j(jbase, 2 * h, wtop, wbot), d1 = 2 * h + 1 < NPX ? diff_j(jbase, 2 * h + 1, wtop, wbot) : 0;
+        const int d0 = diff_j(jr, 2 * h, wtop, wbot), d1 = 2 * h + 1 < NPX ? diff_j(jr, 2 * h + 1, wtop, wbot) : 0;
         const unsigned pk = __builtin_amdgcn_perm((unsigned)d1, (unsigned)d0, 0x05040100u);  // |J - I| <= 8160: (d0, d1) as two int16
         lk_s2 dp;
         __builtin_memcpy(&dp, &pk, 4);
@@ -577,6 +601,7 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
         st = false;
         continue;
       }
+      if (!ERR) continue;  // (the range test above is the status' last word: it stays)
       if (!j_staged || iex < jox || iex > jox + 2 * kJMargin || iey < joy || iey > joy + 2 * kJMargin) stage_j(iex, iey);
       float aa = ex - iex, bb = ey - iey;
       lk_weights(aa, bb, iw00, iw01, iw10, iw11);
@@ -584,9 +609,11 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
       const lk_us2 wtop = {(unsigned short)iw00, (unsigned short)iw01};
       const lk_s2 wbot = {(short)iw10, (short)iw11};
       const int jbase = __mul24(iey - joy, kJS) + (iex - jox);
+      uint32_t jr[NPX + 1];
+      load_j(jbase, jr);
 #pragma unroll
       for (int q = 0; q < NPX; q++) {
-        const int d = abs(diff_j(jbase, q, wtop, wbot));
+        const int d = abs(diff_j(jr, q, wtop, wbot));
         pe += lane < 3 * kWin ? d : 0;
       }
       const int se = wave_sum_i32(pe);  // <= 441 * 16320 < 2^23
@@ -596,7 +623,7 @@ __global__ __launch_bounds__(256, 6) void lk_track_kernel(const uint8_t *prev_py
   if (lane == 0) {
     next_pts[pidx] = nxx, next_pts[pidx + 1] = nxy;
     status[(size_t)seq * P.cap + pt] = st ? 1 : 0;
-    err[(size_t)seq * P.cap + pt] = er;
+    if (ERR) err[(size_t)seq * P.cap + pt] = er;
   }
 }
 
@@ -2137,8 +2164,8 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
       hipLaunchKernelGGL((lk_track_kernel<true>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
                          fe->forw_pts.p, fe->lk_status.p, fe->lk_err.p, fe->lk_stats.p);
     else
-      hipLaunchKernelGGL((lk_track_kernel<false>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
-                         fe->forw_pts.p, fe->lk_status.p, fe->lk_err.p, (unsigned long long *)nullptr);
+      hipLaunchKernelGGL((lk_track_kernel<false, false>), grd, dim3(256), 0, st, fe->pyr[fe->cur_idx].p, forw, P, fe->n_pts.p, fe->cur_pts.p,
+                         fe->forw_pts.p, fe->lk_status.p, (float *)nullptr, (unsigned long long *)nullptr);  // (nobody reads the step's LK error)
   }
   int rcu = launch_track_update(fe, publish, st);
   if (rcu != VIO_OK) return rcu;
