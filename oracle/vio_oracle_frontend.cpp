@@ -353,15 +353,18 @@ bool have_collinear(const float *p, int count) {  // haveCollinearPoints: checks
   return false;
 }
 
-int solve_cubic(const double c[4], double r[3]) {  // cv::solveCubic (core/src/mathfuncs.cpp)
+// `tr` (here and below): optional path counters of oracle_fundamental_ransac_trace; they never change a result.
+int solve_cubic(const double c[4], double r[3], OracleRansacTrace *tr = nullptr) {  // cv::solveCubic (core/src/mathfuncs.cpp)
   double a0 = c[0], a1 = c[1], a2 = c[2], a3 = c[3];
   double x0 = 0, x1 = 0, x2 = 0;
   int n = 0;
   if (a0 == 0) {
     if (a1 == 0) {
+      if (tr) (a2 == 0 ? tr->cubic_none : tr->cubic_linear)++;
       if (a2 == 0) n = a3 == 0 ? -1 : 0;
       else x0 = -a3 / a2, n = 1;
     } else {
+      if (tr) tr->cubic_quadratic++;
       double d = a2 * a2 - 4 * a1 * a3;
       if (d >= 0) {
         d = sqrt(d);
@@ -375,6 +378,7 @@ int solve_cubic(const double c[4], double r[3]) {  // cv::solveCubic (core/src/m
     a0 = 1. / a0, a1 *= a0, a2 *= a0, a3 *= a0;
     double Q = (a1 * a1 - 3 * a2) * (1. / 9), R = (2 * a1 * a1 * a1 - 9 * a1 * a2 + 27 * a3) * (1. / 54);
     double Qcubed = Q * Q * Q, d = Qcubed - R * R;
+    if (tr) (d >= 0 ? tr->cubic_three : tr->cubic_one)++;
     if (d >= 0) {
       double theta = acos(R / sqrt(Qcubed)), sqrtQ = sqrt(Q);
       double t0 = -2 * sqrtQ, t1 = theta * (1. / 3), t2 = a1 * (1. / 3);
@@ -393,7 +397,7 @@ int solve_cubic(const double c[4], double r[3]) {  // cv::solveCubic (core/src/m
 }
 
 // Null space (dimension 2) of the 7x9 epipolar system by Gauss-Jordan with complete pivoting.
-void null_space_7x9(double a[63], double f1[9], double f2[9]) {
+void null_space_7x9(double a[63], double f1[9], double f2[9], OracleRansacTrace *tr = nullptr) {
   int colperm[9];
   for (int j = 0; j < 9; j++) colperm[j] = j;
   for (int k = 0; k < 7; k++) {
@@ -409,7 +413,10 @@ void null_space_7x9(double a[63], double f1[9], double f2[9]) {
       std::swap(colperm[k], colperm[pc]);
     }
     double d = a[k * 9 + k];
-    if (d == 0.0) continue;
+    if (d == 0.0) {
+      if (tr) tr->zero_pivots++;
+      continue;
+    }
     for (int j = 0; j < 9; j++) a[k * 9 + j] /= d;
     for (int i = 0; i < 7; i++)
       if (i != k) {
@@ -427,7 +434,7 @@ void null_space_7x9(double a[63], double f1[9], double f2[9]) {
   }
 }
 
-int run7point(const float *m1, const float *m2, double *fmatrix) {  // fundam.cpp run7Point
+int run7point(const float *m1, const float *m2, double *fmatrix, OracleRansacTrace *tr = nullptr) {  // fundam.cpp run7Point
   double a[63], f1[9], f2[9], c[4], r[3];
   for (int i = 0; i < 7; i++) {
     double x0 = m1[2 * i], y0 = m1[2 * i + 1], x1 = m2[2 * i], y1 = m2[2 * i + 1];
@@ -435,7 +442,7 @@ int run7point(const float *m1, const float *m2, double *fmatrix) {  // fundam.cp
     row[0] = x1 * x0, row[1] = x1 * y0, row[2] = x1, row[3] = y1 * x0, row[4] = y1 * y0, row[5] = y1, row[6] = x0,
     row[7] = y0, row[8] = 1;
   }
-  null_space_7x9(a, f1, f2);
+  null_space_7x9(a, f1, f2, tr);
   for (int i = 0; i < 9; i++) f1[i] -= f2[i];
   double t0 = f2[4] * f2[8] - f2[5] * f2[7], t1 = f2[3] * f2[8] - f2[5] * f2[6], t2 = f2[3] * f2[7] - f2[4] * f2[6];
   c[3] = f2[0] * t0 - f2[1] * t1 + f2[2] * t2;
@@ -449,18 +456,27 @@ int run7point(const float *m1, const float *m2, double *fmatrix) {  // fundam.cp
          f2[6] * (f1[1] * f1[5] - f1[2] * f1[4]) - f2[7] * (f1[0] * f1[5] - f1[2] * f1[3]) +
          f2[8] * (f1[0] * f1[4] - f1[1] * f1[3]);
   c[0] = f1[0] * t0 - f1[1] * t1 + f1[2] * t2;
-  int n = solve_cubic(c, r);
+  int n = solve_cubic(c, r, tr);
   if (n < 1 || n > 3) return n;
+  if (tr) tr->models += n;
   for (int k = 0; k < n; k++, fmatrix += 9) {
     double lambda = r[k], mu = 1., s = f1[8] * r[k] + f2[8];
     if (fabs(s) > 2.220446049250313e-16) mu = 1. / s, lambda *= mu, fmatrix[8] = 1.;
     else fmatrix[8] = 0.;
+    if (tr && fmatrix[8] == 0.) tr->models_f8_zero++;
     for (int i = 0; i < 8; i++) fmatrix[i] = f1[i] * lambda + f2[i] * mu;
   }
   return n;
 }
 
-int find_inliers(const float *m1, const float *m2, int count, const double *F, double thresh, uint8_t *mask) {
+void count_nan(OracleRansacTrace *tr, float e) {
+  int32_t bits;
+  memcpy(&bits, &e, 4);
+  tr->nan_errors++, tr->nan_errors_positive += bits >= 0;
+}
+
+int find_inliers(const float *m1, const float *m2, int count, const double *F, double thresh, uint8_t *mask,
+                 OracleRansacTrace *tr = nullptr) {
   float t = (float)(thresh * thresh);
   int nz = 0;
   for (int i = 0; i < count; i++) {  // FMEstimatorCallback::computeError
@@ -473,6 +489,7 @@ int find_inliers(const float *m1, const float *m2, int count, const double *F, d
     s1 = 1. / (a * a + b * b);
     d1 = x1 * a + y1 * b + c;
     float e = (float)std::max(d1 * d1 * s1, d2 * d2 * s2);
+    if (tr && e != e) count_nan(tr, e);
     int f = e <= t;
     mask[i] = (uint8_t)f, nz += f;
   }
@@ -501,7 +518,7 @@ float epipolar_error(const double *F, float fx1, float fy1, float fx2, float fy2
 }
 
 // getSubset(..., maxAttempts = 10000), checkPartialSubsets == false (ptsetreg.cpp), shared by both registrators
-bool get_subset(CvRng &rng, const float *m1, const float *m2, int count, float ms1[14], float ms2[14]) {
+bool get_subset(CvRng &rng, const float *m1, const float *m2, int count, float ms1[14], float ms2[14], int *redraws = nullptr) {
   const int model_points = 7, max_attempts = 10000;
   int idx[7], i = 0, iters = 0;
   for (; iters < max_attempts; iters++) {
@@ -518,35 +535,57 @@ bool get_subset(CvRng &rng, const float *m1, const float *m2, int count, float m
       ms2[2 * i] = m2[2 * idx_i], ms2[2 * i + 1] = m2[2 * idx_i + 1];
       i++;
     }
-    if (i == model_points && (have_collinear(ms1, i) || have_collinear(ms2, i))) continue;
+    if (i == model_points && (have_collinear(ms1, i) || have_collinear(ms2, i))) {
+      if (redraws) ++*redraws;
+      continue;
+    }
     break;
   }
   return i == model_points && iters < max_attempts;
 }
 
+// get_subset for hypothesis `iter`, with the counters of the trace
+bool traced_subset(CvRng &rng, const float *m1, const float *m2, int count, float ms1[14], float ms2[14], int iter,
+                   OracleRansacTrace *tr) {
+  int redraws = 0;
+  bool found = get_subset(rng, m1, m2, count, ms1, ms2, &redraws);
+  if (tr) {
+    if (redraws > 0 && tr->first_redraw_iteration < 0) tr->first_redraw_iteration = iter;
+    if (redraws > 0 && iter < 64) tr->redraw_mask |= 1ULL << iter;
+    tr->subset_redraws += redraws;
+    if (!found) tr->subset_failed = 1, tr->subset_failed_iteration = iter;
+  }
+  return found;
+}
+
 // LMeDSPointSetRegistrator::run (ptsetreg.cpp, OpenCV 3.0.0): outlierRatio 0.45, niters fixed up front (300 for
 // confidence 0.99 and 7-point models), the model with the smallest median error wins (strictly smaller, so the first
 // of equals), inliers = error <= sigma^2 with sigma = 2.5 * 1.4826 * (1 + 5 / (count - 7)) * sqrt(median).
-bool fundamental_lmeds(const float *m1, const float *m2, int count, double confidence, uint8_t *out_mask) {
+bool fundamental_lmeds(const float *m1, const float *m2, int count, double confidence, uint8_t *out_mask, OracleRansacTrace *tr) {
   const int model_points = 7, max_iters = 1000;
   const int niters = ransac_update_num_iters(confidence, 0.45, model_points, max_iters);
   CvRng rng((uint64_t)-1);
   double min_median = 1.7976931348623157e308, best[9];
   float ms1[14], ms2[14];
   std::vector<float> err(count);
+  if (tr) tr->lmeds = 1, tr->niters = niters;
   for (int iter = 0; iter < niters; iter++) {
-    if (!get_subset(rng, m1, m2, count, ms1, ms2)) {
+    if (!traced_subset(rng, m1, m2, count, ms1, ms2, iter, tr)) {
       if (iter == 0) {
         for (int q = 0; q < count; q++) out_mask[q] = 1;
         return false;
       }
       break;
     }
+    if (tr) tr->iterations = iter + 1;
     double F[27];
-    int nmodels = run7point(ms1, ms2, F);
+    int nmodels = run7point(ms1, ms2, F, tr);
     if (nmodels <= 0) continue;
     for (int k = 0; k < nmodels; k++) {
-      for (int i = 0; i < count; i++) err[i] = epipolar_error(F + 9 * k, m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1]);
+      for (int i = 0; i < count; i++) {
+        err[i] = epipolar_error(F + 9 * k, m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1]);
+        if (tr && err[i] != err[i]) count_nan(tr, err[i]);
+      }
       // std::sort(errf.ptr<int>(), ...): the float bit patterns are ordered as integers
       std::vector<int32_t> bits(count);
       memcpy(bits.data(), err.data(), sizeof(float) * count);
@@ -556,13 +595,14 @@ bool fundamental_lmeds(const float *m1, const float *m2, int count, double confi
       if (median < min_median) {
         min_median = median;
         memcpy(best, F + 9 * k, sizeof(best));
+        if (tr) tr->best_updates++, tr->last_best_iteration = iter, tr->min_median = median;
       }
     }
   }
   if (min_median < 1.7976931348623157e308) {
     double sigma = 2.5 * 1.4826 * (1 + 5. / (count - model_points)) * std::sqrt(min_median);
     sigma = std::max(sigma, 0.001);
-    int good = find_inliers(m1, m2, count, best, sigma, out_mask);  // the mask is copied out before `result` is formed
+    int good = find_inliers(m1, m2, count, best, sigma, out_mask, tr);  // the mask is copied out before `result` is formed
     return good >= model_points;
   }
   for (int q = 0; q < count; q++) out_mask[q] = 1;  // no model at all: the reference would read an empty status vector
@@ -570,12 +610,17 @@ bool fundamental_lmeds(const float *m1, const float *m2, int count, double confi
 }
 
 // RANSACPointSetRegistrator::run with FMEstimatorCallback, modelPoints 7, maxIters 1000 (ptsetreg.cpp)
-bool fundamental_ransac(const float *m1, const float *m2, int count, double threshold, double confidence, uint8_t *out_mask) {
+bool fundamental_ransac(const float *m1, const float *m2, int count, double threshold, double confidence, uint8_t *out_mask,
+                        OracleRansacTrace *tr = nullptr) {
+  if (tr) {
+    memset(tr, 0, sizeof(*tr));
+    tr->first_redraw_iteration = tr->subset_failed_iteration = tr->last_best_iteration = -1;
+  }
   const int model_points = 7, max_iters = 1000;
   if (count < 15) {
     // findFundamentalMat (fundam.cpp, 3.0.0): "(method & ~3) == FM_RANSAC && npoints >= 15" else LMedS. The tracker only
     // calls with >= 8 points (feature_tracker.cpp:92,196); fewer than 8 keeps everything (7 would run the plain solver).
-    if (count >= 8) return fundamental_lmeds(m1, m2, count, confidence, out_mask);
+    if (count >= 8) return fundamental_lmeds(m1, m2, count, confidence, out_mask, tr);
     for (int i = 0; i < count; i++) out_mask[i] = 1;
     return false;
   }
@@ -583,44 +628,30 @@ bool fundamental_ransac(const float *m1, const float *m2, int count, double thre
   int niters = max_iters, max_good = 0;
   std::vector<uint8_t> mask(count), best(count, 0);
   float ms1[14], ms2[14];
+  if (tr) tr->niters = niters;
   for (int iter = 0; iter < niters; iter++) {
-    // getSubset(..., maxAttempts = 10000), checkPartialSubsets == false
-    int idx[7], i = 0, iters = 0;
-    const int max_attempts = 10000;
-    for (; iters < max_attempts; iters++) {
-      for (i = 0; i < model_points && iters < max_attempts;) {
-        int idx_i = 0;
-        for (;;) {
-          idx_i = idx[i] = rng.uniform(0, count);
-          int j;
-          for (j = 0; j < i; j++)
-            if (idx_i == idx[j]) break;
-          if (j == i) break;
-        }
-        ms1[2 * i] = m1[2 * idx_i], ms1[2 * i + 1] = m1[2 * idx_i + 1];
-        ms2[2 * i] = m2[2 * idx_i], ms2[2 * i + 1] = m2[2 * idx_i + 1];
-        i++;
-      }
-      if (i == model_points && (have_collinear(ms1, i) || have_collinear(ms2, i))) continue;
-      break;
-    }
-    bool found = i == model_points && iters < max_attempts;
-    if (!found) {
+    if (!traced_subset(rng, m1, m2, count, ms1, ms2, iter, tr)) {
       if (iter == 0) {
         for (int q = 0; q < count; q++) out_mask[q] = 1;
         return false;
       }
       break;
     }
+    if (tr) tr->iterations = iter + 1;
     double F[27];
-    int nmodels = run7point(ms1, ms2, F);
+    int nmodels = run7point(ms1, ms2, F, tr);
     if (nmodels <= 0) continue;
     for (int k = 0; k < nmodels; k++) {
-      int good = find_inliers(m1, m2, count, F + 9 * k, threshold, mask.data());
+      int good = find_inliers(m1, m2, count, F + 9 * k, threshold, mask.data(), tr);
       if (good > std::max(max_good, model_points - 1)) {
         std::swap(mask, best);
         max_good = good;
+        const int before = niters;
         niters = ransac_update_num_iters(confidence, (double)(count - good) / count, model_points, niters);
+        if (tr) {
+          tr->best_updates++, tr->last_best_iteration = iter, tr->max_good = good, tr->niters = niters;
+          if (niters < before) tr->niters_lowered++;
+        }
       }
     }
   }
@@ -781,10 +812,17 @@ int oracle_good_features(const VioConfig *cfg, const uint8_t *img, const uint8_t
   return VIO_OK;
 }
 
-int oracle_fundamental_ransac(const VioConfig *cfg, const float *pts1, const float *pts2, int32_t n, uint8_t *inlier_mask) {
-  fundamental_ransac(pts1, pts2, n, cfg->f_threshold, cfg->f_confidence, inlier_mask);
+int oracle_fundamental_ransac_trace(const VioConfig *cfg, const float *pts1, const float *pts2, int32_t n, uint8_t *inlier_mask,
+                                    OracleRansacTrace *trace) {
+  fundamental_ransac(pts1, pts2, n, cfg->f_threshold, cfg->f_confidence, inlier_mask, trace);
   return VIO_OK;
 }
+
+int oracle_fundamental_ransac(const VioConfig *cfg, const float *pts1, const float *pts2, int32_t n, uint8_t *inlier_mask) {
+  return oracle_fundamental_ransac_trace(cfg, pts1, pts2, n, inlier_mask, nullptr);
+}
+
+int oracle_run7point(const float ms1[14], const float ms2[14], double F[27]) { return run7point(ms1, ms2, F); }
 
 oracle_tracker_t *oracle_tracker_create(const VioConfig *cfg) {
   oracle_tracker *t = new oracle_tracker();

@@ -17,6 +17,14 @@ _dp = C.POINTER(C.c_double)
 _oracle = None
 
 
+class OracleRansacTrace(C.Structure):  # oracle/vio_oracle.h
+    _fields_ = [(k, C.c_int32) for k in (
+        "lmeds", "iterations", "niters", "niters_lowered", "models", "subset_redraws", "first_redraw_iteration",
+        "subset_failed", "subset_failed_iteration", "zero_pivots", "cubic_three", "cubic_one", "cubic_quadratic",
+        "cubic_linear", "cubic_none", "models_f8_zero", "best_updates", "last_best_iteration", "max_good",
+        "nan_errors", "nan_errors_positive")] + [("redraw_mask", C.c_uint64), ("min_median", C.c_double)]
+
+
 def oracle_lib():
     """oracle/libvio_oracle.so (plain C++ restatement); built on demand with g++."""
     global _oracle
@@ -37,6 +45,8 @@ def oracle_lib():
         lib.oracle_min_eigen_map.argtypes = [u8p, C.c_int32, C.c_int32, C.c_int32, fp]
         lib.oracle_good_features.argtypes = [cfgp, u8p, u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, ip]
         lib.oracle_fundamental_ransac.argtypes = [cfgp, fp, fp, C.c_int32, u8p]
+        lib.oracle_fundamental_ransac_trace.argtypes = [cfgp, fp, fp, C.c_int32, u8p, C.POINTER(OracleRansacTrace)]
+        lib.oracle_run7point.argtypes = [fp, fp, _dp]
         lib.oracle_tracker_create.restype = C.c_void_p
         lib.oracle_tracker_create.argtypes = [cfgp]
         lib.oracle_tracker_destroy.argtypes = [C.c_void_p]
@@ -160,6 +170,27 @@ def oracle_ransac(cfg, p1, p2):
     m = np.zeros(len(p1), np.uint8)
     lib.oracle_fundamental_ransac(C.byref(cfg), p1.ctypes.data_as(_fp), p2.ctypes.data_as(_fp), len(p1), m.ctypes.data_as(_u8p))
     return m
+
+
+def oracle_ransac_trace(cfg, p1, p2):
+    """-> (mask, dict of the OracleRansacTrace counters) of one oracle findFundamentalMat call."""
+    lib = oracle_lib()
+    p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+    p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+    m, t = np.zeros(len(p1), np.uint8), OracleRansacTrace()
+    lib.oracle_fundamental_ransac_trace(C.byref(cfg), p1.ctypes.data_as(_fp), p2.ctypes.data_as(_fp), len(p1), m.ctypes.data_as(_u8p),
+                                        C.byref(t))
+    return m, {k: getattr(t, k) for k, _ in OracleRansacTrace._fields_}
+
+
+def oracle_run7point(ms1, ms2):
+    """run7Point on seven pairs -> [n, 3, 3] models (n <= 3; empty when the solver returns none)."""
+    lib = oracle_lib()
+    ms1 = np.ascontiguousarray(ms1, np.float32).reshape(7, 2)
+    ms2 = np.ascontiguousarray(ms2, np.float32).reshape(7, 2)
+    F = np.zeros(27)
+    n = lib.oracle_run7point(ms1.ctypes.data_as(_fp), ms2.ctypes.data_as(_fp), F.ctypes.data_as(_dp))
+    return F[: 9 * max(n, 0)].reshape(-1, 3, 3).copy()
 
 
 class OracleTracker:

@@ -811,7 +811,13 @@ __device__ __forceinline__ float epipolar_error(const double *F, float x1f, floa
   a = F[0] * x2 + F[3] * y2 + F[6], b = F[1] * x2 + F[4] * y2 + F[7], c = F[2] * x2 + F[5] * y2 + F[8];
   double s1 = 1. / (a * a + b * b);
   double d1 = x1 * a + y1 * b + c;
-  return (float)fmax(d1 * d1 * s1, d2 * d2 * s2);
+  // std::max(e1, e2), not fmax: where the epipolar line in image 1 degenerates exactly (x2 on the epipole: 0 * inf)
+  // e1 is NaN, and std::max keeps a NaN first operand while fmax drops it. LMedS sorts the errors' bit patterns as
+  // integers: the host's NaN (x86: sign bit set) sorts first, the device's default NaN (sign bit clear) would sort
+  // last, so a NaN is returned as the host makes it. Reached by tests/ransac_cases.py zoom_small_*.
+  const double e1 = d1 * d1 * s1, e2 = d2 * d2 * s2;
+  const float e = (float)((e1 < e2) ? e2 : e1);
+  return e != e ? __int_as_float((int)0xffc00000u) : e;
 }
 __device__ __forceinline__ bool epipolar_inlier(const double *F, float x1f, float y1f, float x2f, float y2f, float t) {
   return epipolar_error(F, x1f, y1f, x2f, y2f) <= t;
