@@ -741,7 +741,7 @@ typedef struct VioEstimatorStatus {
   double r_drift[9], t_drift[3];                 /* VINS.hpp r_drift / t_drift    */
   double relative_t[3], relative_q[4], relative_yaw, loop_pose[7]; /* front_pose  */
   int32_t resident;             /* 1: the landmark list lives in the device store */
-  int32_t reserved;
+  int32_t init_device_count;    /* solveInitial runs whose bundle adjustment ran on the device (set_init_device) */
 } VioEstimatorStatus;
 
 /* tic [3], ric [9] row-major: the camera-to-body extrinsic (TIC_*, RIC_*).     */
@@ -758,6 +758,14 @@ int vio_estimator_clear(vio_estimator_t *est, int32_t seq);                     
  * tie-breaker (mode 1: succeeds on the first frame with enough parallax, planar scenes
  * included).                                                                      */
 int vio_estimator_enable_initialization(vio_estimator_t *est, int32_t enable);
+/* Where solveInitial's bundle adjustment (the "full BA" of GlobalSFM::construct, inital_sfm.cpp:229-296) runs. 0 (default):
+ * on the host, inside each sequence's phase of process_images. 1: relativePose and construct() up to the bundle adjustment
+ * run on the host pool, the bundle adjustments of ALL sequences that got this far in the call go to the device in one
+ * vio_init_ba_solve launch, and the rest of solveInitial continues on the pool. Every failure branch acts as before
+ * (VINS.cpp:893-917). A problem beyond the context's capacity (cfg.max_features point_ok landmarks, cfg.max_factors +
+ * cfg.max_features observations, VIO_INIT_BA_MAX_FRAMES frames) takes the host route. The context is created at the first
+ * such call and lives as long as the estimator; VioEstimatorStatus.init_device_count counts the device-route runs.          */
+int vio_estimator_set_init_device(vio_estimator_t *est, int32_t enable);
 int vio_estimator_process_imu(vio_estimator_t *est, int32_t seq, double dt, const double acc[3],
                               const double gyr[3]);                                /* processIMU */
 /* processIMU for all sequences in one call (spread over host threads): sequence q
@@ -932,6 +940,40 @@ int vio_init_bundle_adjust(int32_t frame_num, int32_t l, double *c_rotation, dou
 int vio_init_sfm(int32_t frame_num, int32_t l, const double relative_R[9], const double relative_T[3], int32_t n_features,
                  const int32_t *feat_start, const int32_t *obs_frame, const double *obs_xy, double *q, double *T,
                  double *points, uint8_t *point_ok, int32_t *ok);
+
+/* That bundle adjustment (inital_sfm.cpp:229-296) for n independent problems in one
+ * device launch, one workgroup per problem: the arithmetic of vio_init_bundle_adjust
+ * iterate by iterate (trust_region_minimizer.cc loop, Levenberg-Marquardt, the points
+ * eliminated as 3x3 blocks, LLT of the reduced camera matrix), every sum in an order
+ * the problem fixes: a problem gives the same bits alone and in any slot of any batch.
+ * The reduced camera matrix lives in LDS, which bounds the window: VIO_INIT_BA_MAX_FRAMES
+ * frames (the reference's WINDOW_SIZE + 1 is 11; a 31-frame window's 180 x 180 matrix
+ * does not fit next to the rest and has no second layout).                          */
+#define VIO_INIT_BA_MAX_FRAMES 16
+typedef struct vio_init_ba vio_init_ba_t;
+typedef struct VioInitBaProblem {   /* the arguments of one vio_init_bundle_adjust call  */
+  int32_t frame_num, l, n_points;
+  double *c_rotation;               /* [frame_num][4] w x y z, in/out                    */
+  double *c_translation;            /* [frame_num][3], in/out                            */
+  double *points;                   /* [n_points][3], in/out where point_ok              */
+  const uint8_t *point_ok;          /* [n_points]                                        */
+  const int32_t *feat_start;        /* [n_points + 1]                                    */
+  const int32_t *obs_frame;         /* [feat_start[n_points]]                            */
+  const double *obs_xy;             /* [feat_start[n_points]][2]                         */
+  int32_t ok;                       /* out: CONVERGENCE || final_cost < 3e-3 (:279)      */
+} VioInitBaProblem;
+/* Capacities: problems per launch, frames, point_ok landmarks and their observations per
+ * problem. VIO_ENODEV without a device; VIO_ECAP for max_frames > VIO_INIT_BA_MAX_FRAMES. */
+int vio_init_ba_create(int32_t max_batch, int32_t max_frames, int32_t max_points, int32_t max_obs, vio_init_ba_t **out);
+void vio_init_ba_destroy(vio_init_ba_t *c);
+int vio_init_ba_get_device(const vio_init_ba_t *c, int32_t *device);
+/* Everything is checked on the host before anything is written or sent: VIO_EINVAL where
+ * vio_init_bundle_adjust returns it (and for a feat_start that is negative or descends);
+ * VIO_ECAP for n > max_batch, a problem beyond the capacities, or a landmark with two
+ * observations in one frame (the reference's per-frame observation lists cannot hold
+ * one). In either case no array of any problem has been touched. n = 0 is VIO_OK.       */
+int vio_init_ba_solve(vio_init_ba_t *c, VioInitBaProblem *problems, int32_t n, VioSolveStats *stats /* [n] or NULL */);
+int vio_init_ba_kernel_ms(vio_init_ba_t *c, double *ms_avg, int32_t *launches);
 
 /* ------------------------------------------------------------------------- */
 /* Replay I/O: the record / playback formats of the app and the IMU-image

@@ -17,6 +17,7 @@ VIO_OK = 0
 VIO_EINVAL, VIO_ENODEV, VIO_ENOMEM, VIO_ECAP, VIO_ESTATE, VIO_ETIMEOUT = -1, -2, -3, -4, -5, -6
 VIO_MAX_PRIOR_BLOCKS = 96
 VIO_MAX_TRACE = 64
+VIO_INIT_BA_MAX_FRAMES = 16
 VIO_BLOCK_POSE, VIO_BLOCK_SPEEDBIAS, VIO_BLOCK_EXPOSE = 0, 1, 2
 VIO_MARGIN_OLD, VIO_MARGIN_SECOND_NEW, VIO_MARGIN_NONE = 0, 1, 2
 STAGES = ["setup_imu", "setup_prior", "eval_prior", "eval_imu", "eval_proj", "scale", "schur", "rhs", "cholesky",
@@ -164,12 +165,18 @@ class VioFrameResult(C.Structure):
                 ("n_factors", C.c_int32), ("n_loop_factors", C.c_int32), ("stats", VioSolveStats)]
 
 
+class VioInitBaProblem(C.Structure):
+    _fields_ = [("frame_num", C.c_int32), ("l", C.c_int32), ("n_points", C.c_int32), ("c_rotation", _dp), ("c_translation", _dp),
+                ("points", _dp), ("point_ok", C.POINTER(C.c_uint8)), ("feat_start", _ip), ("obs_frame", _ip), ("obs_xy", _dp),
+                ("ok", C.c_int32)]
+
+
 class VioEstimatorStatus(C.Structure):
     _fields_ = [("frame_count", C.c_int32), ("solver_flag", C.c_int32), ("marginalization_flag", C.c_int32),
                 ("failure_occur", C.c_int32), ("prior_rows", C.c_int32), ("final_cost", C.c_double),
                 ("r_drift", C.c_double * 9), ("t_drift", C.c_double * 3), ("relative_t", C.c_double * 3),
                 ("relative_q", C.c_double * 4), ("relative_yaw", C.c_double), ("loop_pose", C.c_double * 7),
-                ("resident", C.c_int32), ("reserved", C.c_int32)]
+                ("resident", C.c_int32), ("init_device_count", C.c_int32)]
 
 
 VIO_SOLVER_INITIAL, VIO_SOLVER_NON_LINEAR = 0, 1
@@ -550,6 +557,12 @@ def load_product():
     lib.vio_init_pnp.argtypes = [_dp, _dp, C.c_int32, _dp, _dp, _ip]
     lib.vio_init_triangulate_point.argtypes = [_dp, _dp, _dp, _dp, _dp]
     lib.vio_init_bundle_adjust.argtypes = [C.c_int32, C.c_int32, _dp, _dp, C.c_int32, _dp, u8p, _ip, _ip, _dp, C.POINTER(VioSolveStats), _ip]
+    lib.vio_init_ba_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    lib.vio_init_ba_destroy.argtypes = [vp]
+    lib.vio_init_ba_destroy.restype = None
+    lib.vio_init_ba_get_device.argtypes = [vp, _ip]
+    lib.vio_init_ba_solve.argtypes = [vp, C.POINTER(VioInitBaProblem), C.c_int32, C.POINTER(VioSolveStats)]
+    lib.vio_init_ba_kernel_ms.argtypes = [vp, _dp, _ip]
     lib.vio_init_sfm.argtypes = [C.c_int32, C.c_int32, _dp, _dp, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp, u8p, _ip]
     lib.vio_visual_imu_alignment.argtypes = [cfgp, _dp, C.POINTER(VioInitFrame), C.c_int32, C.c_int32, _dp, _dp, _dp, _ip]
     resp, stp = C.POINTER(VioFrameResult), C.POINTER(VioEstimatorStatus)
@@ -559,6 +572,7 @@ def load_product():
     lib.vio_estimator_clear.argtypes = [vp, C.c_int32]
     lib.vio_estimator_enable_initialization.argtypes = [vp, C.c_int32]
     lib.vio_estimator_set_resident.argtypes = [vp, C.c_int32]
+    lib.vio_estimator_set_init_device.argtypes = [vp, C.c_int32]
     lib.vio_features_scale_depth.argtypes = [vp, C.c_double]
     lib.vio_estimator_process_imu.argtypes = [vp, C.c_int32, C.c_double, _dp, _dp]
     lib.vio_estimator_process_imu_batch.argtypes = [vp, _ip, C.c_int32, _dp, _dp, _dp]

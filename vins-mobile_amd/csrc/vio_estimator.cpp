@@ -103,9 +103,31 @@ struct Sequence {
   std::vector<int> pre_merge;
 };
 
+// solve_initial between its host halves: what relativePose and GlobalSFM::construct have produced when the bundle adjustment
+// starts, and that bundle adjustment's arguments in the layout of vio_init_ba_solve.
+struct InitStage {
+  int l = -1;
+  std::vector<init::SfmFeature> sfm_f;
+  std::vector<double> cq, tc;  // [P][4] w x y z, [P][3]: world -> camera, in/out of the bundle adjustment
+  std::vector<double> points, xy;
+  std::vector<uint8_t> ok;
+  std::vector<int32_t> start, frame;
+  int n_ok = 0;
+  int device_rc = VIO_OK, ba_ok = 0;
+};
+
 const double kI3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 
 }  // namespace
+
+// The device side of solveInitial's bundle adjustment is vio_sfm.hip. This file is also built without any device code (the
+// sanitizer walk of the tests links the host sources alone, with the back-end's entry points it needs stubbed): weak
+// references, and where they are absent vio_estimator_set_init_device leaves every bundle adjustment on the host route.
+extern "C" {
+__attribute__((weak)) int vio_init_ba_create(int32_t, int32_t, int32_t, int32_t, vio_init_ba_t **);
+__attribute__((weak)) void vio_init_ba_destroy(vio_init_ba_t *);
+__attribute__((weak)) int vio_init_ba_solve(vio_init_ba_t *, VioInitBaProblem *, int32_t, VioSolveStats *);
+}
 
 struct vio_estimator {
   VioConfig cfg;
@@ -139,6 +161,13 @@ struct vio_estimator {
   std::vector<VioWindow> staged;   // per sequence, built in parallel, compacted into `windows`
   std::vector<char> wants_solve;
   double ms_pre = 0, ms_solve = 0, ms_post = 0;  // wall time of the last process_images call, by phase
+  // vio_estimator_set_init_device: the bundle adjustment of solveInitial for every sequence that reaches it in one call goes to
+  // the device in one launch (vio_init_ba_solve); the context exists from the first such call on
+  bool init_device = false;
+  vio_init_ba_t *init_ba = nullptr;
+  std::vector<InitStage> init_stage;     // per sequence: solve_initial between its two host halves
+  std::vector<char> ba_wait;             // per sequence: its bundle adjustment is part of this call's launch
+  std::vector<int> init_device_count;    // per sequence: initialisations whose bundle adjustment ran on the device
 };
 
 namespace {
@@ -519,8 +548,10 @@ void g2R(const double g[3], double R0[9]) {  // Utility::g2R (utility.cpp:11-21)
   mat3mul(Y, T, R0);
 }
 
-// VINS::solveInitial + relativePose + visualInitialAlign (VINS.cpp:833-1145).
-bool solve_initial(vio_estimator *e, Sequence &s) {
+// VINS::solveInitial + relativePose + visualInitialAlign (VINS.cpp:833-1145), in two halves around the bundle adjustment
+// that closes GlobalSFM::construct: solve_initial_head runs relativePose and construct up to it, solve_initial_tail the
+// rest (the tail of construct, PnP of the in-between frames, the alignment).
+bool solve_initial_head(vio_estimator *e, Sequence &s, InitStage &st) {
   const int W = e->W, P = W + 1;
   // the landmark store as SfM features (VINS.cpp:883-899) and as correspondences (getCorresponding)
   int nfe = 0, npts = 0;
@@ -528,7 +559,8 @@ bool solve_initial(vio_estimator *e, Sequence &s) {
   std::vector<VioFeatureInfo> info(nfe > 0 ? nfe : 1);
   std::vector<double> pts(3 * (size_t)(npts > 0 ? npts : 1));
   if (vio_features_dump(s.fm, info.data(), nfe, &nfe, pts.data(), npts, &npts) != VIO_OK) return false;
-  std::vector<init::SfmFeature> sfm_f(nfe);
+  std::vector<init::SfmFeature> &sfm_f = st.sfm_f;
+  sfm_f.assign(nfe, init::SfmFeature());
   std::vector<size_t> first(nfe);
   {
     size_t off = 0;
@@ -572,12 +604,44 @@ bool solve_initial(vio_estimator *e, Sequence &s) {
     }
   }
   if (l < 0) return false;
-  std::vector<double> Q(4 * (size_t)P), T(3 * (size_t)P);
-  std::map<int, std::vector<double>> tracked;
-  if (!init::sfm_construct(P, Q.data(), T.data(), l, relative_R, relative_T, sfm_f, tracked)) {
+  st.l = l;
+  if (!init::sfm_construct_before_ba(P, l, relative_R, relative_T, sfm_f, st.cq, st.tc)) {
     s.marginalization_flag = VIO_MARGIN_OLD;  // FAIL_SFM (VINS.cpp:915-917)
     return false;
   }
+  return true;
+}
+
+// The bundle adjustment's arguments as vio_init_ba_solve takes them (the layout of vio_init_bundle_adjust).
+void stage_ba_problem(InitStage &st) {
+  const size_t n = st.sfm_f.size();
+  st.points.assign(3 * n + 3, 0.0), st.ok.assign(n + 1, 0), st.start.assign(n + 1, 0), st.frame.clear(), st.xy.clear();
+  st.n_ok = 0;
+  for (size_t j = 0; j < n; j++) {
+    const init::SfmFeature &f = st.sfm_f[j];
+    memcpy(&st.points[3 * j], f.position, 24), st.ok[j] = f.state ? 1 : 0, st.n_ok += f.state ? 1 : 0;
+    for (const auto &o : f.observation) st.frame.push_back(o.first), st.xy.push_back(o.second.first), st.xy.push_back(o.second.second);
+    st.start[j + 1] = (int32_t)st.frame.size();
+  }
+  if (st.frame.empty()) st.frame.push_back(0), st.xy.resize(2, 0.0);  // (non-null pointers for a problem without observations)
+}
+int staged_observations(const InitStage &st) {  // of the point_ok landmarks: what the context's max_obs counts
+  int n = 0;
+  for (size_t j = 0; j < st.sfm_f.size(); j++)
+    if (st.sfm_f[j].state) n += (int)st.sfm_f[j].observation.size();
+  return n;
+}
+
+// ba_ok: the bundle adjustment's verdict (inital_sfm.cpp:279).
+bool solve_initial_tail(vio_estimator *e, Sequence &s, InitStage &st, bool ba_ok) {
+  const int W = e->W, P = W + 1;
+  if (!ba_ok) {  // "vision only BA not converge"
+    s.marginalization_flag = VIO_MARGIN_OLD;  // FAIL_SFM (VINS.cpp:915-917)
+    return false;
+  }
+  std::vector<double> Q(4 * (size_t)P), T(3 * (size_t)P);
+  std::map<int, std::vector<double>> tracked;
+  init::sfm_construct_after_ba(P, st.cq, st.tc, st.sfm_f, Q.data(), T.data(), tracked);
   // PnP for every frame of all_image_frame (VINS.cpp:926-1003)
   double ricT[9];
   mat3T(e->ric, ricT);
@@ -674,6 +738,11 @@ bool solve_initial(vio_estimator *e, Sequence &s) {
     mat3mul(Rd, &s.Rs[9 * k], M), memcpy(&s.Rs[9 * k], M, 72);
   }
   return true;
+}
+
+bool solve_initial(vio_estimator *e, Sequence &s, InitStage &st) {
+  if (!solve_initial_head(e, s, st)) return false;
+  return solve_initial_tail(e, s, st, init::bundle_adjust(e->W + 1, st.l, st.cq, st.tc, st.sfm_f, nullptr));
 }
 
 void remember_last(vio_estimator *e, Sequence &s) {  // VINS.cpp:431-434, 472-475
@@ -874,6 +943,7 @@ int vio_estimator_create(const VioConfig *cfg, int32_t n_seq, const double tic[3
     clear_state(e, s);
   }
   e->windows.resize(n_seq), e->stats.resize(n_seq);
+  e->init_stage.resize(n_seq), e->ba_wait.assign(n_seq, 0), e->init_device_count.assign(n_seq, 0);
   *out = e;
   return VIO_OK;
 }
@@ -884,6 +954,7 @@ void vio_estimator_destroy(vio_estimator_t *e) {
     if (s.fm) vio_features_destroy(s.fm);
   for (int g = 0; g < vio_estimator::kMaxGroups; g++)
     if (e->be[g]) vio_backend_destroy(e->be[g]);
+  if (e->init_ba && vio_init_ba_destroy) vio_init_ba_destroy(e->init_ba);
   delete e;
 }
 
@@ -891,6 +962,12 @@ int vio_estimator_enable_initialization(vio_estimator_t *e, int32_t enable) {
   if (!e) return VIO_EINVAL;
   e->enable_init = enable != 0;
   e->init_relpose_fit = enable == 2;
+  return VIO_OK;
+}
+
+int vio_estimator_set_init_device(vio_estimator_t *e, int32_t enable) {
+  if (!e) return VIO_EINVAL;
+  e->init_device = enable != 0;
   return VIO_OK;
 }
 
@@ -1028,6 +1105,23 @@ int vio_estimator_process_images(vio_estimator_t *e, const VioObs *obs, const in
   // INITIAL / NON_LINEAR branch, triangulation, the window as solve_ceres hands it to the solver
   e->staged.resize(e->n_seq);
   e->wants_solve.assign(e->n_seq, 0);
+  // the window of a sequence that solves in this call, as solve_ceres hands it to the solver
+  auto stage_window = [&](int q) {
+    Sequence &s = e->seq[q];
+    VioFrameResult &res = results[q];
+    const int rc = build_window(e, s, &e->staged[q]);
+    if (rc != VIO_OK) {
+      // (typically VIO_ECAP: more landmarks / factors than cfg.max_features / max_factors.) The frame's observations
+      // are in the landmark store but the window will not slide: without a restart add_check_parallax refuses every
+      // following frame and the sequence stays stuck until the caller clears it.
+      clear_state(e, s);
+      res.action = VIO_FRAME_ERROR, res.error = rc;
+      return;
+    }
+    e->wants_solve[q] = 1;
+  };
+  // what the bundle adjustment context takes (vio_init_ba_create below): a larger problem stays on the host
+  const int ba_max_points = e->cfg.max_features, ba_max_obs = e->cfg.max_factors + e->cfg.max_features;
   auto phase_a = [&](int q) {
     VioFrameResult &res = results[q];
     memset(&res, 0, sizeof(res));
@@ -1091,8 +1185,23 @@ int vio_estimator_process_images(vio_estimator_t *e, const VioObs *obs, const in
         } else {
           bool result = false;
           if (e->enable_init && headers[q] - s.initial_timestamp > 0.3) {  // VINS.cpp:413-417
-            result = solve_initial(e, s);
-            s.initial_timestamp = headers[q];
+            InitStage &st = e->init_stage[q];
+            if (e->init_device) {
+              const bool head = solve_initial_head(e, s, st);
+              s.initial_timestamp = headers[q];
+              if (head && P <= VIO_INIT_BA_MAX_FRAMES) {
+                stage_ba_problem(st);
+                if (st.n_ok <= ba_max_points && staged_observations(st) <= ba_max_obs) {
+                  e->ba_wait[q] = 1;  // phase A continues in phase_a_after_ba, after this call's launch
+                  return;
+                }
+              }
+              result = head && solve_initial_tail(e, s, st, init::bundle_adjust(P, st.l, st.cq, st.tc, st.sfm_f, nullptr));
+            } else {
+              result = solve_initial(e, s, st);
+              s.initial_timestamp = headers[q];
+            }
+            st = InitStage();
           }
           if (result) {
             solve = true;
@@ -1109,18 +1218,53 @@ int vio_estimator_process_images(vio_estimator_t *e, const VioObs *obs, const in
       vio_features_triangulate(s.fm, s.Ps.data(), s.Rs.data(), e->tic, e->ric);
       solve = true;
     }
-    if (solve) {
-      rc = build_window(e, s, &e->staged[q]);
-      if (rc != VIO_OK) {
-        // (typically VIO_ECAP: more landmarks / factors than cfg.max_features / max_factors.) The frame's observations
-        // are in the landmark store but the window will not slide: without a restart add_check_parallax refuses every
-        // following frame and the sequence stays stuck until the caller clears it.
-        clear_state(e, s);
-        res.action = VIO_FRAME_ERROR, res.error = rc;
-        return;
-      }
-      e->wants_solve[q] = 1;
+    if (solve) stage_window(q);
+  };
+  // the rest of phase A for a sequence whose bundle adjustment was part of this call's launch
+  auto phase_a_after_ba = [&](int q) {
+    Sequence &s = e->seq[q];
+    InitStage &st = e->init_stage[q];
+    bool ba_ok;
+    if (st.device_rc == VIO_OK) {
+      for (size_t j = 0; j < st.sfm_f.size(); j++)
+        if (st.sfm_f[j].state) memcpy(st.sfm_f[j].position, &st.points[3 * j], 24);
+      ba_ok = st.ba_ok != 0;
+      e->init_device_count[q]++;
+    } else {  // (no device context, or the launch failed: nothing was written, the host route takes over)
+      ba_ok = init::bundle_adjust(P, st.l, st.cq, st.tc, st.sfm_f, nullptr);
     }
+    const bool result = solve_initial_tail(e, s, st, ba_ok);
+    st = InitStage();
+    if (result) {
+      stage_window(q);
+    } else {
+      slide_window(e, s);
+      results[q].action = VIO_FRAME_WAIT_INIT;
+    }
+  };
+  // phase A of sequences [q0, q1): the host pool, then one launch for the bundle adjustments that came up, then the pool again
+  auto run_phase_a = [&](int q0, int q1) {
+    HostPool::get().parallel_for(q1 - q0, [&](int i) { phase_a(q0 + i); });
+    std::vector<int> wait;
+    for (int q = q0; q < q1; q++)
+      if (e->ba_wait[q]) wait.push_back(q), e->ba_wait[q] = 0;
+    if (wait.empty()) return;
+    int rcb = vio_init_ba_create && vio_init_ba_solve ? VIO_OK : VIO_ENODEV;
+    if (rcb == VIO_OK && !e->init_ba) {
+      rcb = vio_init_ba_create(e->n_seq, P, ba_max_points, ba_max_obs, &e->init_ba);
+      if (rcb != VIO_OK) fprintf(stderr, "vio_amd: no device context for the initial bundle adjustment (%d): it runs on the host\n", rcb);
+    }
+    std::vector<VioInitBaProblem> pr(wait.size());
+    for (size_t i = 0; i < wait.size(); i++) {
+      InitStage &st = e->init_stage[wait[i]];
+      VioInitBaProblem &p = pr[i];
+      p.frame_num = P, p.l = st.l, p.n_points = (int32_t)st.sfm_f.size();
+      p.c_rotation = st.cq.data(), p.c_translation = st.tc.data(), p.points = st.points.data();
+      p.point_ok = st.ok.data(), p.feat_start = st.start.data(), p.obs_frame = st.frame.data(), p.obs_xy = st.xy.data(), p.ok = 0;
+    }
+    if (rcb == VIO_OK) rcb = vio_init_ba_solve(e->init_ba, pr.data(), (int32_t)pr.size(), nullptr);
+    for (size_t i = 0; i < wait.size(); i++) e->init_stage[wait[i]].device_rc = rcb, e->init_stage[wait[i]].ba_ok = pr[i].ok;
+    HostPool::get().parallel_for((int)wait.size(), [&](int i) { phase_a_after_ba(wait[i]); });
   };
   // phase C, per solved sequence: double2vector, loop bookkeeping, failure detection, slide
   auto phase_c = [&](int k) {
@@ -1177,8 +1321,8 @@ int vio_estimator_process_images(vio_estimator_t *e, const VioObs *obs, const in
     const auto ta = std::chrono::steady_clock::now();
     // (small groups: one sweep of the pool over all sequences is cheaper than a sweep per group -- measured 5.15 vs 5.4 ms
     // per frame with 2 x 128 sequences, 12.1 vs 15.5 ms the other way round with 4 x 256)
-    if (!pipelined && g == 0) HostPool::get().parallel_for(e->n_seq, [&](int q) { phase_a(q); });
-    if (pipelined) HostPool::get().parallel_for(q1 - q0, [&](int i) { phase_a(q0 + i); });
+    if (!pipelined && g == 0) run_phase_a(0, e->n_seq);
+    if (pipelined) run_phase_a(q0, q1);
     g0[g] = (int)e->solving.size();
     for (int q = q0; q < q1; q++) {
       if (results[q].action == VIO_FRAME_ERROR && first_error == VIO_OK) first_error = results[q].error;
@@ -1279,6 +1423,7 @@ int vio_estimator_get_status(vio_estimator_t *e, int32_t seq, VioEstimatorStatus
   st->relative_yaw = s.front.relative_yaw;
   memcpy(st->loop_pose, s.front.loop_pose, sizeof(st->loop_pose));
   st->resident = s.on_device ? 1 : 0;
+  st->init_device_count = e->init_device_count[seq];
   return VIO_OK;
 }
 

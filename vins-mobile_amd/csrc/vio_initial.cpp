@@ -786,12 +786,16 @@ bool bundle_adjust(int frame_num, int l, std::vector<double> &cq, std::vector<do
   return termination == 1 || x_cost < 3e-03;
 }
 
-bool sfm_construct(int frame_num, double *q, double *T, int l, const double relative_R[9], const double relative_T[3],
-                   std::vector<SfmFeature> &sfm_f, std::map<int, std::vector<double>> &tracked_points) {
+// GlobalSFM::construct up to its bundle adjustment (inital_sfm.cpp:117-227): the PnP chain and the triangulations. Leaves
+// the bundle adjustment's in/out arrays: cq [frame_num][4] (w x y z) and tc [frame_num][3], world -> camera, and the
+// triangulated landmarks in sfm_f.
+bool sfm_construct_before_ba(int frame_num, int l, const double relative_R[9], const double relative_T[3],
+                             std::vector<SfmFeature> &sfm_f, std::vector<double> &cq, std::vector<double> &tc) {
   if (frame_num < 2 || l < 0 || l >= frame_num - 1) return false;
   const int last = frame_num - 1;
   // camera -> reference poses (q, T) and their inverses, world -> camera (c_Rotation, c_Translation)
-  std::vector<double> Rc(9 * (size_t)frame_num, 0.0), tc(3 * (size_t)frame_num, 0.0), P(12 * (size_t)frame_num, 0.0);
+  std::vector<double> Rc(9 * (size_t)frame_num, 0.0), P(12 * (size_t)frame_num, 0.0);
+  tc.assign(3 * (size_t)frame_num, 0.0);
   const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   memcpy(&Rc[9 * l], I3, sizeof(I3));
   mat3T(relative_R, &Rc[9 * last]);
@@ -831,12 +835,18 @@ bool sfm_construct(int frame_num, double *q, double *T, int l, const double rela
     f.state = true;
   }
   // 5: full BA over (c_rotation = Quaterniond(c_Rotation[i]) as w x y z, c_translation)
-  std::vector<double> cq(4 * (size_t)frame_num);
+  cq.assign(4 * (size_t)frame_num, 0.0);
   for (int i = 0; i < frame_num; i++) {
     const Quat qi = RtoQ(&Rc[9 * i]);
     cq[4 * i] = qi.w, cq[4 * i + 1] = qi.x, cq[4 * i + 2] = qi.y, cq[4 * i + 3] = qi.z;
   }
-  if (!bundle_adjust(frame_num, l, cq, tc, sfm_f, nullptr)) return false;  // "vision only BA not converge"
+  return true;
+}
+
+// ... and what follows an accepted bundle adjustment (inital_sfm.cpp:287-314): the poses inverted, the landmarks by id.
+void sfm_construct_after_ba(int frame_num, const std::vector<double> &cq, const std::vector<double> &tc,
+                            const std::vector<SfmFeature> &sfm_f, double *q, double *T,
+                            std::map<int, std::vector<double>> &tracked_points) {
   for (int i = 0; i < frame_num; i++) {
     const Quat qi = qinv(Quat{cq[4 * i + 1], cq[4 * i + 2], cq[4 * i + 3], cq[4 * i]});  // q[i] = c_rotation^-1 (:287-295)
     double v[3];
@@ -846,6 +856,14 @@ bool sfm_construct(int frame_num, double *q, double *T, int l, const double rela
   }
   for (const SfmFeature &f : sfm_f)
     if (f.state) tracked_points[f.id] = std::vector<double>(f.position, f.position + 3);
+}
+
+bool sfm_construct(int frame_num, double *q, double *T, int l, const double relative_R[9], const double relative_T[3],
+                   std::vector<SfmFeature> &sfm_f, std::map<int, std::vector<double>> &tracked_points) {
+  std::vector<double> cq, tc;
+  if (!sfm_construct_before_ba(frame_num, l, relative_R, relative_T, sfm_f, cq, tc)) return false;
+  if (!bundle_adjust(frame_num, l, cq, tc, sfm_f, nullptr)) return false;  // "vision only BA not converge"
+  sfm_construct_after_ba(frame_num, cq, tc, sfm_f, q, T, tracked_points);
   return true;
 }
 

@@ -53,6 +53,16 @@ int recover_pose(const double E[9], const double *xy0, const double *xy1, int n,
 // GlobalSFM::construct (inital_sfm.cpp:117-316): q [frame_num][4] (x y z w), T [frame_num][3] = camera-to-frame-l poses.
 bool sfm_construct(int frame_num, double *q, double *T, int l, const double relative_R[9], const double relative_T[3],
                    std::vector<SfmFeature> &sfm_f, std::map<int, std::vector<double>> &tracked_points);
+// Its two halves around the bundle adjustment (sfm_construct = before, init::bundle_adjust, after), for a caller that runs
+// the bundle adjustment elsewhere: cq [frame_num][4] (w x y z) / tc [frame_num][3], world -> camera, and sfm_f are the
+// bundle adjustment's in/out arguments.
+bool sfm_construct_before_ba(int frame_num, int l, const double relative_R[9], const double relative_T[3],
+                             std::vector<SfmFeature> &sfm_f, std::vector<double> &cq, std::vector<double> &tc);
+void sfm_construct_after_ba(int frame_num, const std::vector<double> &cq, const std::vector<double> &tc,
+                            const std::vector<SfmFeature> &sfm_f, double *q, double *T,
+                            std::map<int, std::vector<double>> &tracked_points);
+bool bundle_adjust(int frame_num, int l, std::vector<double> &cq, std::vector<double> &ct, std::vector<SfmFeature> &sfm_f,
+                   VioSolveStats *stats);
 
 // cv::solvePnP(..., useExtrinsicGuess = true, ITERATIVE) with K = I: refines R, t (world -> camera) from the guess.
 bool pnp_refine(const std::vector<double> &pts3, const std::vector<double> &pts2, double R[9], double t[3]);

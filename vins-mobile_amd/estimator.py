@@ -55,6 +55,11 @@ class Estimator:
         (vio_estimator_set_resident; include/vio_amd.h)."""
         self._check(self.lib.vio_estimator_set_resident(self._h, 1 if on else 0), "set_resident")
 
+    def set_init_device(self, on=True):
+        """The bundle adjustments of solveInitial of all sequences that reach it in one call in one device launch
+        (vio_estimator_set_init_device; include/vio_amd.h). status(seq).init_device_count counts them."""
+        self._check(self.lib.vio_estimator_set_init_device(self._h, 1 if on else 0), "set_init_device")
+
     def clear(self, seq=0):
         self._check(self.lib.vio_estimator_clear(self._h, seq), "clear")
 
