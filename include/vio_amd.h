@@ -550,6 +550,35 @@ int  vio_loop_detector_erase(vio_loop_detector_t *d, int32_t session, int32_t n,
 int  vio_loop_detector_clear(vio_loop_detector_t *d, int32_t session);   /* clear() :882-886: database + window      */
 int  vio_loop_detector_size(const vio_loop_detector_t *d, int32_t session, int32_t *n_entries);
 int  vio_loop_detector_kernel_ms(vio_loop_detector_t *d, float *ms);     /* device time of the last detect           */
+/* KeyFrame::findConnectionWithOldFrame (loop/keyframe.cpp:267-273: searchByDes :161-190, rejectWithF :35-58; the call
+ * at ViewController.mm:946-952) for one (current, old) pair of entries of n sessions in one batch of launches, both
+ * keyframes read from the detector's own device copies: no descriptor or keypoint is uploaded. The queries of pair i
+ * are the LAST n_window[i] descriptors of entry cur_entry[i] (BriefExtractor appends the window points behind the FAST
+ * corners, :401-406; extractBrief takes them from there, :65-70) and their keys are the measurements; the old keyframe
+ * is every key and descriptor of old_entry[i]. Semantics of vio_loop_find_connection, bit for bit: the best match is
+ * the smallest Hamming distance, the first index on ties; a query with nothing closer than 256 bits means no
+ * connection (status all 0, n_kept 0, matched_old_pts not written); from 8 queries on
+ * findFundamentalMat(measurements, matched old keys, FM_RANSAC, 2.0, 0.99) decides status; fewer than 8 keep everything
+ * and have no normalised points (kept_old_norm not written, connected = 0).
+ * Rows of `stride` per pair: status [n_window]; matched_old_pts [n_window][2] pixels (optional); kept_index [n_kept] =
+ * the window indices with status 1, ascending (reduceVector :52-56); kept_ids[k] = ids[kept_index[k]] (both NULL or
+ * both given); kept_old_norm [n_kept][2] = (double)((matched old key - (cx, cy)) / (fx, fy)) in float as :45-46 --
+ * what vio_estimator_set_relocalization takes. VIO_EINVAL, with nothing launched or written: a session twice in one
+ * call, an entry outside [0, size), old_entry >= cur_entry, an erased entry, n_window > stride or larger than the
+ * current entry's key count.                                                                                       */
+typedef struct VioLoopConnection {
+  int32_t n_window;    /* queries = window descriptors of the current entry                         */
+  int32_t ransac_ran;  /* 1 when rejectWithF ran (n_window >= 8 and every query found a match)      */
+  int32_t n_kept;      /* status == 1                                                               */
+  int32_t connected;   /* ransac_ran && n_kept > min_loop_num   (ViewController.mm:952)             */
+} VioLoopConnection;
+int  vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg /* fx fy cx cy */,
+                               int32_t min_loop_num /* MIN_LOOP_NUM = 22 */, int32_t n, const int32_t *session,
+                               const int32_t *cur_entry, const int32_t *old_entry, const int32_t *n_window,
+                               const int32_t *ids /* [n][stride] or NULL */, int32_t stride, VioLoopConnection *out,
+                               uint8_t *status /* [n][stride] */, float *matched_old_pts /* [n][stride][2] or NULL */,
+                               int32_t *kept_index /* [n][stride] */, int32_t *kept_ids /* [n][stride], with ids */,
+                               double *kept_old_norm /* [n][stride][2] */);
 
 /* Keyframe descriptor extraction: BriefExtractor::operator() (loop/keyframe.cpp:395-409) =
  * cv::FAST(im, keys, 20, true); keys += window_pts; DVision::BRIEF::compute
@@ -689,6 +718,17 @@ int vio_features_dump(vio_features_t *fm, VioFeatureInfo *info, int32_t cap, int
 /* The inverse of vio_features_dump: the list becomes exactly these entries (list order; points [sum n_obs][3]). Used
  * when a sequence's list returns from the device-resident store (vio_estimator_set_resident). */
 int vio_features_load(vio_features_t *fm, const VioFeatureInfo *info, int32_t n, const double *points);
+/* KeyFrame::buildKeyFrameFeatures (loop/keyframe.cpp:128-155, called at ViewController.mm:818) on a landmark list, as
+ * written and in list order: used_num = n_obs for every landmark; a landmark is kept iff n_obs >= 2 && start_frame <
+ * W - 2 (:133) and then start_frame + n_obs >= W - 1 && n_obs >= 3 (:136). For a kept one, p = obs[W - 2 - start_frame]:
+ * px = (float)(fx p.x / p.z + cx), (float)(fy p.y / p.z + cy) (measurements); norm = (float)(p.x / p.z), (float)(p.y /
+ * p.z) (pts_normalize); ids = feature_id; cloud = Rs[start] (ric (obs[0] estimated_depth) + tic) + Ps[start]
+ * (point_clouds). No test of the depth's sign or of solve_flag: the reference has none. Ps [W+1][3], Rs [W+1][9] are
+ * the states of the moment (vio_estimator_get_window). The call writes used_num and nothing else of the list.
+ * VIO_ECAP with *n = -(needed) when more than cap landmarks qualify (the first cap are written).                   */
+int vio_features_keyframe(vio_features_t *fm, const VioConfig *cfg /* fx fy cx cy */, const double *Ps, const double *Rs,
+                          const double tic[3], const double ric[9], int32_t cap, int32_t *ids, float *px /* [cap][2] */,
+                          float *norm /* [cap][2] */, double *cloud /* [cap][3] */, int32_t *n);
 
 /* failureDetection VINS.cpp:214-265 on the newest frame after a solve (the
  * failure_hand switch of the UI stays with the caller). reasons: bit mask.    */
@@ -809,6 +849,15 @@ int vio_estimator_get_timing(vio_estimator_t *est, double ms[3]);
  * and when vio_estimator_features() asks for the list. */
 int vio_estimator_set_resident(vio_estimator_t *est, int32_t enable);
 int vio_estimator_features(vio_estimator_t *est, int32_t seq, vio_features_t **fm);
+/* vio_features_keyframe for n sequences (each at most once per call: VIO_EINVAL) with the states the estimator holds
+ * now -- what vio_estimator_get_window returns, the moment ViewController.mm:791-822 builds a keyframe. Rows of `stride`
+ * per sequence: ids [n][stride], px / norm [n][stride][2], cloud [n][stride][3], count [n]. A sequence whose list is in
+ * the device store is served there (a fourth pass of the store kernels: all such sequences of a back-end group share one
+ * launch and one download) and STAYS resident: nothing is fetched, VioEstimatorStatus.resident is still 1. A sequence
+ * on the host-side list goes through vio_features_keyframe. count[i] = -1 for a sequence that is not NON_LINEAR with a
+ * full window; count[i] = -(needed), and VIO_ECAP after the others have been filled, where stride is too small.     */
+int vio_estimator_keyframe_features(vio_estimator_t *est, int32_t n, const int32_t *seq, int32_t stride, int32_t *ids,
+                                    float *px, float *norm, double *cloud, int32_t *count);
 
 /* ------------------------------------------------------------------------- */
 /* Motion-only window of the front-end: vinsPnP (vins_pnp.hpp:45-91), the 30 Hz

@@ -8,6 +8,9 @@
 //   store_pack     para_Feature + the factor list + the (host, target) buckets of pack_window (batch.h) for window b
 //   store_finish   setDepth (:300-313), failureDetection (VINS.cpp:214-265), removeBackShiftDepth / removeFront
 //                  (:250-257, :343-372), removeFailures (:259-268), compacted into the other bank of the store
+// and a fourth one on request, between two frames:
+//   store_keyframe KeyFrame::buildKeyFrameFeatures (loop/keyframe.cpp:128-155): the keyframe's measurements, ids and point
+//                  cloud straight from the live bank, in list order (the list stays where it is)
 //
 // The host-side list (vio_window.cpp) stays the restatement the estimator uses while a sequence initializes; every
 // function here performs the same floating-point operations in the same order (this file is compiled with
@@ -15,6 +18,7 @@
 // functions on the host through the SIMT emulator against vio_features_* on random frame streams.
 #pragma once
 
+#include "keyframe_core.h"
 #include "solver_core.h"
 #include "vio_amd.h"
 
@@ -747,6 +751,55 @@ VIO_DEV void store_finish(const Cx &cx, const Dims &d, const Bank &bk, const Ban
   }
   STORE_STAMP(l, 19);
   if (t == 0) ctl[C_N] = n_alive, ctl[C_BANK] ^= 1;
+}
+
+// ---- pass 4 -----------------------------------------------------------------------------------------------------------
+// buildKeyFrameFeatures (keyframe.cpp:128-155) on the live bank: what vio_features_keyframe gives on the host-side list, in
+// list order, with the arithmetic of keyframe_core.h. Ps [P][3], Rs [P][9]: the window states of the moment (the host's,
+// after the slide: the store's own copies are the pre-solve states of the last frame). The list is walked nt landmarks
+// at a time; a kept landmark's place is the running count of the trips before + the kept ones of the waves before it in
+// this trip + those of the lanes below it in its wave (a ballot): no atomics, so the order is the list's whatever the
+// timing. Rows of o.cap entries; more than o.cap qualify: the first o.cap are written and count = -(needed).
+struct KeyOut {
+  int *ids;       // [cap]
+  float *px;      // [cap][2] measurements (pixels)
+  float *norm;    // [cap][2] pts_normalize
+  double *cloud;  // [cap][3] point_clouds
+  int *count;
+  int cap;
+};
+
+VIO_DEV void store_keyframe(const Cx &cx, const Dims &d, const Bank &bk, const int *ctl, ldsi part /* [nt / 64 + 1] */, const double *Ps,
+                            const double *Rs, const double *tic, const double *ric, double fx, double fy, double pcx, double pcy,
+                            const KeyOut &o) {
+  const int W = d.W, P = W + 1;
+  const int t = VIO_TID(cx), lane = t & 63, wave = t >> 6, nw = (cx.nt + 63) >> 6;
+  const int n = ctl[C_N] < d.Lcap ? ctl[C_N] : d.Lcap;
+  int run = 0;  // kept landmarks of the trips before this one (the same number in every work-item)
+  for (int base = 0; base < n; base += cx.nt) {
+    const int i = base + t;
+    const bool have = i < n;
+    const int no = have ? bk.nobs[i] : 0, s = have ? bk.start[i] : 0;
+    // (s >= 0 && s + no <= P holds for every list the store takes: asked again because s and no become addresses here)
+    const bool keep = have && s >= 0 && s + no <= P && keyframe::verdict(no, s, W) == 0;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
+    if (lane == 0) part[wave] = __builtin_popcountll(m);
+    VIO_SYNC();
+    int k = run + __builtin_popcountll(m & ((1ull << lane) - 1)), total = 0;
+    for (int w = 0; w < nw; w++) {
+      const int c = part[w];
+      k += w < wave ? c : 0, total += c;
+    }
+    if (keep && k < o.cap) {
+      const double *p0 = bk.obs + (size_t)i * P * 3;
+      keyframe::measurement(fx, fy, pcx, pcy, p0 + 3 * (W - 2 - s), o.px + 2 * k, o.norm + 2 * k);
+      o.ids[k] = bk.fid[i];
+      keyframe::cloud(Rs + 9 * s, Ps + 3 * s, ric, tic, p0, bk.depth[i], o.cloud + 3 * k);
+    }
+    run += total;
+    VIO_SYNC();  // (part is written again in the next trip)
+  }
+  if (t == 0) *o.count = run > o.cap ? -run : run;
 }
 
 }  // namespace store

@@ -47,6 +47,13 @@ struct vio_resident {
   std::vector<int> active_list;  // slots whose window was solved in this frame
   std::vector<char> solved;
   int phase = 0;  // 0 idle / collected, 1 begun, 2 ingested, 3 launched
+  // vio_backend_resident_keyframe: the jobs and their window states up, the sections of one download back
+  DevBuf<int> kf_jobs;
+  DevBuf<double> kf_states;
+  DevBuf<unsigned char> kf_out;
+  std::vector<int> kf_hjobs;
+  std::vector<double> kf_hstates;
+  HostVec<unsigned char> kf_hout;  // (page-locked: the download is a few MB at 512 slots)
   template <class T>
   T *hp(size_t off) { return reinterpret_cast<T *>(h_in.data() + off); }
   template <class T>
@@ -296,6 +303,73 @@ int vio_backend_resident_fetch(vio_backend_t *be, int32_t slot, VioFeatureInfo *
     return VIO_ENOMEM;
   }
   return VIO_OK;
+}
+
+int vio_backend_resident_keyframe(vio_backend_t *be, int32_t n, const int32_t *slots, const int32_t *rows, const double *const *Ps,
+                                  const double *const *Rs, const double intr[4], int32_t stride, int32_t *ids, float *px, float *norm,
+                                  double *cloud, int32_t *count) {
+  if (!be || !be->res) return VIO_ESTATE;
+  vio_resident *r = be->res.get();
+  if (n < 0 || stride < 0 || (n > 0 && (!slots || !rows || !Ps || !Rs || !intr || !count)) || (n > 0 && stride > 0 && (!ids || !px || !norm || !cloud)))
+    return VIO_EINVAL;
+  if (n == 0) return VIO_OK;
+  if (n > r->n_slots) return VIO_EINVAL;
+  if (r->phase != 0) return VIO_ESTATE;
+  const int P = r->P;
+  try {
+    std::vector<char> seen(r->n_slots, 0);
+    for (int k = 0; k < n; k++) {
+      if (slots[k] < 0 || slots[k] >= r->n_slots || seen[slots[k]] || rows[k] < 0 || !Ps[k] || !Rs[k]) return VIO_EINVAL;
+      seen[slots[k]] = 1;
+    }
+    VIO_ON_DEVICE_OF(be);
+    hipStream_t st = be->stream;
+    // a list holds at most Lcap landmarks: device rows never need to be wider
+    const int cap = std::max(1, std::min((int)stride, r->sd.Lcap));
+    const size_t N = r->n_slots, T = (size_t)n * cap;
+    int rc = r->kf_jobs.ensure(N);
+    if (rc == VIO_OK) rc = r->kf_states.ensure(N * 12 * P);
+    if (rc == VIO_OK) rc = r->kf_out.ensure(44 * N * (size_t)r->sd.Lcap + 4 * N);
+    if (rc != VIO_OK) return rc;
+    r->kf_hjobs.assign(slots, slots + n);
+    r->kf_hstates.resize((size_t)n * 12 * P);
+    for (int k = 0; k < n; k++) {
+      memcpy(&r->kf_hstates[(size_t)k * 12 * P], Ps[k], sizeof(double) * 3 * P);
+      memcpy(&r->kf_hstates[(size_t)k * 12 * P + 3 * P], Rs[k], sizeof(double) * 9 * P);
+    }
+    // the sections of the download: cloud | px | norm | ids | count
+    const size_t o_cloud = 0, o_px = 24 * T, o_norm = 32 * T, o_ids = 40 * T, o_count = 44 * T, bytes = 44 * T + 4 * (size_t)n;
+    if (r->kf_hout.size() < bytes) r->kf_hout.resize(bytes);
+    unsigned char *D = r->kf_out.p, *Hb = r->kf_hout.data();
+    HIP_OK(hipMemcpyAsync(r->kf_jobs.p, r->kf_hjobs.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(r->kf_states.p, r->kf_hstates.data(), sizeof(double) * (size_t)n * 12 * P, hipMemcpyHostToDevice, st));
+    vio::StoreKeyframe K;
+    K.jobs = r->kf_jobs.p, K.states = r->kf_states.p, K.fx = intr[0], K.fy = intr[1], K.cx = intr[2], K.cy = intr[3], K.cap = cap;
+    K.cloud = (double *)(D + o_cloud), K.px = (float *)(D + o_px), K.norm = (float *)(D + o_norm), K.ids = (int *)(D + o_ids);
+    K.count = (int *)(D + o_count);
+    rc = vio::store_launch_keyframe(resident_store_dev(be), K, n, st);
+    if (rc != VIO_OK) return rc;
+    HIP_OK(hipMemcpyAsync(Hb, D, bytes, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const int *cnt = (const int *)(Hb + o_count);
+    int out_rc = VIO_OK;
+    for (int k = 0; k < n; k++) {
+      const size_t src = (size_t)k * cap, dst = (size_t)rows[k] * stride;
+      int c = cnt[k];
+      if (c < 0) c = -c;                       // (the device row was narrower than the list: only when stride was)
+      count[rows[k]] = c > stride ? -c : c;
+      if (c > stride) out_rc = VIO_ECAP;
+      const size_t m = (size_t)std::min(c, std::min(cap, (int)stride));
+      if (m == 0) continue;
+      memcpy(cloud + 3 * dst, Hb + o_cloud + 24 * src, 24 * m);
+      memcpy(px + 2 * dst, Hb + o_px + 8 * src, 8 * m);
+      memcpy(norm + 2 * dst, Hb + o_norm + 8 * src, 8 * m);
+      memcpy(ids + dst, Hb + o_ids + 4 * src, 4 * m);
+    }
+    return out_rc;
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
 }
 
 int vio_backend_resident_begin(vio_backend_t *be) {

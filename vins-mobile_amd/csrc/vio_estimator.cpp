@@ -128,6 +128,10 @@ __attribute__((weak)) int vio_init_ba_create(int32_t, int32_t, int32_t, int32_t,
 __attribute__((weak)) void vio_init_ba_destroy(vio_init_ba_t *);
 __attribute__((weak)) int vio_init_ba_solve(vio_init_ba_t *, VioInitBaProblem *, int32_t, VioSolveStats *);
 }
+// (the same for the store's keyframe pass, vio_resident.h: a C++ entry of vio_backend.hip)
+__attribute__((weak)) int vio_backend_resident_keyframe(vio_backend_t *, int32_t, const int32_t *, const int32_t *, const double *const *,
+                                                        const double *const *, const double *, int32_t, int32_t *, float *, float *, double *,
+                                                        int32_t *);
 
 struct vio_estimator {
   VioConfig cfg;
@@ -1462,6 +1466,59 @@ int vio_estimator_features(vio_estimator_t *e, int32_t seq, vio_features_t **fm)
   }
   *fm = e->seq[seq].fm;
   return VIO_OK;
+}
+
+// KeyFrame::buildKeyFrameFeatures (loop/keyframe.cpp:128-155) with the states of the moment, the ones get_window returns:
+// the sequences on the host-side list on the host pool, the resident ones group by group on the device, where they stay.
+int vio_estimator_keyframe_features(vio_estimator_t *e, int32_t n, const int32_t *seq, int32_t stride, int32_t *ids, float *px, float *norm,
+                                    double *cloud, int32_t *count) {
+  if (!e || n < 0 || stride < 0 || (n > 0 && (!seq || !count)) || (n > 0 && stride > 0 && (!ids || !px || !norm || !cloud))) return VIO_EINVAL;
+  if (n > e->n_seq) return VIO_EINVAL;  // (some sequence would be named twice)
+  std::vector<char> seen(e->n_seq, 0);
+  for (int i = 0; i < n; i++) {
+    if (seq[i] < 0 || seq[i] >= e->n_seq || seen[seq[i]]) return VIO_EINVAL;
+    seen[seq[i]] = 1;
+  }
+  std::vector<int> host_rows;
+  std::vector<std::vector<int>> dev_rows(e->n_groups);
+  for (int i = 0; i < n; i++) {
+    const Sequence &s = e->seq[seq[i]];
+    count[i] = -1;
+    if (s.solver_flag != VIO_SOLVER_NON_LINEAR || s.frame_count != e->W) continue;
+    if (s.on_device) dev_rows[group_of(e, s)].push_back(i);
+    else host_rows.push_back(i);
+  }
+  int first_error = VIO_OK;
+  auto note = [&first_error](int rc) {
+    if (rc != VIO_OK && (first_error == VIO_OK || first_error == VIO_ECAP)) first_error = rc;  // (a real error outranks "stride too small")
+  };
+  std::vector<int> host_rc(host_rows.size(), VIO_OK);
+  HostPool::get().parallel_for((int)host_rows.size(), [&](int k) {
+    const int i = host_rows[k];
+    Sequence &s = e->seq[seq[i]];
+    const size_t o = (size_t)i * stride;
+    host_rc[k] = vio_features_keyframe(s.fm, &e->cfg, s.Ps.data(), s.Rs.data(), e->tic, e->ric, stride, ids + o, px + 2 * o, norm + 2 * o, cloud + 3 * o,
+                                       &count[i]);
+  });
+  for (int rc : host_rc) note(rc);
+  const double intr[4] = {e->cfg.fx, e->cfg.fy, e->cfg.cx, e->cfg.cy};
+  for (int g = 0; g < e->n_groups; g++) {
+    const std::vector<int> &rows = dev_rows[g];
+    if (rows.empty()) continue;
+    if (!vio_backend_resident_keyframe || !e->be[g]) {
+      note(VIO_ENODEV);
+      continue;
+    }
+    std::vector<int32_t> slots;
+    std::vector<const double *> pp, rr;
+    for (int i : rows) {
+      const Sequence &s = e->seq[seq[i]];
+      slots.push_back(slot_of(e, s)), pp.push_back(s.Ps.data()), rr.push_back(s.Rs.data());
+    }
+    note(vio_backend_resident_keyframe(e->be[g], (int)rows.size(), slots.data(), rows.data(), pp.data(), rr.data(), intr, stride, ids, px, norm, cloud,
+                                       count));
+  }
+  return first_error;
 }
 
 }  // extern "C"

@@ -25,6 +25,11 @@
 //   round B  ld_match_kernel     (sessions that reached the geometric check) neighbour-ratio matches per common node,
 //                                claims resolved in parallel to the reference's order (proof at the kernel)
 //            vio::fundamental_ransac_batch (vio_frontend.hip), ld_keep_kernel   the kept pairs, compacted in order
+// vio_loop_detector_connect is the step behind a detected loop, KeyFrame::findConnectionWithOldFrame (VINS_ios/loop/keyframe.cpp
+// :267-273) for one (current, old) pair of entries per session, read from the slabs above: no descriptor crosses the bus.
+//   ld_connect_search_kernel   searchByDes :161-190 (search_by_des_kernel of vio_loop.hip on slab offsets)
+//   ld_connect_count_kernel    the pairs whose queries all found a match go to the RANSAC
+//   vio::fundamental_ransac_batch, ld_connect_keep_kernel   rejectWithF :35-58 and its reduceVector calls, one download
 // There is no CPU path: without a device vio_loop_detector_create answers VIO_ENODEV.
 #include <hip/hip_runtime.h>
 
@@ -420,6 +425,101 @@ __global__ __launch_bounds__(64) void ld_keep_kernel(const int *n_pairs, int min
   if (lane == 0) n_kept[g] = cnt;
 }
 
+// ---- findConnectionWithOldFrame on the slabs ---------------------------------------------------------------------------
+constexpr int kCnWaves = 4;    // queries per workgroup, one wave each
+constexpr int kCnStage = 512;  // old descriptors staged per round: 16 KB of LDS (kStage of vio_loop.hip)
+
+struct LdPair {
+  int session, n_window, n_old;
+  int cur_off, old_off;  // slab slots of the first window descriptor of the current entry / the first one of the old entry
+};
+
+// search_by_des_kernel (vio_loop.hip) on the slabs: grid (ceil(stride / 4), n pairs), one wave per window descriptor, the
+// old entry's descriptors staged through LDS once per workgroup. key = distance << 16 | index: the minimum is the smallest
+// distance and, among equals, the first index. Rows of `stride` (the call's largest n_window) per pair: p_cur = the window
+// keys (the measurements), p_old = the key of the best old descriptor, unmatched = nothing closer than 256 bits.
+__global__ __launch_bounds__(64 * kCnWaves) void ld_connect_search_kernel(const LdPair *pairs, LdStore st, int stride, float *p_cur, float *p_old,
+                                                                           int *unmatched) {
+  __shared__ unsigned long long stage[kCnStage][4];
+  const LdPair pr = pairs[blockIdx.y];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nc = pr.n_window, no = pr.n_old;
+  if ((int)blockIdx.x * kCnWaves >= nc) return;  // (uniform per workgroup)
+  const int q = blockIdx.x * kCnWaves + wave;
+  const bool have = q < nc;
+  const size_t sb = (size_t)pr.session * st.cap;
+  unsigned long long a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+  if (have) {
+    const unsigned long long *c = st.desc + 4 * (sb + pr.cur_off + q);
+    a0 = c[0], a1 = c[1], a2 = c[2], a3 = c[3];
+  }
+  unsigned best = 256u << 16;  // bestDist = 256, bestIndex = -1 (keyframe.cpp:169-170)
+  const unsigned long long *ob = st.desc + 4 * (sb + pr.old_off);
+  for (int j0 = 0; j0 < no; j0 += kCnStage) {
+    const int nj = min(kCnStage, no - j0);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nj * 4; e += blockDim.x) (&stage[0][0])[e] = ob[4 * (size_t)j0 + e];
+    __syncthreads();
+    if (have)
+      for (int j = lane; j < nj; j += 64) {
+        const unsigned d = __popcll(a0 ^ stage[j][0]) + __popcll(a1 ^ stage[j][1]) + __popcll(a2 ^ stage[j][2]) + __popcll(a3 ^ stage[j][3]);
+        const unsigned key = (d << 16) | (unsigned)(j0 + j);
+        best = key < best ? key : best;
+      }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = __shfl_xor(best, o, 64);
+    best = t < best ? t : best;
+  }
+  if (have && lane == 0) {
+    const bool hit = (best >> 16) < 256u;  // `if (bestDist < 256)` (:182)
+    const size_t o = (size_t)blockIdx.y * stride + q, ck = sb + pr.cur_off + q, ok = sb + pr.old_off + (hit ? (best & 0xffffu) : 0u);
+    p_cur[2 * o] = st.keys[2 * ck], p_cur[2 * o + 1] = st.keys[2 * ck + 1];
+    p_old[2 * o] = hit ? st.keys[2 * ok] : 0.f, p_old[2 * o + 1] = hit ? st.keys[2 * ok + 1] : 0.f;
+    unmatched[o] = hit ? 0 : 1;
+  }
+}
+
+// one wave per pair: count = n_window when every query found a match, else 0 (the reference's arrays go out of step there:
+// "no connection", as vio_loop_find_connection restates it). The RANSAC runs on the pairs with count >= 8.
+__global__ __launch_bounds__(64) void ld_connect_count_kernel(const LdPair *pairs, int stride, const int *unmatched, int *count) {
+  const int p = blockIdx.x, lane = threadIdx.x, n = pairs[p].n_window;
+  bool any = false;
+  for (int i = lane; i < n; i += 64) any = any || unmatched[(size_t)p * stride + i] != 0;
+  if (__ballot(any) != 0ull) any = true;
+  if (lane == 0) count[p] = any ? 0 : n;
+}
+
+// rejectWithF :35-58 behind the RANSAC, one wave per pair: status, and the reduceVector calls as one ballot compaction in
+// window order. The batch RANSAC leaves the mask of a problem below 8 pairs unwritten: fewer than 8 keep everything (and
+// have no normalised points, measurements_old_norm stays empty), an unmatched query keeps nothing.
+// hdr [n][2] = n_kept, ransac_ran.
+__global__ __launch_bounds__(64) void ld_connect_keep_kernel(const LdPair *pairs, int stride, const int *count, const unsigned char *mask,
+                                                              const float *p_old, const int *ids, float cx, float cy, float fx, float fy,
+                                                              unsigned char *status, int *kept_index, int *kept_ids, double *kept_norm, int *hdr) {
+  const int p = blockIdx.x, lane = threadIdx.x, n = pairs[p].n_window;
+  const size_t o = (size_t)p * stride;
+  const bool matched = count[p] == n, ran = matched && n >= 8;
+  int cnt = 0;
+  for (int b = 0; b < n; b += 64) {
+    const int i = b + lane;
+    const bool keep = i < n && matched && (!ran || mask[o + i] != 0);
+    if (i < n) status[o + i] = keep ? 1 : 0;
+    const unsigned long long m = __ballot(keep);
+    if (keep) {
+      const size_t k = o + cnt + __popcll(m & ((1ull << lane) - 1));
+      kept_index[k] = i;
+      if (ids) kept_ids[k] = ids[o + i];
+      if (ran) {  // (pt - (cx, cy)) / (fx, fy) in float (:45-46), widened
+        kept_norm[2 * k] = (double)((p_old[2 * (o + i)] - cx) / fx);
+        kept_norm[2 * k + 1] = (double)((p_old[2 * (o + i) + 1] - cy) / fy);
+      }
+    }
+    cnt += __popcll(m);
+  }
+  if (lane == 0) hdr[2 * p] = cnt, hdr[2 * p + 1] = ran ? 1 : 0;
+}
+
 struct Island {  // tIsland
   int first, last, best_entry;
   double score, best_score;
@@ -454,10 +554,19 @@ struct vio_loop_detector {
   DevBuf<int> t_word, t_node, t_off, q_count, q_word, flag, n_cand, cand, n_top, top_id, n_pairs, n_kept;
   DevBuf<double> t_weight, q_value, cscore, top_score, ns;
   DevBuf<unsigned char> mask;
+  // vio_loop_detector_connect (sized by S * K at its first call): the pairs, the callers' ids, the unmatched flags, and the
+  // sections of one download (kept_old_norm | matched old points | kept_index | kept_ids | hdr | status)
+  DevBuf<LdPair> cn_pairs;
+  DevBuf<int> cn_ids, cn_unmatched;
+  DevBuf<unsigned char> cn_out;
+  vio::PinnedBuf<unsigned char> cn_host;  // (page-locked: the one download of a call)
+  std::vector<LdPair> cn_hpairs;
+  std::vector<char> cn_seen;
   // host mirror of every session
   struct Session {
     int n_entries = 0, n_post = 0, cur = 0;
     std::vector<int> off, bow;  // [E + 1] feature slots, [E] BowVector sizes (0 once erased)
+    std::vector<char> erased;   // [E] vio_loop_detector_erase named the entry (an empty keyframe has bow == 0 as well)
     int win_n = 0, win_first = 0, win_last = 0, win_query = 0;  // m_window
   };
   std::vector<Session> sess;
@@ -542,7 +651,7 @@ int vio_loop_detector_create(vio_vocabulary_t *v, const VioLoopDetectorParams *p
   d->height = v->height, d->nid_level = v->L - p->di_levels, d->accumulate = v->weighting == 0 || v->weighting == 1;
   try {
     d->sess.resize(n_sessions);
-    for (auto &s : d->sess) s.off.assign((size_t)max_entries + 1, 0), s.bow.assign(max_entries, 0);
+    for (auto &s : d->sess) s.off.assign((size_t)max_entries + 1, 0), s.bow.assign(max_entries, 0), s.erased.assign(max_entries, 0);
   } catch (const std::bad_alloc &) {
     delete d;
     return VIO_ENOMEM;
@@ -640,6 +749,7 @@ int vio_loop_detector_erase(vio_loop_detector_t *d, int32_t session, int32_t n, 
       HIP_OK(hipGetLastError());
       s.cur = 1 - s.cur, s.n_post -= nw, s.bow[e] = 0;
     }
+    s.erased[e] = 1;
     HIP_OK(hipMemsetAsync(d->e_bow.p + eb + e, 0, 4, st));  // m_dBowfile[entry].clear(); m_dfile[entry].clear()
     HIP_OK(hipMemsetAsync(d->e_fv.p + eb + e, 0, 4, st));
   }
@@ -728,7 +838,7 @@ int vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *s
     // the add has happened on the device: the host mirror follows
     for (int q = 0; q < n; q++) {
       vio_loop_detector::Session &s = d->sess[session[q]];
-      s.off[s.n_entries + 1] = s.off[s.n_entries] + n_keys[q], s.bow[s.n_entries] = h_count[q];
+      s.off[s.n_entries + 1] = s.off[s.n_entries] + n_keys[q], s.bow[s.n_entries] = h_count[q], s.erased[s.n_entries] = 0;
       if (h_count[q] > 0) s.cur = 1 - s.cur, s.n_post += h_count[q];
       s.n_entries++;
     }
@@ -845,6 +955,80 @@ int vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *s
           if (old_pts) memcpy(old_pts + o, h_old.data() + 2 * (size_t)g * widest, 8 * (size_t)h_kept[g]);
         }
       }
+    }
+    return VIO_OK;
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+}
+
+int vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg, int32_t min_loop_num, int32_t n, const int32_t *session,
+                              const int32_t *cur_entry, const int32_t *old_entry, const int32_t *n_window, const int32_t *ids, int32_t stride,
+                              VioLoopConnection *out, uint8_t *status, float *matched_old_pts, int32_t *kept_index, int32_t *kept_ids,
+                              double *kept_old_norm) {
+  if (!d || !cfg || n < 1 || !session || !cur_entry || !old_entry || !n_window || stride < 0 || !out || !status || !kept_index || !kept_old_norm)
+    return VIO_EINVAL;
+  if (ids && !kept_ids) return VIO_EINVAL;
+  if (n > d->S) return VIO_EINVAL;  // (some session would be named twice)
+  try {
+    // every refusal is decided on the host mirror, before anything is launched or written
+    d->cn_hpairs.resize(d->S), d->cn_seen.assign(d->S, 0);
+    int wmax = 0;
+    for (int i = 0; i < n; i++) {
+      if (session[i] < 0 || session[i] >= d->S || d->cn_seen[session[i]]) return VIO_EINVAL;
+      d->cn_seen[session[i]] = 1;
+      const vio_loop_detector::Session &s = d->sess[session[i]];
+      const int c = cur_entry[i], o = old_entry[i], nw = n_window[i];
+      if (c < 0 || c >= s.n_entries || o < 0 || o >= c || s.erased[c] || s.erased[o]) return VIO_EINVAL;
+      if (nw < 0 || nw > stride || nw > s.off[c + 1] - s.off[c]) return VIO_EINVAL;
+      d->cn_hpairs[i] = LdPair{session[i], nw, s.off[o + 1] - s.off[o], s.off[c + 1] - nw, s.off[o]};
+      wmax = std::max(wmax, nw);
+    }
+    for (int i = 0; i < n; i++) memset(&out[i], 0, sizeof(out[i])), out[i].n_window = n_window[i];
+    if (wmax == 0) return VIO_OK;  // (no queries anywhere: nothing kept, nothing connected)
+    VIO_ON_DEVICE_OF(d);
+    hipStream_t st = d->stream;
+    const size_t SK = (size_t)d->S * d->K, T = (size_t)n * wmax;  // T <= SK: n <= S, n_window <= the entry's keys <= K
+    const size_t full = 33 * SK + 8 * (size_t)d->S;
+    int rc = d->cn_pairs.ensure(d->S);
+    if (rc == VIO_OK) rc = d->cn_ids.ensure(SK);
+    if (rc == VIO_OK) rc = d->cn_unmatched.ensure(SK);
+    if (rc == VIO_OK) rc = d->cn_out.ensure(full);
+    // (page-locked memory for what this call brings back; it grows to the largest call seen and stays)
+    if (rc == VIO_OK) rc = d->cn_host.ensure(33 * T + 8 * (size_t)n);
+    if (rc != VIO_OK) return rc;
+    // the sections of the download, rows of wmax per pair
+    const size_t o_norm = 0, o_pts = 16 * T, o_kidx = 24 * T, o_kids = 28 * T, o_hdr = 32 * T, o_status = 32 * T + 8 * (size_t)n;
+    const size_t bytes = o_status + T;
+    unsigned char *D = d->cn_out.p, *Hb = d->cn_host.p;
+    HIP_OK(hipMemcpyAsync(d->cn_pairs.p, d->cn_hpairs.data(), sizeof(LdPair) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (ids)
+      HIP_OK(hipMemcpy2DAsync(d->cn_ids.p, 4 * (size_t)wmax, ids, 4 * (size_t)stride, 4 * (size_t)wmax, n, hipMemcpyHostToDevice, st));
+    const LdStore S = d->store();
+    hipLaunchKernelGGL(ld_connect_search_kernel, dim3((wmax + kCnWaves - 1) / kCnWaves, n), dim3(64 * kCnWaves), 0, st, d->cn_pairs.p, S, wmax,
+                       d->p_cur.p, (float *)(D + o_pts), d->cn_unmatched.p);
+    hipLaunchKernelGGL(ld_connect_count_kernel, dim3(n), dim3(64), 0, st, d->cn_pairs.p, wmax, d->cn_unmatched.p, d->n_pairs.p);
+    HIP_OK(hipGetLastError());
+    // cv::findFundamentalMat(measurements, measurements_old, FM_RANSAC, 2.0, 0.99) (:49)
+    rc = vio::fundamental_ransac_batch(st, d->p_cur.p, (const float *)(D + o_pts), d->n_pairs.p, n, wmax, 8, 2.0f, 0.99, d->mask.p);
+    if (rc != VIO_OK) return rc;
+    hipLaunchKernelGGL(ld_connect_keep_kernel, dim3(n), dim3(64), 0, st, d->cn_pairs.p, wmax, d->n_pairs.p, d->mask.p, (const float *)(D + o_pts),
+                       ids ? d->cn_ids.p : nullptr, (float)cfg->cx, (float)cfg->cy, (float)cfg->fx, (float)cfg->fy, D + o_status,
+                       (int *)(D + o_kidx), (int *)(D + o_kids), (double *)(D + o_norm), (int *)(D + o_hdr));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(Hb, D, bytes, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const int *hdr = (const int *)(Hb + o_hdr);
+    for (int i = 0; i < n; i++) {
+      const int nw = n_window[i], nk = hdr[2 * i], ran = hdr[2 * i + 1];
+      const size_t src = (size_t)i * wmax, dst = (size_t)i * stride;
+      out[i].ransac_ran = ran, out[i].n_kept = nk, out[i].connected = ran && nk > min_loop_num ? 1 : 0;
+      memcpy(status + dst, Hb + o_status + src, (size_t)nw);
+      const bool matched = nw < 8 ? nk == nw : ran != 0;  // (with an unmatched query the old points mean nothing: not written)
+      if (matched_old_pts && matched) memcpy(matched_old_pts + 2 * dst, Hb + o_pts + 8 * src, 8 * (size_t)nw);
+      memcpy(kept_index + dst, Hb + o_kidx + 4 * src, 4 * (size_t)nk);
+      if (ids) memcpy(kept_ids + dst, Hb + o_kids + 4 * src, 4 * (size_t)nk);
+      if (ran) memcpy(kept_old_norm + 2 * dst, Hb + o_norm + 16 * src, 16 * (size_t)nk);
     }
     return VIO_OK;
   } catch (const std::bad_alloc &) {

@@ -45,6 +45,14 @@ int vio_backend_resident_load_batch(vio_backend_t *be, int32_t n, const int32_t 
                                     const double *last_R /* [n][9] */);
 int vio_backend_resident_fetch(vio_backend_t *be, int32_t slot, VioFeatureInfo *info, int32_t cap, int32_t *n, double *points,
                                int32_t cap_points, int32_t *n_points);
+// KeyFrame::buildKeyFrameFeatures (store_core.h pass 4) for n slots (distinct) in one launch and one download, between two
+// frames (VIO_ESTATE otherwise): on the back-end's stream, behind the last collect. The lists stay where they are. Ps / Rs:
+// per slot the window states of the moment, [W+1][3] and [W+1][9]; intr: fx fy cx cy. Slot k fills row rows[k] of the
+// outputs (rows of `stride`: ids, px / norm [.][2], cloud [.][3]) and count[rows[k]] (-(needed) when stride is too small:
+// the call then returns VIO_ECAP after filling the others).
+int vio_backend_resident_keyframe(vio_backend_t *be, int32_t n, const int32_t *slots, const int32_t *rows, const double *const *Ps,
+                                  const double *const *Rs, const double intr[4], int32_t stride, int32_t *ids, float *px, float *norm,
+                                  double *cloud, int32_t *count);
 int vio_backend_resident_begin(vio_backend_t *be);
 // prior: the header of the slot's prior (n, blocks) or null; its data is in the slot of the prior store.
 // loop_frame >= 0: the window frame a relocalization frame is matched to, with the matched landmark ids (ascending, at

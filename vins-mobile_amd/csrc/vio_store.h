@@ -42,10 +42,23 @@ struct StoreDev {
   const double *noise;             // [18] diagonal of the IMU noise (integration_base.h:30-36)
 };
 
+// Pass 4 (store_keyframe) for a batch of slots: job j reads slot jobs[j] and the window states the host sent with the call,
+// and fills row j of the outputs (rows of `cap`).
+struct StoreKeyframe {
+  const int *jobs;       // [n_jobs]
+  const double *states;  // [n_jobs][12 P]: Ps [P][3] | Rs [P][9]
+  double fx, fy, cx, cy;
+  int cap;
+  int *ids, *count;      // [n_jobs][cap], [n_jobs]
+  float *px, *norm;      // [n_jobs][cap][2]
+  double *cloud;         // [n_jobs][cap][3]
+};
+
 int store_launch_imu(const StoreDev &S, hipStream_t st);
 int store_launch_ingest(const StoreDev &S, hipStream_t st);
 int store_launch_pack(const StoreDev &S, const BatchPtrs &B, int chunk, hipStream_t st);
 int store_launch_finish(const StoreDev &S, const BatchPtrs &B, hipStream_t st);
+int store_launch_keyframe(const StoreDev &S, const StoreKeyframe &K, int n_jobs, hipStream_t st);
 size_t store_pack_lds_bytes(const store::Dims &d, int Mcap);
 
 }  // namespace vio

@@ -145,6 +145,23 @@ __global__ __launch_bounds__(st::kThreads) void store_finish_kernel(StoreDev S, 
   }
 }
 
+// Pass 4, one workgroup per job: slot jobs[j] with the window states states[j] = Ps [P][3] | Rs [P][9], rows of K.cap.
+__global__ __launch_bounds__(st::kThreads) void store_keyframe_kernel(StoreDev S, StoreKeyframe K) {
+  __shared__ int part[st::kThreads / 64 + 1];  // the waves' counts of a trip: all the LDS this pass needs
+  const int j = blockIdx.x, slot = K.jobs[j];
+  if (slot < 0 || slot >= S.n_slots) {  // (uniform per workgroup; the host refuses such a job before it gets here)
+    if (threadIdx.x == 0) K.count[j] = 0;
+    return;
+  }
+  st::Cx cx{(int)threadIdx.x, (int)blockDim.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x & ~63)};
+  const int *ctl = S.ctl + (size_t)slot * st::C_COUNT;
+  const int P = S.d.W + 1;
+  const double *Ps = K.states + (size_t)j * 12 * P, *Rs = Ps + 3 * P;
+  const size_t r = (size_t)j * K.cap;
+  const st::KeyOut o{K.ids + r, K.px + 2 * r, K.norm + 2 * r, K.cloud + 3 * r, K.count + j, K.cap};
+  st::store_keyframe(cx, S.d, bank_of(S, slot, ctl[st::C_BANK] & 1), ctl, (ldsi)part, Ps, Rs, S.tic, S.ric, K.fx, K.fy, K.cx, K.cy, o);
+}
+
 }  // namespace
 
 namespace vio {
@@ -198,6 +215,15 @@ int store_launch_finish(const StoreDev &S, const BatchPtrs &B, hipStream_t strea
   const int rc = raise_lds((const void *)store_finish_kernel, lds);
   if (rc != VIO_OK) return rc;
   hipLaunchKernelGGL(store_finish_kernel, dim3(S.n_slots), dim3(st::kThreads), lds, stream, S, B);
+  HIP_OK(hipGetLastError());
+  return VIO_OK;
+}
+
+int store_launch_keyframe(const StoreDev &S, const StoreKeyframe &K, int n_jobs, hipStream_t stream) {
+  if (n_jobs < 1) return VIO_OK;
+  // (a few ints of static LDS, not a block of the window kernel's size: this pass runs between two frames, when no window
+  // kernel of this context is in flight, and is bound by its reads of the bank)
+  hipLaunchKernelGGL(store_keyframe_kernel, dim3(n_jobs), dim3(st::kThreads), 0, stream, S, K);
   HIP_OK(hipGetLastError());
   return VIO_OK;
 }

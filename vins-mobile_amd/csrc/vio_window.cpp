@@ -13,6 +13,7 @@
 #include <list>
 #include <vector>
 
+#include "keyframe_core.h"
 #include "vio_amd.h"
 #include "vio_math.h"
 
@@ -417,6 +418,27 @@ int vio_failure_detection(int32_t last_track_num, const double Bg_newest[3], con
   if (delta_angle > 40) r |= VIO_FAIL_ROTATION;
   *reasons = r;
   return VIO_OK;
+}
+
+// KeyFrame::buildKeyFrameFeatures (loop/keyframe.cpp:128-155) as written, in list order (keyframe_core.h: shared with the
+// fourth pass of the device store).
+int vio_features_keyframe(vio_features_t *fm, const VioConfig *cfg, const double *Ps, const double *Rs, const double tic[3],
+                          const double ric[9], int32_t cap, int32_t *ids, float *px, float *norm, double *cloud, int32_t *n) {
+  if (!fm || !cfg || !Ps || !Rs || !tic || !ric || !n || cap < 0 || (cap > 0 && (!ids || !px || !norm || !cloud))) return VIO_EINVAL;
+  const int W = fm->window_size;
+  int k = 0;
+  for (Feature &f : fm->feature) {
+    f.used_num = (int)f.obs.size();
+    if (keyframe::verdict(f.used_num, f.start_frame, W) != 0) continue;
+    if (k < cap) {
+      keyframe::measurement(cfg->fx, cfg->fy, cfg->cx, cfg->cy, f.obs[W - 2 - f.start_frame].point, px + 2 * k, norm + 2 * k);
+      ids[k] = f.feature_id;
+      keyframe::cloud(Rs + 9 * f.start_frame, Ps + 3 * f.start_frame, ric, tic, f.obs[0].point, f.estimated_depth, cloud + 3 * k);
+    }
+    k++;
+  }
+  *n = k > cap ? -k : k;  // (the convention of vio_vocabulary_transform: -(needed))
+  return k > cap ? VIO_ECAP : VIO_OK;
 }
 
 int vio_features_load(vio_features_t *fm, const VioFeatureInfo *info, int32_t n, const double *points) {

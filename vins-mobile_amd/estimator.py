@@ -156,6 +156,26 @@ class Estimator:
         self._check(self.lib.vio_estimator_get_corrected_window(self._h, seq, _p(Ps), _p(Rs)), "get_corrected_window")
         return Ps, Rs
 
+    def keyframe_features(self, seqs, stride=1024):
+        """KeyFrame::buildKeyFrameFeatures for these sequences with the states of the moment (vio_estimator_keyframe_features):
+        resident sequences are served on the device and stay resident. -> rc (VIO_OK or VIO_ECAP), per sequence
+        (count, ids [n], px [n][2], norm [n][2], cloud [n][3]); count -1: no full NON_LINEAR window, -(needed): stride too
+        small (the first stride entries are returned)."""
+        seqs = np.ascontiguousarray(seqs, np.int32)
+        n, c = len(seqs), max(stride, 1)
+        ids, px, norm = np.zeros((n, c), np.int32), np.zeros((n, c, 2), np.float32), np.zeros((n, c, 2), np.float32)
+        cloud, count = np.zeros((n, c, 3)), np.zeros(max(n, 1), np.int32)
+        fp = C.POINTER(C.c_float)
+        rc = self.lib.vio_estimator_keyframe_features(self._h, n, seqs.ctypes.data_as(_ip), stride, ids.ctypes.data_as(_ip),
+                                                      px.ctypes.data_as(fp), norm.ctypes.data_as(fp), _p(cloud), count.ctypes.data_as(_ip))
+        if rc not in (abi.VIO_OK, abi.VIO_ECAP):
+            self._check(rc, "keyframe_features")
+        out = []
+        for i in range(n):
+            k = min(abs(int(count[i])), stride) if count[i] != -1 else 0
+            out.append((int(count[i]), ids[i, :k].copy(), px[i, :k].copy(), norm[i, :k].copy(), cloud[i, :k].copy()))
+        return rc, out
+
     def features(self, seq=0):
         """A non-owning FeatureManager view of the sequence's landmark store."""
         from . import window

@@ -268,6 +268,10 @@ class VioLoopDetection(C.Structure):
                 ("n_di_matches", C.c_int32), ("n_inliers", C.c_int32)]
 
 
+class VioLoopConnection(C.Structure):
+    _fields_ = [("n_window", C.c_int32), ("ransac_ran", C.c_int32), ("n_kept", C.c_int32), ("connected", C.c_int32)]
+
+
 LOOP_STATUS = ("LOOP_DETECTED", "CLOSE_MATCHES_ONLY", "NO_DB_RESULTS", "LOW_NSS_FACTOR", "LOW_SCORES", "NO_GROUPS",
                "NO_TEMPORAL_CONSISTENCY", "NO_GEOMETRICAL_CONSISTENCY")   # DetectionStatus, TemplatedLoopDetector.h:46-64
 
@@ -285,6 +289,8 @@ def bind_loop_detector(lib):
     lib.vio_loop_detector_clear.argtypes = [vp, C.c_int32]
     lib.vio_loop_detector_size.argtypes = [vp, C.c_int32, _i32p]
     lib.vio_loop_detector_kernel_ms.argtypes = [vp, _fp]
+    lib.vio_loop_detector_connect.argtypes = [vp, C.POINTER(abi.VioConfig), C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int32,
+                                              C.POINTER(VioLoopConnection), _u8p, _fp, _i32p, _i32p, C.POINTER(C.c_double)]
     return lib
 
 
@@ -345,6 +351,45 @@ class LoopDetector:
             m = r["n_inliers"] if r["status"] == 0 else 0
             res.append((r, cur[q, :m].copy(), old[q, :m].copy()))
         return res
+
+    def connect(self, cfg, sessions, cur_entries, old_entries, n_window, ids=None, min_loop_num=22, stride=None, out=None):
+        """findConnectionWithOldFrame for one (current, old) pair of entries per session, read from the detector's slabs.
+        ids: per pair the feature ids of its window points (or None). -> per pair a dict of the VioLoopConnection fields
+        plus status [n_window], matched_old_pts [n_window][2] (None without a connection), kept_index / kept_ids
+        [n_kept], kept_old_norm [n_kept][2] (empty unless ransac_ran). out: the five raw arrays to fill (tests)."""
+        n = len(sessions)
+        ses, cur, old = (np.ascontiguousarray(a, np.int32) for a in (sessions, cur_entries, old_entries))
+        nw = np.ascontiguousarray(n_window, np.int32)
+        if stride is None:
+            stride = max(1, int(nw.max()) if n else 1)
+        idp = None
+        if ids is not None:
+            idp = np.zeros((n, stride), np.int32)
+            for i, a in enumerate(ids):
+                idp[i, :min(len(a), stride)] = np.asarray(a, np.int32)[:stride]
+        res = (VioLoopConnection * max(n, 1))()
+        if out is None:
+            out = (np.zeros((n, stride), np.uint8), np.zeros((n, stride, 2), np.float32), np.zeros((n, stride), np.int32),
+                   np.zeros((n, stride), np.int32), np.zeros((n, stride, 2), np.float64))
+        status, pts, kidx, kids, norm = out
+        rc = self.lib.vio_loop_detector_connect(self._h, C.byref(cfg), min_loop_num, n, ses.ctypes.data_as(_i32p), cur.ctypes.data_as(_i32p),
+                                                old.ctypes.data_as(_i32p), nw.ctypes.data_as(_i32p),
+                                                idp.ctypes.data_as(_i32p) if idp is not None else None, stride, res,
+                                                status.ctypes.data_as(_u8p), pts.ctypes.data_as(_fp), kidx.ctypes.data_as(_i32p),
+                                                kids.ctypes.data_as(_i32p), norm.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_connect", rc)
+        got = []
+        for i in range(n):
+            r = {f: getattr(res[i], f) for f, _ in VioLoopConnection._fields_}
+            m, k = r["n_window"], r["n_kept"]
+            r["status"] = status[i, :m].copy()
+            r["matched_old_pts"] = pts[i, :m].copy() if (r["ransac_ran"] or (m < 8 and k == m)) else None
+            r["kept_index"] = kidx[i, :k].copy()
+            r["kept_ids"] = kids[i, :k].copy() if ids is not None else None
+            r["kept_old_norm"] = norm[i, :k].copy() if r["ransac_ran"] else np.zeros((0, 2))
+            got.append(r)
+        return got
 
     def erase(self, session, entries):
         e = np.ascontiguousarray(entries, np.int32)

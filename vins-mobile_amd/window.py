@@ -104,6 +104,33 @@ class FeatureManager:
                         for f in info[:n.value]], dtype=np.float64).reshape(-1, 8)
         return rec, pts[:npts.value].copy()
 
+    def load(self, info, points):
+        """vio_features_load: the list becomes these entries. info: rows (id, start_frame, n_obs, used_num, solve_flag,
+        is_outlier, fixed, estimated_depth) as dump() gives them; points [sum n_obs][3]."""
+        rec = (abi.VioFeatureInfo * max(len(info), 1))()
+        for f, r in zip(rec, info):
+            f.id, f.start_frame, f.n_obs, f.used_num, f.solve_flag, f.is_outlier, f.fixed = (int(x) for x in r[:7])
+            f.estimated_depth = float(r[7])
+        pts = _d(points).reshape(-1, 3)
+        self._check(self.lib.vio_features_load(self._h, rec, len(info), pts.ctypes.data_as(_dp)), "load")
+
+    def keyframe(self, cfg, Ps, Rs, tic, ric, cap=4096):
+        """KeyFrame::buildKeyFrameFeatures (vio_features_keyframe) -> rc, count, ids [n], px [n][2], norm [n][2], cloud [n][3];
+        rc VIO_ECAP and count = -(needed) when more than cap landmarks qualify (the first cap are returned)."""
+        Ps, Rs, tic, ric = _d(Ps).reshape(-1, 3), _d(Rs).reshape(-1, 9), _d(tic), _d(ric).reshape(9)
+        assert len(Ps) == self.W + 1 and len(Rs) == self.W + 1
+        c = max(cap, 1)
+        ids, px, norm, cloud = np.zeros(c, np.int32), np.zeros((c, 2), np.float32), np.zeros((c, 2), np.float32), np.zeros((c, 3))
+        n = C.c_int32()
+        fp = C.POINTER(C.c_float)
+        rc = self.lib.vio_features_keyframe(self._h, C.byref(cfg), Ps.ctypes.data_as(_dp), Rs.ctypes.data_as(_dp), tic.ctypes.data_as(_dp),
+                                            ric.ctypes.data_as(_dp), cap, ids.ctypes.data_as(_ip), px.ctypes.data_as(fp),
+                                            norm.ctypes.data_as(fp), cloud.ctypes.data_as(_dp), C.byref(n))
+        if rc not in (abi.VIO_OK, abi.VIO_ECAP):
+            self._check(rc, "keyframe")
+        k = min(abs(n.value), cap)
+        return rc, n.value, ids[:k].copy(), px[:k].copy(), norm[:k].copy(), cloud[:k].copy()
+
 
 def failure_detection(last_track_num, Bg, P, R, last_P, last_R, lib=None):
     """failureDetection (VINS.cpp:214-265) -> bit mask of VIO_FAIL_* reasons (0 = healthy)."""
