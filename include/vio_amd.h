@@ -661,6 +661,74 @@ int vio_posegraph_apply(const VioPoseGraphKeyframe *kf, int32_t n_kf, const doub
                         double *yaw_drift, double *r_drift /* [9] */, double *t_drift /* [3] */);
 
 /* ------------------------------------------------------------------------- */
+/* KeyFrameDatabase (VINS_ios/loop/keyfame_database.{h,cpp}) for n_sessions    */
+/* independent keyframe lists whose poses stay in device memory. The pose     */
+/* graph of optimize4DoFLoopPoseGraph is built on the device from the         */
+/* resident list, solved there (the kernel of vio_posegraph_optimize) and     */
+/* applied to the list there; per call the host uploads a few scalars per     */
+/* session and downloads the drift and the solve statistics. A session may    */
+/* appear at most once per call (VIO_EINVAL), as in vio_loop_detector_detect. */
+/* Every argument error is found before anything is launched or changed.      */
+typedef struct vio_keyframe_db vio_keyframe_db_t;
+/* max_keyframes bounds one list (and so one graph); max_frame_num is the reference's 500 (keyfame_database.cpp:16).
+ * max_graphs = sessions one optimize call may carry: it sizes the solver's dense scratch, which is
+ * 2 x (4 max_keyframes)^2 x 8 bytes per graph (two square matrices of doubles over the unknowns); VIO_ENOMEM when
+ * the device does not have that, VIO_ECAP beyond the solver's ~730 keyframes, VIO_ENODEV without a device.       */
+int vio_keyframe_db_create(int32_t n_sessions, int32_t max_keyframes, int32_t max_graphs, int32_t max_frame_num,
+                           vio_keyframe_db_t **out);
+int vio_keyframe_db_get_device(const vio_keyframe_db_t *db, int32_t *device);
+void vio_keyframe_db_destroy(vio_keyframe_db_t *db);
+/* The constructor's state (keyfame_database.cpp:10-20): empty list, no drift, segment 0, global_index from 0.     */
+int vio_keyframe_db_clear(vio_keyframe_db_t *db, int32_t session);
+int vio_keyframe_db_size(const vio_keyframe_db_t *db, int32_t session, int32_t *n);
+/* KeyFrame::KeyFrame (loop/keyframe.cpp:4-14) + KeyFrameDatabase::add (keyfame_database.cpp:21-42) for one new
+ * keyframe of each of n sessions: the origin pose is the pose given, the current pose r_drift P + t_drift,
+ * r_drift R; total_length and last_P advance; segment_index = the session's cur_seg_index; global_index = the
+ * session's count of adds since clear, never reused (the entry ids of vio_loop_detector_detect count the same
+ * way). VIO_ECAP with nothing changed when a session is full.                                                    */
+int vio_keyframe_db_add(vio_keyframe_db_t *db, int32_t n, const int32_t *session, const double *header,
+                        const double *P /* [n][3] */, const double *R /* [n][9] */, int32_t *global_index_out);
+/* max_seg_index++; cur_seg_index = max_seg_index (ViewController.mm:776-777). */
+int vio_keyframe_db_new_segment(vio_keyframe_db_t *db, int32_t session);
+/* cur_kf->detectLoop(old_index); old_kf->is_looped = 1 (ViewController.mm:969-971, keyframe.cpp:356-360).
+ * VIO_EINVAL for unknown or erased indices or old_index >= cur_index.                                            */
+int vio_keyframe_db_set_loop(vio_keyframe_db_t *db, int32_t session, int32_t cur_index, int32_t old_index);
+/* getKeyframe(index)->getPose for n sessions in one download: what RetriveData.P_old / Q_old are made of
+ * (ViewController.mm:946, 955-960). P / R / header may be NULL.                                                  */
+int vio_keyframe_db_get_pose(vio_keyframe_db_t *db, int32_t n, const int32_t *session, const int32_t *index,
+                             double *P /* [n][3] */, double *R /* [n][9] */, double *header /* [n] */);
+/* The per-solved-frame block ViewController.mm:831-873 for n sessions in one launch. (a) loop_kf[i] >= 0 (the
+ * front_pose.cur_index of a frame whose header was found in the window): |relative_yaw| > 30 or |relative_t| > 10
+ * -> removeLoop (has_loop = 0), otherwise updateLoopConnection: loop_info = t, q (w x y z), yaw. relative_q is
+ * x y z w as VioEstimatorStatus gives it. (b) the newest 2 window_size + 1 keyframes are searched for header0
+ * (search_cnt > 2 * WINDOW_SIZE breaks after the miss, :870); the one found takes updateOriginPose(P0, R0), and
+ * optimize_index_out[i] is its global_index when it has a loop (start_global_optimization), -1 otherwise.        */
+int vio_keyframe_db_update(vio_keyframe_db_t *db, int32_t n, const int32_t *session, const int32_t *loop_kf,
+                           const double *relative_t /* [n][3] */, const double *relative_q /* [n][4] */,
+                           const double *relative_yaw /* [n] */, int32_t window_size, const double *header0 /* [n] */,
+                           const double *P0 /* [n][3] */, const double *R0 /* [n][9] */, int32_t *optimize_index_out);
+/* optimize4DoFLoopPoseGraph (keyfame_database.cpp:140-356) for n sessions: earliest_loop_index, need_resample,
+ * parameter values and edges (:166-291), the solve (:297), the poses of the graph, the drift, the keyframes after
+ * cur_index, the segment relabelling and updateVisualization (:301-378), all on the device. max_iterations is 5 in
+ * the reference. yaw_drift [n], r_drift [n][9], t_drift [n][3] (loop_correct_r / loop_correct_t) and stats [n] may
+ * be NULL. VIO_EINVAL with nothing launched or changed when cur_index is unknown or has no loop (the reference
+ * asserts, :148) or a loop inside the range points before earliest_loop_index (asserts, :276-280); VIO_ECAP when
+ * n > max_graphs.                                                                                                */
+int vio_keyframe_db_optimize(vio_keyframe_db_t *db, int32_t n, const int32_t *session, const int32_t *cur_index,
+                             int32_t max_iterations, double *yaw_drift, double *r_drift, double *t_drift,
+                             VioSolveStats *stats);
+/* resample (keyfame_database.cpp:44-76), with its early return below max_frame_num (n_erased = 0): the list is
+ * compacted in order, total_length recomputed (updateVisualization); the erased global_index values come back
+ * ascending: what vio_loop_detector_erase takes. cap must hold size - 1 entries (VIO_ECAP, nothing changed).    */
+int vio_keyframe_db_resample(vio_keyframe_db_t *db, int32_t session, int32_t *erase_index_out, int32_t cap,
+                             int32_t *n_erased);
+/* The whole list of a session (kf / header / segment_index may be NULL, cap entries each) for tests and for
+ * vio_replay_write_keyframes. state [17]: total_length, last_P [3], yaw_drift, r_drift [9], t_drift [3];
+ * index_state [3]: earliest_loop_index, cur_seg_index, max_seg_index.                                            */
+int vio_keyframe_db_download(vio_keyframe_db_t *db, int32_t session, VioPoseGraphKeyframe *kf, double *header,
+                             int32_t *segment_index, int32_t cap, int32_t *n, double *state, int32_t *index_state);
+
+/* ------------------------------------------------------------------------- */
 /* Window bookkeeping around the solve (host side): FeatureManager            */
 /* (VINS_ios/feature_manager.hpp:71-103). It decides which landmarks and      */
 /* observations become factors of a VioWindow; the window size is a run-time  */
@@ -788,7 +856,7 @@ typedef struct VioEstimatorStatus {
 int vio_estimator_create(const VioConfig *cfg, int32_t n_seq, const double tic[3], const double ric[9],
                          vio_estimator_t **out);
 void vio_estimator_destroy(vio_estimator_t *est);
-int vio_estimator_clear(vio_estimator_t *est, int32_t seq);                       /* clearState */
+int vio_estimator_clear(vio_estimator_t *est, int32_t seq);   /* clearState + the constructor's r_drift / t_drift */
 /* solveInitial (VINS.cpp:833-1145) inside process_image when the window is full and no
  * state was handed over: relative pose, global SfM, PnP of the in-between frames,
  * visual-inertial alignment. Off by default (0): the caller hands states over.
@@ -835,6 +903,11 @@ int vio_estimator_get_window(vio_estimator_t *est, int32_t seq, double *Ps, doub
                              double *Bgs, double *headers);
 /* update_loop_correction VINS.cpp:302-331: r_drift * Ps + t_drift, r_drift * Rs. */
 int vio_estimator_get_corrected_window(vio_estimator_t *est, int32_t seq, double *correct_Ps, double *correct_Rs);
+/* globalLoopThread hands the pose graph's drift to the estimator: vins.t_drift = loop_correct_t; vins.r_drift =
+ * loop_correct_r (ViewController.mm:998-999). Only the two fields that get_status and get_corrected_window read
+ * are written; vio_estimator_clear puts the identity back (VINS.cpp:19-20).      */
+int vio_estimator_set_drift(vio_estimator_t *est, int32_t seq, const double *r_drift /* [9] */,
+                            const double *t_drift /* [3] */);
 /* Wall time (ms) of the last process_image(s) call by phase: bookkeeping before
  * the solve, vio_backend_solve_windows (pack, upload, kernel, download), and
  * the bookkeeping after it.                                                    */

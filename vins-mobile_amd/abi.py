@@ -583,6 +583,7 @@ def load_product():
     lib.vio_estimator_get_status.argtypes = [vp, C.c_int32, stp]
     lib.vio_estimator_get_window.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
     lib.vio_estimator_get_corrected_window.argtypes = [vp, C.c_int32, _dp, _dp]
+    lib.vio_estimator_set_drift.argtypes = [vp, C.c_int32, _dp, _dp]
     lib.vio_estimator_features.argtypes = [vp, C.c_int32, C.POINTER(vp)]
     lib.vio_estimator_get_timing.argtypes = [vp, _dp]
     lib.vio_backend_set_profile.argtypes = [vp, C.c_int32]

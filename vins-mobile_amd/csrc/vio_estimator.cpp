@@ -990,7 +990,12 @@ int vio_estimator_set_resident(vio_estimator_t *e, int32_t enable) {
 
 int vio_estimator_clear(vio_estimator_t *e, int32_t seq) {
   if (!e || seq < 0 || seq >= e->n_seq) return VIO_EINVAL;
-  clear_state(e, e->seq[seq]);
+  Sequence &s = e->seq[seq];
+  clear_state(e, s);
+  // a manual reset starts the sequence over as the constructor leaves it (VINS.cpp:19-21): no loop drift either. The
+  // clearState of a failure inside process_image keeps the drift, as in the reference.
+  memcpy(s.r_drift, kI3, 72);
+  for (int k = 0; k < 3; k++) s.t_drift[k] = 0;
   return VIO_OK;
 }
 
@@ -1455,6 +1460,13 @@ int vio_estimator_get_corrected_window(vio_estimator_t *e, int32_t seq, double *
     for (int k = 0; k < 3; k++) correct_Ps[3 * i + k] = t[k] + s.t_drift[k];
     mat3mul(s.r_drift, &s.Rs[9 * i], &correct_Rs[9 * i]);
   }
+  return VIO_OK;
+}
+
+// vins.t_drift = loop_correct_t; vins.r_drift = loop_correct_r (ViewController.mm:998-999)
+int vio_estimator_set_drift(vio_estimator_t *e, int32_t seq, const double *r_drift, const double *t_drift) {
+  if (!e || seq < 0 || seq >= e->n_seq || !r_drift || !t_drift) return VIO_EINVAL;
+  memcpy(e->seq[seq].r_drift, r_drift, 72), memcpy(e->seq[seq].t_drift, t_drift, 24);
   return VIO_OK;
 }
 

@@ -29,27 +29,11 @@
 #include "solver_core.h"
 #include "batch.h"
 #include "marg_core.h"
+#include "vio_posegraph_launch.h"
 
 using namespace vio;
 
 namespace {
-
-constexpr int kPgThreads = 512;
-constexpr int kPgHdr = 4;  // n_nodes, n_edges, N, max_iterations
-
-struct PgPtrs {
-  int ld;          // leading dimension of the dense matrices = 4 * max_nodes rounded up to 16
-  int node_cap, edge_cap;
-  const int *hdr;           // [g][kPgHdr]
-  const int *col;           // [g][node_cap]: node -> first of its 4 unknowns, -1 constant / not in the program
-  const double *node0;      // [g][node_cap][4]: yaw, t of every node as given
-  const int *edge_i, *edge_j, *edge_kind;  // [g][edge_cap]
-  const double *meas;       // [g][edge_cap][6]
-  double *H, *A;            // [g][ld * ld]
-  double *xout;             // [g][ld]
-  double *stats_d;          // [g][kStatsDoubles]
-  int *stats_i;             // [g][kStatsInts]
-};
 
 struct PgView {
   int n_nodes, n_edges, N, nt, ld, max_iter;
@@ -420,6 +404,16 @@ struct Mirrored {
 
 }  // namespace
 
+namespace vio {
+hipError_t pg_prepare() {
+  return hipFuncSetAttribute((const void *)posegraph_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vio::kLdsBytes);
+}
+hipError_t launch_posegraph(const PgPtrs &P, int n, size_t lds_bytes, hipStream_t stream) {
+  hipLaunchKernelGGL(posegraph_kernel, dim3(n), dim3(kPgThreads), lds_bytes, stream, P);
+  return hipGetLastError();
+}
+}  // namespace vio
+
 struct vio_posegraph {
   int device = 0;
   int max_nodes = 0, max_edges = 0, n_graphs = 0, ld = 0;
@@ -442,8 +436,8 @@ int vio_posegraph_create(int32_t max_nodes, int32_t max_edges, int32_t n_graphs,
   if (!pg) return VIO_ENOMEM;
   pg->device = vio::current_device();
   pg->max_nodes = max_nodes, pg->max_edges = max_edges, pg->n_graphs = n_graphs;
-  pg->ld = (4 * max_nodes + 15) / 16 * 16;
-  pg->lds_bytes = ((size_t)7 * pg->ld + 6 * (kPgThreads / 64) + 2) * sizeof(double) + ((size_t)2 * (pg->ld / 16) + 4) * sizeof(int);
+  pg->ld = vio::pg_ld(max_nodes);
+  pg->lds_bytes = vio::pg_lds_bytes(pg->ld);
   if (pg->lds_bytes > vio::kLdsBytes) {  // seven N-vectors in LDS: at most 160 KB / 56 B = ~2900 unknowns = ~730 keyframes
     delete pg;
     return VIO_ECAP;
@@ -465,7 +459,7 @@ int vio_posegraph_create(int32_t max_nodes, int32_t max_edges, int32_t n_graphs,
   // memory may reach the matrix cores (their rows are independent, but a NaN pattern need not stay that way)
   if (hipMemsetAsync(pg->H.p, 0, G * mat * sizeof(double), pg->stream) != hipSuccess ||
       hipMemsetAsync(pg->A.p, 0, G * mat * sizeof(double), pg->stream) != hipSuccess || hipStreamSynchronize(pg->stream) != hipSuccess ||
-      hipFuncSetAttribute((const void *)posegraph_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vio::kLdsBytes) != hipSuccess) {
+      vio::pg_prepare() != hipSuccess) {
     delete pg;
     return VIO_ENODEV;
   }
@@ -529,8 +523,7 @@ int vio_posegraph_optimize(vio_posegraph_t *pg, VioPoseGraph *graphs, int32_t n,
   P.ld = pg->ld, P.node_cap = NC, P.edge_cap = EC;
   P.hdr = pg->hdr.d.p, P.col = pg->col.d.p, P.node0 = pg->node0.d.p, P.edge_i = pg->ei.d.p, P.edge_j = pg->ej.d.p, P.edge_kind = pg->ek.d.p;
   P.meas = pg->meas.d.p, P.H = pg->H.p, P.A = pg->A.p, P.xout = pg->xout.d.p, P.stats_d = pg->stats_d.d.p, P.stats_i = pg->stats_i.d.p;
-  hipLaunchKernelGGL(posegraph_kernel, dim3(n), dim3(kPgThreads), pg->lds_bytes, st, P);
-  HIP_OK(hipGetLastError());
+  HIP_OK(vio::launch_posegraph(P, n, pg->lds_bytes, st));
   HIP_OK(hipMemcpyAsync(pg->xout.h.p, pg->xout.d.p, (size_t)n * pg->ld * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_OK(hipMemcpyAsync(pg->stats_d.h.p, pg->stats_d.d.p, (size_t)n * kStatsDoubles * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_OK(hipMemcpyAsync(pg->stats_i.h.p, pg->stats_i.d.p, (size_t)n * kStatsInts * sizeof(int), hipMemcpyDeviceToHost, st));

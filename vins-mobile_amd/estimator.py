@@ -156,6 +156,12 @@ class Estimator:
         self._check(self.lib.vio_estimator_get_corrected_window(self._h, seq, _p(Ps), _p(Rs)), "get_corrected_window")
         return Ps, Rs
 
+    def set_drift(self, r_drift, t_drift, seq=0):
+        """vins.r_drift / vins.t_drift = the pose graph's loop_correct_r / loop_correct_t (ViewController.mm:998-999)."""
+        r, t = _d(r_drift), _d(t_drift)
+        assert r.size == 9 and t.size == 3
+        self._check(self.lib.vio_estimator_set_drift(self._h, seq, _p(r), _p(t)), "set_drift")
+
     def keyframe_features(self, seqs, stride=1024):
         """KeyFrame::buildKeyFrameFeatures for these sequences with the states of the moment (vio_estimator_keyframe_features):
         resident sequences are served on the device and stay resident. -> rc (VIO_OK or VIO_ECAP), per sequence
