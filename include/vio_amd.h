@@ -275,7 +275,11 @@ typedef struct VioTrackViz { /* good_pts / track_len (UI only), optional */
  * corner detector on every published frame of every sequence; by default a
  * sequence that still tracks max_corners features skips it, like the
  * reference's n_max_cnt > 0 test (feature_tracker.cpp:256-266) -- the results
- * are the same either way.                                                    */
+ * are the same either way. VIO_AMD_REDO_REPORT=1 (measurement aid) makes
+ * vio_frontend_destroy print on stderr how many sequence-frames had more
+ * corner candidates than the detector's lists hold (plateaus of equal
+ * eigenvalues) and were redone from a full-size list; the corners are exact
+ * either way.                                                                 */
 int vio_frontend_create(const VioConfig *cfg, int32_t n_seq, vio_frontend_t **out);
 int vio_frontend_get_device(const vio_frontend_t *fe, int32_t *device);
 void vio_frontend_destroy(vio_frontend_t *fe);

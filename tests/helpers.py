@@ -163,6 +163,35 @@ def oracle_good_features(cfg, img, mask, max_corners):
     return corners[: n.value].copy()
 
 
+def oracle_min_eigen_map(img):
+    """cornerMinEigenVal(img, blockSize 3, Sobel 3) of the CPU oracle -> float32 [rows, cols]."""
+    lib = oracle_lib()
+    img = np.ascontiguousarray(img, np.uint8)
+    eig = np.zeros(img.shape, np.float32)
+    rc = lib.oracle_min_eigen_map(img.ctypes.data_as(_u8p), img.shape[0], img.shape[1], img.shape[1], eig.ctypes.data_as(_fp))
+    assert rc == 0, rc
+    return eig
+
+
+def detector_candidates(img, mask=None):
+    """The detector's candidate rule before the quality threshold, from the oracle's eigenvalue map alone: boolean map of
+    v > 0 && v == max3x3(v), 1 <= x < cols - 1, 1 <= y < rows - 1, inside the mask."""
+    eig = oracle_min_eigen_map(img)
+    rows, cols = eig.shape
+    pad = np.full((rows + 2, cols + 2), -np.inf, np.float32)
+    pad[1:-1, 1:-1] = eig
+    m = eig.copy()
+    for dy in range(3):
+        for dx in range(3):
+            m = np.maximum(m, pad[dy:dy + rows, dx:dx + cols])
+    cand = (eig > 0) & (eig == m)
+    cand[0, :] = cand[-1, :] = False
+    cand[:, 0] = cand[:, -1] = False
+    if mask is not None:
+        cand &= np.asarray(mask) != 0
+    return cand
+
+
 def oracle_ransac(cfg, p1, p2):
     lib = oracle_lib()
     p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)

@@ -17,6 +17,7 @@ namespace vio {
 //     LOCAL_WORLD_SIZE, OMPI_COMM_WORLD_LOCAL_SIZE, MV2_COMM_WORLD_LOCAL_SIZE   ranks on this node, the first that is set
 //   read at create:
 //     VIO_AMD_DETECT_ALWAYS=1       front-end: run corner detection also for sequences that need no new corner
+//     VIO_AMD_REDO_REPORT=1         front-end: destroy prints how many sequence-frames the detector redid from a full-size list
 //     VIO_AMD_CS_PROF=1             front-end: cycle stamps of corner_select_kernel on stderr (synchronizes every publish step)
 //     VIO_AMD_HOST_PRIORS=1         estimator: marginalization priors travel through host memory
 //     VIO_AMD_RESIDENT=0            estimator: no device-resident landmark store

@@ -21,6 +21,7 @@
 #include "lk_layout.h"
 #include "vio_exact_math.h"
 
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1398,44 +1399,49 @@ __device__ __forceinline__ float sqrt_rn_normal(float x) {
   return y;
 }
 
-template <bool IMG_MASK>
-__global__ __launch_bounds__(256) void detect_kernel(const uint8_t *img_base, size_t img_stride, const uint8_t *mask_base,
-                                                     size_t mask_stride, const int *kept_xy, const int *n_kept, int cap,
-                                                     const int *hw, int radius, unsigned *max_bits, int rows, int cols,
-                                                     unsigned long long *cand_base, int seg_cap, int *n_cand, const int *n_have,
-                                                     int max_corners) {
-  // n_max_cnt = MAX_CNT - forw_pts.size() <= 0: the reference does not call goodFeaturesToTrack at all (feature_tracker.cpp:256-266);
-  // the sequence's candidate counters and maxima stay zero, which is "no corners" to the selection kernel
-  if (n_have && n_have[blockIdx.z] >= max_corners) return;
-  constexpr int kCandLds = kDetWaves * kDetW * kDetR / 4 + 64;  // a 3x3 maximum occupies at most one pixel in four
-  __shared__ unsigned long long s_mask[kDetWaves][kDetR];
-  __shared__ unsigned long long s_cand[kCandLds];
+// One tile of the detector: NW waves side by side (NW * kDetW output columns), one strip of kDetR rows, tile (bxi, byi) of
+// sequence `seq`. FULL = false is the product path (detect_kernel): candidates go to the workgroup's LDS list and from there
+// to the strip's segment of the sequence's list, and a list that cannot take them all raises the sequence's flag in `ovf`.
+// FULL = true is the exact redo of a flagged sequence (corner_select_kernel's redo workgroups): every pixel of the tile writes
+// its key, or 0 when it is no candidate, to its own place y * cols + x of `full` -- no list, no counter, nothing to overflow.
+template <bool IMG_MASK, bool FULL, int NW>
+__device__ __forceinline__ void detect_tile(const uint8_t *img_base, size_t img_stride, const uint8_t *mask_base, size_t mask_stride,
+                                            const int *kept_xy, const int *n_kept, int cap, const int *hw, int radius,
+                                            unsigned *max_bits, int rows, int cols, unsigned long long *cand_base, int seg_cap,
+                                            int *n_cand, int *ovf, int epoch, unsigned long long *full, int seq, int bxi, int byi, int nseg) {
+  // Equal eigenvalues (a plateau: a tiled pattern, upscaled or saturated content) make EVERY pixel of the plateau a candidate
+  // -- `v == m` holds for all of them, as in the reference's val == dilated --, so no list shorter than the tile holds every
+  // input. The lists are sized for what ordinary images produce (a strict 3x3 maximum occupies at most one pixel in four);
+  // what does not fit is not kept, the flag is raised, and the sequence is redone exactly behind this kernel.
+  constexpr int kCandLds = NW * kDetW * kDetR / 4 + 64;
+  __shared__ unsigned long long s_mask[NW][kDetR];
+  __shared__ unsigned long long s_cand[FULL ? 1 : kCandLds];
   __shared__ unsigned smax;
   __shared__ int s_ncand, s_base, s_ndisc;
   __shared__ int2 s_disc[kMaxCap];
-  const int seq = blockIdx.z, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const uint8_t *img = img_base + (size_t)seq * img_stride;
-  const int XB = blockIdx.x * (kDetWaves * kDetW), Y0 = blockIdx.y * kDetR;
+  const int XB = bxi * (NW * kDetW), Y0 = byi * kDetR;
   const int X0 = XB + wave * kDetW;  // first output column of this wave; lane l <-> extended column X0 - 2 + l
   if (tid == 0) smax = 0, s_ncand = 0, s_ndisc = 0;
-  if (tid < kDetWaves * kDetR) s_mask[tid / kDetR][tid % kDetR] = 0ull;
+  if (tid < NW * kDetR) s_mask[tid / kDetR][tid % kDetR] = 0ull;
   __syncthreads();
   if (!IMG_MASK) {
     // disc rows that cross this workgroup's strip -> bits of the (wave, row) words
     // (1) every thread tests one kept feature against the strip, the few that touch it are listed in LDS;
     // (2) one item per (listed disc, strip row, wave) ORs the lanes the disc covers on that row.
     const int nk = n_kept[seq];
-    for (int k = tid; k < nk; k += 256) {
+    for (int k = tid; k < nk; k += NW * 64) {
       const int cx = kept_xy[((size_t)seq * cap + k) * 2], cy = kept_xy[((size_t)seq * cap + k) * 2 + 1];
-      if (cy + radius >= Y0 && cy - radius < Y0 + kDetR && cx + radius >= XB - 2 && cx - radius < XB + kDetWaves * kDetW + 2) {
+      if (cy + radius >= Y0 && cy - radius < Y0 + kDetR && cx + radius >= XB - 2 && cx - radius < XB + NW * kDetW + 2) {
         const int slot = atomicAdd(&s_ndisc, 1);
         s_disc[slot] = make_int2(cx, cy);  // (at most cap entries: every feature at most once)
       }
     }
     __syncthreads();
     const int nd = s_ndisc;
-    for (int it = tid; it < nd * kDetR * kDetWaves; it += 256) {
-      const int wv = it % kDetWaves, r = (it / kDetWaves) % kDetR, dsc = it / (kDetWaves * kDetR);
+    for (int it = tid; it < nd * kDetR * NW; it += NW * 64) {
+      const int wv = it % NW, r = (it / NW) % kDetR, dsc = it / (NW * kDetR);
       const int cx = s_disc[dsc].x, dy = Y0 + r - s_disc[dsc].y;
       if (dy < -radius || dy > radius) continue;
       const int h = hw[radius + dy];
@@ -1542,7 +1548,11 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t *img_base, si
           bool unmasked;
           if (IMG_MASK) unmasked = mask_base[(size_t)seq * mask_stride + (size_t)y * cols + xe] != 0;
           else unmasked = ((s_mask[wave][r] >> lane) & 1ull) == 0ull;
-          if (unmasked) {
+          if (FULL) {
+            const bool is_cand = unmasked && xe >= 1 && xe < cols - 1 && (INNER || (y >= 1 && y < rows - 1)) && v > 0.f && v == m;
+            const unsigned idx = (unsigned)y << 16 | (unsigned)xe;
+            full[(size_t)y * cols + xe] = is_cand ? ((unsigned long long)__float_as_uint(v) << 32) | (0xffffffffu - idx) : 0ull;
+          } else if (unmasked) {
             my_max = fmaxf(my_max, v);
             if (xe >= 1 && xe < cols - 1 && (INNER || (y >= 1 && y < rows - 1)) && v > 0.f && v == m) {
               const int slot = atomicAdd(&s_ncand, 1);
@@ -1561,6 +1571,7 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t *img_base, si
   };  // strip
   if (inner_rows) strip(std::true_type{});
   else strip(std::false_type{});
+  if (FULL) return;  // (the masked maximum is the first pass's: a list that overflows loses candidates, not the maximum)
   // masked maximum: wave max on the DPP/shuffle network, then one LDS atomic per wave
   {
     unsigned m = my_max == -INFINITY ? 0u : ordered_bits(my_max);
@@ -1571,16 +1582,34 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t *img_base, si
   __syncthreads();
   // every strip of a sequence owns a segment of the candidate list and a counter / maximum slot, so the global
   // atomics of one address come from the few workgroups of that strip only
-  const int nseg = gridDim.y;
-  const size_t segi = (size_t)seq * nseg + blockIdx.y;
+  const size_t segi = (size_t)seq * nseg + byi;
   const int nc = min(s_ncand, kCandLds);
   if (tid == 0 && nc) s_base = atomicAdd(&n_cand[segi], nc);
   __syncthreads();
-  for (int i = tid; i < nc; i += 256) {
+  for (int i = tid; i < nc; i += NW * 64) {
     const int slot = s_base + i;
     if (slot < seg_cap) cand_base[segi * seg_cap + slot] = s_cand[i];
   }
   if (tid == 0 && smax) atomicMax(&max_bits[segi], smax);
+  // candidates this workgroup's list or the strip's segment had no slot for: the sequence is redone (every workgroup that sees
+  // it stores the same value; which candidates were dropped depends on the order the atomics arrived in, the flag does not).
+  // The flag is this detection pass's number and is never cleared: a redo workgroup that cleared it could do so before the
+  // sequence's ordinary selection workgroup has read it.
+  if (tid == 0 && (s_ncand > kCandLds || (nc && s_base + nc > seg_cap))) ovf[seq] = epoch;
+}
+
+template <bool IMG_MASK>
+__global__ __launch_bounds__(256) void detect_kernel(const uint8_t *img_base, size_t img_stride, const uint8_t *mask_base,
+                                                     size_t mask_stride, const int *kept_xy, const int *n_kept, int cap,
+                                                     const int *hw, int radius, unsigned *max_bits, int rows, int cols,
+                                                     unsigned long long *cand_base, int seg_cap, int *n_cand, int *ovf,
+                                                     int epoch, const int *n_have, int max_corners) {
+  // n_max_cnt = MAX_CNT - forw_pts.size() <= 0: the reference does not call goodFeaturesToTrack at all (feature_tracker.cpp:256-266);
+  // the sequence's candidate counters and maxima stay zero, which is "no corners" to the selection kernel
+  if (n_have && n_have[blockIdx.z] >= max_corners) return;
+  detect_tile<IMG_MASK, false, kDetWaves>(img_base, img_stride, mask_base, mask_stride, kept_xy, n_kept, cap, hw, radius, max_bits, rows,
+                                          cols, cand_base, seg_cap, n_cand, ovf, epoch, (unsigned long long *)nullptr, blockIdx.z, blockIdx.x,
+                                          blockIdx.y, gridDim.y);
 }
 
 #undef LANE_LEFT
@@ -1608,16 +1637,18 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 // goodFeaturesToTrack back half: quality threshold, then greedy pick in sorted order with the min-distance rule
 // == repeat { take the best alive candidate; kill everything closer than min_dist }. Then addPoints / updateID /
 // image_msg and the end-of-publish copies (feature_tracker.cpp:271-307).
-__global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned long long *cand_base, int seg_cap, int nseg,
-                                                                    int *n_cand, unsigned *max_bits,
-                                                                    double quality, SelectParams P, float *forw_pts,
-                                                                    float *cur_pts, float *pre_pts, int *ids, int *track_cnt,
-                                                                    int *n_forw, int *n_pts, int *n_id, VioObs *obs,
-                                                                    int *n_obs, long long *prof) {
+// Sequence `seq` from the list `cand`: nseg segments of seg_cap keys. full = false: the detector's ordinary list, segment g
+// holds n_cand[g] keys. full = true: the redo's list, one slot per pixel (seg_cap = kDetR * cols, key or 0), every slot of a
+// strip's rows is visited. skip: the detector flagged the sequence and a redo workgroup has it -- nothing is written (the flag is
+// loaded with the sequence's counters and looked at behind them, so that it adds no trip to memory of its own in front of the work).
+__device__ __forceinline__ void select_sequence(unsigned long long *cand, int seg_cap, int nseg, int *n_cand, unsigned *max_bits,
+                                                double quality, const SelectParams &P, float *forw_pts, float *cur_pts,
+                                                float *pre_pts, int *ids, int *track_cnt, int *n_forw, int *n_pts, int *n_id,
+                                                VioObs *obs, int *n_obs, long long *prof, int seq, bool full, bool skip) {
   // prof: null, or cycle stamps of sequence 0's workgroup (VIO_AMD_CS_PROF, tools/cs_prof.sh)
 #define CS_STAMP(k)                                                  \
   do {                                                               \
-    if (prof && blockIdx.x == 0 && threadIdx.x == 0) prof[k] = clock64(); \
+    if (prof && seq == 0 && threadIdx.x == 0) prof[k] = clock64(); \
   } while (0)
   CS_STAMP(0);
   __shared__ unsigned long long keys[kSelLds];
@@ -1628,9 +1659,8 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
   __shared__ unsigned s_pick[kMaxCap];  // y << 16 | x of the corners taken, by output position
   __shared__ int s_wnew[kSelThreads / 64];
   static_assert(kMaxCap <= kSelThreads, "the id pass gives every feature slot its own work-item");
-  const int seq = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
   const int lane = tid & 63, wave = tid >> 6;
-  unsigned long long *cand = cand_base + (size_t)seq * nseg * seg_cap;  // nseg segments of seg_cap keys
   const size_t base = (size_t)seq * P.cap;
   const int n_old = n_forw[seq];
   int n = n_old;
@@ -1652,7 +1682,8 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
     unsigned mb = 0;
     for (int g0 = 0; g0 < nseg; g0 += 64) {
       const int g = g0 + lane;
-      const int c = g < nseg ? min(n_cand[(size_t)seq * nseg + g], seg_cap) : 0;
+      int c = 0;
+      if (g < nseg) c = full ? min(kDetR, P.rows - g * kDetR) * P.cols : min(n_cand[(size_t)seq * nseg + g], seg_cap);
       mb = max(mb, g < nseg ? max_bits[(size_t)seq * nseg + g] : 0u);
       int incl = c;
 #pragma unroll
@@ -1668,6 +1699,7 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
     if (lane == 0) s_off[nseg] = carry, s_mb = mb, s_n = n, s_cnt = 0;
   }
   __syncthreads();
+  if (skip) return;  // (uniform)
   const unsigned mb = s_mb;
   const float thr = mb ? (float)((double)from_ordered_bits(mb) * quality) : 3.4e38f;
   const int real = s_off[nseg];
@@ -1846,6 +1878,65 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
 #undef CS_STAMP
 }
 
+constexpr int kRedoSlots = 4;  // full-size candidate lists a context owns: flagged sequences redone at the same time
+
+struct RedoParams {  // what a redo workgroup needs to run the detector again, and where it finds the flags
+  const uint8_t *img_base, *mask_base;
+  size_t img_stride, mask_stride;
+  const int *kept_xy, *n_kept, *hw;
+  int radius;
+  unsigned long long *full;  // [redo workgroups][rows * cols]
+  const int *ovf;            // [n_seq] number of the last detection pass that dropped candidates of the sequence
+  int epoch, n_seq, n_wg;    // this detection pass; redo workgroups behind the n_seq ordinary ones
+  int *n_redo;               // sequences redone so far (statistics)
+};
+
+// Workgroups [0, n_seq): sequence blockIdx.x from the detector's list, unless the detector flagged it.
+// Workgroups [n_seq, gridDim.x), the redo workgroups: the flagged sequences, each by ONE workgroup from start to end -- the
+// detector again over the whole frame, tile by tile, into the workgroup's own full-size list (one key per pixel), then the same
+// selection on that list. Redo workgroup k takes the flagged sequences k, k + n, k + 2n, ... in turn (n = redo workgroups), so
+// any number of flagged sequences is served by n lists, no workgroup waits for another, and nothing depends on an order of
+// arrival. With no flag up -- every frame of an ordinary stream -- a redo workgroup reads its share of the flags and exits.
+// (Slow where it runs, one workgroup per frame: it is the exact answer for inputs the lists are not sized for, not a fast path.)
+template <bool IMG_MASK>
+__global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned long long *cand_base, int seg_cap, int nseg,
+                                                                    int *n_cand, unsigned *max_bits, RedoParams R,
+                                                                    double quality, SelectParams P, float *forw_pts,
+                                                                    float *cur_pts, float *pre_pts, int *ids, int *track_cnt,
+                                                                    int *n_forw, int *n_pts, int *n_id, VioObs *obs,
+                                                                    int *n_obs, long long *prof) {
+  const bool redo = (int)blockIdx.x >= R.n_seq;
+  const int slot = (int)blockIdx.x - R.n_seq, n_slots = R.n_wg;
+  if (redo) {
+    int any = 0;
+    for (int s = slot + n_slots * (int)threadIdx.x; s < R.n_seq; s += n_slots * kSelThreads) any |= R.ovf[s] == R.epoch;
+    if (!__syncthreads_or(any)) return;
+  }
+  // (one call site of select_sequence for both kinds of workgroup: its 64 KB key list exists once)
+  for (int seq = redo ? slot : (int)blockIdx.x; seq < R.n_seq; seq += redo ? n_slots : R.n_seq) {
+    const bool flagged = R.ovf[seq] == R.epoch;  // (uniform)
+    if (redo && !flagged) continue;
+    unsigned long long *cand = cand_base + (size_t)seq * nseg * seg_cap;
+    int cand_seg = seg_cap;
+    if (redo) {
+      cand = R.full + (size_t)slot * P.rows * P.cols, cand_seg = kDetR * P.cols;
+      constexpr int NW = kSelThreads / 64;
+      const int nbx = (P.cols + NW * kDetW - 1) / (NW * kDetW);
+      for (int by = 0; by < nseg; by++)
+        for (int bx = 0; bx < nbx; bx++) {
+          detect_tile<IMG_MASK, true, NW>(R.img_base, R.img_stride, R.mask_base, R.mask_stride, R.kept_xy, R.n_kept, P.cap, R.hw, R.radius,
+                                          (unsigned *)nullptr, P.rows, P.cols, (unsigned long long *)nullptr, 0, (int *)nullptr,
+                                          (int *)nullptr, 0, cand, seq, bx, by, nseg);
+          __syncthreads();  // (the next tile clears the mask words this one reads; behind the last tile: the list is written)
+        }
+      if (threadIdx.x == 0) atomicAdd(R.n_redo, 1);
+    }
+    select_sequence(cand, cand_seg, nseg, n_cand, max_bits, quality, P, forw_pts, cur_pts, pre_pts, ids, track_cnt, n_forw, n_pts, n_id,
+                    obs, n_obs, redo ? (long long *)nullptr : prof, seq, redo, !redo && flagged);
+    if (redo) __syncthreads();  // (the next sequence reuses the selection's LDS)
+  }
+}
+
 void circle_halfwidths(int radius, std::vector<int> &hw) {  // cv::circle filled midpoint raster (drawing.cpp Circle())
   hw.assign(2 * radius + 1, -1);
   int err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
@@ -1885,6 +1976,12 @@ struct vio_frontend {
   DevBuf<unsigned long long> cand;
   int nseg = 0, seg_cap = 0;  // candidate list: one segment per strip of kDetR rows
   DevBuf<int> n_cand;
+  // a detection pass that had to drop candidates (a plateau of equal eigenvalues) stamps its number into the sequence's ovf[]; the
+  // selection kernel's redo workgroups then redo that sequence exactly, each in its own full-size list of redo_full
+  DevBuf<int> ovf, n_redo;
+  DevBuf<unsigned long long> redo_full;  // [n_redo_wg][rows * cols]
+  int n_redo_wg = 0, det_epoch = 0;
+  bool redo_report = false;  // VIO_AMD_REDO_REPORT=1 (measurement aid): destroy prints how many sequences were redone
   DevBuf<float> cur_pts, pre_pts, forw_pts, lk_err;
   DevBuf<unsigned long long> lk_stats;  // [64][16] iteration counters of lk_track_kernel (vio_frontend_lk_iterations)
   bool lk_stats_on = false;
@@ -1922,6 +2019,11 @@ struct vio_frontend {
   std::vector<VioObs> h_obs;
   std::vector<int> h_nobs;
   ~vio_frontend() {
+    if (redo_report && n_redo.p) {
+      int n = -1;
+      if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(&n, n_redo.p, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
+        fprintf(stderr, "detector: %d sequence-frames redone from the full-size candidate list (%d detection passes)\n", n, det_epoch);
+    }
     if (async) {
       {
         std::lock_guard<std::mutex> lk(async->m);
@@ -1937,6 +2039,19 @@ struct vio_frontend {
 };
 
 namespace {
+
+int next_epoch(vio_frontend *fe) {  // number of the detection pass being launched: never 0, which is what ovf[] starts as
+  fe->det_epoch = fe->det_epoch == INT_MAX ? 1 : fe->det_epoch + 1;
+  return fe->det_epoch;
+}
+
+RedoParams redo_params(vio_frontend *fe, const uint8_t *img_base, size_t img_stride, const uint8_t *mask_base, size_t mask_stride, int radius) {
+  RedoParams R;
+  R.img_base = img_base, R.mask_base = mask_base, R.img_stride = img_stride, R.mask_stride = mask_stride;
+  R.kept_xy = fe->kept_xy.p, R.n_kept = fe->n_kept.p, R.hw = fe->hw.p, R.radius = radius;
+  R.full = fe->redo_full.p, R.ovf = fe->ovf.p, R.epoch = fe->det_epoch, R.n_seq = fe->n_seq, R.n_wg = fe->n_redo_wg, R.n_redo = fe->n_redo.p;
+  return R;
+}
 
 // The same for source rows that are whole dwords (scols % 4 == 0, dword-aligned level offsets): the patch arrives as 4
 // pixels per lane and per load instead of 1, the output leaves as 4 pixels per store. One workgroup = 64 x 16 output
@@ -2179,12 +2294,14 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
     dim3 tb(256), tg((cols + kDetWaves * kDetW - 1) / (kDetWaves * kDetW), fe->nseg, S);
     hipLaunchKernelGGL(detect_kernel<false>, tg, tb, 0, st, alias0 ? d_frames : forw, alias0 ? img_bytes : fe->ld.pyr_bytes, (const uint8_t *)nullptr, (size_t)0,
                        fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist, fe->max_bits.p, rows, cols, fe->cand.p,
-                       fe->seg_cap, fe->n_cand.p, fe->detect_always ? (const int *)nullptr : fe->n_forw.p, fe->cfg.max_corners);
+                       fe->seg_cap, fe->n_cand.p, fe->ovf.p, next_epoch(fe), fe->detect_always ? (const int *)nullptr : fe->n_forw.p,
+                       fe->cfg.max_corners);
     SelectParams SP;
     SP.cap = cap, SP.rows = rows, SP.cols = cols, SP.max_corners = fe->cfg.max_corners, SP.min_dist = (float)fe->cfg.min_dist;
     SP.fx = fe->cfg.fx, SP.fy = fe->cfg.fy, SP.cx = fe->cfg.cx, SP.cy = fe->cfg.cy;
-    hipLaunchKernelGGL(corner_select_kernel, dim3(S), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg, fe->n_cand.p,
-                       fe->max_bits.p, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
+    const RedoParams RP = redo_params(fe, alias0 ? d_frames : forw, alias0 ? img_bytes : fe->ld.pyr_bytes, nullptr, 0, fe->cfg.min_dist);
+    hipLaunchKernelGGL(corner_select_kernel<false>, dim3(S + fe->n_redo_wg), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg,
+                       fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
                        fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p, fe->cs_prof ? fe->d_cs_prof.p : nullptr);
     if (fe->cs_prof) {  // (debug only: synchronises)
       long long h[5];
@@ -2230,14 +2347,19 @@ int vio_frontend_create(const VioConfig *cfg, int32_t n_seq, vio_frontend_t **ou
     delete fe;
     return VIO_ECAP;
   }
-  fe->seg_cap = kDetR * cfg->image_cols / 4;  // a 3x3 local maximum can occupy at most one pixel in four
+  // a STRICT 3x3 local maximum occupies at most one pixel in four. Equal neighbours are all candidates (a plateau): a strip that
+  // has more of them than this raises the sequence's flag and the sequence is redone from a full-size list (corner_select_kernel)
+  fe->seg_cap = kDetR * cfg->image_cols / 4;
+  fe->n_redo_wg = (int)std::min<size_t>(S, kRedoSlots);
+  fe->redo_report = vio::env_flag("VIO_AMD_REDO_REPORT");
   if (hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking) != hipSuccess) {
     delete fe;
     return VIO_ENODEV;
   }
   if (fe->pyr[0].ensure(S * ld.pyr_bytes) != VIO_OK || fe->pyr[1].ensure(S * ld.pyr_bytes) != VIO_OK ||
       fe->max_bits.ensure(S * fe->nseg) != VIO_OK || fe->cand.ensure(S * fe->nseg * fe->seg_cap) != VIO_OK ||
-      fe->n_cand.ensure(S * fe->nseg) != VIO_OK || fe->cur_pts.ensure(S * cap * 2) != VIO_OK ||
+      fe->n_cand.ensure(S * fe->nseg) != VIO_OK || fe->ovf.ensure(S) != VIO_OK || fe->n_redo.ensure(1) != VIO_OK ||
+      fe->redo_full.ensure((size_t)fe->n_redo_wg * cfg->image_rows * cfg->image_cols) != VIO_OK || fe->cur_pts.ensure(S * cap * 2) != VIO_OK ||
       fe->pre_pts.ensure(S * cap * 2) != VIO_OK || fe->forw_pts.ensure(S * cap * 2) != VIO_OK || fe->lk_err.ensure(S * cap) != VIO_OK ||
       fe->ids.ensure(S * cap) != VIO_OK || fe->track_cnt.ensure(S * cap) != VIO_OK || fe->n_pts.ensure(S) != VIO_OK ||
       fe->n_forw.ensure(S) != VIO_OK || fe->n_id.ensure(S) != VIO_OK || fe->kept_xy.ensure(S * cap * 2) != VIO_OK ||
@@ -2252,6 +2374,7 @@ int vio_frontend_create(const VioConfig *cfg, int32_t n_seq, vio_frontend_t **ou
   if (hipMemcpy(fe->hw.p, hw.data(), hw.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(fe->max_bits.p, 0, sizeof(unsigned) * S * fe->nseg) != hipSuccess ||
       hipMemset(fe->n_cand.p, 0, sizeof(int) * S * fe->nseg) != hipSuccess || hipMemset(fe->n_pts.p, 0, sizeof(int) * S) != hipSuccess ||
+      hipMemset(fe->ovf.p, 0, sizeof(int) * S) != hipSuccess || hipMemset(fe->n_redo.p, 0, sizeof(int)) != hipSuccess ||
       hipMemset(fe->n_forw.p, 0, sizeof(int) * S) != hipSuccess || hipMemset(fe->n_id.p, 0, sizeof(int) * S) != hipSuccess ||
       hipMemset(fe->n_kept.p, 0, sizeof(int) * S) != hipSuccess || hipMemset(fe->n_pnp.p, 0, sizeof(int) * S) != hipSuccess ||
       hipMemset(fe->n_obs.p, 0, sizeof(int) * S) != hipSuccess) {
@@ -2698,12 +2821,14 @@ int vio_good_features(const VioConfig *cfg, const uint8_t *img, const uint8_t *m
     return VIO_ENODEV;
   dim3 tb(256), tg((cols + kDetWaves * kDetW - 1) / (kDetWaves * kDetW), fe->nseg, 1);
   hipLaunchKernelGGL(detect_kernel<true>, tg, tb, 0, st, fe->pyr[0].p, fe->ld.pyr_bytes, fe->mask.p, px, fe->kept_xy.p, fe->n_kept.p,
-                     fe->cap, fe->hw.p, c.min_dist, fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, (const int *)nullptr, 0);
+                     fe->cap, fe->hw.p, c.min_dist, fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, fe->ovf.p,
+                     next_epoch(fe.get()), (const int *)nullptr, 0);
   SelectParams SP;
   SP.cap = fe->cap, SP.rows = rows, SP.cols = cols, SP.max_corners = max_corners, SP.min_dist = (float)c.min_dist;
   SP.fx = c.fx, SP.fy = c.fy, SP.cx = c.cx, SP.cy = c.cy;
-  hipLaunchKernelGGL(corner_select_kernel, dim3(1), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg, fe->n_cand.p, fe->max_bits.p,
-                     c.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p, fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p,
+  const RedoParams RP = redo_params(fe.get(), fe->pyr[0].p, fe->ld.pyr_bytes, fe->mask.p, px, c.min_dist);
+  hipLaunchKernelGGL(corner_select_kernel<true>, dim3(1 + fe->n_redo_wg), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg,
+                     fe->n_cand.p, fe->max_bits.p, RP, c.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p, fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p,
                      fe->n_id.p, fe->obs.p, fe->n_obs.p, (long long *)nullptr);
   if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
   int n = 0;
