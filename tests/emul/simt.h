@@ -1,7 +1,7 @@
 // tests/emul/simt.h — TEST-ONLY wave64 SIMT emulator for the device sections of the kernel sources.
 //
-// The -DVIO_EMUL build (emul_backend.cpp) runs scalar stand-ins of the wave-level sections (matrix cores, DPP,
-// v_readlane): index maths and control flow of the phase code, but not one of the sections that actually run on the
+// The -DVIO_EMUL build (emul_pnp.cpp: spmd.h, factors.h, pnp_core.h) runs scalar stand-ins of the wave-level sections (the
+// DPP reductions of spmd.h): index maths and control flow of the phase code, but not one of the sections that actually run on the
 // GPU. This header closes that gap: with -DVIO_SIMT the DEVICE sections themselves are compiled for the host and every
 // work-item of a workgroup runs as a fiber. A lane runs until it reaches a wave-level operation (v_mfma_f64_16x16x4,
 // v_readlane, DPP moves, ballot, wave barrier) or s_barrier; when all 64 lanes of its wave (all waves of the workgroup)

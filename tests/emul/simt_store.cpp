@@ -44,7 +44,7 @@ struct SimStore {
   st::Dims d;
   std::vector<int> fid[2], start[2], nobs[2], flag[2], ctl;
   std::vector<double> depth[2], obs[2], ctld;
-  std::vector<int> lds_i;
+  std::vector<int> lds_words;
   SimStore(int W, int Lcap, int Ocap) {
     d.W = W, d.Lcap = Lcap, d.Ocap = Ocap;
     for (int b = 0; b < 2; b++) {
@@ -53,13 +53,13 @@ struct SimStore {
       obs[b].assign((size_t)Lcap * (W + 1) * 3, std::numeric_limits<double>::quiet_NaN());
     }
     ctl.assign(st::C_COUNT, 0), ctld.assign(st::kCtlDoubles, 0);
-    lds_i.assign(st::lds_bytes(d) / sizeof(int) + 16, -1);
+    lds_words.assign(st::lds_bytes(d) / sizeof(int) + 16, -1);
   }
   st::Bank bank(int b) { return st::Bank{fid[b].data(), start[b].data(), nobs[b].data(), flag[b].data(), depth[b].data(), obs[b].data()}; }
   st::Lds lds() {
     double *dbase;
-    std::fill(lds_i.begin(), lds_i.end(), -1);  // nothing survives in LDS from one launch to the next
-    return st::carve_lds<int *, double *>(d, lds_i.data(), &dbase);
+    std::fill(lds_words.begin(), lds_words.end(), -1);  // nothing survives in LDS from one launch to the next
+    return st::carve_lds<int *, double *>(d, lds_words.data(), &dbase);
   }
 };
 

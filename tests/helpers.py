@@ -62,6 +62,23 @@ def oracle_backend():
     return abi.bind_backend_solver(oracle_lib(), "oracle")
 
 
+EMUL_DIR = os.path.join(ROOT, "tests", "emul")
+
+
+def build_emul_lib(source_name, so_name, define, extra_flags=()):
+    """tests/emul/<source_name> compiled for the host with -D<define> (VIO_SIMT: every work-item a fiber of simt.h; VIO_EMUL:
+    one thread) into tests/emul/<so_name>, loaded. Rebuilt when the library is older than its source or ANY header the
+    kernel sources could reach: a hand-kept list goes stale the day a header is split."""
+    csrc, inc = os.path.join(ROOT, "vins-mobile_amd", "csrc"), os.path.join(ROOT, "include")
+    so, src = os.path.join(EMUL_DIR, so_name), os.path.join(EMUL_DIR, source_name)
+    deps = [src] + [f for pat in ((csrc, "*.h"), (csrc, "*.inc"), (csrc, "*.cpp"), (EMUL_DIR, "*.h"), (inc, "*.h"))
+                    for f in glob.glob(os.path.join(*pat))]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-psabi", *extra_flags, "-D" + define,
+                               "-I" + inc, "-I" + csrc, "-I" + EMUL_DIR, "-shared", "-o", so, src])
+    return C.CDLL(so)
+
+
 def ref_lib_or_none():
     so = os.path.join(ROOT, "oracle", "_ref", "libvio_ref.so")
     return C.CDLL(so) if os.path.exists(so) else None

@@ -7,9 +7,7 @@ and tests/golden/init_sfm_edges.npz (shape edges, make_init_sfm_edges_golden.py)
 test_initial_sfm.py::_compare. GPU: the same recordings through vio_init_ba_solve, bit-for-bit determinism across slots,
 batches and runs, capacities and arguments, context reuse."""
 import ctypes as C
-import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,21 +17,12 @@ import test_initial_sfm as T
 
 abi = H.abi
 init_ba = H.pkg.init_ba
-EMUL_DIR = os.path.join(H.ROOT, "tests", "emul")
 EDGES = os.path.join(H.ROOT, "tests", "golden", "init_sfm_edges.npz")
 
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libvio_simt_sfm.so")
-    csrc = os.path.join(H.ROOT, "vins-mobile_amd", "csrc")
-    srcs = glob.glob(os.path.join(csrc, "*.h")) + [os.path.join(EMUL_DIR, "simt_sfm.cpp"), os.path.join(EMUL_DIR, "simt.h"),
-                                                   os.path.join(H.ROOT, "include", "vio_amd.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-psabi", "-DVIO_SIMT",
-                               "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-I" + EMUL_DIR, "-shared", "-o", so,
-                               os.path.join(EMUL_DIR, "simt_sfm.cpp")])
-    lib = C.CDLL(so)
+    lib = H.build_emul_lib("simt_sfm.cpp", "libvio_simt_sfm.so", "VIO_SIMT")
     lib.simt_sfm_solve.argtypes = [C.POINTER(abi.VioInitBaProblem), C.c_int, C.POINTER(abi.VioSolveStats), C.c_int, C.c_int]
     return lib
 

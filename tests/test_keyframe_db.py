@@ -18,7 +18,6 @@ RefDb records the smallest margin of every walk and the tests assert it before c
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -28,7 +27,6 @@ from test_posegraph import TOL_GPU, TOL_ORACLE   # the project's two numbers: or
 
 pkg = H.pkg
 abi, pg, synth, kdb = pkg.abi, pkg.posegraph, pkg.synth, pkg.keyframe_db
-EMUL_DIR = os.path.join(H.ROOT, "tests", "emul")
 _dp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 MARGIN = 1e-3
 
@@ -339,16 +337,9 @@ def test_entry_points_are_exported_and_validate_arguments():
 # ---- 2. the list passes on the SIMT emulator ------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libvio_simt_kfdb.so")
-    csrc = os.path.join(H.ROOT, "vins-mobile_amd", "csrc")
-    src = os.path.join(EMUL_DIR, "simt_kfdb.cpp")
-    deps = [src, os.path.join(EMUL_DIR, "simt.h")] + [os.path.join(csrc, f) for f in ("kfdb_core.h", "solver_core.h", "vio_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
-        # (-fno-builtin-sin / -cos: g++ would merge sin(x) and cos(x) into one sincos(x), which is not the same libm entry as
-        # the sin and cos the product's host object calls and differs from them in the last bit for a few arguments)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-builtin-sin", "-fno-builtin-cos", "-Wno-psabi",
-                               "-DVIO_SIMT", "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-I" + EMUL_DIR, "-shared", "-o", so, src])
-    l = C.CDLL(so)
+    # (-fno-builtin-sin / -cos: g++ would merge sin(x) and cos(x) into one sincos(x), which is not the same libm entry as
+    # the sin and cos the product's host object calls and differs from them in the last bit for a few arguments)
+    l = H.build_emul_lib("simt_kfdb.cpp", "libvio_simt_kfdb.so", "VIO_SIMT", extra_flags=("-fno-builtin-sin", "-fno-builtin-cos"))
     kfp = C.POINTER(pg.VioPoseGraphKeyframe)
     l.simt_kfdb_build.argtypes = [kfp, C.c_int, C.c_int, C.c_double] + [C.c_int] * 4 + [_ip, _ip, _dp, _ip, _ip, _ip, _dp, _ip, _dp]
     l.simt_kfdb_apply.argtypes = [kfp, _dp, _ip] + [C.c_int] * 7 + [_ip, _ip, _dp, _dp, _ip, _dp, _dp, _dp]

@@ -18,7 +18,6 @@ from helpers import abi, pkg, synth
 sys.path.insert(0, os.path.join(H.ROOT, "tools"))
 import replay_synthetic as RS  # noqa: E402
 
-EMUL_DIR = os.path.join(H.ROOT, "tests", "emul")
 _ip, _dp, _fp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float)
 FIRST, REACH, FEW, KEPT = 1, 2, 3, 0
 
@@ -151,14 +150,7 @@ def test_host_function_matches_the_restatement(W):
 # ---- 2. pass 4 of store_core.h on the SIMT emulator ----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libvio_simt_keyframe.so")
-    csrc = os.path.join(H.ROOT, "vins-mobile_amd", "csrc")
-    src = os.path.join(EMUL_DIR, "simt_keyframe.cpp")
-    deps = [src, os.path.join(EMUL_DIR, "simt.h")] + [os.path.join(csrc, f) for f in ("store_core.h", "keyframe_core.h", "solver_core.h", "vio_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-psabi", "-DVIO_SIMT",
-                               "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-I" + EMUL_DIR, "-shared", "-o", so, src])
-    l = C.CDLL(so)
+    l = H.build_emul_lib("simt_keyframe.cpp", "libvio_simt_keyframe.so", "VIO_SIMT")
     l.simt_store_keyframe.argtypes = [C.c_int] * 4 + [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _ip, _fp, _fp, _dp, _ip]
     return l
 

@@ -14,9 +14,7 @@ reference itself reproduces to 1e-8 under a 1e-13 change of its inputs, reaches 
 constructed to force it. Neither is a solve that meets the function tolerance exactly at its threshold (a solved window
 solved a third time): the reference's own route depends on the last bits there."""
 import ctypes as C
-import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,7 +23,6 @@ import helpers as H
 from helpers import abi, pkg, synth
 
 GOLDEN = os.path.join(H.ROOT, "tests", "golden", "pnp_windows.npz")
-EMUL_DIR = os.path.join(H.ROOT, "tests", "emul")
 TOL = 1e-6
 
 # (seed, frames, features per frame, fixed frames, perturbation scale)
@@ -186,13 +183,7 @@ def edge_windows(cfg):
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libvio_emul_pnp.so")
-    csrc = os.path.join(H.ROOT, "vins-mobile_amd", "csrc")
-    srcs = glob.glob(os.path.join(csrc, "*.h")) + [os.path.join(EMUL_DIR, "emul_pnp.cpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-DVIO_EMUL", "-I" + os.path.join(H.ROOT, "include"),
-                               "-I" + csrc, "-shared", "-o", so, os.path.join(EMUL_DIR, "emul_pnp.cpp")])
-    lib = C.CDLL(so)
+    lib = H.build_emul_lib("emul_pnp.cpp", "libvio_emul_pnp.so", "VIO_EMUL")
     lib.emul_pnp_solve.argtypes = None
     return lib
 

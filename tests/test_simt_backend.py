@@ -1,6 +1,6 @@
-"""CPU test of the DEVICE SECTIONS of the kernel source: vins-mobile_amd/csrc/solver_core.h + marg_core.h compiled with
--DVIO_SIMT and executed by the wave64 SIMT emulator of tests/emul/simt.h (one fiber per work-item; v_mfma_f64_16x16x4,
-v_readlane, DPP moves, ballot and s_barrier evaluated with the hardware's lane semantics), through the same pack / view
+"""CPU test of the DEVICE SECTIONS of the kernel source: vins-mobile_amd/csrc/solver_core.h (over spmd.h, factors.h,
+mfma_tiles.h) + marg_core.h compiled with -DVIO_SIMT and executed by the wave64 SIMT emulator of tests/emul/simt.h
+(one fiber per work-item; v_mfma_f64_16x16x4, v_readlane, DPP moves, ballot and s_barrier evaluated with the hardware's lane semantics), through the same pack / view
 / carve / unpack code and the same kernel body as the device path, against the reference's golden outputs.
 
 (The scalar one-thread emulation of rounds 1-2 only walked stand-ins of those sections; it is gone.) Lanes run in three
@@ -8,9 +8,6 @@ different orders between rendezvous points: a missing barrier or an undeclared r
 the result.
 Test-only build (tests/emul/); the product library has no CPU path."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,19 +15,10 @@ import pytest
 import helpers as H
 from helpers import abi, synth
 
-EMUL_DIR = os.path.join(H.ROOT, "tests", "emul")
-
 
 @pytest.fixture(scope="module")
 def simt():
-    so = os.path.join(EMUL_DIR, "libvio_simt.so")
-    csrc = os.path.join(H.ROOT, "vins-mobile_amd", "csrc")
-    srcs = glob.glob(os.path.join(csrc, "*.h")) + [os.path.join(EMUL_DIR, "simt_backend.cpp"), os.path.join(EMUL_DIR, "simt.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-psabi", "-DVIO_SIMT",
-                               "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-I" + EMUL_DIR, "-shared", "-o", so,
-                               os.path.join(EMUL_DIR, "simt_backend.cpp")])
-    lib = C.CDLL(so)
+    lib = H.build_emul_lib("simt_backend.cpp", "libvio_simt.so", "VIO_SIMT")
     lib.simt_solve_window.argtypes = [C.POINTER(abi.VioConfig), C.POINTER(abi.VioWindow), C.POINTER(abi.VioSolveStats),
                                       C.c_int, C.c_int, C.c_int]
     return lib

@@ -5,28 +5,15 @@ on seeded streams: list entries, observations, depth bits, keyframe decisions, f
 identical, through keyframes, non-keyframes, negative depths, a failure-detection reset and re-promotion.
 Test-only build (tests/emul/simt_store.cpp); the product library has no CPU path."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import pytest
 
 import helpers as H
 
-EMUL_DIR = os.path.join(H.ROOT, "tests", "emul")
-
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL_DIR, "libvio_simt_store.so")
-    csrc = os.path.join(H.ROOT, "vins-mobile_amd", "csrc")
-    srcs = glob.glob(os.path.join(csrc, "*.h")) + [os.path.join(csrc, "vio_window.cpp"), os.path.join(EMUL_DIR, "simt_store.cpp"),
-                                                   os.path.join(EMUL_DIR, "simt.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-psabi", "-DVIO_SIMT",
-                               "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-I" + EMUL_DIR, "-shared", "-o", so,
-                               os.path.join(EMUL_DIR, "simt_store.cpp")])
-    l = C.CDLL(so)
+    l = H.build_emul_lib("simt_store.cpp", "libvio_simt_store.so", "VIO_SIMT")
     l.simt_store_fuzz.argtypes = [C.c_int] * 5 + [C.c_char_p, C.c_int, C.POINTER(C.c_longlong)]
     return l
 

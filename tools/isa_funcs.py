@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """isa_funcs.py <kernel.s> [kernel-symbol-prefix] -- static instruction counts of one kernel attributed to the FUNCTIONS of
-solver_core.h / marg_core.h / batch.h (innermost inlined location of a -gline-tables-only --save-temps build, see isa_lines.py),
+solver_core.h and its layers (spmd.h, factors.h, mfma_tiles.h) / marg_core.h / batch.h (innermost inlined location of a -gline-tables-only --save-temps build, see isa_lines.py),
 with the classes the instruction diet of round 6 tracks: matrix, LDS, global, scalar, v_readlane / v_writelane (scalar
 spills), waitcnt, the rest of the vector unit."""
 import collections, os, re, sys
@@ -13,7 +13,7 @@ def func_ranges(fn):
         m = re.match(r'^(?:VIO_DEV|VIO_HD|__device__ __forceinline__|template.*\n)?\s*(?:VIO_DEV|VIO_HD|__device__ __forceinline__|inline)\s+[\w:<>\*& ]+?\s+(\w+)\s*\(', l)
         if m and not l.startswith(' '): out.append((i + 1, m.group(1)))
     return out
-ranges = {fn: func_ranges(fn) for fn in ('solver_core.h', 'marg_core.h', 'batch.h', 'vio_math.h', 'vio_window_kernel.inc')}
+ranges = {fn: func_ranges(fn) for fn in ('spmd.h', 'factors.h', 'mfma_tiles.h', 'solver_core.h', 'marg_core.h', 'batch.h', 'vio_math.h', 'vio_window_kernel.inc')}
 def func_of(fn, line):
     best = '?'
     for l0, name in ranges.get(fn, []):

@@ -1,4 +1,4 @@
-// band_bench.hip — the wave-level pieces of the structured factorization (csrc/solver_core.h) in isolation (tools
+// band_bench.hip — the wave-level pieces of the structured factorization (csrc/mfma_tiles.h) in isolation (tools
 // only, not product): s_memtime cycles per call for one workgroup of 256 threads on an otherwise idle CU.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -I../../include -I../../vins-mobile_amd/csrc -o bin/band_bench band_bench.hip
 #include <hip/hip_runtime.h>
@@ -7,7 +7,7 @@
 #include <stdlib.h>
 #include <vector>
 
-#include "solver_core.h"
+#include "mfma_tiles.h"
 
 using namespace vio;
 

@@ -366,8 +366,8 @@ inline int stage_chunk_slots(const BatchDims &d, bool lds_matrix, int nthreads) 
 
 // ---- host-side staging ---------------------------------------------------------------------------------
 // Staging vectors live in page-locked memory in the device build (hipMemcpyAsync then runs at link speed and really is
-// asynchronous); the host emulation of the kernel (tests/emul, -DVIO_EMUL) uses plain vectors.
-#if defined(__HIPCC__) && !defined(VIO_EMUL)
+// asynchronous); the host emulation of the kernel (tests/emul, -DVIO_SIMT) uses plain vectors.
+#if defined(__HIPCC__)
 template <class T>
 struct PinnedAllocator {
   typedef T value_type;

@@ -17,7 +17,7 @@
 // the SIMT emulator against the two host functions.
 #pragma once
 
-#include "solver_core.h"
+#include "spmd.h"
 #include "vio_amd.h"
 #include "vio_math.h"
 
@@ -32,7 +32,7 @@ constexpr int kDriftD = 13;  // what an optimize hands back per session: yaw_dri
 
 struct Cx {
   int tid, nt;
-  int wave64 = 0;  // (VIO_TID of solver_core.h)
+  int wave64 = 0;  // (VIO_TID of spmd.h)
 };
 
 struct List {

@@ -123,7 +123,6 @@ VIO_HD size_t carve_marg(const Dims &d, bool lds_matrix, ldsd base_after_state, 
   return c.bytes;
 }
 
-#ifndef VIO_EMUL
 // ---- tiled factorization of the dense marginalization matrix on the matrix cores ----------------------------------
 // 16 x 16 tiles of the row-major pos x pos matrix (leading dimension ld), the structure of cholesky_blocks
 // (solver_core.h): one wave factors the diagonal tile and produces its inverse, TRSM and the trailing update are MFMA
@@ -171,7 +170,7 @@ VIO_DEV void potrf16_cut_wave(MP D, LP Lprev, int ld, int nvalid, bool with_upda
       A = mfma_f64(-ls, ls, A);
     }
   }
-  // (round 6: four pivots per step like potrf16_wave of solver_core.h -- M = the inverse Cholesky factor of the 4 x 4 diagonal block,
+  // (round 6: four pivots per step like potrf16_wave of mfma_tiles.h -- M = the inverse Cholesky factor of the 4 x 4 diagonal block,
   // V = M R and T -= V^T V one matrix instruction each; a cut pivot has y = 0: its row of M, hence its column of L, its row of L^-1
   // and its reciprocal are zero, exactly what the rank-1 form left)
   double keep[4] = {0.0, 0.0, 0.0, 0.0}, myinv = 0.0;
@@ -351,7 +350,6 @@ VIO_DEV void marg_cholesky_tiles(const Ctx &cx, MW &m, int pos) {
     VIO_SYNC();
   }
 }
-#endif
 
 template <class MW>
 VIO_DEV void marginalize_window_impl(const Ctx &cx, const WinView &v, cldsd xpose, cldsd xsb, cldsd xfeat, cldsd ex,

@@ -15,7 +15,9 @@
 // loop is the one of the window solver (solver_core.h::minimize, i.e. Ceres' TrustRegionMinimizer + DoglegStrategy,
 // CSI/trust_region_minimizer.cc, CSI/dogleg_strategy.cc) without landmark blocks.
 #pragma once
-#include "solver_core.h"
+#include "solve_trace.h"
+#include "spmd.h"
+#include "factors.h"
 
 namespace vio {
 namespace pnp {
@@ -23,14 +25,13 @@ namespace pnp {
 constexpr int kMaxFrames = 8;
 constexpr int kDof = 9;  // pose 6 + speed 3 per free frame
 constexpr int kMaxDim = kMaxFrames * kDof;
-constexpr int kPreDoubles = 17 + 225 + 225;  // VioPreintegration as doubles
 
 struct View {  // one window, all pointers into global memory
   int n, M;
   const int *fixed;       // [n]
   const int *feat_start;  // [n+1]
   const double *pose0, *speed0, *bias, *ex;
-  const double *preint;   // [n-1][kPreDoubles]
+  const double *preint;   // [n-1][kPreintDoubles]
   const double *obs;      // [M][2]
   const double *pos;      // [M][3]
   const int *track;       // [M]
@@ -147,7 +148,7 @@ VIO_DEV double evaluate(const Ctx &cx, const View &v, Work<P> &w, P pose, P spee
     for (int c = 0; c < 7; c++) pi7[c] = pose[7 * k + c], pj7[c] = pose[7 * (k + 1) + c];
     for (int c = 0; c < 3; c++) sbi[c] = speed[3 * k + c], sbj[c] = speed[3 * (k + 1) + c];
     for (int c = 0; c < 6; c++) sbi[3 + c] = v.bias[6 * k + c], sbj[3 + c] = v.bias[6 * (k + 1) + c];
-    imu_eval_raw(v.gravity, v.preint + (size_t)k * kPreDoubles, pi7, sbi, pj7, sbj, res, want_lin ? v.Jraw + (size_t)k * 450 : nullptr);
+    imu_eval_raw(v.gravity, v.preint + (size_t)k * kPreintDoubles, pi7, sbi, pj7, sbj, res, want_lin ? v.Jraw + (size_t)k * 450 : nullptr);
     for (int a = 0; a < 15; a++) {
       double s = 0;
       for (int b = a; b < 15; b++) s += w.Ul[k * 225 + a * 15 + b] * res[b];
@@ -333,7 +334,7 @@ VIO_DEV void solve(const Ctx &cx, const View &v, Work<P> &w) {
   VIO_PARFOR(i, 7 * v.n) w.xp[i] = v.pose0[i];
   VIO_PARFOR(i, 3 * v.n) w.xs[i] = v.speed0[i];
   VIO_PARFOR(k, v.n - 1) {
-    if (!imu_sqrt_info(v.preint + (size_t)k * kPreDoubles + 17 + 225, w.Ul + k * 225, w.Jw + k * 270))
+    if (!imu_sqrt_info(v.preint + (size_t)k * kPreintDoubles + 17 + 225, w.Ul + k * 225, w.Jw + k * 270))
       for (int i = 0; i < 225; i++) w.Ul[k * 225 + i] = (i % 16 == 0) ? 1.0 : 0.0;
     for (int i = 0; i < 450; i++) v.Jraw[(size_t)k * 450 + i] = 0.0;
   }

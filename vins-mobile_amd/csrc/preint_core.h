@@ -9,7 +9,7 @@
 // the SIMT emulator against host::propagate).
 #pragma once
 
-#include "solver_core.h"
+#include "spmd.h"
 #include "vio_amd.h"
 
 namespace vio {

@@ -27,16 +27,9 @@
 #include <string.h>
 
 #include "solve_trace.h"
+#include "spmd.h"
 #include "vio_amd.h"
 #include "vio_math.h"
-
-#if defined(VIO_SIMT)
-#define SFM_DEV inline
-#define SFM_AS3
-#else
-#define SFM_DEV __device__ __forceinline__
-#define SFM_AS3 __attribute__((address_space(3)))
-#endif
 
 namespace vio {
 namespace sfm {
@@ -53,9 +46,6 @@ enum { OB_JC = 0, OB_JX = 12, OB_R = 18, OB_COST = 20, kObsRows = 21, OB_HS = 0,
 constexpr int kWalk = 8;  // observations of a frame's list an owner has in flight: their loads do not wait for one another
 // per-landmark state, SoA: field f of landmark p at pt[f * pts + p]
 enum { PT_X = 0 /* two sets of 3 */, PT_HPP = 6, PT_GP = 15, PT_EINV = 18, PT_SP = 27, PT_DG = 30, PT_Y = 33, kPointDoubles = 36 };
-
-typedef SFM_AS3 double *lds_d;
-typedef SFM_AS3 int *lds_i;
 
 // One launch: n problems padded to the launch's largest frame / landmark / observation counts.
 //   ints    [n][int_stride]: hdr[8] = F, l, np, nobs, nc | off_q[Fm] | off_t[Fm] | fr_start[Fm+1] | pt_start[Pm+1] |
@@ -103,17 +93,17 @@ VIO_HD View view_of(const Batch &B, int b) {
   return v;
 }
 
-// LDS of one workgroup. PP: where the landmark state lives (lds_d, or double * for the global slab).
+// LDS of one workgroup. PP: where the landmark state lives (ldsd, or double * for the global slab).
 template <class PP>
 struct Work {
-  lds_d S;                       // reduced camera matrix, lower triangle, row stride nc; its Cholesky factor below the diagonal
-  lds_d Ld, v, z, yc;            // the factor's diagonal; right-hand side / forward / backward work vectors: nc each
-  lds_d gc, sc, dg;              // camera gradient (unscaled), Jacobi scaling, LM diagonal
-  lds_d Hcc;                     // [F][6][6] diagonal camera blocks (unscaled; rotation columns 0-2, translation 3-5)
-  lds_d R;                       // [F][9] rotations of the pose set under evaluation
-  lds_d pose;                    // two pose sets of [4F | 3F]: iterate and candidate
-  lds_d red;                     // [3][kThreads] reductions
-  lds_i col_frame, col_li, flag; // frame and local column (0-5) of a camera column; flag[0]: every e-block factored
+  ldsd S;                       // reduced camera matrix, lower triangle, row stride nc; its Cholesky factor below the diagonal
+  ldsd Ld, v, z, yc;            // the factor's diagonal; right-hand side / forward / backward work vectors: nc each
+  ldsd gc, sc, dg;              // camera gradient (unscaled), Jacobi scaling, LM diagonal
+  ldsd Hcc;                     // [F][6][6] diagonal camera blocks (unscaled; rotation columns 0-2, translation 3-5)
+  ldsd R;                       // [F][9] rotations of the pose set under evaluation
+  ldsd pose;                    // two pose sets of [4F | 3F]: iterate and candidate
+  ldsd red;                     // [3][kThreads] reductions
+  ldsi col_frame, col_li, flag; // frame and local column (0-5) of a camera column; flag[0]: every e-block factored
   PP pt;
   int pts;
 };
@@ -131,34 +121,34 @@ VIO_HD size_t lds_bytes(int Fm, int lds_points) {
 VIO_HD bool points_fit_lds(int Fm, int Pm) { return lds_bytes(Fm, Pm) <= (size_t)kLdsBudget; }
 
 template <class PP>
-SFM_DEV void carve(int Fm, lds_d base, PP pt, int pts, Work<PP> *w) {
+VIO_DEV void carve(int Fm, ldsd base, PP pt, int pts, Work<PP> *w) {
   const int ncm = max_columns(Fm);
-  lds_d p = base;
+  ldsd p = base;
   w->S = p, p += (size_t)ncm * ncm;
   w->Ld = p, p += ncm, w->v = p, p += ncm, w->z = p, p += ncm, w->yc = p, p += ncm;
   w->gc = p, p += ncm, w->sc = p, p += ncm, w->dg = p, p += ncm;
   w->Hcc = p, p += 36 * Fm, w->R = p, p += 9 * Fm, w->pose = p, p += 14 * Fm, w->red = p, p += 3 * kThreads;
-  lds_d after = p;
+  ldsd after = p;
   if (pt == nullptr) pt = (PP)p, after = p + (size_t)kPointDoubles * pts;
   w->pt = pt, w->pts = pts;
-  lds_i q = (lds_i)after;
+  ldsi q = (ldsi)after;
   w->col_frame = q, q += ncm, w->col_li = q, q += ncm, w->flag = q;
 }
 
 struct OpSum {
-  SFM_DEV double operator()(double a, double b) const { return a + b; }
+  VIO_DEV double operator()(double a, double b) const { return a + b; }
 };
 struct OpMax {  // std::max(a, b): a NaN on the right is dropped
-  SFM_DEV double operator()(double a, double b) const { return a < b ? b : a; }
+  VIO_DEV double operator()(double a, double b) const { return a < b ? b : a; }
 };
 // v[0..N) over the workgroup, the same tree for every problem and every launch; every work-item gets the result.
 template <int N, class OP>
-SFM_DEV void block_reduce(int tid, lds_d red, double (&val)[N], OP op) {
+VIO_DEV void block_reduce(int tid, ldsd red, double (&val)[N], OP op) {
   for (int n = 0; n < N; n++) red[n * kThreads + tid] = val[n];
   __syncthreads();
   if (tid < 64)
     for (int n = 0; n < N; n++) {
-      lds_d r = red + n * kThreads + tid;
+      ldsd r = red + n * kThreads + tid;
       r[0] = op(op(op(r[0], r[64]), r[128]), r[192]);
     }
   __syncthreads();
@@ -171,7 +161,7 @@ SFM_DEV void block_reduce(int tid, lds_d red, double (&val)[N], OP op) {
 }
 
 // QuaternionParameterization::Plus on (w x y z) (vio_initial.cpp ba_quat_plus)
-SFM_DEV void quat_plus(const double q[4], const double d[3], double out[4]) {
+VIO_DEV void quat_plus(const double q[4], const double d[3], double out[4]) {
   const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
   if (nd > 0.0) {
     const double k = sin(nd) / nd;
@@ -183,17 +173,17 @@ SFM_DEV void quat_plus(const double q[4], const double d[3], double out[4]) {
 }
 
 // camera column of local column li (0-2 rotation, 3-5 translation) of frame f, -1 = constant
-SFM_DEV int column_of(const View &v, int f, int li) {
+VIO_DEV int column_of(const View &v, int f, int li) {
   const int o = li < 3 ? v.off_q[f] : v.off_t[f];
   return o < 0 ? -1 : o + (li < 3 ? li : li - 3);
 }
 
 // ba_evaluate: cost at pose / landmark set `s`; with jac, H_pp, g_p, H_cc and g_c of that set as well.
 template <class PP>
-SFM_DEV double evaluate(int tid, const View &v, const Work<PP> &w, int s, bool jac) {
+VIO_DEV double evaluate(int tid, const View &v, const Work<PP> &w, int s, bool jac) {
   const int F = v.F, np = v.np, nobs = v.nobs, P = w.pts;
   const size_t os = v.ostride;
-  lds_d pq = w.pose + s * 7 * F, ptr = pq + 4 * F;
+  ldsd pq = w.pose + s * 7 * F, ptr = pq + 4 * F;
   if (tid < F) {  // QuaternionRotatePoint normalizes its quaternion
     double R[9];
     qtoR(qnormalized(Quat{pq[4 * tid + 1], pq[4 * tid + 2], pq[4 * tid + 3], pq[4 * tid]}), R);
@@ -269,7 +259,7 @@ SFM_DEV double evaluate(int tid, const View &v, const Work<PP> &w, int s, bool j
 
 // |Plus(x, -g) - x|_inf (trust_region_minimizer.cc:270-284) at pose set s
 template <class PP>
-SFM_DEV double gradient_max(int tid, const View &v, const Work<PP> &w, int s) {
+VIO_DEV double gradient_max(int tid, const View &v, const Work<PP> &w, int s) {
   const int F = v.F, np = v.np, P = w.pts;
   double m[1] = {0.0};
   OpMax mx;
@@ -293,7 +283,7 @@ SFM_DEV double gradient_max(int tid, const View &v, const Work<PP> &w, int s) {
 
 // Hs = S_c J_c^T J_p S_p of every observation (the scaling is fixed after iteration 0, so once per accepted iterate)
 template <class PP>
-SFM_DEV void scaled_blocks(int tid, const View &v, const Work<PP> &w) {
+VIO_DEV void scaled_blocks(int tid, const View &v, const Work<PP> &w) {
   const size_t os = v.ostride;
   const int P = w.pts;
   for (int k = tid; k < v.nobs; k += kThreads) {
@@ -313,7 +303,7 @@ SFM_DEV void scaled_blocks(int tid, const View &v, const Work<PP> &w) {
 // ba_solve: (Hs + D^2) y = gs with D^2 = dg / radius. y: PT_Y of every landmark and w.yc. False where the host code's
 // returns false (an e-block or the reduced matrix not positive definite, a non-finite step).
 template <class PP>
-SFM_DEV bool linear_solve(int tid, const View &v, const Work<PP> &w, double radius, double *a_out, double *b_out) {
+VIO_DEV bool linear_solve(int tid, const View &v, const Work<PP> &w, double radius, double *a_out, double *b_out) {
   const int np = v.np, nc = v.nc, nobs = v.nobs, P = w.pts;
   const size_t os = v.ostride;
   // (the caller's barrier after the diagonal phase has passed; flag[0] == 1)
@@ -463,7 +453,7 @@ SFM_DEV bool linear_solve(int tid, const View &v, const Work<PP> &w, double radi
 
 // init::bundle_adjust for one problem.
 template <class PP>
-SFM_DEV void solve(int tid, const View &v, const Work<PP> &w) {
+VIO_DEV void solve(int tid, const View &v, const Work<PP> &w) {
   const int F = v.F, np = v.np, nc = v.nc, P = w.pts;
   for (int i = tid; i < 4 * F; i += kThreads) w.pose[i] = v.cq0[i];
   for (int i = tid; i < 3 * F; i += kThreads) w.pose[4 * F + i] = v.ct0[i];
@@ -528,8 +518,8 @@ SFM_DEV void solve(int tid, const View &v, const Work<PP> &w) {
     }
     if (tid < F) {
       const int i = tid;
-      lds_d q = w.pose + cur * 7 * F + 4 * i, qn = w.pose + cand * 7 * F + 4 * i;
-      lds_d t = w.pose + cur * 7 * F + 4 * F + 3 * i, tn = w.pose + cand * 7 * F + 4 * F + 3 * i;
+      ldsd q = w.pose + cur * 7 * F + 4 * i, qn = w.pose + cand * 7 * F + 4 * i;
+      ldsd t = w.pose + cur * 7 * F + 4 * F + 3 * i, tn = w.pose + cand * 7 * F + 4 * F + 3 * i;
       if (v.off_q[i] >= 0) {
         double d[3], q0[4], q1[4];
         for (int k = 0; k < 3; k++) d[k] = -w.yc[v.off_q[i] + k] * w.sc[v.off_q[i] + k];

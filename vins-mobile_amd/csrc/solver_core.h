@@ -6,8 +6,8 @@
 // sequences) is the grid.
 //
 // The code is written as barrier-separated parallel-for phases (VIO_PARFOR / VIO_SYNC). Under hipcc it is the
-// body of the gfx950 kernel in vio_backend.hip; with -DVIO_EMUL (tests only, never in the product library) the same
-// source runs with one "thread" on the host so that index maths and control flow can be debugged without a GPU.
+// body of the gfx950 kernel in vio_backend.hip; with -DVIO_SIMT (tests only, never in the product library) the same
+// source runs on the host, one fiber per work-item, so that index maths and control flow can be debugged without a GPU.
 //
 // Algorithm notes (what differs from the reference's *route*, not its result):
 //  * Ceres materialises a scaled Jacobian J_s = J diag(scale). Everything the minimizer needs is a function of
@@ -34,163 +34,19 @@
 #include "solve_trace.h"
 #include "vio_math.h"
 
-// Three builds of this file:
-//   hipcc (product)   the gfx950 kernel body;
-//   -DVIO_EMUL        tests only: ONE emulated thread, no barriers, scalar stand-ins for the wave-level sections;
-//   -DVIO_SIMT        tests only: the DEVICE sections themselves on the host, every work-item a fiber and every
-//                     wave-level instruction (v_mfma, v_readlane, DPP, ballot, s_barrier) evaluated with the hardware's
-//                     lane semantics by tests/emul/simt.h (included by the test harness before this file).
-#if defined(VIO_EMUL) || defined(VIO_SIMT)
-#define VIO_HOST_BUILD 1
-#endif
-#ifdef VIO_HOST_BUILD
-#define VIO_DEV inline
-#define VIO_ATOMIC_ADD(p, v) ::vio::atomic_add((p), (v))
-#else
-#define VIO_DEV __device__ __forceinline__
-#define VIO_ATOMIC_ADD(p, v) ::vio::atomic_add((p), (v))
-#endif
-#if defined(VIO_EMUL)
-#define VIO_SYNC() ((void)0)
-#define VIO_SYNC_LDS() ((void)0)
-#elif defined(VIO_SIMT)
-#define VIO_SYNC() __syncthreads()
-#define VIO_SYNC_LDS() __syncthreads()
-#else
-#define VIO_SYNC() __syncthreads()
-// Workgroup barrier that only orders LDS traffic: __syncthreads() waits for every outstanding memory operation of the
-// wave (s_waitcnt vmcnt(0)), which puts an L2 round trip behind each barrier a global prefetch is meant to cross.
-// ONLY where the waves exchange nothing through global memory across the barrier.
-#define VIO_SYNC_LDS()                                                      \
-  do {                                                                      \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");         \
-    __builtin_amdgcn_s_barrier();                                           \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");         \
-  } while (0)
-#endif
-// The thread index every phase starts from passes through an empty asm: LLVM otherwise hoists the per-lane address
-// arithmetic of ALL phases out of the trust-region loop (loop-invariant), keeps hundreds of values alive across the whole
-// kernel and spills them to scratch -- a scratch_load (L2 latency) where two integer instructions would do.
-#ifdef VIO_HOST_BUILD
-#define VIO_TID(cx) ((int)(cx).tid)
-#else
-// (round 6: the index is REBUILT where it is asked for -- lane count of the wave + the wave's first index from a scalar register, two
-// vector instructions -- instead of passing the kernel's v0 through the empty asm: the register allocator kept that one value in
-// scratch and every phase began with a scratch_load of it, 111 of them in the W = 10 variant)
-#define VIO_TID(cx) ::vio::hw_tid((cx).wave64)
-#endif
-#define VIO_PARFOR(i, n) for (int i = VIO_TID(cx); i < (int)(n); i += (int)cx.nt)
-// The same for any per-lane value inside a loop: per-lane addresses that do not depend on the loop counter (the 60 tile
-// offsets of a panel step, say) are otherwise computed once, kept alive around the loop and come back as scratch loads.
-#ifdef VIO_HOST_BUILD
-#define VIO_OPAQUE(x) (x)
-#else
-#define VIO_OPAQUE(x) ::vio::opaque_tid(x)
-#endif
-
-// LDS pointers carry their address space in the type: generic pointers make hipcc emit flat_load/flat_store for every
-// LDS access (no ds_read/ds_write at all in the first version of this kernel), which is several times slower.
-#ifdef VIO_HOST_BUILD
-#define VIO_AS3
-#else
-#define VIO_AS3 __attribute__((address_space(3)))
-#endif
+// Two builds of this file: hipcc (product) and -DVIO_SIMT (tests only); spmd.h says what each build mode means, and the
+// third, one-thread mode ends below this file. Layers under it: spmd.h (the SPMD vocabulary: macros, LDS pointer types,
+// Ctx, block reductions), factors.h (the factor evaluations), mfma_tiles.h (wave-level tiles on the matrix cores).
+#include "spmd.h"
+#include "factors.h"
+#include "mfma_tiles.h"
 
 namespace vio {
 
-#ifndef VIO_HOST_BUILD
-__device__ __forceinline__ int opaque_tid(int t) {
-  asm volatile("" : "+v"(t));
-  return t;
-}
-__device__ __forceinline__ int hw_tid(int wave64) {
-  int t;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, %1\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(t) : "s"(wave64));
-  return t;
-}
-#endif
-
-typedef VIO_AS3 double *ldsd;
-typedef const VIO_AS3 double *cldsd;
-typedef VIO_AS3 int *ldsi;
-
-#ifdef VIO_HOST_BUILD
-inline void atomic_add(double *p, double v) { *p += v; }
-inline void atomic_add_noret(double *p, double v) { *p += v; }
-#else
-// Global memory that several workgroups of ONE window may add to (cooperative windows): device scope. No return value: the
-// instruction is fire-and-forget (global_atomic_add_f64 at the L2).
-__device__ __forceinline__ void atomic_add_noret(double *p, double v) {
-  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void atomic_add(ldsd p, double v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void atomic_add(double *p, double v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // only this workgroup touches its scratch
-}
-#endif
-
 constexpr int kBS = 15;          // unknowns per frame in the pose-side vectors: pose 6 + speed-bias 9 (frame-major)
-constexpr int kSB = 9;           // speed-bias block
 constexpr int kSS = kSB * kSB;   // 81
 constexpr int kAW = 18;          // pose columns an IMU chain couples a speed-bias block to: frames k-1, k, k+1
 constexpr int kAS = kSB * kAW;   // 162
-constexpr int kPreintDoubles = 467;
-
-// Per-stage cycle counters (the kernel-side counterpart of the reference's TS/TE timers, global_param.hpp:85-92).
-enum Stage {
-  ST_SETUP_IMU = 0, ST_SETUP_PRIOR, ST_EVAL_PRIOR, ST_EVAL_IMU, ST_EVAL_PROJ, ST_SCALE, ST_SCHUR, ST_RHS, ST_CHOL,
-  ST_TRISOLVE, ST_QUADFORM, ST_DOGLEG, ST_COST_EVAL, ST_NEW2OLD, ST_MARG_BUILD, ST_MARG_CHOL, ST_TOTAL,
-  // finer attribution (sub-stages; their cycles are NOT included in the stages above)
-  ST_P_ZERO, ST_P_FACT, ST_P_GRAM, ST_P_FEAT,      // projection factors: zeroing, evaluation+staging, Gram, per-feature
-  ST_C_POTRF, ST_C_TRSM,                           // Cholesky: first diagonal block, panel
-  ST_IMU_RAW,                                      // raw IMU residual/Jacobian (one thread per factor)
-  ST_C_WAIT, ST_Q_W, ST_BACKSOLVE, ST_C_AHEAD,     // trailing-update wait, W part of quad_form, back-substitution, wave-0 look-ahead
-  ST_TR_VEC,                                       // trust-region vector phase before the linear solve
-  ST_M_PRIOR, ST_M_IMU, ST_M_FACT, ST_M_GRAM,      // marginalization: prior/setup, IMU factor, factor staging, Gram
-  ST_D0, ST_D1, ST_D2, ST_D3, ST_D4, ST_D5,         // free slots for timing experiments (VIO_AMD_PROF_TID picks the clock's lane)
-  // round 6: the O(n) vector phases of a trust-region iteration, one slot per barrier interval
-  ST_V_GD,                                         // |g_d|^2, Cauchy direction, quad_form vectors (one pass + reduction)
-  ST_V_DOT, ST_V_STEP,                             // dogleg: the two inner products (+ reduction); step -> t2 / tf (+ barrier)
-  ST_V_PLUS,                                       // Plus in place, stash of the iterate, norms (+ reduction)
-  ST_V_GMAX,                                       // gradient max norm + the iteration record
-  ST_V_REST,                                       // restore after a rejected step
-  ST_B_INIT, ST_B_POSE, ST_B_ASP, ST_B_BAND, ST_B_GN,  // backsolve: copies; pose tiles; A_sp z_p; band chains (+ landmarks); GN step
-  ST_E_HEAD, ST_E_COPY, ST_E_H0DX, ST_E_TAIL,      // evaluate(jac): rotations + zeroing; AppPr + PP copy (+ raw IMU); H0 dx + diagonal blocks; diag / scaling tail
-  ST_X0, ST_X1, ST_X2, ST_X3,
-  ST_COUNT = 64                                    // (last slot = time of the previous stamp)
-};
-
-struct Ctx {
-  int tid, nt;
-  int wave64 = 0;     // index of the wave's first work-item (device: a scalar register, VIO_TID builds the index from it)
-  ldsd red;           // LDS scratch for block reductions: two halves of [3 nt/64]
-  mutable int red_phase = 0;  // which half the next reduction writes (uniform across the block)
-  long long *prof;    // global [ST_COUNT] cycle accumulators of this window, or null; prof[ST_COUNT-1] = last stamp
-  int wrot = 0;       // rotation of the wave ROLES in the serial phases: role = (wave + wrot) mod waves, role 0 runs the pivot
-                      // chains. Two workgroups share a CU and the hardware puts wave w of both on the same SIMD: with the
-                      // same roles the two chains would fight over one SIMD's matrix pipe while three stand idle.
-  int prof_tid = 0;   // the work-item that keeps the stage clock (0; another wave's first lane to time what wave 0 does not run)
-  VIO_AS3 long long *lprof;  // the same counters while the kernel runs (LDS); copied to prof at the end
-  // cooperative windows (round 5): `coop` workgroups serve one window; member 0 owns the solve, the others wait for commands
-  int coop = 1, member = 0;
-  unsigned coop_spin = 1u << 24;  // polls before a wait between the workgroups of a window gives up (BatchPtrs::coop_spin)
-  mutable unsigned coop_seq = 0;  // commands issued (owner) / served (helper) so far: the same value in every work-item
-};
-
-// Charges the cycles since the previous stamp to `stage` (thread 0 only; call between barriers).
-VIO_DEV void stamp(const Ctx &cx, int stage) {
-#if !defined(VIO_EMUL)
-  if (cx.prof && cx.tid == cx.prof_tid) {  // accumulators live in LDS (a global read-modify-write per stamp costs ~3k cycles)
-    long long t = clock64();
-    cx.lprof[stage] += t - cx.lprof[ST_COUNT - 1];
-    cx.lprof[ST_COUNT - 1] = t;
-  }
-#else
-  (void)cx, (void)stage;
-#endif
-}
 
 // Per-window view of the packed batch (all pointers device-global unless noted).
 struct WinView {
@@ -440,109 +296,13 @@ VIO_DEV void coop_done(const Ctx &cx, const WinView &v) {
 }
 #endif
 
-// ---- block reductions: every thread receives the same value ------------------------------------------------------
-// Wave level on the DPP network (row_shr 1/2/4/8, row_bcast 15/31; total in lane 63, broadcast through SGPRs), block
-// level through cx.red. Two alternating halves of cx.red make ONE barrier per reduction enough: a half is rewritten
-// two calls later, and the barrier of the call in between orders that against its last readers.
-#ifndef VIO_EMUL
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_move_f64(double v) {
-  int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROWMASK, 0xf, false);
-  int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROWMASK, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  v += dpp_move_f64<0x111, 0xf>(v);
-  v += dpp_move_f64<0x112, 0xf>(v);
-  v += dpp_move_f64<0x114, 0xf>(v);
-  v += dpp_move_f64<0x118, 0xf>(v);
-  v += dpp_move_f64<0x142, 0xa>(v);
-  v += dpp_move_f64<0x143, 0xc>(v);
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-__device__ __forceinline__ double wave_max_f64(double v) {  // operands >= 0 (norms, flags): a shifted-in 0 is neutral
-  v = fmax(v, dpp_move_f64<0x111, 0xf>(v));
-  v = fmax(v, dpp_move_f64<0x112, 0xf>(v));
-  v = fmax(v, dpp_move_f64<0x114, 0xf>(v));
-  v = fmax(v, dpp_move_f64<0x118, 0xf>(v));
-  v = fmax(v, dpp_move_f64<0x142, 0xa>(v));
-  v = fmax(v, dpp_move_f64<0x143, 0xc>(v));
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-#endif
-VIO_DEV double block_sum(const Ctx &cx, double v) {
-#ifdef VIO_EMUL
-  return v;
-#else
-  const int nw = cx.nt >> 6;
-  ldsd red = cx.red + (cx.red_phase ^= 1) * 3 * nw;
-  v = wave_sum_f64(v);
-  if ((cx.tid & 63) == 0) red[cx.tid >> 6] = v;
-  VIO_SYNC();
-  double s = 0;
-  for (int w = 0; w < nw; w++) s += red[w];
-  return s;
-#endif
-}
-// Three sums with one barrier.
-VIO_DEV void block_sum3(const Ctx &cx, double &a, double &b, double &c) {
-#ifndef VIO_EMUL
-  const int nw = cx.nt >> 6;
-  ldsd red = cx.red + (cx.red_phase ^= 1) * 3 * nw;
-  a = wave_sum_f64(a), b = wave_sum_f64(b), c = wave_sum_f64(c);
-  if ((cx.tid & 63) == 0) red[cx.tid >> 6] = a, red[nw + (cx.tid >> 6)] = b, red[2 * nw + (cx.tid >> 6)] = c;
-  VIO_SYNC();
-  a = b = c = 0;
-  for (int w = 0; w < nw; w++) a += red[w], b += red[nw + w], c += red[2 * nw + w];
-#else
-  (void)cx, (void)a, (void)b, (void)c;
-#endif
-}
-// Maximum of non-negative values.
-VIO_DEV double block_max(const Ctx &cx, double v) {
-#ifdef VIO_EMUL
-  return v;
-#else
-  const int nw = cx.nt >> 6;
-  ldsd red = cx.red + (cx.red_phase ^= 1) * 3 * nw;
-  v = wave_max_f64(v);
-  if ((cx.tid & 63) == 0) red[cx.tid >> 6] = v;
-  VIO_SYNC();
-  double s = red[0];
-  for (int w = 1; w < nw; w++) s = fmax(s, red[w]);
-  return s;
-#endif
-}
-
-// Issue priority of the wave that walks a serial chain (pivots, band substitutions): with two windows per CU its SIMD is shared
-// with a wave of the other window, and every cycle that wave wins the issue slot is a cycle on this window's critical path.
-#if defined(VIO_HOST_BUILD)
-#define VIO_PRIO(n) ((void)0)
-#else
-#define VIO_PRIO(n) __builtin_amdgcn_s_setprio(n)
-#endif
-// A flag in LDS that one wave posts and others poll (factor_band_regs)
-#if defined(VIO_HOST_BUILD)
-#define VIO_FLAG_STORE(p, x) (*(volatile int *)(p) = (x))
-#define VIO_FLAG_LOAD(p) (*(volatile int *)(p))
-#else
-#define VIO_FLAG_STORE(p, x) __hip_atomic_store((p), (x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define VIO_FLAG_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#endif
-#if defined(VIO_HOST_BUILD)
-#define VIO_SCHED_FENCE() ((void)0)
-#else
-#define VIO_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 // W lives in global memory (L2): a dependent load costs ~3k cycles here, so the mat-vecs with W fetch a whole strip
 // (up to kWStrip entries, predicated) before the first multiply. Strided form: column f of WT (stride Fpad).
 constexpr int kWStrip = 24;
 VIO_DEV void wt_strip_load(const double *p, size_t stride, int n, double x[kWStrip]) {
 #pragma unroll
   for (int j = 0; j < kWStrip; j++) x[j] = p[(size_t)(j < n ? j : 0) * stride];
-#ifndef VIO_EMUL
   __builtin_amdgcn_sched_barrier(0);
-#endif
 }
 // Splits n6 rows over the threads available per feature: (feature, part) items, <= kWStrip rows per part.
 VIO_DEV void wt_parts(int nt, int F, int n6, int &nparts, int &per) {
@@ -577,292 +337,15 @@ VIO_DEV void dense_matvec_cols(const Ctx &cx, const double *M, int n, XP x, ADD 
   }
 }
 
-// ProjectionFactor::Evaluate (projection_facor.cpp:16-99) in local coordinates. Jex optional.
-template <class PA, class PE>
-VIO_DEV void projection_eval(double s_info, PA pose_i, PA pose_j, PE ex, double inv_dep, const double *pts_i,
-                             const double *pts_j, bool jac, double *r, double *Ji, double *Jj, double *Jex, double *Jl) {
-  Quat Qi{pose_i[3], pose_i[4], pose_i[5], pose_i[6]}, Qj{pose_j[3], pose_j[4], pose_j[5], pose_j[6]},
-      qic{ex[3], ex[4], ex[5], ex[6]};
-  double pc_i[3] = {pts_i[0] / inv_dep, pts_i[1] / inv_dep, pts_i[2] / inv_dep};
-  double t[3], p_imu_i[3], p_w[3], p_imu_j[3], p_c_j[3];
-  qrot(qic, pc_i, t);
-  for (int k = 0; k < 3; k++) p_imu_i[k] = t[k] + ex[k];
-  qrot(Qi, p_imu_i, t);
-  for (int k = 0; k < 3; k++) p_w[k] = t[k] + pose_i[k];
-  double d[3] = {p_w[0] - pose_j[0], p_w[1] - pose_j[1], p_w[2] - pose_j[2]};
-  qrot(qinv(Qj), d, p_imu_j);
-  double e[3] = {p_imu_j[0] - ex[0], p_imu_j[1] - ex[1], p_imu_j[2] - ex[2]};
-  qrot(qinv(qic), e, p_c_j);
-  double dep_j = p_c_j[2];
-  r[0] = s_info * (p_c_j[0] / dep_j - pts_j[0]);
-  r[1] = s_info * (p_c_j[1] / dep_j - pts_j[1]);
-  if (!jac) return;
-  double Ri[9], Rj[9], ric[9], ricT[9], RjT[9];
-  qtoR(Qi, Ri), qtoR(Qj, Rj), qtoR(qic, ric);
-  mat3T(ric, ricT), mat3T(Rj, RjT);
-  double red[6] = {s_info * (1. / dep_j), 0, s_info * (-p_c_j[0] / (dep_j * dep_j)),
-                   0, s_info * (1. / dep_j), s_info * (-p_c_j[1] / (dep_j * dep_j))};
-  double A[9], B[9], S[9], T9[9];
-  mat3mul(ricT, RjT, A);
-  mat3mul(A, Ri, B);
-  skew3(p_imu_i, S);
-  mat3mul(B, S, T9);
-  for (int i = 0; i < 2; i++)
-    for (int j = 0; j < 3; j++) {
-      Ji[i * 6 + j] = red[i * 3] * A[j] + red[i * 3 + 1] * A[3 + j] + red[i * 3 + 2] * A[6 + j];
-      Ji[i * 6 + 3 + j] = -(red[i * 3] * T9[j] + red[i * 3 + 1] * T9[3 + j] + red[i * 3 + 2] * T9[6 + j]);
-    }
-  skew3(p_imu_j, S);
-  mat3mul(ricT, S, T9);
-  for (int i = 0; i < 2; i++)
-    for (int j = 0; j < 3; j++) {
-      Jj[i * 6 + j] = -(red[i * 3] * A[j] + red[i * 3 + 1] * A[3 + j] + red[i * 3 + 2] * A[6 + j]);
-      Jj[i * 6 + 3 + j] = red[i * 3] * T9[j] + red[i * 3 + 1] * T9[3 + j] + red[i * 3 + 2] * T9[6 + j];
-    }
-  double Bric[9], v3[3];
-  mat3mul(B, ric, Bric);
-  if (Jex) {  // projection_facor.cpp:76-86 (the extrinsic is a kept block of the marginalization prior)
-    double RjTRi[9], M1[9], C1[9], Spc[9], T1[9], v[3], Sv[9], u[3], w3[3], Sw[9];
-    mat3mul(RjT, Ri, RjTRi);
-    for (int i = 0; i < 9; i++) M1[i] = RjTRi[i] - (i % 4 == 0);
-    mat3mul(ricT, M1, C1);
-    skew3(pc_i, Spc);
-    mat3mul(Bric, Spc, T1);
-    mat3vec(Bric, pc_i, v);
-    skew3(v, Sv);
-    double exv[3] = {ex[0], ex[1], ex[2]};
-    mat3vec(Ri, exv, u);
-    for (int k = 0; k < 3; k++) u[k] += pose_i[k] - pose_j[k];
-    mat3vec(RjT, u, w3);
-    for (int k = 0; k < 3; k++) w3[k] -= ex[k];
-    mat3vec(ricT, w3, u);
-    skew3(u, Sw);
-    for (int i = 0; i < 2; i++)
-      for (int j = 0; j < 3; j++) {
-        Jex[i * 6 + j] = red[i * 3] * C1[j] + red[i * 3 + 1] * C1[3 + j] + red[i * 3 + 2] * C1[6 + j];
-        double c0 = -T1[j] + Sv[j] + Sw[j], c1 = -T1[3 + j] + Sv[3 + j] + Sw[3 + j],
-               c2 = -T1[6 + j] + Sv[6 + j] + Sw[6 + j];
-        Jex[i * 6 + 3 + j] = red[i * 3] * c0 + red[i * 3 + 1] * c1 + red[i * 3 + 2] * c2;
-      }
-  }
-  mat3vec(Bric, pts_i, v3);
-  for (int i = 0; i < 2; i++)
-    Jl[i] = (red[i * 3] * v3[0] + red[i * 3 + 1] * v3[1] + red[i * 3 + 2] * v3[2]) * -1.0 / (inv_dep * inv_dep);
-}
-
-// The same factor from rotation MATRICES prepared once per evaluation (w.rot: one per frame, then r_ic), for the
-// solver's inner loops: four mat-vecs for the residual and, with jac, (reduce A) chained through R_i and r_ic instead
-// of five dense 3x3 products. Equal to projection_eval up to rounding (different association of the same products).
-template <class PR, class PA, class PE>
-VIO_DEV void projection_eval_rot(double s_info, PR Ri_, PA pose_i, PR Rj_, PA pose_j, PR ric_, PE ex, double inv_dep,
-                                 const double *pts_i, const double *pts_j, bool jac, double *r, double *Ji, double *Jj,
-                                 double *Jl) {
-  double Ri[9], Rj[9], ric[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) Ri[k] = Ri_[k], Rj[k] = Rj_[k], ric[k] = ric_[k];
-  const double tic[3] = {ex[0], ex[1], ex[2]};
-  const double pi3[3] = {pts_i[0], pts_i[1], pts_i[2]};
-  const double dep_i = rcp_f(inv_dep);
-  const double pc_i[3] = {pi3[0] * dep_i, pi3[1] * dep_i, pi3[2] * dep_i};
-  double p_imu_i[3], p_w[3], p_imu_j[3], p_c_j[3], d[3], e[3];
-  for (int a = 0; a < 3; a++) p_imu_i[a] = ric[3 * a] * pc_i[0] + ric[3 * a + 1] * pc_i[1] + ric[3 * a + 2] * pc_i[2] + tic[a];
-  for (int a = 0; a < 3; a++) p_w[a] = Ri[3 * a] * p_imu_i[0] + Ri[3 * a + 1] * p_imu_i[1] + Ri[3 * a + 2] * p_imu_i[2] + pose_i[a];
-  for (int a = 0; a < 3; a++) d[a] = p_w[a] - pose_j[a];
-  for (int a = 0; a < 3; a++) p_imu_j[a] = Rj[a] * d[0] + Rj[3 + a] * d[1] + Rj[6 + a] * d[2];  // R_j^T d
-  for (int a = 0; a < 3; a++) e[a] = p_imu_j[a] - tic[a];
-  for (int a = 0; a < 3; a++) p_c_j[a] = ric[a] * e[0] + ric[3 + a] * e[1] + ric[6 + a] * e[2];  // r_ic^T e
-  const double idep_j = rcp_f(p_c_j[2]);
-  r[0] = s_info * (p_c_j[0] * idep_j - pts_j[0]);
-  r[1] = s_info * (p_c_j[1] * idep_j - pts_j[1]);
-  if (!jac) return;
-  // reduce (2x3, projection_facor.cpp:46-50) has the sparsity [s/z 0 -s x/z^2 ; 0 s/z -s y/z^2]
-  const double rz = s_info * idep_j, rx = -(rz * p_c_j[0]) * idep_j, ry = -(rz * p_c_j[1]) * idep_j;
-  double A[9];  // r_ic^T R_j^T
-  for (int a = 0; a < 3; a++)
-    for (int b = 0; b < 3; b++) A[3 * a + b] = ric[a] * Rj[3 * b] + ric[3 + a] * Rj[3 * b + 1] + ric[6 + a] * Rj[3 * b + 2];
-  double RA[6], RB[6], RC[6], RT[6];
-  for (int b = 0; b < 3; b++) RA[b] = rz * A[b] + rx * A[6 + b], RA[3 + b] = rz * A[3 + b] + ry * A[6 + b];  // reduce A
-  for (int i = 0; i < 2; i++)
-    for (int b = 0; b < 3; b++) {
-      RB[3 * i + b] = RA[3 * i] * Ri[b] + RA[3 * i + 1] * Ri[3 + b] + RA[3 * i + 2] * Ri[6 + b];        // reduce A R_i
-      RT[3 * i + b] = (i == 0 ? rz * ric[3 * b] : rz * ric[3 * b + 1]) + (i == 0 ? rx : ry) * ric[3 * b + 2];  // reduce r_ic^T
-    }
-  for (int i = 0; i < 2; i++)
-    for (int b = 0; b < 3; b++)
-      RC[3 * i + b] = RB[3 * i] * ric[b] + RB[3 * i + 1] * ric[3 + b] + RB[3 * i + 2] * ric[6 + b];     // reduce A R_i r_ic
-  for (int i = 0; i < 2; i++) {
-    const double *u = RB + 3 * i, *t = RT + 3 * i;
-    // u skew(p) = (u1 p2 - u2 p1, u2 p0 - u0 p2, u0 p1 - u1 p0)
-    Ji[i * 6 + 0] = RA[3 * i], Ji[i * 6 + 1] = RA[3 * i + 1], Ji[i * 6 + 2] = RA[3 * i + 2];
-    Ji[i * 6 + 3] = -(u[1] * p_imu_i[2] - u[2] * p_imu_i[1]);
-    Ji[i * 6 + 4] = -(u[2] * p_imu_i[0] - u[0] * p_imu_i[2]);
-    Ji[i * 6 + 5] = -(u[0] * p_imu_i[1] - u[1] * p_imu_i[0]);
-    Jj[i * 6 + 0] = -RA[3 * i], Jj[i * 6 + 1] = -RA[3 * i + 1], Jj[i * 6 + 2] = -RA[3 * i + 2];
-    Jj[i * 6 + 3] = t[1] * p_imu_j[2] - t[2] * p_imu_j[1];
-    Jj[i * 6 + 4] = t[2] * p_imu_j[0] - t[0] * p_imu_j[2];
-    Jj[i * 6 + 5] = t[0] * p_imu_j[1] - t[1] * p_imu_j[0];
-    Jl[i] = -(RC[3 * i] * pi3[0] + RC[3 * i + 1] * pi3[1] + RC[3 * i + 2] * pi3[2]) * (dep_i * dep_i);
-  }
-}
-
-// Raw (un-whitened) IMU residual and, if Jraw != NULL, the dense 15x30 Jacobian [pose_i 6 | sb_i 9 | pose_j 6 | sb_j 9]
-// (imu_factor.h:68-180 before the sqrt_info multiplication; integration_base.h:171-198).
-template <class PA>
-VIO_DEV void imu_eval_raw(double gravity, const double *pre, PA pose_i, PA sb_i, PA pose_j, PA sb_j, double *res,
-                          double *Jraw) {
-  const double sum_dt = pre[0];
-  const double *delta_p = pre + 1, *delta_q = pre + 4, *delta_v = pre + 8, *lin_ba = pre + 11, *lin_bg = pre + 14;
-  const double *J = pre + 17;
-  PA Pi = pose_i, Pj = pose_j, Vi = sb_i, Bai = sb_i + 3, Bgi = sb_i + 6, Vj = sb_j, Baj = sb_j + 3, Bgj = sb_j + 6;
-  Quat Qi{pose_i[3], pose_i[4], pose_i[5], pose_i[6]}, Qj{pose_j[3], pose_j[4], pose_j[5], pose_j[6]};
-  Quat dq{delta_q[0], delta_q[1], delta_q[2], delta_q[3]};
-  double dp_dba[9], dp_dbg[9], dq_dbg[9], dv_dba[9], dv_dbg[9];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      dp_dba[i * 3 + j] = J[(0 + i) * 15 + 9 + j];
-      dp_dbg[i * 3 + j] = J[(0 + i) * 15 + 12 + j];
-      dq_dbg[i * 3 + j] = J[(3 + i) * 15 + 12 + j];
-      dv_dba[i * 3 + j] = J[(6 + i) * 15 + 9 + j];
-      dv_dbg[i * 3 + j] = J[(6 + i) * 15 + 12 + j];
-    }
-  double dba[3], dbg[3], th[3], t1[3], t2[3], cdv[3], cdp[3];
-  for (int k = 0; k < 3; k++) dba[k] = Bai[k] - lin_ba[k], dbg[k] = Bgi[k] - lin_bg[k];
-  mat3vec(dq_dbg, dbg, th);
-  Quat cdq = qmul(dq, Quat{th[0] / 2.0, th[1] / 2.0, th[2] / 2.0, 1.0});
-  mat3vec(dv_dba, dba, t1), mat3vec(dv_dbg, dbg, t2);
-  for (int k = 0; k < 3; k++) cdv[k] = delta_v[k] + t1[k] + t2[k];
-  mat3vec(dp_dba, dba, t1), mat3vec(dp_dbg, dbg, t2);
-  for (int k = 0; k < 3; k++) cdp[k] = delta_p[k] + t1[k] + t2[k];
-  const double T = sum_dt;
-  const double G[3] = {0, 0, gravity};
-  Quat Qi_inv = qinv(Qi);
-  double a[3], b[3], ra[3], rb[3];
-  for (int k = 0; k < 3; k++) {
-    a[k] = 0.5 * G[k] * T * T + Pj[k] - Pi[k] - Vi[k] * T;
-    b[k] = G[k] * T + Vj[k] - Vi[k];
-  }
-  qrot(Qi_inv, a, ra), qrot(Qi_inv, b, rb);
-  Quat qr = qmul(qinv(cdq), qmul(Qi_inv, Qj));
-  for (int k = 0; k < 3; k++) {
-    res[0 + k] = ra[k] - cdp[k];
-    res[6 + k] = rb[k] - cdv[k];
-    res[9 + k] = Baj[k] - Bai[k];
-    res[12 + k] = Bgj[k] - Bgi[k];
-  }
-  res[3] = 2 * qr.x, res[4] = 2 * qr.y, res[5] = 2 * qr.z;
-  if (!Jraw) return;
-  // Jraw was zeroed once per solve (setup_imu_info); every evaluation overwrites the same non-zero 3x3 blocks
-  double Rinv[9], M[9], S[9], Mq[9];
-  qtoR(Qi_inv, Rinv);
-  // columns: pose_i [0,6), sb_i [6,15), pose_j [15,21), sb_j [21,30)
-  const int ld = 30, cpi = 0, csi = 6, cpj = 15, csj = 21;
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) Jraw[(0 + i) * ld + cpi + j] = -Rinv[i * 3 + j];
-  skew3(ra, S);
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) Jraw[(0 + i) * ld + cpi + 3 + j] = S[i * 3 + j];
-  qleft_qright33(qmul(qinv(Qj), Qi), cdq, M);
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) Jraw[(3 + i) * ld + cpi + 3 + j] = -M[i * 3 + j];
-  skew3(rb, S);
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) Jraw[(6 + i) * ld + cpi + 3 + j] = S[i * 3 + j];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      Jraw[(0 + i) * ld + csi + 0 + j] = -Rinv[i * 3 + j] * T;
-      Jraw[(0 + i) * ld + csi + 3 + j] = -dp_dba[i * 3 + j];
-      Jraw[(0 + i) * ld + csi + 6 + j] = -dp_dbg[i * 3 + j];
-      Jraw[(6 + i) * ld + csi + 0 + j] = -Rinv[i * 3 + j];
-      Jraw[(6 + i) * ld + csi + 3 + j] = -dv_dba[i * 3 + j];
-      Jraw[(6 + i) * ld + csi + 6 + j] = -dv_dbg[i * 3 + j];
-      Jraw[(9 + i) * ld + csi + 3 + j] = -(double)(i == j);
-      Jraw[(12 + i) * ld + csi + 6 + j] = -(double)(i == j);
-    }
-  qleft33(qmul(qmul(qinv(Qj), Qi), cdq), M);
-  mat3mul(M, dq_dbg, Mq);
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) Jraw[(3 + i) * ld + csi + 6 + j] = -Mq[i * 3 + j];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) Jraw[(0 + i) * ld + cpj + j] = Rinv[i * 3 + j];
-  qleft33(qmul(qmul(qinv(cdq), Qi_inv), Qj), M);
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) Jraw[(3 + i) * ld + cpj + 3 + j] = M[i * 3 + j];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      Jraw[(6 + i) * ld + csj + 0 + j] = Rinv[i * 3 + j];
-      Jraw[(9 + i) * ld + csj + 3 + j] = (double)(i == j);
-      Jraw[(12 + i) * ld + csj + 6 + j] = (double)(i == j);
-    }
-}
-
-// dx of one prior block (marginalization_factor.cpp:349-367)
-template <class PX, class PD>
-VIO_DEV void prior_block_dx(int gsize, PX x, const double *x0, PD dx) {
-  if (gsize != 7) {
-    for (int k = 0; k < gsize; k++) dx[k] = x[k] - x0[k];
-    return;
-  }
-  for (int k = 0; k < 3; k++) dx[k] = x[k] - x0[k];
-  Quat q = qmul(qinv(qfrom_pose(x0)), Quat{x[3], x[4], x[5], x[6]});
-  double sgn = (q.w >= 0) ? 1.0 : -1.0;
-  dx[3] = sgn * 2.0 * q.x, dx[4] = sgn * 2.0 * q.y, dx[5] = sgn * 2.0 * q.z;
-}
-
 // =====================================================================================================
 // One-off setup per solve
 // =====================================================================================================
 
 // cov^-1 for every IMU factor: Gauss-Jordan with partial pivoting on [cov | I] (the same elimination order as the
 // CPU restatement, so the two agree bit for bit), then the lower triangle is mirrored (Eigen's LLT only reads it).
-#ifdef VIO_EMUL
-template <class MP>
-VIO_DEV void setup_imu_info(const Ctx &cx, const WinView &v, MP) {
-  const int W = v.W;
-  VIO_PARFOR(q, W * 450) {
-    int f = q / 450, e = q % 450, r = e / 30, c = e % 30;
-    v.imu_aug[q] = c < 15 ? v.preint[f * kPreintDoubles + 242 + r * 15 + c] : (double)(c - 15 == r);
-  }
-  VIO_SYNC();
-  for (int c = 0; c < 15; c++) {
-    // pivot search + row swap: one thread per factor (15 compares), then normalisation and elimination in parallel
-    VIO_PARFOR(f, W) {
-      double *A = v.imu_aug + f * 450;
-      int piv = c;
-      for (int r = c + 1; r < 15; r++)
-        if (fabs(A[r * 30 + c]) > fabs(A[piv * 30 + c])) piv = r;
-      if (piv != c)
-        for (int j = 0; j < 30; j++) {
-          double t = A[c * 30 + j];
-          A[c * 30 + j] = A[piv * 30 + j];
-          A[piv * 30 + j] = t;
-        }
-      double d = A[c * 30 + c];
-      for (int j = 0; j < 30; j++) A[c * 30 + j] /= d;
-      // stash the multipliers of this column (they are overwritten during elimination)
-      for (int r = 0; r < 15; r++) v.imu_Mr[f * 15 + r] = A[r * 30 + c];
-    }
-    VIO_SYNC();
-    VIO_PARFOR(q, W * 450) {
-      int f = q / 450, e = q % 450, r = e / 30, j = e % 30;
-      if (r != c) {
-        double fac = v.imu_Mr[f * 15 + r];
-        if (fac != 0.0) v.imu_aug[q] -= fac * v.imu_aug[f * 450 + c * 30 + j];
-      }
-    }
-    VIO_SYNC();
-  }
-  VIO_PARFOR(q, W * 225) {
-    int f = q / 225, e = q % 225, r = e / 15, c = e % 15;
-    int rr = r >= c ? r : c, cc = r >= c ? c : r;  // lower triangle mirrored
-    v.imu_info[q] = v.imu_aug[f * 450 + rr * 30 + 15 + cc];
-  }
-  VIO_PARFOR(q, W * 450) v.imu_J[q] = 0.0;
-  VIO_SYNC();
-}
-#else
 // Device form of the Gauss-Jordan elimination: 32 lanes per factor, lane j keeps column j of [cov | I] in registers through all
 // 15 pivots; the pivot column travels through a 16-double mailbox per factor (in the still unused matrix buffer). Same
-// arithmetic, same order as the loop above. Since round 6 the fallback of setup_imu_info below (a covariance that is not
+// arithmetic, same order as the restatement. Since round 6 the fallback of setup_imu_info below (a covariance that is not
 // positive definite to working precision).
 template <class MP>
 VIO_DEV void setup_imu_info_gj(const Ctx &cx, const WinView &v, MP mbox) {
@@ -927,19 +410,6 @@ VIO_DEV void setup_imu_info_gj(const Ctx &cx, const WinView &v, MP mbox) {
   }
   VIO_SYNC();
 }
-#endif
-
-#ifndef VIO_EMUL
-#ifdef VIO_SIMT
-typedef ::simt::v4d v4d;
-#else
-typedef double v4d __attribute__((ext_vector_type(4)));
-#endif
-
-// v_mfma_f64_16x16x4_f64: D = A(16x4) B(4x16) + C. Lane l supplies A[l&15][l>>4] and B[l>>4][l&15]; it receives
-// D[(l>>4) + 4 r][l&15] in element r (the f64 C/D map differs from the f32 one, cdna_hip_programming.md §3).
-VIO_DEV v4d mfma_f64(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-#endif
 
 // Prior constants. MarginalizationFactor evaluates r = r0 + J0 dx with a constant J0 (marginalization_factor.cpp:
 // 336-384); everything the solver takes from it is a function of  H0 = J0^T J0  and  b0 = J0^T r0:
@@ -966,7 +436,6 @@ VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
     VIO_PARFOR(q, n * n) Js[q] = v.pr_J[q];
     VIO_SYNC();
   }
-#ifndef VIO_EMUL
   // H0 = J0^T J0 on the matrix cores: one 16 x 16 tile of the lower triangle per wave visit (mirrored on store), the
   // k loop in chunks of 8 steps whose 16 operand fetches (4 row segments of 128 B each) are issued together
   {
@@ -1010,25 +479,6 @@ VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
       }
     }
   }
-  if (false) {
-    const int tid_ = 0, kLanes = 1, lane = 0, nwv = 1;
-#else
-  // rows of the symmetric H0 by wave, columns by lane: no integer division per element
-  {
-    const int tid_ = VIO_TID(cx), kLanes = (int)cx.nt < 64 ? (int)cx.nt : 64, lane = tid_ % kLanes, nwv = (int)cx.nt / kLanes;  // (host emulation: one thread)
-#endif
-    for (int a = tid_ / kLanes; a < n; a += nwv)
-      for (int b = lane; b < n; b += kLanes) {
-        double s = 0;
-        if (stage) {
-#pragma unroll 5
-          for (int k = 0; k < n; k++) s = fma(Js[k * n + a], Js[k * n + b], s);
-        } else {
-          for (int k = 0; k < n; k++) s = fma(v.pr_J[k * n + a], v.pr_J[k * n + b], s);
-        }
-        v.prH0[a * n + b] = s;
-      }
-  }
   VIO_PARFOR(a, n) {
     double s = 0;
     if (stage) {
@@ -1059,389 +509,6 @@ VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
   VIO_SYNC();
 }
 
-// ---- wave-level device helpers (matrix cores, v_readlane) ------------------------------------------
-#ifndef VIO_EMUL
-
-// Value of x held by `lane` (compile-time constant) broadcast to the whole wave through SGPRs.
-VIO_DEV double lane_bcast(double x, int lane) {
-  int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-  int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-  return __hiloint2double(hi, lo);
-}
-// Sum over the four lanes of a quad (DPP quad_perm [1,0,3,2] then [2,3,0,1]); every lane of the quad gets the total.
-VIO_DEV double quad_sum_f64(double v) {
-  v += dpp_move_f64<0xB1, 0xf>(v);
-  v += dpp_move_f64<0x4E, 0xf>(v);
-  return v;
-}
-
-// Layouts of v_mfma_f64_16x16x4 (lane l: li = l & 15, kq = l >> 4):
-//   operand layout of a tile X: k-step s takes X[li][4 s + kq] as A operand (rows of the product) and, for products
-//   with X^T on the right, as B operand;  accumulator layout: element r is [kq + 4 r][li].
-// The accumulator layout of a tile T is at the same time the B-operand layout of T over four k-steps (element r = k-step
-// r), so chains of products M1 (M2 T) never leave the registers.
-
-// Under register pressure the scheduler sinks every LDS read to its first use: a ds_read, s_waitcnt lgkmcnt(0), the
-// select that masks it, the next ds_read... -- one LDS latency (~120 cycles) per VALUE on the serial chains of the
-// factorization. The fetch helpers below therefore read raw (clamped addresses, nothing consumes the value), then a
-// scheduling fence, then mask: one latency per batch.
-
-// ---- 9 x 9 speed-bias blocks (row-major, ld 9) in 16 x 16 register tiles --------------------------------------------
-// X[li][4 s + kq], zero outside the block (k-steps 0..2 cover k < 12)
-VIO_DEV void load_op9_raw(cldsd X, int li, int kq, double out[3]) {
-  cldsd p = X + (li < kSB ? li : 0) * kSB + kq;
-  out[0] = p[0], out[1] = p[4], out[2] = p[kq == 0 ? 8 : 0];
-}
-VIO_DEV void mask_op9(int li, int kq, double out[3]) {
-  const bool iok = li < kSB;
-  out[0] = iok ? out[0] : 0.0, out[1] = iok ? out[1] : 0.0, out[2] = (iok && kq == 0) ? out[2] : 0.0;
-}
-VIO_DEV void load_op9(cldsd X, int li, int kq, double out[3]) {
-  load_op9_raw(X, li, kq, out);
-  VIO_SCHED_FENCE();
-  mask_op9(li, kq, out);
-}
-// Linv[li][4 s + kq] of a factored diagonal block (potrf9_inv_wave): strict lower part of L^-1 transposed above the
-// diagonal (D[kk][n] = Linv[n][kk], kk < n), 1 / L_nn in ldinv_k. As A operand: Linv (.) ; as B operand: (.) L^-T.
-VIO_DEV void load_linv9_raw(cldsd D, cldsd ldinv_k, int li, int kq, double out[4]) {
-  const int n = li < kSB ? li : 0;
-  out[3] = ldinv_k[n];
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const int kk = 4 * s + kq;
-    out[s] = D[(kk < n ? kk : 0) * kSB + n];
-  }
-}
-VIO_DEV void mask_linv9(int li, int kq, double out[4]) {
-  const bool iok = li < kSB;
-  const int n = iok ? li : 0;
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const int kk = 4 * s + kq;
-    out[s] = (iok && kk < n) ? out[s] : ((iok && kk == n) ? out[3] : 0.0);
-  }
-}
-VIO_DEV void load_linv9(cldsd D, cldsd ldinv_k, int li, int kq, double out[4]) {
-  load_linv9_raw(D, ldinv_k, li, kq, out);
-  VIO_SCHED_FENCE();
-  mask_linv9(li, kq, out);
-}
-
-// Cholesky of one 9 x 9 diagonal block AND the inverse of its factor by one wave, entirely on the matrix cores.
-// The block lives in the f64 accumulator layout as a full symmetric matrix; pivot c: row c sits in the 16 lanes
-// kq == (c & 3), element c >> 2, which is exactly where the A and the B operand of k-slot (c & 3) are fetched from, so the
-// rank-1 update D -= l l^T is ONE v_mfma with a = b = l and no data movement. ET (initially I) receives the same
-// eliminations, ET -= l e^T with e = ET[c][:] / L_cc, which leaves e = row c of L^-1. with_update: D -= E E^T first
-// (E = the factored coupling block to the frame eliminated before, operand layout from LDS) -- the look-ahead of the
-// band. Stored: L in the lower triangle (with diagonal), L^-1's strict lower part TRANSPOSED in the strict upper
-// triangle, 1 / L_cc in ldinv_k. Returns false if a pivot is <= 0.
-// (Four pivots per step like potrf16_wave -- 4 + 4 + 1 -- was built for this block as well: 2 196 against 2 124 cycles alone, 2 473
-// against 2 440 with the E update, window kernel +0.5 %: with ONE matrix instruction per pivot and the next pivot's reciprocal root in
-// its shadow the rank-1 form is already at the cost of the blocked one. Not kept.)
-VIO_DEV bool potrf9_inv_wave(ldsd D, cldsd Eprev, bool with_update, ldsd ldinv_k, int lane) {
-  // Round 6: ONE matrix instruction per pivot. The block only fills 9 x 9 of the 16 x 16 tile; the inverse rides in the rest of
-  // the SAME tile as a symmetric border:  T = [ A  E ; E^T  * ],  E = columns 0..6 of the running inverse (rows 0..8, tile
-  // columns 9..15; initially the identity). The rank-1 update T -= v v^T with v = (row c of T) / L_cc = [l | e] then applies
-  // A -= l l^T and E -= l e^T at once -- rounds 3-5 kept the inverse in a second accumulator and paid a second 64-cycle
-  // instruction per pivot (an f64 matrix instruction is 16 passes of the vector unit's own double-precision pipe on this chip).
-  // Column 7 of the inverse has ONE entry below the diagonal, L^-1[8][7] = -L[8][7] / (L_77 L_88): formed by hand; column 8 none.
-  const int n = lane & 15, kq = lane >> 4;
-  v4d A;
-  double l[3];
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int m = kq + 4 * r;
-    const bool ok = m < kSB && n < kSB;
-    const int hi = m > n ? m : n, lo = m > n ? n : m;
-    A[r] = D[ok ? hi * kSB + lo : 0];
-  }
-  load_op9_raw(Eprev, n, kq, l);
-  VIO_SCHED_FENCE();
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int m = kq + 4 * r;
-    // (the border: E[m][n - 9] = [m == n - 9] right of the block, its transpose below it)
-    A[r] = (m < kSB && n < kSB) ? A[r] : ((m + 9 == n || n + 9 == m) ? 1.0 : 0.0);
-  }
-  if (with_update) {
-    mask_op9(n, kq, l);
-#pragma unroll
-    for (int s = 0; s < 3; s++) A = mfma_f64(-l[s], l[s], A);
-  }
-  // Everything in this loop is on the critical path of the solve and nothing in a wave overlaps its own matrix
-  // instructions, so the loop carries no bookkeeping: a pivot <= 0 shows up as a NaN / inf reciprocal root and is tested
-  // once at the end.
-  double keep[3] = {0.0, 0.0, 0.0}, myinv = 0.0, l87 = 0.0, y7 = 0.0, linv87 = 0.0;
-  double dcc = lane_bcast(A[0], 0);
-#pragma unroll
-  for (int c = 0; c < kSB; c++) {
-    double y = __builtin_amdgcn_rsq(dcc);
-    const double h = 0.5 * dcc;
-    y = y * fma(-h * y, y, 1.5);  // (v_rsq_f64 is specified to 2^29 ulp, ~2^-23 relative: one Newton step leaves ~1.5 e^2 = ~2^-45
-                                  //  in every pivot, nine orders below the 1e-6 bar against the reference
-                                  //  (tests/test_backend_gpu.py::test_step_quality_traces_on_badly_conditioned_windows holds low-parallax windows at
-                                  //  the smallest mu to it); the second step cost 3 dependent operations on the pivot chain)
-    const bool sel = kq == (c & 3);
-    const double a = sel ? A[c >> 2] * y : 0.0;  // v: l[n] = L[n][c] for n < 9 (n == c: dcc / sqrt(dcc)), e[n - 9] = L^-1[c][n - 9] right of it
-    keep[c >> 2] = sel ? a : keep[c >> 2];
-    myinv = (n == c) ? y : myinv;
-    if (c == 7) l87 = lane_bcast(a, 16 * 3 + 8), y7 = y;
-    if (c == 8) linv87 = -(l87 * y7) * y;
-    if (c + 1 < kSB) {
-      // the next pivot D[c+1][c+1] - l[c+1]^2 is formed ahead of the matrix instruction, so its rsqrt chain runs in
-      // its shadow instead of behind it
-      const double lnext = lane_bcast(a, 16 * (c & 3) + c + 1);
-      const double dold = lane_bcast(A[(c + 1) >> 2], 16 * ((c + 1) & 3) + c + 1);
-      dcc = fma(-lnext, lnext, dold);
-    }
-    A = mfma_f64(-a, a, A);
-  }
-  // lane (n, kq) captured, at pivot c = kq + 4 j, L[n][c] (n >= c) or -- in the border -- L^-1[c][n - 9] (n - 9 < c), which goes
-  // TRANSPOSED above the diagonal of the stored block
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    const int c = kq + 4 * j;
-    if (c < kSB) {
-      if (n < kSB && n >= c) D[n * kSB + c] = keep[j];
-      if (n >= kSB && n - kSB < c) D[(n - kSB) * kSB + c] = keep[j];
-    }
-  }
-  if (lane == 0) D[7 * kSB + 8] = linv87;
-  if (kq == 0 && n < kSB) ldinv_k[n] = myinv;
-  // rsq of a pivot <= 0 (or NaN) is NaN / inf, and every later pivot inherits it
-  const bool bad = n < kSB && !(myinv > 0.0 && myinv < 1.7976931348623157e308);
-  return __builtin_amdgcn_ballot_w64(bad) == 0;
-}
-
-// ---- 16 x 16 tiles of a row-major matrix (leading dimension per tile row) -------------------------------------------
-// operand X[li][kq + 4 s]; rows >= rows are zero (the lane reads row 0 instead)
-template <class MP>
-VIO_DEV void tile_load_op_raw(MP X, int ld, int rows, int li, int kq, double out[4]) {
-  auto p = X + (li < rows ? li : 0) * ld + kq;
-  out[0] = p[0], out[1] = p[4], out[2] = p[8], out[3] = p[12];
-}
-VIO_DEV void tile_mask_op(int rows, int li, double out[4]) {
-  const bool ok = li < rows;
-  out[0] = ok ? out[0] : 0.0, out[1] = ok ? out[1] : 0.0, out[2] = ok ? out[2] : 0.0, out[3] = ok ? out[3] : 0.0;
-}
-template <class MP>
-VIO_DEV void tile_load_op(MP X, int ld, int rows, int li, int kq, double out[4]) {
-  tile_load_op_raw(X, ld, rows, li, kq, out);
-  VIO_SCHED_FENCE();
-  tile_mask_op(rows, li, out);
-}
-template <class MP>
-VIO_DEV v4d tile_load_acc_raw(MP C, int ld, int rows, int li, int kq) {
-  v4d a;
-#pragma unroll
-  for (int r = 0; r < 4; r++) a[r] = C[(kq + 4 * r < rows ? kq + 4 * r : 0) * ld + li];
-  return a;
-}
-VIO_DEV v4d tile_mask_acc(v4d a, int rows, int kq) {
-#pragma unroll
-  for (int r = 0; r < 4; r++) a[r] = kq + 4 * r < rows ? a[r] : 0.0;
-  return a;
-}
-template <class MP>
-VIO_DEV v4d tile_load_acc(MP C, int ld, int rows, int li, int kq) {
-  v4d a = tile_load_acc_raw(C, ld, rows, li, kq);
-  VIO_SCHED_FENCE();
-  return tile_mask_acc(a, rows, kq);
-}
-template <class MP>
-VIO_DEV void tile_store_acc(MP C, int ld, int rows, int li, int kq, v4d a) {
-  if (rows >= 16) {  // (uniform: four plain stores instead of four exec-masked regions)
-    auto p = C + kq * ld + li;
-    p[0] = a[0], p[4 * ld] = a[1], p[8 * ld] = a[2], p[12 * ld] = a[3];
-    return;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; r++)
-    if (kq + 4 * r < rows) C[(kq + 4 * r) * ld + li] = a[r];
-}
-// Diagonal tile of the pose matrix: like potrf9_inv_wave on 16 x 16. nvalid rows / columns of the tile exist, the first
-// npiv of them are pivots; rows past npiv (the carried right-hand side) are eliminated along and end up as their row of L.
-// with_update: D -= Lprev Lprev^T first (the panel tile left of D, same tile row).
-// Round 6: FOUR pivots per step. A rank-1 update used one of the four k-slots of the matrix instruction (a = b = the scaled pivot
-// row in the lanes kq == c & 3, zeros elsewhere) and every pivot paid the chain matrix instruction -> vector read -> two broadcasts
-// -> reciprocal root: ~306 cycles x 16. The rows 4 cb .. 4 cb + 3 of the running matrix are accumulator element cb of ALL lanes, i.e.
-// exactly the B operand of one k-step: with M = L44^-1, the inverse Cholesky factor of the 4 x 4 diagonal block (ten broadcasts, then
-// formed redundantly by every lane: four reciprocal roots, ~40 multiply-adds),
-//     V = M R          one matrix instruction (A operand: M in the lanes li < 4; B operand: accumulator element cb)
-//     T -= V^T V       one matrix instruction with a = b = V -- its four rows land in element 0 of the lanes kq = row: operand layout
-// eliminates four pivots; the same M applied to the rows of the inverse's accumulator gives its four rows. 4 matrix instructions per
-// four pivots instead of 8, and one broadcast / reciprocal-root round per block instead of four.
-template <class MP>
-VIO_DEV bool potrf16_wave(MP D, MP Lprev, int ld, int nvalid, int npiv, bool with_update, ldsd ldinv_k, int lane) {
-  const int n = lane & 15, kq = lane >> 4;
-  v4d A, E;
-  double l[4];
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int m = kq + 4 * r;
-    const bool ok = m < nvalid && n < nvalid;
-    const int hi = m > n ? m : n, lo = m > n ? n : m;
-    A[r] = D[ok ? hi * ld + lo : 0];
-  }
-  tile_load_op_raw(Lprev, ld, nvalid, n, kq, l);
-  VIO_SCHED_FENCE();
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int m = kq + 4 * r;
-    A[r] = (m < nvalid && n < nvalid) ? A[r] : 0.0;
-    E[r] = (m == n) ? 1.0 : 0.0;
-  }
-  if (with_update) {
-    tile_mask_op(nvalid, n, l);
-#pragma unroll
-    for (int s = 0; s < 4; s++) A = mfma_f64(-l[s], l[s], A);
-  }
-  double keep[4] = {0.0, 0.0, 0.0, 0.0}, myinv = 0.0;
-  const int mi = (n < 4 && kq <= n) ? n * (n + 1) / 2 + kq : -1;  // which entry of M this lane feeds into the A operand
-#pragma unroll
-  for (int cb = 0; cb < 4; cb++) {
-    if (4 * cb < npiv) {  // (uniform)
-      // the diagonal block: element (row 4 cb + i, column 4 cb + j) is accumulator element cb of lane (n = 4 cb + j, kq = i)
-      double b[10];
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) b[i * (i + 1) / 2 + j] = lane_bcast(A[cb], 16 * i + 4 * cb + j);
-      const bool p1 = 4 * cb + 1 < npiv, p2 = 4 * cb + 2 < npiv, p3 = 4 * cb + 3 < npiv;  // (pivots past npiv: their row of M is zero)
-      auto rsq1 = [](double d) {
-        double y = __builtin_amdgcn_rsq(d);
-        return y * fma(-(0.5 * d) * y, y, 1.5);  // (one Newton step: potrf9_inv_wave)
-      };
-      const double y0 = rsq1(b[0]);
-      const double l10 = b[1] * y0, l20 = b[3] * y0, l30 = b[6] * y0;
-      const double y1 = rsq1(fma(-l10, l10, b[2]));
-      const double l21 = fma(-l20, l10, b[4]) * y1, l31 = fma(-l30, l10, b[7]) * y1;
-      const double y2 = rsq1(fma(-l21, l21, fma(-l20, l20, b[5])));
-      const double l32 = fma(-l31, l21, fma(-l30, l20, b[8])) * y2;
-      const double y3 = rsq1(fma(-l32, l32, fma(-l31, l31, fma(-l30, l30, b[9]))));
-      // M = L44^-1 (lower), row i scaled by y_i
-      double M[10];
-      M[0] = y0;
-      M[1] = p1 ? -(l10 * y0) * y1 : 0.0, M[2] = p1 ? y1 : 0.0;
-      M[3] = p2 ? -fma(l21, M[1], l20 * y0) * y2 : 0.0, M[4] = p2 ? -(l21 * M[2]) * y2 : 0.0, M[5] = p2 ? y2 : 0.0;
-      M[6] = p3 ? -fma(l32, M[3], fma(l31, M[1], l30 * y0)) * y3 : 0.0, M[7] = p3 ? -fma(l32, M[4], l31 * M[2]) * y3 : 0.0;
-      M[8] = p3 ? -(l32 * M[5]) * y3 : 0.0, M[9] = p3 ? y3 : 0.0;
-      double mop = 0.0;
-#pragma unroll
-      for (int q = 0; q < 10; q++) mop = mi == q ? M[q] : mop;
-      const v4d z = {0.0, 0.0, 0.0, 0.0};
-      const v4d V = mfma_f64(mop, A[cb], z), VE = mfma_f64(mop, E[cb], z);
-      const double vv = V[0], ve = VE[0];
-      A = mfma_f64(-vv, vv, A);
-      E = mfma_f64(-vv, ve, E);
-      const int c = 4 * cb + kq;  // this lane's pivot of the block: column c of L below the diagonal, row c of L^-1 left of it
-      keep[cb] = n >= c ? vv : ve;
-      const double yn = (n & 3) == 0 ? y0 : (n & 3) == 1 ? y1 : (n & 3) == 2 ? y2 : y3;  // (1 / L_nn in every lane of column n)
-      myinv = (n >> 2) == cb ? yn : myinv;
-    }
-  }
-  if (n < nvalid) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int c = kq + 4 * j;
-      if (c < npiv) D[n * ld + c] = keep[j];
-    }
-    if (kq == 0 && n < npiv) ldinv_k[n] = myinv;
-  }
-  const bool bad = n < npiv && !(myinv > 0.0 && myinv < 1.7976931348623157e308);
-  return __builtin_amdgcn_ballot_w64(bad) == 0;
-}
-// (the rank-1 form of rounds 2-5: one pivot per step; tools/microbench/band_bench.hip times the two side by side)
-template <class MP>
-VIO_DEV bool potrf16_wave_rank1(MP D, MP Lprev, int ld, int nvalid, int npiv, bool with_update, ldsd ldinv_k, int lane) {
-  const int n = lane & 15, kq = lane >> 4;
-  v4d A, E;
-  double l[4];
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int m = kq + 4 * r;
-    const bool ok = m < nvalid && n < nvalid;
-    const int hi = m > n ? m : n, lo = m > n ? n : m;
-    A[r] = D[ok ? hi * ld + lo : 0];
-  }
-  tile_load_op_raw(Lprev, ld, nvalid, n, kq, l);
-  VIO_SCHED_FENCE();
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int m = kq + 4 * r;
-    A[r] = (m < nvalid && n < nvalid) ? A[r] : 0.0;
-    E[r] = (m == n) ? 1.0 : 0.0;
-  }
-  if (with_update) {
-    tile_mask_op(nvalid, n, l);
-#pragma unroll
-    for (int s = 0; s < 4; s++) A = mfma_f64(-l[s], l[s], A);
-  }
-  double keep[4] = {0.0, 0.0, 0.0, 0.0}, myinv = 0.0;
-  double dcc = lane_bcast(A[0], 0);
-#pragma unroll
-  for (int c = 0; c < 16; c++) {  // (constant trip count: c is a compile-time constant in every copy of the body)
-    if (c < npiv) {
-      double y = __builtin_amdgcn_rsq(dcc);
-      const double h = 0.5 * dcc;
-      y = y * fma(-h * y, y, 1.5);  // (one Newton step: potrf9_inv_wave)
-      const bool sel = kq == (c & 3);
-      const double a = sel ? A[c >> 2] * y : 0.0;
-      const double e = sel ? E[c >> 2] * y : 0.0;
-      keep[c >> 2] = sel ? (n >= c ? a : e) : keep[c >> 2];
-      myinv = (n == c) ? y : myinv;
-      if (c + 1 < 16) {
-        const double lnext = lane_bcast(a, 16 * (c & 3) + c + 1);
-        const double dold = lane_bcast(A[(c + 1) >> 2], 16 * ((c + 1) & 3) + c + 1);
-        dcc = fma(-lnext, lnext, dold);
-      }
-      A = mfma_f64(-a, a, A);
-      E = mfma_f64(-a, e, E);
-    }
-  }
-  if (n < nvalid) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int c = kq + 4 * j;
-      if (c < npiv) D[n * ld + c] = keep[j];
-    }
-    if (kq == 0 && n < npiv) ldinv_k[n] = myinv;
-  }
-  const bool bad = n < npiv && !(myinv > 0.0 && myinv < 1.7976931348623157e308);
-  return __builtin_amdgcn_ballot_w64(bad) == 0;
-}
-// A_ik <- A_ik L_kk^-T (panel tile below a factored FULL diagonal tile: 16 pivots)
-template <class MP>
-VIO_DEV void tile_trsm(MP Aik, int ld_i, int rows, MP Dkk, int ld_k, cldsd ldinv_k, int li, int kq) {
-  double a[4], x[4];
-  tile_load_op_raw(Aik, ld_i, rows, li, kq, a);
-  const double dg = ldinv_k[li];
-#pragma unroll
-  for (int s = 0; s < 4; s++) x[s] = Dkk[(4 * s + kq) * ld_k + li];  // B[kk][li] = Linv[li][kk]: above the diagonal of Dkk for kk < li
-  VIO_SCHED_FENCE();
-  tile_mask_op(rows, li, a);
-  v4d acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    const int kk = 4 * s + kq;
-    const double bb = kk < li ? x[s] : (kk == li ? dg : 0.0);
-    acc = mfma_f64(a[s], bb, acc);
-  }
-  tile_store_acc(Aik, ld_i, rows, li, kq, acc);
-}
-// C_ij -= A_ik A_jk^T
-template <class MP>
-VIO_DEV void tile_update(MP C, int ld_i, int rows_i, MP A, MP B, int ld_j, int rows_j, int li, int kq) {
-  double a[4], b[4];
-  tile_load_op_raw(A, ld_i, rows_i, li, kq, a), tile_load_op_raw(B, ld_j, rows_j, li, kq, b);
-  v4d acc = tile_load_acc_raw(C, ld_i, rows_i, li, kq);
-  VIO_SCHED_FENCE();
-  tile_mask_op(rows_i, li, a), tile_mask_op(rows_j, li, b);
-  acc = tile_mask_acc(acc, rows_i, kq);
-#pragma unroll
-  for (int s = 0; s < 4; s++) acc = mfma_f64(-a[s], b[s], acc);
-  tile_store_acc(C, ld_i, rows_i, li, kq, acc);
-}
 // cov^-1 of every IMU factor (round 6): the covariance of a pre-integration is symmetric positive definite, so one wave
 // factors it on the matrix cores -- potrf16_wave on a 15-pivot tile, which leaves L and L^-1 -- and forms cov^-1 = L^-T L^-1
 // as ONE Gram product of the inverse factor: 15 pivots + 4 matrix instructions per factor, 10 factors on 4 waves. The
@@ -1509,9 +576,7 @@ VIO_DEV void setup_imu_info(const Ctx &cx, const WinView &v, MP mbox) {
   VIO_SYNC();
   if (fallback) setup_imu_info_gj(cx, v, mbox);
 }
-#endif  // !VIO_EMUL
 
-#ifndef VIO_EMUL  // (the host emulation build only takes the factor evaluations and reductions above: pnp_core.h)
 // =====================================================================================================
 // Evaluation: cost, and (jac) H -> App / Dss / Css / Asp (unfactored reduced system), WTf, hff, gp, gf, dp
 // =====================================================================================================
@@ -4070,13 +3135,11 @@ VIO_DEV void solve_window(const Ctx &cx, const WinView &v, WK &w, const VP &fres
   if (cx.tid == 0) w.flag[0] = w.flag[1] = w.flag[2] = w.flag[3] = 0;
   init_band_reach(cx, v, w);
   VIO_SYNC();
-#ifndef VIO_EMUL
   if (cx.prof && cx.tid == cx.prof_tid) {
     for (int q = 0; q < ST_COUNT; q++) cx.lprof[q] = 0;
     cx.lprof[ST_COUNT - 1] = clock64();
     cx.lprof[ST_TOTAL] = -cx.lprof[ST_COUNT - 1];
   }
-#endif
   VIO_PARFOR(q, v.nslots) v.sfact[q] = -1;
   VIO_SYNC();
   VIO_PARFOR(q, v.nslots) v.srec_i[q] = -1;
@@ -4142,6 +3205,5 @@ VIO_DEV void solve_window(const Ctx &cx, const WinView &v, WK &w, const VP &fres
   stamp(cx, ST_NEW2OLD);
 }
 
-#endif  // !VIO_EMUL
 
 }  // namespace vio

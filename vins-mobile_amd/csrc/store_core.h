@@ -19,7 +19,7 @@
 #pragma once
 
 #include "keyframe_core.h"
-#include "solver_core.h"
+#include "spmd.h"
 #include "vio_amd.h"
 
 namespace vio {
@@ -99,7 +99,7 @@ VIO_DEV Lds carve_lds(const Dims &d, PI ibase, PD *dbase_out) {
 
 struct Cx {
   int tid, nt;
-  int wave64 = 0;  // (VIO_TID of solver_core.h)
+  int wave64 = 0;  // (VIO_TID of spmd.h)
 };
 
 #ifdef VIO_HOST_BUILD

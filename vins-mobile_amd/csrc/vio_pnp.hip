@@ -36,7 +36,7 @@ __global__ __launch_bounds__(kThreads) void pnp_window_kernel(PnpBatch B) {
   v.fixed = h + 4, v.feat_start = h + 4 + F;
   v.pose0 = B.pose + (size_t)b * 7 * F, v.speed0 = B.speed + (size_t)b * 3 * F, v.bias = B.bias + (size_t)b * 6 * F;
   v.ex = B.ex + (size_t)b * 7;
-  v.preint = B.preint + (size_t)b * (F - 1) * pnp::kPreDoubles;
+  v.preint = B.preint + (size_t)b * (F - 1) * kPreintDoubles;
   v.obs = B.obs + (size_t)b * 2 * B.max_factors, v.pos = B.pos + (size_t)b * 3 * B.max_factors;
   v.track = B.track + (size_t)b * B.max_factors;
   v.out_pose = B.out_pose + (size_t)b * 7 * F, v.out_speed = B.out_speed + (size_t)b * 3 * F;
@@ -108,8 +108,8 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
   const size_t N = n, hs = 4 + 2 * (size_t)F + 1;
   std::vector<int> hdr(N * hs, 0), track(N * Mmax, 1);
   std::vector<double> pose(N * 7 * F, 0.0), speed(N * 3 * F, 0.0), bias(N * 6 * F, 0.0), ex(N * 7, 0.0),
-      pre(N * (F - 1) * pnp::kPreDoubles, 0.0), obs(N * 2 * Mmax, 0.0), pos(N * 3 * Mmax, 1.0);
-  static_assert(sizeof(VioPreintegration) == pnp::kPreDoubles * sizeof(double), "VioPreintegration layout");
+      pre(N * (F - 1) * kPreintDoubles, 0.0), obs(N * 2 * Mmax, 0.0), pos(N * 3 * Mmax, 1.0);
+  static_assert(sizeof(VioPreintegration) == kPreintDoubles * sizeof(double), "VioPreintegration layout");
   for (int b = 0; b < n; b++) {
     const VioPnpWindow &w = windows[b];
     const int nf = w.n_frames, M = w.feat_start[nf];
@@ -121,7 +121,7 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
     memcpy(&speed[(size_t)b * 3 * F], w.speed, sizeof(double) * 3 * nf);
     memcpy(&bias[(size_t)b * 6 * F], w.bias, sizeof(double) * 6 * nf);
     memcpy(&ex[(size_t)b * 7], w.ex_pose, sizeof(double) * 7);
-    memcpy(&pre[(size_t)b * (F - 1) * pnp::kPreDoubles], w.preint, sizeof(VioPreintegration) * (nf - 1));
+    memcpy(&pre[(size_t)b * (F - 1) * kPreintDoubles], w.preint, sizeof(VioPreintegration) * (nf - 1));
     if (M) {
       memcpy(&obs[(size_t)b * 2 * Mmax], w.observation, sizeof(double) * 2 * M);
       memcpy(&pos[(size_t)b * 3 * Mmax], w.position, sizeof(double) * 3 * M);

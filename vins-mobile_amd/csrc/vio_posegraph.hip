@@ -26,7 +26,8 @@
 
 #include "vio_amd.h"
 #include "vio_device.h"
-#include "solver_core.h"
+#include "spmd.h"
+#include "mfma_tiles.h"
 #include "batch.h"
 #include "marg_core.h"
 #include "vio_posegraph_launch.h"

@@ -24,12 +24,12 @@ __global__ __launch_bounds__(sfm::kThreads, 2) void sfm_ba_kernel(sfm::Batch B) 
   extern __shared__ __attribute__((aligned(16))) double sfm_smem[];
   const sfm::View v = sfm::view_of(B, blockIdx.x);
   if constexpr (kLdsPoints) {
-    sfm::Work<sfm::lds_d> w;
-    sfm::carve<sfm::lds_d>(B.Fm, (sfm::lds_d)sfm_smem, nullptr, B.Pm, &w);
+    sfm::Work<ldsd> w;
+    sfm::carve<ldsd>(B.Fm, (ldsd)sfm_smem, nullptr, B.Pm, &w);
     sfm::solve(threadIdx.x, v, w);
   } else {
     sfm::Work<double *> w;
-    sfm::carve<double *>(B.Fm, (sfm::lds_d)sfm_smem, v.slab, B.Pm, &w);
+    sfm::carve<double *>(B.Fm, (ldsd)sfm_smem, v.slab, B.Pm, &w);
     sfm::solve(threadIdx.x, v, w);
   }
 }
