@@ -238,6 +238,11 @@ int vio_backend_download(vio_backend_t *be, VioWindow *windows, int32_t n, VioSo
 /* Average device time (ms) of the solve kernel over the launches since the
  * last call, measured with HIP events on the launch stream.                  */
 int vio_backend_kernel_ms(vio_backend_t *be, double *ms_avg, int32_t *launches);
+/* Workgroups per window that the last launch gave its large windows (pose
+ * matrix in global scratch): 1, 2 or 4. 1 when the launch had none, when the
+ * batch did not fit the chip at a larger width, and while the stage clock
+ * below is on (it follows one workgroup per window).                         */
+int vio_backend_coop_width(const vio_backend_t *be, int32_t *width);
 
 /* Per-stage device cycle counters of the solve kernel: the kernel-side counterpart
  * of the reference's TS()/TE() printf timers (global_param.hpp:85-92, VINS.cpp:657-662,

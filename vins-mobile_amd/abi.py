@@ -464,6 +464,7 @@ def load_product():
     lib.vio_backend_sync.argtypes = [vp]
     lib.vio_backend_download.argtypes = [vp, C.POINTER(VioWindow), C.c_int32, C.POINTER(VioSolveStats)]
     lib.vio_backend_kernel_ms.argtypes = [vp, _dp, _ip]
+    lib.vio_backend_coop_width.argtypes = [vp, C.POINTER(C.c_int32)]
     u8p, fp = C.POINTER(C.c_uint8), C.POINTER(C.c_float)
     cfgp = C.POINTER(VioConfig)
     lib.vio_frontend_create.argtypes = [cfgp, C.c_int32, C.POINTER(vp)]

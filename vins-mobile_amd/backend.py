@@ -60,6 +60,12 @@ class WindowSolver:
         self._check(self.lib.vio_backend_get_device(self._h, C.byref(d)), "get_device")
         return d.value
 
+    def coop_width(self):
+        """Workgroups per large window in the last launch (1, 2 or 4; 1 while the stage clock is on)."""
+        n = C.c_int32(0)
+        self._check(self.lib.vio_backend_coop_width(self._h, C.byref(n)), "coop_width")
+        return n.value
+
     def reserve_priors(self, n_slots):
         """Device-resident prior chain: Window.resident_prior = k selects slot k-1 (vio_amd.h)."""
         self._check(self.lib.vio_backend_reserve_priors(self._h, n_slots), "reserve_priors")

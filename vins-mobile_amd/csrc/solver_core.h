@@ -17,9 +17,10 @@
 //    as a block-lower matrix of 15x15 blocks (frame i -> [pose 6 | speed-bias 9]).
 //  * The Jacobi-scaled system (S H S + mu D^2) y = S g is solved as (H + mu C) z = g, C = D^2 / S^2, y = z / s: no
 //    scaling pass over the matrix or the landmark coupling (build_reduced_system).
-//  * After H + mu C = L L^T the quadratic forms v^T (S H S + mu D^2) v that the Cauchy point and model_cost_change
-//    need are evaluated with u = S v as sum_f E_f (u_f + w_f^T u_p / E_f)^2 + |L^T u_p|^2, so the un-factored matrix
-//    is not kept.
+//  * The quadratic form a^T (S H S) a of the Cauchy point is evaluated on the UNFACTORED system (quad_form_H; the form through
+//    the factor, sum_f E_f (u_f + w_f^T u_p / E_f)^2 + |L^T u_p|^2, would need the band's fill kept), and only for a
+//    linearization whose dogleg step leaves the trust region (minimize, `cauchy_known`): Ceres forms the Cauchy point at
+//    every linearization and reads it only then. model_cost_change is a combination of inner products reduced already.
 //  * IMUFactor's sqrt_info = LLT(cov^-1).L^T (imu_factor.h:72) is recomputed by the reference on every
 //    Evaluate; it is constant during a solve, so cov^-1 is formed once and H += J^T cov^-1 J, g += J^T cov^-1 r,
 //    cost += r^T cov^-1 r / 2 are used (identical to whitening by any square root of cov^-1).
@@ -98,6 +99,7 @@ struct WinView {
   double *coop;      // cooperative windows: flags + payload shared by the workgroups of this window (CoopLayout)
   double *stash;     // iterate and the vectors of its linearization while the candidate is evaluated in their place (minimize):
                      // pose 7 (P + 1) | sb 9 P | feat F | gp dp gnp (nblk 15 each) | gf hff gnf (F each); read back after a rejected step
+                     // (the gnp / gnf slots also hold the Gauss-Newton step while the on-demand Cauchy point linearizes at x)
   // outputs
   double *out_pose, *out_sb, *out_feat, *raw_pose, *raw_sb, *raw_feat, *out_loop;
   double *stats_d;
@@ -1267,7 +1269,7 @@ VIO_DEV double pose_gd(const WK &w, int i) {
 // (dogleg_strategy.cc:172-192); the first two versions evaluated it after the factorization through L, which forced the
 // fill of the factor to be kept. Uses w.t1 (u_p, frame-major), w.xt (u_p by pose index) and w.tf as scratch.
 template <class WK>
-VIO_DEV double quad_form_H(const Ctx &cx, const WinView &v, WK &w, cldsd vp, cldsd vf, bool prepared = false, bool w_part = true) {
+VIO_DEV double quad_form_H(const Ctx &cx, const WinView &v, WK &w, cldsd vp, cldsd vf, bool prepared = false) {
   const int np = v.np, F = v.F, n6 = v.n6, P = v.P;
   if (!prepared) {  // (prepared: the caller's pass that formed vp also left t1 / xt / tf = 0 behind, barrier included)
     VIO_PARFOR(f, F) w.tf[f] = 0.0;
@@ -1281,8 +1283,7 @@ VIO_DEV double quad_form_H(const Ctx &cx, const WinView &v, WK &w, cldsd vp, cld
   }
   int nparts, per;
   wt_parts((int)cx.nt, F, n6, nparts, per);
-  // (w_part = false: the caller takes 2 u_f^T W^T u_p from the Schur sweep that follows, schur_ksplit5; tf stays zero here)
-  if (w_part) VIO_PARFOR(q, F * nparts) {  // (W^T u_p)_f += sum_{a in part} W[f][a] u_p[a]
+  VIO_PARFOR(q, F * nparts) {  // (W^T u_p)_f += sum_{a in part} W[f][a] u_p[a]
     const int part = q / F, f = q - part * F;
     const int a0 = part * per, a1 = a0 + per < n6 ? a0 + per : n6;
     double x[kWStrip], sacc = 0;
@@ -1348,7 +1349,7 @@ VIO_DEV double quad_form_H(const Ctx &cx, const WinView &v, WK &w, cldsd vp, cld
     for (int j = 0; j < 16; j++) s3 = fma(xs[j], j0 + j < n6 ? w.xt[j0 + j] : 0.0, s3);
     acc = fma(2.0 * w.t1[kBS * kpr + 6 + c], s3, acc);
   }
-  if (w_part) VIO_SYNC();  // tf complete
+  VIO_SYNC();  // tf complete
   VIO_PARFOR(f, F) {
     const double u = w.sf[f] * vf[f];
     acc = fma(u, fma(w.hff[f], u, 2.0 * w.tf[f]), acc);
@@ -1361,12 +1362,9 @@ VIO_DEV double quad_form_H(const Ctx &cx, const WinView &v, WK &w, cldsd vp, cld
 // A and B operands are the same 5 loads per k-step (A = W e^-1, B = W), so a chunk of 5 k-steps is 25 global loads (one
 // latency) feeding 75 matrix instructions; the partial results of the waves meet through the callers' atomic adds:
 // flush_tile(row, col <= row, value), flush_rhs(index, value). ge = g_f / E_f.
-// up / tq (optional): the same sweep also leaves tq[f] = sum_a W[f][a] up[a] (the landmark coupling applied to a pose-index
-// vector: the W part of the Cauchy point's quadratic form) -- five multiply-adds and a 16-lane DPP sum per k-step in the
-// shadow of its 15 matrix instructions instead of another pass over W in global memory.
 template <class FT, class FR>
 VIO_DEV void schur_ksplit5(const Ctx &cx, const double *Wf, int ldw, int n6, int F, cldsd einv, cldsd ge, FT flush_tile,
-                           FR flush_rhs, cldsd up = nullptr, ldsd tq = nullptr) {
+                           FR flush_rhs) {
   constexpr int kT = 5;  // row tiles the K-split form holds in registers (15 accumulators)
   const int tid_ = VIO_TID(cx), wave = tid_ >> 6, lane = tid_ & 63, nw = cx.nt >> 6;
   const int li = lane & 15, kq = lane >> 4;
@@ -1379,9 +1377,6 @@ VIO_DEV void schur_ksplit5(const Ctx &cx, const double *Wf, int ldw, int n6, int
   for (int q = 0; q < kT * (kT + 1) / 2; q++) acc[q] = v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int t = 0; t < kT; t++) rp[t] = 0.0;
-  double u5[kT];
-#pragma unroll
-  for (int t = 0; t < kT; t++) u5[t] = (tq && 16 * t + li < n6) ? up[16 * t + li] : 0.0;
   for (int s0 = s_begin; s0 < s_end; s0 += 5) {
     double wv[5][kT], ev[5], gv[5];
 #pragma unroll
@@ -1404,16 +1399,6 @@ VIO_DEV void schur_ksplit5(const Ctx &cx, const double *Wf, int ldw, int n6, int
       for (int t = 0; t < kT; t++) {
         wv[j][t] = (vf && 16 * t + li < n6) ? wv[j][t] : 0.0;
         rp[t] = fma(wv[j][t], gv[j], rp[t]);
-      }
-      if (tq) {  // (uniform) row f of W against up: this lane's five columns, then the 16 lanes of the row (total in lane 15)
-        double pq = wv[j][0] * u5[0];
-#pragma unroll
-        for (int t = 1; t < kT; t++) pq = fma(wv[j][t], u5[t], pq);
-        pq += dpp_move_f64<0x111, 0xf>(pq);
-        pq += dpp_move_f64<0x112, 0xf>(pq);
-        pq += dpp_move_f64<0x114, 0xf>(pq);
-        pq += dpp_move_f64<0x118, 0xf>(pq);
-        if (li == 15 && vf) tq[f] = pq;
       }
 #pragma unroll
       for (int ti = 0; ti < kT; ti++) {
@@ -1459,11 +1444,9 @@ VIO_DEV void schur_add(ldsd p, double v) { atomic_add(p, v); }
 // flush(row, col <= row, value, parts): parts = true -> the element has several writers, add atomically.
 // ge / flush_rhs: the same fetch also yields c = W (g_f / E_f) -- the diagonal blocks, which have a matrix instruction to spare, multiply
 // the two strips they load by ge[f] on the way; flush_rhs(index, partial) is called by every lane group and part (add atomically).
-// up / tq (optional): the diagonal blocks also leave tq[f] += sum_a W[f][a] up[a] over their 32 columns (the W part of the Cauchy point's
-// quadratic form, as in schur_ksplit5) -- tq zeroed by the caller, LDS atomics: every feature meets every diagonal block once.
 template <class FT, class FR>
 VIO_DEV void schur_blocks(const Ctx &cx, const double *Wf, int ldw, int n6, int F, cldsd einv, cldsd ge, int share, int nshare, FT flush_el,
-                          FR flush_rhs, cldsd up = nullptr, ldsd tq = nullptr) {
+                          FR flush_rhs) {
   const int T = (n6 + 15) / 16, NB = (T + 1) / 2, nblocks = NB * (NB + 1) / 2;
   const int tid_ = VIO_TID(cx), wave = tid_ >> 6, lane = tid_ & 63, nw = cx.nt >> 6;
   const int li = lane & 15, kq = lane >> 4;
@@ -1497,12 +1480,6 @@ VIO_DEV void schur_blocks(const Ctx &cx, const double *Wf, int ldw, int n6, int 
     }
     v4d c00 = {0.0, 0.0, 0.0, 0.0}, c01 = c00, c10 = c00, c11 = c00;  // c_xy: row tile ta[x], column tile tb[y]
     double rp[2] = {0.0, 0.0};
-    const bool do_tq = diag && tq != nullptr;
-    double u2[2] = {0.0, 0.0};
-    if (do_tq) {
-#pragma unroll
-      for (int q = 0; q < 2; q++) u2[q] = va[q] ? up[16 * ta[q] + li] : 0.0;
-    }
     for (int s0 = s_lo; s0 < s_hi; s0 += kChunk) {
       double av[2][kChunk], bv[2][kChunk], ev[kChunk], gv[kChunk];
 #pragma unroll
@@ -1518,20 +1495,11 @@ VIO_DEV void schur_blocks(const Ctx &cx, const double *Wf, int ldw, int n6, int 
       for (int j = 0; j < kChunk; j++) {
         const int f = 4 * (s0 + j) + kq;
         const bool vf = f < F && s0 + j < s_hi;
-        double pq = 0.0;
 #pragma unroll
         for (int q = 0; q < 2; q++) {
           const double a_raw = (va[q] && vf) ? av[q][j] : 0.0;
           if (diag) rp[q] = fma(a_raw, gv[j], rp[q]);  // (uniform)
-          if (do_tq) pq = fma(a_raw, u2[q], pq);
           av[q][j] = a_raw * ev[j], bv[q][j] = (vb[q] && vf) ? bv[q][j] : 0.0;
-        }
-        if (do_tq) {  // (uniform) this block's part of row f against up: the 16 lanes of the row (total in lane 15)
-          pq += dpp_move_f64<0x111, 0xf>(pq);
-          pq += dpp_move_f64<0x112, 0xf>(pq);
-          pq += dpp_move_f64<0x114, 0xf>(pq);
-          pq += dpp_move_f64<0x118, 0xf>(pq);
-          if (li == 15 && vf) VIO_ATOMIC_ADD(tq + f, pq);
         }
       }
 #pragma unroll
@@ -1561,9 +1529,8 @@ VIO_DEV void schur_blocks(const Ctx &cx, const double *Wf, int ldw, int n6, int 
 // The landmark Schur term of the general path (more than 5 tile rows) and the right-hand side row: App -= (W E^-1) W^T,
 // App[n6][:] -= W (g_f / E_f). share / nshare: the units and right-hand side items of THIS workgroup of a cooperative window (App
 // is global scratch in this variant).
-// tq (optional, zeroed by the caller): += W^T u_p of this workgroup's diagonal blocks, u_p by pose index in w.xt.
 template <class WK>
-VIO_DEV void schur_general(const Ctx &cx, const WinView &v, WK &w, int share, int nshare, ldsd tq = nullptr) {
+VIO_DEV void schur_general(const Ctx &cx, const WinView &v, WK &w, int share, int nshare) {
   const int n6 = v.n6, F = v.F;
   schur_blocks(
       cx, v.WTf, v.n6cap, n6, F, w.einv, w.tf, share, nshare,
@@ -1571,15 +1538,14 @@ VIO_DEV void schur_general(const Ctx &cx, const WinView &v, WK &w, int share, in
         if (parts) schur_add(w.App + tri_at(arow, bcol), -val);
         else w.App[tri_at(arow, bcol)] -= val;  // (one writer per tile: plain read-modify-write)
       },
-      [&](int a, double val) { schur_add(w.App + tri_at(n6, a), -val); },  // rhs_p -= sum_f W_f (g_f / E_f)
-      w.xt, tq);
+      [&](int a, double val) { schur_add(w.App + tri_at(n6, a), -val); });  // rhs_p -= sum_f W_f (g_f / E_f)
   stamp(cx, ST_SCHUR);
 }
 
 // In place: (H + mu C) on the diagonals, then the landmark Schur term  App -= (W E^-1) W^T  and the right-hand side row
 // App[n6][:] = g_p - W (g_f / E_f). Returns false if some E_f <= 0.
 template <class WK>
-VIO_DEV bool build_reduced_system(const Ctx &cx, const WinView &v, WK &w, double mu, ldsd tq = nullptr) {
+VIO_DEV bool build_reduced_system(const Ctx &cx, const WinView &v, WK &w, double mu) {
   const int np = v.np, F = v.F;
   stamp(cx, ST_TR_VEC);
   // Ceres solves (S H S + mu D^2) y = S g with the Jacobi scaling S and D^2 = clamp(diag(S H S)). The same system in
@@ -1594,8 +1560,6 @@ VIO_DEV bool build_reduced_system(const Ctx &cx, const WinView &v, WK &w, double
     w.tf[f] = w.gf[f] * ei;  // g_f / E_f
     if (!(e > 0.0)) w.flag[0] = 1;
   }
-  const bool tq_general = tq != nullptr && ((v.n6 + 15) >> 4) > 5;  // (the general path accumulates tq: zeroed here, ahead of the barrier)
-  if (tq_general) VIO_PARFOR(f, F) tq[f] = 0.0;
   VIO_PARFOR(i, np) {
     const int f = i / kBS, c = i - f * kBS;
     const double cc = w.dp[i] * rcp_f(w.sp[i]);
@@ -1620,7 +1584,7 @@ VIO_DEV bool build_reduced_system(const Ctx &cx, const WinView &v, WK &w, double
     if (T <= kT) {
       schur_ksplit5(cx, v.WTf, v.n6cap, n6, F, w.einv, w.tf,
                     [&](int arow, int bcol, double val) { VIO_ATOMIC_ADD(w.App + tri_at(arow, bcol), -val); },
-                    [&](int a, double val) { VIO_ATOMIC_ADD(w.App + tri_at(n6, a), -val); }, w.xt, tq);
+                    [&](int a, double val) { VIO_ATOMIC_ADD(w.App + tri_at(n6, a), -val); });
     } else {
 #ifndef VIO_HOST_BUILD
       if (cx.coop > 1) {
@@ -1628,20 +1592,12 @@ VIO_DEV bool build_reduced_system(const Ctx &cx, const WinView &v, WK &w, double
         // share of the tile pairs, the owner goes on when all of them are done
         const CoopLayout L = CoopLayout::make(v.Pcap, v.Fcap, v.nblk_cap);
         VIO_PARFOR(f, F) v.coop[L.o_einv + f] = w.einv[f], v.coop[L.o_tf + f] = w.tf[f];
-        if (tq) VIO_PARFOR(q, 16 * T) v.coop[L.o_pose + q] = w.xt[q];  // u_p for the helpers' part of W^T u_p (the pose slot is free here)
         coop_post(cx, v, COOP_SCHUR);
-        schur_general(cx, v, w, 0, cx.coop, tq);
+        schur_general(cx, v, w, 0, cx.coop);
         coop_wait_helpers(cx, v);
-        if (tq) {  // the helpers' parts of W^T u_p (left in the per-landmark slot of their partial records)
-          VIO_SYNC();
-          for (int m = 1; m < cx.coop; m++) {
-            const double *pr = v.coop + L.o_part + (size_t)(m - 1) * L.part;
-            VIO_PARFOR(f, F) tq[f] += pr[L.p_f + f];
-          }
-        }
       } else
 #endif
-        schur_general(cx, v, w, 0, 1, tq);
+        schur_general(cx, v, w, 0, 1);
     }
   }
   VIO_SYNC();
@@ -2748,8 +2704,8 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
   double min_rec = x_cost;
   if (cx.tid == 0) trace.record(0, x_cost, radius, 0, 0, gmax, true, true);
   if (cx.tid == 0) trace.initial(x_cost);
-  double gd_sq = 0, mu_used = mu, qf_cauchy = 0, qf_part = 0;
-  bool qf_pending = false;  // the W part of the Cauchy point's quadratic form is still to be added (first dogleg step after a solve)
+  double gd_sq = 0, mu_used = mu, qf_cauchy = 0;
+  bool cauchy_known = false;  // alpha / qf_cauchy / gd_sq belong to the linearization at x (formed by the first dogleg step that needs them)
   // a linearization at x is due at the head of the next iteration: after a step that was accepted on a cost-only evaluation
   // (relin_reuse: the raw IMU Jacobians and the prior's dx of that evaluation are still valid; rec_*: the iteration record
   // waits for the gradient norm) or after an invalid step (the matrix buffer holds a factorization)
@@ -2789,33 +2745,12 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
         ldsi pi = reinterpret_cast<ldsi>(park + 12);
         pi[0] = it, pi[1] = n_ok, pi[2] = n_bad, pi[3] = invalid_run, pi[4] = termination, pi[5] = recorded, pi[6] = last_ok ? 1 : 0;
       }
-      // |g_d|^2, the Cauchy direction a = D^-2 S g (-> t2 poses, stf landmarks) and the vectors quad_form_H starts from
-      // (u = S a frame-major -> t1, by pose index -> xt, its landmark accumulator tf = 0) in ONE pass; the reduction's barrier
-      // publishes them. Cauchy point: alpha = |g_d|^2 / |J_s (g_d / d)|^2 (dogleg_strategy.cc:172-192); |J_s a|^2 = u^T H u
-      // is taken from the unfactored system, i.e. before the linear solve consumes it (it does not depend on mu).
-      {
-        double part = 0;
-        VIO_PARFOR(i, np) {
-          const int f = i / kBS, c = i - f * kBS;
-          const double g = pose_gd(w, i), a = g * rcp_f(w.dp[i]), u = w.sp[i] * a;
-          part += g * g;
-          w.t2[i] = a, w.t1[i] = u;
-          if (c < 6) w.xt[6 * f + c] = u;
-        }
-        VIO_PARFOR(f, F) {
-          const double d2 = feat_d2(w, f), sg = w.sf[f] * w.gf[f], g = sg * rsqrt_f(d2);
-          part += g * g;
-          w.stf[f] = sg * rcp_f(d2), w.tf[f] = 0.0;
-        }
-        gd_sq = block_sum(cx, part);
-      }
-      stamp(cx, ST_V_GD);
-      // (pose matrices of up to five tile rows: the W part of the form, 2 u_f^T W^T u_p, comes out of the Schur sweep of
-      // build_reduced_system -- tq -> cfeat, dead between a linearization and the next Plus -- and joins the reductions of the
-      // dogleg step below: one pass over W in global memory and one barrier less per iteration)
-      const bool fuse_qw = true;  // (round 6: the general path's blocked product accumulates it as well, schur_blocks)
-      const double qf_h0 = quad_form_H(cx, fresh(), w, w.t2, w.stf, /*prepared=*/true, /*w_part=*/!fuse_qw);
-      stamp(cx, ST_QUADFORM);
+      // The Cauchy point (alpha = |g_d|^2 / |J_s (g_d / d)|^2, dogleg_strategy.cc:172-192) is NOT formed here. Ceres computes it
+      // at every new linearization, but ComputeTraditionalDoglegStep reads it only when the Gauss-Newton step leaves the trust
+      // region, which in a steady-state window it never does. |g_d|^2, the Cauchy direction and its quadratic form u^T H u
+      // are left to the first dogleg step of this linearization that needs them (below, `!cauchy_known`). What that saves and
+      // what the rare path costs: DESIGN 3.2, profiles/r09_a_solver_stage_cycles.txt.
+      cauchy_known = false, gd_sq = 0, qf_cauchy = 0, alpha = 0;
       // Gauss-Newton step: (S H S + mu D^2) y = S g, features eliminated (dogleg_strategy.cc:515-612)
       solver_ok = false;
       bool first_try = true;
@@ -2823,22 +2758,12 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
         if (!first_try) {
           // retry with a larger mu: the in-place system was consumed, rebuild H from the factors (rare path)
           evaluate(cx, fresh(), w, w.xpose, w.xsb, w.xfeat, true, true);
-          // (the Schur sweep below takes u_p = S D^-2 S g from xt for the W part of the Cauchy form: a first try that got as far
-          // as the back-substitution has left z there)
-          if (fuse_qw) {
-            VIO_PARFOR(i, np) {
-              const int f = i / kBS, c = i - f * kBS;
-              const double u = w.sp[i] * (pose_gd(w, i) * rcp_f(w.dp[i]));
-              w.t1[i] = u;
-              if (c < 6) w.xt[6 * f + c] = u;
-            }
-          }
         }
         first_try = false;
         if (cx.tid == 0) w.flag[0] = 0, w.flag[1] = 0, w.flag[2] = 0, w.flag[3] = 0;
         VIO_PARFOR(k, v.P) w.ready[k] = 0;
         VIO_SYNC();
-        bool ok = build_reduced_system(cx, fresh(), w, mu, fuse_qw ? w.cfeat : nullptr);
+        bool ok = build_reduced_system(cx, fresh(), w, mu);
         if (ok) {
           if constexpr (REGS) ok = factor_band_regs<kPanelTiles, NW>(cx, fresh(), w);
           else ok = factor_band_lds(cx, fresh(), w);
@@ -2873,35 +2798,60 @@ VIO_DEV void minimize(const Ctx &cx, const WinView &v, WK &w_whole, const VP &fr
         ldsi pi = reinterpret_cast<ldsi>(park + 12);
         it = pi[0], n_ok = pi[1], n_bad = pi[2], invalid_run = pi[3], termination = pi[4], recorded = pi[5], last_ok = pi[6] != 0;
       }
-      if (solver_ok) {
-        // mu |D a|^2 of the Cauchy direction a = D^-2 S g for the mu the solve ended with: D a = g_d, so it is mu |g_d|^2
-        qf_part = qf_h0, qf_pending = fuse_qw;
-        if (!fuse_qw) {
-          qf_cauchy = qf_h0 + mu_used * gd_sq;
-          alpha = gd_sq / qf_h0;
-        }
-        stamp(cx, ST_DOGLEG);
-      }
+      if (solver_ok) stamp(cx, ST_DOGLEG);
     }
     (void)have_factor;
     bool step_valid = false;
     double model_cost_change = 0;
     if (solver_ok) {
       // ComputeTraditionalDoglegStep (dogleg_strategy.cc:199-255): dogleg_combination of solve_trace.h, kept in line (need_norm as a flag)
-      double p1 = 0, p2 = 0, p3 = 0;
+      // (two sums through the three-value reduction, as in the Plus pass below: spmd.h has no two-value form, and the idle
+      // third value costs one wave sum and one LDS word per wave behind the same single barrier)
+      double p1 = 0, p2 = 0, dummy3 = 0;
       VIO_PARFOR(i, np) p1 += w.gnp[i] * w.gnp[i], p2 += pose_gd(w, i) * w.gnp[i];
-      VIO_PARFOR(f, F) {
-        p1 += w.gnf[f] * w.gnf[f], p2 += feat_gd(w, f) * w.gnf[f];
-        // (first step after a solve: u_f (W^T u_p)_f of the Cauchy direction, u_f = s_f^2 g_f / D_f^2, W^T u_p from the Schur sweep)
-        if (qf_pending) p3 += 2.0 * (w.sf[f] * w.sf[f] * w.gf[f] * rcp_f(feat_d2(w, f))) * w.cfeat[f];
-      }
-      block_sum3(cx, p1, p2, p3);
+      VIO_PARFOR(f, F) p1 += w.gnf[f] * w.gnf[f], p2 += feat_gd(w, f) * w.gnf[f];
+      block_sum3(cx, p1, p2, dummy3);
       stamp(cx, ST_V_DOT);
-      if (qf_pending) {
-        const double qf_h = qf_part + p3;
+      if (!(sqrt(p1) <= radius) && !cauchy_known) {
+        // The trust region binds and this linearization has no Cauchy point yet (rare: right after a solve whose step is too
+        // long, or on a reused step once rejections have shrunk the radius; kept until the iterate moves, as Ceres keeps alpha
+        // across reused steps). u^T H u needs the unfactored system, and the matrix buffer holds the factorization: linearize
+        // at x once more -- the route of the mu retry above; a cost-only evaluation of a candidate may have overwritten the raw
+        // IMU Jacobians, so nothing is reused. The evaluation's accumulators take the place of the Gauss-Newton step, which
+        // waits in its slots of the stash (free until Plus parks the iterate). The buffer then holds H at x unfactored; nothing
+        // reads it before the next evaluation. (The stage clock of this path -- v_gd, q_w, quad_form and the evaluation's
+        // stages -- next to the common one: profiles/r09_a_solver_stage_cycles.txt.)
+        const int nv_ = v.nblk * kBS, o_gnp = 7 * (v.P + 1) + 9 * v.P + F + 2 * nv_, o_gnf = o_gnp + nv_ + 2 * F;
+        VIO_PARFOR(i, np) v.stash[o_gnp + i] = w.gnp[i];
+        VIO_PARFOR(f, F) v.stash[o_gnf + f] = w.gnf[f];
+        evaluate(cx, fresh(), w, w.xpose, w.xsb, w.xfeat, true, true);
+        // |g_d|^2, the Cauchy direction a = D^-2 S g (-> t2 poses, stf landmarks) and the vectors quad_form_H starts from
+        // (u = S a frame-major -> t1, by pose index -> xt, its landmark accumulator tf = 0) in ONE pass; the reduction's barrier
+        // publishes them. |J_s a|^2 = u^T H u does not depend on mu; mu |D a|^2 = mu |g_d|^2 (D a = g_d) for the mu the solve
+        // ended with completes the form of the regularized system.
+        double part = 0;
+        VIO_PARFOR(i, np) {
+          const int f = i / kBS, c = i - f * kBS;
+          const double g = pose_gd(w, i), a = g * rcp_f(w.dp[i]), u = w.sp[i] * a;
+          part += g * g;
+          w.t2[i] = a, w.t1[i] = u;
+          if (c < 6) w.xt[6 * f + c] = u;
+        }
+        VIO_PARFOR(f, F) {
+          const double d2 = feat_d2(w, f), sg = w.sf[f] * w.gf[f], g = sg * rsqrt_f(d2);
+          part += g * g;
+          w.stf[f] = sg * rcp_f(d2), w.tf[f] = 0.0;
+        }
+        gd_sq = block_sum(cx, part);
+        stamp(cx, ST_V_GD);
+        const double qf_h = quad_form_H(cx, fresh(), w, w.t2, w.stf, /*prepared=*/true);
         qf_cauchy = qf_h + mu_used * gd_sq;
         alpha = gd_sq / qf_h;
-        qf_pending = false;
+        cauchy_known = true;
+        VIO_PARFOR(i, np) w.gnp[i] = v.stash[o_gnp + i];
+        VIO_PARFOR(f, F) w.gnf[f] = v.stash[o_gnf + f];
+        VIO_SYNC();
+        stamp(cx, ST_QUADFORM);
       }
       double gnn2 = p1, gdot = p2;
       double gradient_norm = sqrt(gd_sq), gauss_newton_norm = sqrt(gnn2);
@@ -3103,12 +3053,9 @@ VIO_DEV void coop_helper(const Ctx &cx, const WinView &v, WK &w) {
       }
       if (cx.tid == 0) part[L.p_cost] = cost;
     } else if (cmd == COOP_SCHUR) {
-      VIO_PARFOR(f, F) w.einv[f] = v.coop[L.o_einv + f], w.tf[f] = v.coop[L.o_tf + f], w.cfeat[f] = 0.0;
-      VIO_PARFOR(q, 16 * ((v.n6 + 15) >> 4)) w.xt[q] = v.coop[L.o_pose + q];  // u_p (only meaningful when the owner fuses W^T u_p: read either way)
+      VIO_PARFOR(f, F) w.einv[f] = v.coop[L.o_einv + f], w.tf[f] = v.coop[L.o_tf + f];
       VIO_SYNC();
-      schur_general(cx, v, w, cx.member, cx.coop, w.cfeat);
-      VIO_SYNC();
-      VIO_PARFOR(f, F) part[L.p_f + f] = w.cfeat[f];
+      schur_general(cx, v, w, cx.member, cx.coop);
     } else if (cmd == COOP_SYRK) {
       band_syrk_share(cx, v, w, cx.member, cx.coop);
     } else {

@@ -91,6 +91,7 @@ struct vio_backend {
   size_t lds_bytes = 0;
   int n_cus = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   bool static_w = false;  // every window of the LDS launch has W = vio_wk::kStaticW frames and the batch has that window's capacities
+  int coop_width = 1;    // workgroups per global-matrix window of the last launch (vio_backend_coop_width)
   bool coop_ok = false;  // the global-matrix windows of the uploaded batch may run as cooperative windows (host-packed, no bucket across chunks)
   DevBuf<long long> d_prof;
   HostBatch hb;
@@ -550,6 +551,7 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
     if (be->static_w) variant += 3;  // (every window of the launch has the compile-time window size: vio_window_variants.h)
     vio_wk::variant(variant, be->MP.prof != nullptr).launch(be->n_lds, be->lds_bytes, st, Bl, be->MP);
   }
+  be->coop_width = 1;
   if (be->n_glb > 0) {
     BatchPtrs Bg = be->B;
     Bg.d = be->d_glb, Bg.order = be->d_order.p + be->n_lds;
@@ -577,6 +579,7 @@ int vio_backend_launch(vio_backend_t *be, void *stream) {
       }
     }
     Bg.coop = coop, Bg.n_launch = be->n_glb;
+    be->coop_width = coop;
     {  // test hooks of the timeout path (tests/test_backend_gpu.py): read per launch
       const int spin = vio::env_int("VIO_AMD_COOP_SPIN", 0);
       Bg.coop_spin = spin > 0 ? (unsigned)spin : vio::kCoopSpinLimit;
@@ -606,6 +609,12 @@ int vio_backend_kernel_ms(vio_backend_t *be, double *ms_avg, int32_t *launches) 
   VIO_ON_DEVICE_OF(be);
   HIP_OK(hipDeviceSynchronize());
   return be->timer.drain(ms_avg, launches);
+}
+
+int vio_backend_coop_width(const vio_backend_t *be, int32_t *width) {
+  if (!be || !width) return VIO_EINVAL;
+  *width = be->coop_width;
+  return VIO_OK;
 }
 
 int vio_backend_set_profile(vio_backend_t *be, int32_t enable) {
