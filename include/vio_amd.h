@@ -880,8 +880,14 @@ int vio_estimator_enable_initialization(vio_estimator_t *est, int32_t enable);
  * run on the host pool, the bundle adjustments of ALL sequences that got this far in the call go to the device in one
  * vio_init_ba_solve launch, and the rest of solveInitial continues on the pool. Every failure branch acts as before
  * (VINS.cpp:893-917). A problem beyond the context's capacity (cfg.max_features point_ok landmarks, cfg.max_factors +
- * cfg.max_features observations, VIO_INIT_BA_MAX_FRAMES frames) takes the host route. The context is created at the first
- * such call and lives as long as the estimator; VioEstimatorStatus.init_device_count counts the device-route runs.          */
+ * cfg.max_features observations) or of more than 16 frames (WINDOW_SIZE above 15) takes the host route. vio_init_ba_solve
+ * itself takes VIO_INIT_BA_MAX_FRAMES = 32 frames; the estimator keeps the bound of 16 until an estimator of a larger window
+ * initialises on the host route in a replay the two routes can be compared on (the synthetic ones end in
+ * VIO_FRAME_INIT_FAILED at WINDOW_SIZE 16 and 20 on either route). The context is created at the first such call and lives as
+ * long as the estimator; VioEstimatorStatus.init_device_count counts the device-route runs. Measured on an MI355X
+ * (profiles/init_ba_timing.txt, init_ba_timing_large.txt): one problem is faster on the host (6 ms against 9-10 ms at 21 and 31
+ * frames); the device call overtakes a 16-thread host pool from 64 problems per launch (12-13 ms against 26-28 ms; 256: 19-20 ms
+ * against 97-101 ms). Off by default either way.                                                                            */
 int vio_estimator_set_init_device(vio_estimator_t *est, int32_t enable);
 int vio_estimator_process_imu(vio_estimator_t *est, int32_t seq, double dt, const double acc[3],
                               const double gyr[3]);                                /* processIMU */
@@ -1077,10 +1083,19 @@ int vio_init_sfm(int32_t frame_num, int32_t l, const double relative_R[9], const
  * iterate by iterate (trust_region_minimizer.cc loop, Levenberg-Marquardt, the points
  * eliminated as 3x3 blocks, LLT of the reduced camera matrix), every sum in an order
  * the problem fixes: a problem gives the same bits alone and in any slot of any batch.
- * The reduced camera matrix lives in LDS, which bounds the window: VIO_INIT_BA_MAX_FRAMES
- * frames (the reference's WINDOW_SIZE + 1 is 11; a 31-frame window's 180 x 180 matrix
- * does not fit next to the rest and has no second layout).                          */
-#define VIO_INIT_BA_MAX_FRAMES 16
+ * The reduced camera matrix lives in LDS, in one of two layouts chosen by the problem's
+ * OWN frame count. Up to 16 frames (the reference's WINDOW_SIZE + 1 is 11): the full
+ * square, 256 work-items, two workgroups per compute unit. 17 to VIO_INIT_BA_MAX_FRAMES
+ * frames (windows up to WINDOW_SIZE 31): the packed lower triangle (139 128 B at 32
+ * frames), 512 work-items, one workgroup per compute unit, the diagonal camera blocks and
+ * the landmark state in global memory. A landmark's frames are kept in one 32-bit word,
+ * which sets the bound. vio_init_ba_solve sends a mixed batch as two launches on the
+ * context's stream, the problems of up to 16 frames first, so the guarantee above holds
+ * across the boundary as well: a 31-frame problem gives the same bits alone, twice in a
+ * row and next to 11-frame problems, and an 11-frame problem the bits it gave when 16 was
+ * the bound. (The two layouts sum a block reduction over 4 and over 8 waves: one problem
+ * forced through both gives results that agree to rounding, not to the bit.)          */
+#define VIO_INIT_BA_MAX_FRAMES 32
 typedef struct vio_init_ba vio_init_ba_t;
 typedef struct VioInitBaProblem {   /* the arguments of one vio_init_bundle_adjust call  */
   int32_t frame_num, l, n_points;
@@ -1094,7 +1109,9 @@ typedef struct VioInitBaProblem {   /* the arguments of one vio_init_bundle_adju
   int32_t ok;                       /* out: CONVERGENCE || final_cost < 3e-3 (:279)      */
 } VioInitBaProblem;
 /* Capacities: problems per launch, frames, point_ok landmarks and their observations per
- * problem. VIO_ENODEV without a device; VIO_ECAP for max_frames > VIO_INIT_BA_MAX_FRAMES. */
+ * problem. max_frames up to VIO_INIT_BA_MAX_FRAMES = 32; a context created for more than
+ * 16 frames takes problems of both layouts. Device memory follows the largest launch so
+ * far. VIO_ENODEV without a device; VIO_ECAP for max_frames > VIO_INIT_BA_MAX_FRAMES.   */
 int vio_init_ba_create(int32_t max_batch, int32_t max_frames, int32_t max_points, int32_t max_obs, vio_init_ba_t **out);
 void vio_init_ba_destroy(vio_init_ba_t *c);
 int vio_init_ba_get_device(const vio_init_ba_t *c, int32_t *device);
@@ -1104,6 +1121,8 @@ int vio_init_ba_get_device(const vio_init_ba_t *c, int32_t *device);
  * observations in one frame (the reference's per-frame observation lists cannot hold
  * one). In either case no array of any problem has been touched. n = 0 is VIO_OK.       */
 int vio_init_ba_solve(vio_init_ba_t *c, VioInitBaProblem *problems, int32_t n, VioSolveStats *stats /* [n] or NULL */);
+/* Average kernel time over the launches since the last call. A solve counts one launch per
+ * layout present in its batch: two for a batch that holds problems on both sides of 16 frames. */
 int vio_init_ba_kernel_ms(vio_init_ba_t *c, double *ms_avg, int32_t *launches);
 
 /* ------------------------------------------------------------------------- */

@@ -17,7 +17,7 @@ VIO_OK = 0
 VIO_EINVAL, VIO_ENODEV, VIO_ENOMEM, VIO_ECAP, VIO_ESTATE, VIO_ETIMEOUT = -1, -2, -3, -4, -5, -6
 VIO_MAX_PRIOR_BLOCKS = 96
 VIO_MAX_TRACE = 64
-VIO_INIT_BA_MAX_FRAMES = 16
+VIO_INIT_BA_MAX_FRAMES = 32
 VIO_BLOCK_POSE, VIO_BLOCK_SPEEDBIAS, VIO_BLOCK_EXPOSE = 0, 1, 2
 VIO_MARGIN_OLD, VIO_MARGIN_SECOND_NEW, VIO_MARGIN_NONE = 0, 1, 2
 STAGES = ["setup_imu", "setup_prior", "eval_prior", "eval_imu", "eval_proj", "scale", "schur", "rhs", "cholesky",

@@ -1,6 +1,7 @@
 // sfm_core.h — the closing bundle adjustment of GlobalSFM::construct (VINS_ios/inital_sfm.cpp:229-296) for a batch of
-// independent problems, one workgroup of 256 work-items per problem. Single source: vio_sfm.hip compiles it for gfx950;
-// tests/emul/simt_sfm.cpp compiles the same text for the host with -DVIO_SIMT, every work-item a fiber of tests/emul/simt.h
+// independent problems, one workgroup per problem: 256 work-items in the small layout (up to kSmallFrames frames), 512 in
+// the large one (struct Large below, up to 32 frames). Single source: vio_sfm.hip compiles it for gfx950;
+// tests/emul/simt_sfm.cpp and simt_sfm_large.cpp compile the same text for the host with -DVIO_SIMT, every work-item a fiber of tests/emul/simt.h
 // (the kernel uses nothing but s_barrier between its phases, which that emulator supports in full).
 //
 // The arithmetic is init::bundle_adjust's (vio_initial.cpp), which restates Ceres' TrustRegionMinimizer /
@@ -37,6 +38,28 @@ namespace sfm {
 constexpr int kThreads = 256;
 constexpr int kMaxFrames = VIO_INIT_BA_MAX_FRAMES;
 constexpr int kLdsBudget = 80 * 1024;  // two workgroups per CU (160 KB of LDS): landmark state moves to global memory beyond it
+constexpr int kSmallFrames = 16;       // a problem of up to 16 frames runs the small layout, every other one the large layout
+constexpr int kLdsMax = 160 * 1024;    // what one workgroup may declare
+
+// The two layouts of a workgroup. They fix the number of work-items, how the reduced camera matrix is stored and where
+// the diagonal camera blocks live; the arithmetic of an entry, a landmark or an observation is the same text for both.
+//   Small: the full nc x nc square in LDS (its lower triangle is used), H_cc and the reductions' scratch in LDS.
+//   Large: the lower triangle packed row by row, entry (i, j) at i (i + 1) / 2 + j: 139 128 B at 32 frames, where the
+//          square would take 277 KB. H_cc, read once per matrix entry, lives in the problem's global slab (View::hcc), and
+//          so does the landmark state. The scratch of the block reductions is the head of S: every reduction of the
+//          solve runs while S is dead (each linear_solve builds S from nothing, its back-substitution reads it last). One
+//          workgroup per CU fits, so it has 512 work-items: two waves per SIMD keep the loads of twice as many matrix
+//          entries in flight during the walks.
+struct Small {
+  static constexpr int kThreads = sfm::kThreads;
+  static constexpr bool kPacked = false;
+  typedef ldsd HccPtr;
+};
+struct Large {
+  static constexpr int kThreads = 512;
+  static constexpr bool kPacked = true;
+  typedef double *HccPtr;
+};
 
 // per-observation slab. Rows (SoA: row r of observation k at ob[r * ostride + k]) for what one pass writes and an owner
 // walks element by element: Jacobians, residual, cost term. Then one block of 36 per observation (AoS, at
@@ -57,6 +80,7 @@ struct Batch {
   const double *in;
   double *out, *ob, *slab, *stats_d;
   int *stats_i;
+  double *hcc = nullptr;  // large layout only: [n][36 Fm], the diagonal camera blocks
 };
 VIO_HD size_t int_stride(int Fm, int Pm, int Om) { return 8 + 2 * (size_t)Fm + (Fm + 1) + (Pm + 1) + 4 * (size_t)Om + (size_t)Pm * Fm; }
 VIO_HD size_t dbl_stride(int Fm, int Pm, int Om) { return 7 * (size_t)Fm + 3 * (size_t)Pm + 2 * (size_t)Om; }
@@ -71,6 +95,7 @@ struct View {
   size_t ostride;
   double *slab;  // landmark state when it is not in LDS: [kPointDoubles][Pm]
   int slab_stride;
+  double *hcc;   // large layout: the diagonal camera blocks [F][6][6]
   double *stats_d;
   int *stats_i;
 };
@@ -89,20 +114,22 @@ VIO_HD View view_of(const Batch &B, int b) {
   v.ob = B.ob + (size_t)b * kObsDoubles * (size_t)Om, v.ostride = (size_t)Om;
   v.blk = v.ob + (size_t)kObsRows * Om;
   v.slab = B.slab ? B.slab + (size_t)b * kPointDoubles * (size_t)Pm : nullptr, v.slab_stride = Pm;
+  v.hcc = B.hcc ? B.hcc + (size_t)b * 36 * (size_t)Fm : nullptr;
   v.stats_d = B.stats_d + (size_t)b * kStatsDoubles, v.stats_i = B.stats_i + (size_t)b * kStatsInts;
   return v;
 }
 
 // LDS of one workgroup. PP: where the landmark state lives (ldsd, or double * for the global slab).
-template <class PP>
+template <class PP, class L = Small>
 struct Work {
-  ldsd S;                       // reduced camera matrix, lower triangle, row stride nc; its Cholesky factor below the diagonal
+  typedef L Layout;
+  ldsd S;                       // reduced camera matrix, lower triangle (row stride nc, or packed); its Cholesky factor below the diagonal
   ldsd Ld, v, z, yc;            // the factor's diagonal; right-hand side / forward / backward work vectors: nc each
   ldsd gc, sc, dg;              // camera gradient (unscaled), Jacobi scaling, LM diagonal
-  ldsd Hcc;                     // [F][6][6] diagonal camera blocks (unscaled; rotation columns 0-2, translation 3-5)
+  typename L::HccPtr Hcc;       // [F][6][6] diagonal camera blocks (unscaled; rotation columns 0-2, translation 3-5)
   ldsd R;                       // [F][9] rotations of the pose set under evaluation
   ldsd pose;                    // two pose sets of [4F | 3F]: iterate and candidate
-  ldsd red;                     // [3][kThreads] reductions
+  ldsd red;                     // [3][L::kThreads] reductions (large layout: the head of S)
   ldsi col_frame, col_li, flag; // frame and local column (0-5) of a camera column; flag[0]: every e-block factored
   PP pt;
   int pts;
@@ -135,6 +162,35 @@ VIO_DEV void carve(int Fm, ldsd base, PP pt, int pts, Work<PP> *w) {
   w->col_frame = q, q += ncm, w->col_li = q, q += ncm, w->flag = q;
 }
 
+// ---- the large layout's LDS: S packed | seven nc-vectors | R | pose | integer tables ----
+constexpr size_t large_s_doubles_of(size_t Fm) {  // (the reductions' scratch is the larger one below 14 frames only: a small problem forced here)
+  return (6 * Fm - 6) * (6 * Fm - 5) / 2 > 3 * (size_t)Large::kThreads ? (6 * Fm - 6) * (6 * Fm - 5) / 2 : 3 * (size_t)Large::kThreads;
+}
+constexpr size_t large_lds_bytes_of(size_t Fm) {
+  return (large_s_doubles_of(Fm) + 7 * (6 * Fm - 6) + (9 + 14) * Fm) * sizeof(double) + (2 * (6 * Fm - 6) + 4) * sizeof(int);
+}
+static_assert(large_lds_bytes_of(32) == 139128 + 10416 + 5888 + 1504, "packed triangle, seven nc-vectors, R and pose, integer tables");
+static_assert(large_lds_bytes_of(32) <= (size_t)kLdsMax, "the large layout fits one workgroup's LDS at 32 frames");
+VIO_HD size_t large_lds_bytes(int Fm) { return large_lds_bytes_of((size_t)Fm); }  // bytes of dynamic LDS of the large layout
+
+VIO_DEV void carve_large(int Fm, ldsd base, const View &v, int pts, Work<double *, Large> *w) {
+  const int ncm = max_columns(Fm);
+  ldsd p = base;
+  w->S = p, w->red = p, p += large_s_doubles_of((size_t)Fm);
+  w->Ld = p, p += ncm, w->v = p, p += ncm, w->z = p, p += ncm, w->yc = p, p += ncm;
+  w->gc = p, p += ncm, w->sc = p, p += ncm, w->dg = p, p += ncm;
+  w->R = p, p += 9 * Fm, w->pose = p, p += 14 * Fm;
+  w->Hcc = v.hcc, w->pt = v.slab, w->pts = pts;
+  ldsi q = (ldsi)p;
+  w->col_frame = q, q += ncm, w->col_li = q, q += ncm, w->flag = q;
+}
+
+// entry (i, j), j <= i, of the reduced camera matrix
+template <class L>
+VIO_DEV int s_at(int i, int j, int nc) {
+  return L::kPacked ? i * (i + 1) / 2 + j : i * nc + j;
+}
+
 struct OpSum {
   VIO_DEV double operator()(double a, double b) const { return a + b; }
 };
@@ -142,14 +198,17 @@ struct OpMax {  // std::max(a, b): a NaN on the right is dropped
   VIO_DEV double operator()(double a, double b) const { return a < b ? b : a; }
 };
 // v[0..N) over the workgroup, the same tree for every problem and every launch; every work-item gets the result.
-template <int N, class OP>
+template <int kThreads, int N, class OP>
 VIO_DEV void block_reduce(int tid, ldsd red, double (&val)[N], OP op) {
   for (int n = 0; n < N; n++) red[n * kThreads + tid] = val[n];
   __syncthreads();
   if (tid < 64)
     for (int n = 0; n < N; n++) {
       ldsd r = red + n * kThreads + tid;
-      r[0] = op(op(op(r[0], r[64]), r[128]), r[192]);
+      double a = r[0];
+#pragma unroll
+      for (int i = 64; i < kThreads; i += 64) a = op(a, r[i]);  // ((r[0] + r[64]) + r[128]) + ...: the waves in ascending order
+      r[0] = a;
     }
   __syncthreads();
   for (int n = 0; n < N; n++) {
@@ -179,8 +238,9 @@ VIO_DEV int column_of(const View &v, int f, int li) {
 }
 
 // ba_evaluate: cost at pose / landmark set `s`; with jac, H_pp, g_p, H_cc and g_c of that set as well.
-template <class PP>
-VIO_DEV double evaluate(int tid, const View &v, const Work<PP> &w, int s, bool jac) {
+template <class WK>
+VIO_DEV double evaluate(int tid, const View &v, const WK &w, int s, bool jac) {
+  constexpr int kThreads = WK::Layout::kThreads;
   const int F = v.F, np = v.np, nobs = v.nobs, P = w.pts;
   const size_t os = v.ostride;
   ldsd pq = w.pose + s * 7 * F, ptr = pq + 4 * F;
@@ -253,13 +313,14 @@ VIO_DEV double evaluate(int tid, const View &v, const Work<PP> &w, int s, bool j
       }
     }
   }
-  block_reduce(tid, w.red, cost, OpSum());
+  block_reduce<kThreads>(tid, w.red, cost, OpSum());
   return 0.5 * cost[0];
 }
 
 // |Plus(x, -g) - x|_inf (trust_region_minimizer.cc:270-284) at pose set s
-template <class PP>
-VIO_DEV double gradient_max(int tid, const View &v, const Work<PP> &w, int s) {
+template <class WK>
+VIO_DEV double gradient_max(int tid, const View &v, const WK &w, int s) {
+  constexpr int kThreads = WK::Layout::kThreads;
   const int F = v.F, np = v.np, P = w.pts;
   double m[1] = {0.0};
   OpMax mx;
@@ -277,13 +338,14 @@ VIO_DEV double gradient_max(int tid, const View &v, const Work<PP> &w, int s) {
       for (int k = 0; k < 4; k++) m[0] = mx(m[0], fabs(qn[k] - q[k]));
     }
   }
-  block_reduce(tid, w.red, m, mx);
+  block_reduce<kThreads>(tid, w.red, m, mx);
   return m[0];
 }
 
 // Hs = S_c J_c^T J_p S_p of every observation (the scaling is fixed after iteration 0, so once per accepted iterate)
-template <class PP>
-VIO_DEV void scaled_blocks(int tid, const View &v, const Work<PP> &w) {
+template <class WK>
+VIO_DEV void scaled_blocks(int tid, const View &v, const WK &w) {
+  constexpr int kThreads = WK::Layout::kThreads;
   const size_t os = v.ostride;
   const int P = w.pts;
   for (int k = tid; k < v.nobs; k += kThreads) {
@@ -302,8 +364,10 @@ VIO_DEV void scaled_blocks(int tid, const View &v, const Work<PP> &w) {
 
 // ba_solve: (Hs + D^2) y = gs with D^2 = dg / radius. y: PT_Y of every landmark and w.yc. False where the host code's
 // returns false (an e-block or the reduced matrix not positive definite, a non-finite step).
-template <class PP>
-VIO_DEV bool linear_solve(int tid, const View &v, const Work<PP> &w, double radius, double *a_out, double *b_out) {
+template <class WK>
+VIO_DEV bool linear_solve(int tid, const View &v, const WK &w, double radius, double *a_out, double *b_out) {
+  typedef typename WK::Layout L;
+  constexpr int kThreads = L::kThreads;
   const int np = v.np, nc = v.nc, nobs = v.nobs, P = w.pts;
   const size_t os = v.ostride;
   // (the caller's barrier after the diagonal phase has passed; flag[0] == 1)
@@ -344,9 +408,18 @@ VIO_DEV bool linear_solve(int tid, const View &v, const Work<PP> &w, double radi
   }
   __syncthreads();
   // reduced camera matrix, lower triangle: entry (a, b) walks the observations of a's frame
-  for (int e = tid; e < nc * nc; e += kThreads) {
-    const int a = e / nc, b = e - a * nc;
-    if (b > a) continue;
+  // (the large layout enumerates the packed entries themselves; the square's e < nc * nc idles the lanes above the diagonal)
+  for (int e = tid; e < (L::kPacked ? nc * (nc + 1) / 2 : nc * nc); e += kThreads) {
+    int a, b;
+    if (L::kPacked) {
+      a = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
+      while (a * (a + 1) / 2 > e) a--;  // (the root is exact at these sizes; the two loops make that no assumption)
+      while ((a + 1) * (a + 2) / 2 <= e) a++;
+      b = e - a * (a + 1) / 2;
+    } else {
+      a = e / nc, b = e - a * nc;
+      if (b > a) continue;
+    }
     const int fa = w.col_frame[a], fb = w.col_frame[b], la = w.col_li[a], lb = w.col_li[b];
     double sum = fa == fb ? w.sc[a] * w.Hcc[36 * fa + 6 * la + lb] * w.sc[b] : 0.0;
     const int end = v.fr_start[fa + 1];
@@ -372,7 +445,7 @@ VIO_DEV bool linear_solve(int tid, const View &v, const Work<PP> &w, double radi
           for (int c = 0; c < 3; c++) sum -= wv[u][c] * hv[u][c];
     }
     if (a == b) sum += w.dg[a] / radius;
-    w.S[a * nc + b] = sum;
+    w.S[s_at<L>(a, b, nc)] = sum;
   }
   for (int a = tid; a < nc; a += kThreads) {  // rhs = gs_c - W gs_p
     const int fa = w.col_frame[a], la = w.col_li[a];
@@ -396,28 +469,30 @@ VIO_DEV bool linear_solve(int tid, const View &v, const Work<PP> &w, double radi
   // Eigen::LLT of the reduced camera matrix (schur_complement_solver.cc:201-213), one column per step. Every work-item
   // forms the pivot itself (broadcast reads), so the exit on a non-positive pivot is uniform.
   for (int j = 0; j < nc; j++) {
-    double d = w.S[j * nc + j];
-    for (int k = 0; k < j; k++) d -= w.S[j * nc + k] * w.S[j * nc + k];
+    const int rj = s_at<L>(j, 0, nc);
+    double d = w.S[rj + j];
+    for (int k = 0; k < j; k++) d -= w.S[rj + k] * w.S[rj + k];
     if (!(d > 0.0)) return false;  // (nobody is left behind: the previous step's barrier was passed by all)
     d = sqrt(d);
     if (tid == 0) w.Ld[j] = d;
     for (int i = j + 1 + tid; i < nc; i += kThreads) {
-      double x = w.S[i * nc + j];
-      for (int k = 0; k < j; k++) x -= w.S[i * nc + k] * w.S[j * nc + k];
-      w.S[i * nc + j] = x / d;
+      const int ri = s_at<L>(i, 0, nc);
+      double x = w.S[ri + j];
+      for (int k = 0; k < j; k++) x -= w.S[ri + k] * w.S[rj + k];
+      w.S[ri + j] = x / d;
     }
     __syncthreads();
   }
   for (int i = 0; i < nc; i++) {  // L z = rhs
     const double zi = w.v[i] / w.Ld[i];
     if (tid == 0) w.z[i] = zi;
-    for (int k = i + 1 + tid; k < nc; k += kThreads) w.v[k] -= w.S[k * nc + i] * zi;
+    for (int k = i + 1 + tid; k < nc; k += kThreads) w.v[k] -= w.S[s_at<L>(k, i, nc)] * zi;
     __syncthreads();
   }
   for (int i = nc - 1; i >= 0; i--) {  // L^T yc = z
     const double yi = w.z[i] / w.Ld[i];
     if (tid == 0) w.yc[i] = yi;
-    for (int k = tid; k < i; k += kThreads) w.z[k] -= w.S[i * nc + k] * yi;
+    for (int k = tid; k < i; k += kThreads) w.z[k] -= w.S[s_at<L>(i, k, nc)] * yi;
     __syncthreads();
   }
   // back-substitution yp = E^-1 (gs_p - Hs_pc yc), and the three sums of the step's quality: a = y . gs, b = y . D^2 y
@@ -446,14 +521,15 @@ VIO_DEV bool linear_solve(int tid, const View &v, const Work<PP> &w, double radi
     if (!isfinite(y)) r[2] += 1.0;
   }
   if (!isfinite(r[0]) || !isfinite(r[1])) r[0] = r[1] = 0.0, r[2] += 1.0;
-  block_reduce(tid, w.red, r, OpSum());
+  block_reduce<kThreads>(tid, w.red, r, OpSum());
   *a_out = r[0], *b_out = r[1];
   return r[2] == 0.0;
 }
 
 // init::bundle_adjust for one problem.
-template <class PP>
-VIO_DEV void solve(int tid, const View &v, const Work<PP> &w) {
+template <class PP, class L>
+VIO_DEV void solve(int tid, const View &v, const Work<PP, L> &w) {
+  constexpr int kThreads = L::kThreads;
   const int F = v.F, np = v.np, nc = v.nc, P = w.pts;
   for (int i = tid; i < 4 * F; i += kThreads) w.pose[i] = v.cq0[i];
   for (int i = tid; i < 3 * F; i += kThreads) w.pose[4 * F + i] = v.ct0[i];
@@ -538,7 +614,7 @@ VIO_DEV void solve(int tid, const View &v, const Work<PP> &w) {
         }
       }
     }
-    block_reduce(tid, w.red, sn, OpSum());
+    block_reduce<kThreads>(tid, w.red, sn, OpSum());
     double cand_cost = evaluate(tid, v, w, cand, false);
     if (!isfinite(cand_cost)) cand_cost = 1.7976931348623157e308;
     const double step_norm = sqrt(sn[0]);
@@ -558,7 +634,7 @@ VIO_DEV void solve(int tid, const View &v, const Work<PP> &w) {
         if (v.off_t[tid] >= 0)
           for (int k = 0; k < 3; k++) n2[0] += w.pose[cur * 7 * F + 4 * F + 3 * tid + k] * w.pose[cur * 7 * F + 4 * F + 3 * tid + k];
       }
-      block_reduce(tid, w.red, n2, OpSum());
+      block_reduce<kThreads>(tid, w.red, n2, OpSum());
       x_norm = sqrt(n2[0]);
       x_cost = evaluate(tid, v, w, cur, true);
       __syncthreads();

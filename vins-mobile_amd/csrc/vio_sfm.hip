@@ -34,6 +34,16 @@ __global__ __launch_bounds__(sfm::kThreads, 2) void sfm_ba_kernel(sfm::Batch B) 
   }
 }
 
+// The large layout (more than sfm::kSmallFrames frames): the packed reduced matrix takes up to 157 KB of LDS, so one
+// workgroup per CU, and 512 work-items so that each SIMD still has two waves to switch between during the walks.
+__global__ __launch_bounds__(sfm::Large::kThreads, 1) void sfm_ba_large_kernel(sfm::Batch B) {
+  extern __shared__ __attribute__((aligned(16))) double sfm_smem[];
+  const sfm::View v = sfm::view_of(B, blockIdx.x);
+  sfm::Work<double *, sfm::Large> w;
+  sfm::carve_large(B.Fm, (ldsd)sfm_smem, v, B.Pm, &w);
+  sfm::solve(threadIdx.x, v, w);
+}
+
 }  // namespace
 
 struct vio_init_ba {
@@ -42,7 +52,7 @@ struct vio_init_ba {
   hipStream_t stream = nullptr;
   vio::LaunchTimer timer;
   vio::DevBuf<int> d_ints, d_stats_i;
-  vio::DevBuf<double> d_in, d_out, d_ob, d_slab, d_stats_d;
+  vio::DevBuf<double> d_in, d_out, d_ob, d_slab, d_hcc, d_stats_d;
   ~vio_init_ba() {
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -78,24 +88,17 @@ int vio_init_ba_get_device(const vio_init_ba_t *c, int32_t *device) {
   return VIO_OK;
 }
 
-int vio_init_ba_solve(vio_init_ba_t *c, VioInitBaProblem *problems, int32_t n, VioSolveStats *stats) {
-  if (!c || n < 0 || (n > 0 && !problems)) return VIO_EINVAL;
-  if (n == 0) return VIO_OK;
-  std::vector<sfm::Shape> sh(n);
-  for (int b = 0; b < n; b++) {  // every problem is checked before anything is written or uploaded
-    const int rc = sfm::check_problem(problems[b], &sh[b]);
-    if (rc != VIO_OK) return rc;
-    if (sh[b].F > c->max_frames || sh[b].np > c->max_points || sh[b].nobs > c->max_obs) return VIO_ECAP;
-  }
-  if (n > c->max_batch) return VIO_ECAP;
-  VIO_ON_DEVICE_OF(c);
+// One launch: n problems of one layout (large: every one has more than sfm::kSmallFrames frames), packed, solved and
+// written back to pr[]. The stream is idle again when it returns.
+static int solve_group(vio_init_ba *c, VioInitBaProblem *pr, const sfm::Shape *sh, int n, bool large, VioSolveStats *stats) {
   sfm::HostBatch hb;
-  sfm::pack(problems, sh.data(), n, hb);
+  sfm::pack(pr, sh, n, hb);
   const size_t N = n, out_doubles = sfm::dbl_stride(hb.Fm, hb.Pm, 0) * N;
-  const bool in_lds = sfm::points_fit_lds(hb.Fm, hb.Pm);
+  const bool in_lds = !large && sfm::points_fit_lds(hb.Fm, hb.Pm);
   if (c->d_ints.ensure(hb.ints.size()) != VIO_OK || c->d_in.ensure(hb.in.size()) != VIO_OK || c->d_out.ensure(out_doubles) != VIO_OK ||
       c->d_ob.ensure(N * sfm::kObsDoubles * hb.Om) != VIO_OK || (!in_lds && c->d_slab.ensure(N * sfm::kPointDoubles * hb.Pm) != VIO_OK) ||
-      c->d_stats_d.ensure(N * kStatsDoubles) != VIO_OK || c->d_stats_i.ensure(N * kStatsInts) != VIO_OK)
+      (large && c->d_hcc.ensure(N * 36 * hb.Fm) != VIO_OK) || c->d_stats_d.ensure(N * kStatsDoubles) != VIO_OK ||
+      c->d_stats_i.ensure(N * kStatsInts) != VIO_OK)
     return VIO_ENOMEM;
   hipStream_t st = c->stream;
   HIP_OK(hipMemcpyAsync(c->d_ints.p, hb.ints.data(), hb.ints.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -103,13 +106,14 @@ int vio_init_ba_solve(vio_init_ba_t *c, VioInitBaProblem *problems, int32_t n, V
   sfm::Batch B;
   B.n = n, B.Fm = hb.Fm, B.Pm = hb.Pm, B.Om = hb.Om;
   B.ints = c->d_ints.p, B.in = c->d_in.p, B.out = c->d_out.p, B.ob = c->d_ob.p, B.slab = in_lds ? nullptr : c->d_slab.p;
-  B.stats_d = c->d_stats_d.p, B.stats_i = c->d_stats_i.p;
-  const size_t lds = sfm::lds_bytes(hb.Fm, in_lds ? hb.Pm : 0);
-  const void *fn = in_lds ? (const void *)sfm_ba_kernel<true> : (const void *)sfm_ba_kernel<false>;
+  B.stats_d = c->d_stats_d.p, B.stats_i = c->d_stats_i.p, B.hcc = large ? c->d_hcc.p : nullptr;
+  const size_t lds = large ? sfm::large_lds_bytes(hb.Fm) : sfm::lds_bytes(hb.Fm, in_lds ? hb.Pm : 0);
+  const void *fn = large ? (const void *)sfm_ba_large_kernel : in_lds ? (const void *)sfm_ba_kernel<true> : (const void *)sfm_ba_kernel<false>;
   HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int rc = c->timer.begin(st);
   if (rc != VIO_OK) return rc;
-  if (in_lds) hipLaunchKernelGGL(sfm_ba_kernel<true>, dim3(n), dim3(sfm::kThreads), lds, st, B);
+  if (large) hipLaunchKernelGGL(sfm_ba_large_kernel, dim3(n), dim3(sfm::Large::kThreads), lds, st, B);
+  else if (in_lds) hipLaunchKernelGGL(sfm_ba_kernel<true>, dim3(n), dim3(sfm::kThreads), lds, st, B);
   else hipLaunchKernelGGL(sfm_ba_kernel<false>, dim3(n), dim3(sfm::kThreads), lds, st, B);
   if ((rc = c->timer.end(st)) != VIO_OK) return rc;
   HIP_OK(hipGetLastError());
@@ -123,8 +127,40 @@ int vio_init_ba_solve(vio_init_ba_t *c, VioInitBaProblem *problems, int32_t n, V
   for (int b = 0; b < n; b++) {
     VioSolveStats s;
     unpack_solve_stats(&sd[(size_t)b * kStatsDoubles], &si[(size_t)b * kStatsInts], &s);
-    sfm::unpack(hb, b, out.data(), s, problems[b]);
+    sfm::unpack(hb, b, out.data(), s, pr[b]);
     if (stats) stats[b] = s;
+  }
+  return VIO_OK;
+}
+
+int vio_init_ba_solve(vio_init_ba_t *c, VioInitBaProblem *problems, int32_t n, VioSolveStats *stats) {
+  if (!c || n < 0 || (n > 0 && !problems)) return VIO_EINVAL;
+  if (n == 0) return VIO_OK;
+  std::vector<sfm::Shape> sh(n);
+  int n_large = 0;
+  for (int b = 0; b < n; b++) {  // every problem is checked before anything is written or uploaded
+    const int rc = sfm::check_problem(problems[b], &sh[b]);
+    if (rc != VIO_OK) return rc;
+    if (sh[b].F > c->max_frames || sh[b].np > c->max_points || sh[b].nobs > c->max_obs) return VIO_ECAP;
+    n_large += sh[b].F > sfm::kSmallFrames;
+  }
+  if (n > c->max_batch) return VIO_ECAP;
+  VIO_ON_DEVICE_OF(c);
+  // The layout follows the problem's own frame count: one launch when all share it, else the small ones, then the large ones.
+  if (n_large == 0 || n_large == n) return solve_group(c, problems, sh.data(), n, n_large != 0, stats);
+  for (int large = 0; large < 2; large++) {
+    std::vector<VioInitBaProblem> pr;
+    std::vector<sfm::Shape> gs;
+    std::vector<int> slot;
+    for (int b = 0; b < n; b++)
+      if ((sh[b].F > sfm::kSmallFrames) == (large != 0)) pr.push_back(problems[b]), gs.push_back(sh[b]), slot.push_back(b);
+    std::vector<VioSolveStats> gst(stats ? pr.size() : 0);
+    const int rc = solve_group(c, pr.data(), gs.data(), (int)pr.size(), large != 0, stats ? gst.data() : nullptr);
+    if (rc != VIO_OK) return rc;
+    for (size_t g = 0; g < pr.size(); g++) {
+      problems[slot[g]].ok = pr[g].ok;  // (the arrays were written through the problem's own pointers)
+      if (stats) stats[slot[g]] = gst[g];
+    }
   }
   return VIO_OK;
 }
