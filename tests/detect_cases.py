@@ -1,4 +1,4 @@
-"""Named inputs of the corner detector (detect_kernel + corner_select_kernel, vio_frontend.hip), one for every edge the
+"""Named inputs of the corner detector (detect_kernel + corner_select_kernel, fe_detect.h + fe_select.h), one for every edge the
 smooth synthetic textures never reach: plateaus of equal eigenvalues (every pixel of a plateau is a candidate, so the
 candidate lists sized for "one pixel in four" overflow), the switch of the selection from its LDS list to the in-place
 path, and disc rows of the setMask raster that cover a whole 64-lane word. Every image is deterministic and generated
@@ -10,7 +10,7 @@ import numpy as np
 import helpers as H
 from helpers import abi, synth
 
-# The constants of vins-mobile_amd/csrc/vio_frontend.hip these cases are built around (duplicated on purpose):
+# The constants of vins-mobile_amd/csrc/fe_detect.h and fe_select.h these cases are built around (duplicated on purpose):
 DET_W = 60        # kDetW: output columns per wave                                  (constexpr int kDetW = 60)
 DET_WAVES = 4     # kDetWaves: waves per workgroup, side by side                    (constexpr int kDetWaves = 4)
 DET_R = 32        # kDetR: output rows per strip = one candidate segment            (constexpr int kDetR = 32)

@@ -38,7 +38,7 @@ def test_klt_track_bit_exact(stream):
 
 def test_klt_extreme_contrast_takes_the_split_sums():
     """The wave sums of the LK system run unsplit while every lane's partial is below 2^24 and fall back to the 16-bit split otherwise
-    (vio_frontend.hip wave_all_small). A black / white block pattern drives the derivative products far past that bound
+    (fe_lk.h wave_all_small). A black / white block pattern drives the derivative products far past that bound
     (7 pixels x 4080^2 per lane): the split form must give the oracle's bits too, on the same call as ordinary windows."""
     rng = np.random.default_rng(7)
     soft = synth.make_image_stream(3, 2)[0]

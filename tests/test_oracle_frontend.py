@@ -130,7 +130,7 @@ def test_tracker_bookkeeping():
 
 
 def test_integer_identities_behind_the_lk_kernel():
-    """The arithmetic shortcuts of csrc/vio_frontend.hip's lk_track_kernel, checked on random operands (numpy, no device):
+    """The arithmetic shortcuts of csrc/fe_lk.h's lk_track_kernel, checked on random operands (numpy, no device):
     (1) an exact 36-bit sum hi * 2^16 + lo goes to float with ONE rounding whether it passes through a double or is formed
     as float(hi) * 65536 + float(lo) (both parts and the product are exact floats); (2) the template value folded into the
     accumulator seed: (a + r - (I << n)) >> n == ((a + r) >> n) - I for the arithmetic shift; (3) |x| < 0.01 in double

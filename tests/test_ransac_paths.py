@@ -1,4 +1,4 @@
-"""findFundamentalMat on its rare paths. fundamental_ransac_block (csrc/vio_frontend.hip) restates the sequential
+"""findFundamentalMat on its rare paths. fundamental_ransac_block (csrc/fe_ransac.h) restates the sequential
 RANSAC / LMedS registrators with speculation (rounds of 8, 16, 16, ... hypotheses, subsets drawn as if checkSubset
 passed, a multiply-high modulo, a 16-lane elimination); the named inputs of ransac_cases.py each force one of the paths
 that restatement can get wrong, and the oracle's trace (OracleRansacTrace) proves which path a case took.

@@ -24,7 +24,7 @@
 //   host     per session on those candidates: cut, islands, temporal window (one round trip before, one after)
 //   round B  ld_match_kernel     (sessions that reached the geometric check) neighbour-ratio matches per common node,
 //                                claims resolved in parallel to the reference's order (proof at the kernel)
-//            vio::fundamental_ransac_batch (vio_frontend.hip), ld_keep_kernel   the kept pairs, compacted in order
+//            vio::fundamental_ransac_batch (fe_ransac.h), ld_keep_kernel   the kept pairs, compacted in order
 // vio_loop_detector_connect is the step behind a detected loop, KeyFrame::findConnectionWithOldFrame (VINS_ios/loop/keyframe.cpp
 // :267-273) for one (current, old) pair of entries per session, read from the slabs above: no descriptor crosses the bus.
 //   ld_connect_search_kernel   searchByDes :161-190 (search_by_des_kernel of vio_loop.hip on slab offsets)

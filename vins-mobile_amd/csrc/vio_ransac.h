@@ -1,4 +1,4 @@
-// vio_ransac.h — the tracker's block-cooperative fundamental-matrix RANSAC (vio_frontend.hip) for callers inside the
+// vio_ransac.h — the tracker's block-cooperative fundamental-matrix RANSAC (fe_ransac.h) for callers inside the
 // library that already hold their points on the device.
 #pragma once
 #include <hip/hip_runtime.h>
