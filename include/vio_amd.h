@@ -887,7 +887,16 @@ int vio_estimator_enable_initialization(vio_estimator_t *est, int32_t enable);
  * long as the estimator; VioEstimatorStatus.init_device_count counts the device-route runs. Measured on an MI355X
  * (profiles/init_ba_timing.txt, init_ba_timing_large.txt): one problem is faster on the host (6 ms against 9-10 ms at 21 and 31
  * frames); the device call overtakes a 16-thread host pool from 64 problems per launch (12-13 ms against 26-28 ms; 256: 19-20 ms
- * against 97-101 ms). Off by default either way.                                                                            */
+ * against 97-101 ms). Off by default either way.
+ * 2: the pool keeps only the landmark dump, relativePose's scan (correspondence counts, parallax test, gyroscope hint; with
+ * vio_estimator_enable_initialization(est, 1) the five-point relative pose as well, passed in with relative_mode 0) and the
+ * lists of the frames outside the window; relative pose fit, construct() with its bundle adjustment and the PnP of those frames
+ * (VINS.cpp:926-1003) of ALL sequences that got this far run in one vio_init_sfm_solve; alignment and the first window follow
+ * on the pool. Failure branches, the 16-frame gate, the capacity fallback (also beyond 4 (WINDOW_SIZE + 1) frames outside the
+ * window) and init_device_count as for 1; where the context cannot be created or a launch fails the host route takes over.
+ * Measured on an MI355X (profiles/init_sfm_timing.txt: 11 frames, 150 correspondences, 210 landmarks, 9 extra frames): one
+ * problem is twice as slow on the device (7.7 ms against 3.5 ms), the routes are even at 64 problems per call (71 ms
+ * against 68 ms on a 16-thread pool), at 512 the device call takes 190 ms against 424 ms. Other values: VIO_EINVAL.        */
 int vio_estimator_set_init_device(vio_estimator_t *est, int32_t enable);
 int vio_estimator_process_imu(vio_estimator_t *est, int32_t seq, double dt, const double acc[3],
                               const double gyr[3]);                                /* processIMU */
@@ -1124,6 +1133,73 @@ int vio_init_ba_solve(vio_init_ba_t *c, VioInitBaProblem *problems, int32_t n, V
 /* Average kernel time over the launches since the last call. A solve counts one launch per
  * layout present in its batch: two for a batch that holds problems on both sides of 16 frames. */
 int vio_init_ba_kernel_ms(vio_init_ba_t *c, double *ms_avg, int32_t *launches);
+
+/* Everything solveInitial does between the landmark dump and the alignment, for n independent
+ * start-ups in one call: relativePose's fit (motion_estimator.cpp:200-236, as
+ * vio_init_relative_pose restates it), GlobalSFM::construct (inital_sfm.cpp:117-316: PnP chain,
+ * triangulations, the full BA above, the inversion) and the PnP of the frames outside the
+ * window (VINS.cpp:926-1003). Three device stages on one stream around one upload and one
+ * download: the head (one workgroup per problem: the fit when relative_mode = 1, then
+ * construct's steps 1-4, written straight into the bundle adjustment's batch), the bundle
+ * adjustment kernels of vio_init_ba_solve (both layouts, by frame count), the tail (one
+ * workgroup per problem and per extra frame). The head and the tail form every
+ * floating-point result with the host code's operations in the host code's order (sums over
+ * correspondences and landmarks in ascending index, no atomics), sin / cos / acos correctly
+ * rounded: up to the bundle adjustment the results are the host route's. A problem whose
+ * head fails runs no bundle adjustment iteration. A problem gives the same bits alone, in any
+ * slot of any batch, next to failing problems and run after run.                           */
+#define VIO_INIT_SFM_OK 0
+#define VIO_INIT_SFM_FAIL_RELATIVE 1 /* solveRelativeRT: fewer than 9 correspondences or inliers <= 10   */
+#define VIO_INIT_SFM_FAIL_CHAIN 2    /* construct: a forward frame of the PnP chain (inital_sfm.cpp:47)  */
+#define VIO_INIT_SFM_FAIL_BA 3       /* "vision only BA not converge" (:279)                             */
+#define VIO_INIT_SFM_FAIL_PNP 4      /* an extra frame: fewer than 6 points or solvePnP (VINS.cpp:975-990) */
+typedef struct vio_init_sfm vio_init_sfm_t;
+typedef struct VioInitSfmProblem {
+  /* in: the arguments of vio_init_sfm */
+  int32_t frame_num, l, n_features;
+  const int32_t *feat_start, *obs_frame;
+  const double *obs_xy;
+  int32_t relative_mode;     /* 0: relative_R / relative_T are inputs (vio_init_sfm); 1: fitted on the device from the
+                                features seen in both frame l and frame_num-1, in list order (vio_init_relative_pose) */
+  const double *R_hint;      /* [9] or NULL, mode 1 only */
+  /* in: frames outside the window, placed by PnP after the bundle adjustment (VINS.cpp:926-1003) */
+  int32_t n_extra;
+  const int32_t *extra_guess;    /* [n_extra] window frame whose pose is the guess */
+  const int32_t *extra_start;    /* [n_extra+1] */
+  const int32_t *extra_feature;  /* landmark index; landmarks seen fewer than twice are skipped (not tracked) */
+  const double *extra_xy;
+  /* out */
+  int32_t status;            /* VIO_INIT_SFM_OK, _FAIL_RELATIVE (ok = 0), _FAIL_CHAIN (construct's PnP chain),
+                                _FAIL_BA, _FAIL_PNP (an extra frame) */
+  int32_t inliers;           /* mode 1 */
+  double relative_R[9], relative_T[3];  /* mode 1: written when the fit ran (9 correspondences or more) */
+  double *q, *T;             /* as vio_init_sfm; written when status is _OK or _FAIL_PNP */
+  double *points;            /* as vio_init_sfm; written whenever the head succeeded (status not _FAIL_RELATIVE /
+                                _FAIL_CHAIN), for the landmarks with point_ok; may be NULL */
+  uint8_t *point_ok;         /* written whenever the head succeeded; may be NULL */
+  double *extra_R, *extra_T; /* [n_extra][9], [n_extra][3]: as vio_init_pnp leaves them, for the frames whose PnP ran */
+} VioInitSfmProblem;
+/* Capacities: problems per call, frames (up to VIO_INIT_BA_MAX_FRAMES), landmarks seen at least
+ * twice and their observations per problem, extra frames per problem.                       */
+int vio_init_sfm_create(int32_t max_batch, int32_t max_frames, int32_t max_points, int32_t max_obs, int32_t max_extra,
+                        vio_init_sfm_t **out);
+void vio_init_sfm_destroy(vio_init_sfm_t *c);
+int vio_init_sfm_get_device(const vio_init_sfm_t *c, int32_t *device);
+/* Everything is checked on the host before anything is written or sent: VIO_EINVAL for null or
+ * descending arrays, frame or landmark indices out of range, l outside [0, frame_num - 2],
+ * relative_mode other than 0 / 1; VIO_ECAP for n > max_batch, a problem beyond a capacity, a
+ * landmark seen twice in one frame. In either case no output of any problem has been touched.
+ * n = 0 is VIO_OK. ba_stats [n] (may be NULL): the bundle adjustment's summary and trace
+ * (zeros for a problem whose head failed).                                                  */
+int vio_init_sfm_solve(vio_init_sfm_t *c, VioInitSfmProblem *problems, int32_t n, VioSolveStats *ba_stats /* [n] or NULL */);
+/* Device time per stage (head, bundle adjustment, extra-frame PnP), summed over the launches
+ * since the last call; launches counts them (three per layout present in a batch).          */
+int vio_init_sfm_kernel_ms(vio_init_sfm_t *c, double ms[3] /* head, bundle adjustment, extra-frame PnP */, int32_t *launches);
+/* What the head left for the bundle adjustment of problem `index` of the last solve (a
+ * diagnostic: one small copy from the device): c_rotation [frame_num][4] (w x y z),
+ * c_translation [frame_num][3], points [n_features][3] where point_ok. VIO_ESTATE when that
+ * problem's head failed or no solve has run.                                                */
+int vio_init_sfm_head_state(vio_init_sfm_t *c, int32_t index, double *c_rotation, double *c_translation, double *points);
 
 /* ------------------------------------------------------------------------- */
 /* Replay I/O: the record / playback formats of the app and the IMU-image

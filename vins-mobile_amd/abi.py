@@ -171,6 +171,17 @@ class VioInitBaProblem(C.Structure):
                 ("ok", C.c_int32)]
 
 
+class VioInitSfmProblem(C.Structure):
+    _fields_ = [("frame_num", C.c_int32), ("l", C.c_int32), ("n_features", C.c_int32), ("feat_start", _ip), ("obs_frame", _ip),
+                ("obs_xy", _dp), ("relative_mode", C.c_int32), ("R_hint", _dp), ("n_extra", C.c_int32), ("extra_guess", _ip),
+                ("extra_start", _ip), ("extra_feature", _ip), ("extra_xy", _dp), ("status", C.c_int32), ("inliers", C.c_int32),
+                ("relative_R", C.c_double * 9), ("relative_T", C.c_double * 3), ("q", _dp), ("T", _dp), ("points", _dp),
+                ("point_ok", C.POINTER(C.c_uint8)), ("extra_R", _dp), ("extra_T", _dp)]
+
+
+(VIO_INIT_SFM_OK, VIO_INIT_SFM_FAIL_RELATIVE, VIO_INIT_SFM_FAIL_CHAIN, VIO_INIT_SFM_FAIL_BA, VIO_INIT_SFM_FAIL_PNP) = range(5)
+
+
 class VioEstimatorStatus(C.Structure):
     _fields_ = [("frame_count", C.c_int32), ("solver_flag", C.c_int32), ("marginalization_flag", C.c_int32),
                 ("failure_occur", C.c_int32), ("prior_rows", C.c_int32), ("final_cost", C.c_double),
@@ -564,6 +575,13 @@ def load_product():
     lib.vio_init_ba_get_device.argtypes = [vp, _ip]
     lib.vio_init_ba_solve.argtypes = [vp, C.POINTER(VioInitBaProblem), C.c_int32, C.POINTER(VioSolveStats)]
     lib.vio_init_ba_kernel_ms.argtypes = [vp, _dp, _ip]
+    lib.vio_init_sfm_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    lib.vio_init_sfm_destroy.argtypes = [vp]
+    lib.vio_init_sfm_destroy.restype = None
+    lib.vio_init_sfm_get_device.argtypes = [vp, _ip]
+    lib.vio_init_sfm_solve.argtypes = [vp, C.POINTER(VioInitSfmProblem), C.c_int32, C.POINTER(VioSolveStats)]
+    lib.vio_init_sfm_kernel_ms.argtypes = [vp, _dp, _ip]
+    lib.vio_init_sfm_head_state.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     lib.vio_init_sfm.argtypes = [C.c_int32, C.c_int32, _dp, _dp, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp, u8p, _ip]
     lib.vio_visual_imu_alignment.argtypes = [cfgp, _dp, C.POINTER(VioInitFrame), C.c_int32, C.c_int32, _dp, _dp, _dp, _ip]
     resp, stp = C.POINTER(VioFrameResult), C.POINTER(VioEstimatorStatus)

@@ -114,6 +114,11 @@ struct InitStage {
   std::vector<int32_t> start, frame;
   int n_ok = 0;
   int device_rc = VIO_OK, ba_ok = 0;
+  // vio_estimator_set_init_device(est, 2): the rest of a VioInitSfmProblem and its outputs
+  int mode = 0, status = 0;
+  double relative_R[9], relative_T[3], hint[9];
+  std::vector<int32_t> ex_guess, ex_start, ex_feature;
+  std::vector<double> ex_xy, ex_R, ex_T, q, T;
 };
 
 const double kI3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -127,6 +132,9 @@ extern "C" {
 __attribute__((weak)) int vio_init_ba_create(int32_t, int32_t, int32_t, int32_t, vio_init_ba_t **);
 __attribute__((weak)) void vio_init_ba_destroy(vio_init_ba_t *);
 __attribute__((weak)) int vio_init_ba_solve(vio_init_ba_t *, VioInitBaProblem *, int32_t, VioSolveStats *);
+__attribute__((weak)) int vio_init_sfm_create(int32_t, int32_t, int32_t, int32_t, int32_t, vio_init_sfm_t **);
+__attribute__((weak)) void vio_init_sfm_destroy(vio_init_sfm_t *);
+__attribute__((weak)) int vio_init_sfm_solve(vio_init_sfm_t *, VioInitSfmProblem *, int32_t, VioSolveStats *);
 }
 // (the same for the store's keyframe pass, vio_resident.h: a C++ entry of vio_backend.hip)
 __attribute__((weak)) int vio_backend_resident_keyframe(vio_backend_t *, int32_t, const int32_t *, const int32_t *, const double *const *,
@@ -167,8 +175,11 @@ struct vio_estimator {
   double ms_pre = 0, ms_solve = 0, ms_post = 0;  // wall time of the last process_images call, by phase
   // vio_estimator_set_init_device: the bundle adjustment of solveInitial for every sequence that reaches it in one call goes to
   // the device in one launch (vio_init_ba_solve); the context exists from the first such call on
-  bool init_device = false;
+  // (level 2: the relative pose fit, construct and the PnP of the in-between frames as well, in one vio_init_sfm_solve)
+  int init_device = 0;
   vio_init_ba_t *init_ba = nullptr;
+  vio_init_sfm_t *init_sfm = nullptr;
+  std::vector<char> sfm_wait;            // per sequence: its start-up is part of this call's vio_init_sfm_solve
   std::vector<InitStage> init_stage;     // per sequence: solve_initial between its two host halves
   std::vector<char> ba_wait;             // per sequence: its bundle adjustment is part of this call's launch
   std::vector<int> init_device_count;    // per sequence: initialisations whose bundle adjustment ran on the device
@@ -552,10 +563,9 @@ void g2R(const double g[3], double R0[9]) {  // Utility::g2R (utility.cpp:11-21)
   mat3mul(Y, T, R0);
 }
 
-// VINS::solveInitial + relativePose + visualInitialAlign (VINS.cpp:833-1145), in two halves around the bundle adjustment
-// that closes GlobalSFM::construct: solve_initial_head runs relativePose and construct up to it, solve_initial_tail the
-// rest (the tail of construct, PnP of the in-between frames, the alignment).
-bool solve_initial_head(vio_estimator *e, Sequence &s, InitStage &st) {
+// The decision-free part of the head: the landmark dump and relativePose's scan (VINS.cpp:1106-1145) up to the fit: st.sfm_f,
+// st.l, the correspondences of frames l and W and the gyroscope's rotation between them.
+bool solve_initial_scan(vio_estimator *e, Sequence &s, InitStage &st, std::vector<double> &a, std::vector<double> &b, double hint[9]) {
   const int W = e->W, P = W + 1;
   // the landmark store as SfM features (VINS.cpp:883-899) and as correspondences (getCorresponding)
   int nfe = 0, npts = 0;
@@ -578,10 +588,8 @@ bool solve_initial_head(vio_estimator *e, Sequence &s, InitStage &st) {
     }
   }
   // relativePose (VINS.cpp:1106-1145): the oldest frame with enough parallax against the newest one
-  int l = -1;
-  double relative_R[9], relative_T[3];
   for (int i = 0; i < W; i++) {
-    std::vector<double> a, b;
+    a.clear(), b.clear();
     for (int j = 0; j < nfe; j++)
       if (info[j].start_frame <= i && info[j].start_frame + info[j].n_obs - 1 >= W) {
         const double *pa = &pts[3 * (first[j] + (i - info[j].start_frame))], *pb = &pts[3 * (first[j] + (W - info[j].start_frame))];
@@ -596,20 +604,29 @@ bool solve_initial_head(vio_estimator *e, Sequence &s, InitStage &st) {
       // of the pre-integrated delta_q of the intervals in between (body frame), moved into the camera frame
       Quat dq{0, 0, 0, 1};
       for (int k = i + 1; k <= W; k++) dq = qmul(dq, s.pre[k].dq);
-      double Rb[9], Rt[9], hint[9], ricT[9];
+      double Rb[9], Rt[9], ricT[9];
       qtoR(qnormalized(dq), Rb);
       mat3T(e->ric, ricT);
       mat3mul(ricT, Rb, Rt), mat3mul(Rt, e->ric, hint);
-      const bool got = e->init_relpose_fit ? init::solve_relative_rt(a, b, relative_R, relative_T, nullptr, hint)
-                                           : init::solve_relative_rt_five_point(a, b, relative_R, relative_T, nullptr);
-      if (!got) return false;  // FAIL_RELATIVE
-      l = i;
-      break;
+      st.l = i;
+      return true;
     }
   }
-  if (l < 0) return false;
-  st.l = l;
-  if (!init::sfm_construct_before_ba(P, l, relative_R, relative_T, sfm_f, st.cq, st.tc)) {
+  return false;
+}
+
+// VINS::solveInitial + relativePose + visualInitialAlign (VINS.cpp:833-1145), in two halves around the bundle adjustment
+// that closes GlobalSFM::construct: solve_initial_head runs relativePose and construct up to it, solve_initial_tail the
+// rest (the tail of construct, PnP of the in-between frames, the alignment).
+bool solve_initial_head(vio_estimator *e, Sequence &s, InitStage &st) {
+  std::vector<double> a, b;
+  double hint[9], relative_R[9], relative_T[3];
+  st.l = -1;
+  if (!solve_initial_scan(e, s, st, a, b, hint)) return false;
+  const bool got = e->init_relpose_fit ? init::solve_relative_rt(a, b, relative_R, relative_T, nullptr, hint)
+                                       : init::solve_relative_rt_five_point(a, b, relative_R, relative_T, nullptr);
+  if (!got) return false;  // FAIL_RELATIVE
+  if (!init::sfm_construct_before_ba(e->W + 1, st.l, relative_R, relative_T, st.sfm_f, st.cq, st.tc)) {
     s.marginalization_flag = VIO_MARGIN_OLD;  // FAIL_SFM (VINS.cpp:915-917)
     return false;
   }
@@ -635,6 +652,8 @@ int staged_observations(const InitStage &st) {  // of the point_ok landmarks: wh
     if (st.sfm_f[j].state) n += (int)st.sfm_f[j].observation.size();
   return n;
 }
+
+bool solve_initial_align(vio_estimator *e, Sequence &s);
 
 // ba_ok: the bundle adjustment's verdict (inital_sfm.cpp:279).
 bool solve_initial_tail(vio_estimator *e, Sequence &s, InitStage &st, bool ba_ok) {
@@ -684,7 +703,12 @@ bool solve_initial_tail(vio_estimator *e, Sequence &s, InitStage &st, bool ba_ok
     mat3vec(R_pnp, P_init, v);
     for (int k = 0; k < 3; k++) f.T[k] = -v[k];
   }
-  // visualInitialAlign (VINS.cpp:1021-1104)
+  return solve_initial_align(e, s);
+}
+
+// visualInitialAlign (VINS.cpp:1021-1104), once every frame of all_image_frame has its camera pose.
+bool solve_initial_align(vio_estimator *e, Sequence &s) {
+  const int W = e->W;
   std::vector<init::Frame> frames;
   frames.reserve(s.all_image_frame.size());
   for (auto &kv : s.all_image_frame) frames.push_back(kv.second);
@@ -747,6 +771,83 @@ bool solve_initial_tail(vio_estimator *e, Sequence &s, InitStage &st, bool ba_ok
 bool solve_initial(vio_estimator *e, Sequence &s, InitStage &st) {
   if (!solve_initial_head(e, s, st)) return false;
   return solve_initial_tail(e, s, st, init::bundle_adjust(e->W + 1, st.l, st.cq, st.tc, st.sfm_f, nullptr));
+}
+
+// vio_estimator_set_init_device(est, 2). The pool's part ahead of the device call: the landmark dump, relativePose's scan, on
+// the five-point route the relative pose itself, and the lists of the frames outside the window in the order
+// solve_initial_tail walks them (VINS.cpp:926-1003). False: this attempt ends here, as solve_initial_head's would.
+bool stage_sfm_problem(vio_estimator *e, Sequence &s, InitStage &st) {
+  const int P = e->W + 1;
+  std::vector<double> a, b;
+  st.l = -1;
+  if (!solve_initial_scan(e, s, st, a, b, st.hint)) return false;
+  st.mode = e->init_relpose_fit ? 1 : 0;
+  if (!e->init_relpose_fit && !init::solve_relative_rt_five_point(a, b, st.relative_R, st.relative_T, nullptr)) return false;
+  stage_ba_problem(st);  // (the observation lists; its points / flags are outputs here)
+  st.n_ok = 0;
+  for (const init::SfmFeature &f : st.sfm_f) st.n_ok += f.observation.size() >= 2;
+  std::map<int, int> index_of;
+  for (size_t j = 0; j < st.sfm_f.size(); j++) index_of[st.sfm_f[j].id] = (int)j;
+  st.ex_guess.clear(), st.ex_start.assign(1, 0), st.ex_feature.clear(), st.ex_xy.clear();
+  int i = 0;
+  for (auto &kv : s.all_image_frame) {
+    const init::Frame &f = kv.second;
+    if (i < P && f.header == s.Headers[i]) {
+      i++;
+      continue;
+    }
+    if (i < P && f.header > s.Headers[i]) i++;
+    st.ex_guess.push_back(std::min(i, P - 1));
+    for (const VioObs &o : f.points) {
+      auto it = index_of.find(o.id);
+      if (it == index_of.end()) continue;
+      st.ex_feature.push_back(it->second), st.ex_xy.push_back(o.x), st.ex_xy.push_back(o.y);
+    }
+    st.ex_start.push_back((int32_t)st.ex_feature.size());
+  }
+  const size_t ne = st.ex_guess.size();
+  st.q.assign(4 * (size_t)P, 0.0), st.T.assign(3 * (size_t)P, 0.0), st.ex_R.assign(9 * ne + 9, 0.0), st.ex_T.assign(3 * ne + 3, 0.0);
+  if (st.ex_feature.empty()) st.ex_feature.push_back(0), st.ex_xy.resize(2, 0.0);
+  if (st.ex_guess.empty()) st.ex_guess.push_back(0);
+  return true;
+}
+int staged_observations_seen_twice(const InitStage &st) {
+  int n = 0;
+  for (const init::SfmFeature &f : st.sfm_f)
+    if (f.observation.size() >= 2) n += (int)f.observation.size();
+  return n;
+}
+
+// ... and the pool's part behind it: the failure branches of solveInitial by the call's status, else the frames' camera poses
+// from the call's outputs and the alignment.
+bool finish_sfm_problem(vio_estimator *e, Sequence &s, InitStage &st) {
+  const int P = e->W + 1;
+  if (st.status == VIO_INIT_SFM_FAIL_CHAIN || st.status == VIO_INIT_SFM_FAIL_BA) s.marginalization_flag = VIO_MARGIN_OLD;  // FAIL_SFM (VINS.cpp:915-917)
+  if (st.status != VIO_INIT_SFM_OK) return false;
+  double ricT[9];
+  mat3T(e->ric, ricT);
+  int i = 0, x = 0;
+  for (auto &kv : s.all_image_frame) {
+    init::Frame &f = kv.second;
+    if (i < P && f.header == s.Headers[i]) {
+      double Rq[9];
+      qtoR(Quat{st.q[4 * i], st.q[4 * i + 1], st.q[4 * i + 2], st.q[4 * i + 3]}, Rq);
+      f.is_key_frame = true;
+      mat3mul(Rq, ricT, f.R);
+      memcpy(f.T, &st.T[3 * i], 24);
+      i++;
+      continue;
+    }
+    if (i < P && f.header > s.Headers[i]) i++;
+    f.is_key_frame = false;
+    double R_pnp[9], v[3];
+    mat3T(&st.ex_R[9 * (size_t)x], R_pnp);
+    mat3mul(R_pnp, ricT, f.R);
+    mat3vec(R_pnp, &st.ex_T[3 * (size_t)x], v);
+    for (int k = 0; k < 3; k++) f.T[k] = -v[k];
+    x++;
+  }
+  return solve_initial_align(e, s);
 }
 
 void remember_last(vio_estimator *e, Sequence &s) {  // VINS.cpp:431-434, 472-475
@@ -947,7 +1048,7 @@ int vio_estimator_create(const VioConfig *cfg, int32_t n_seq, const double tic[3
     clear_state(e, s);
   }
   e->windows.resize(n_seq), e->stats.resize(n_seq);
-  e->init_stage.resize(n_seq), e->ba_wait.assign(n_seq, 0), e->init_device_count.assign(n_seq, 0);
+  e->init_stage.resize(n_seq), e->ba_wait.assign(n_seq, 0), e->sfm_wait.assign(n_seq, 0), e->init_device_count.assign(n_seq, 0);
   *out = e;
   return VIO_OK;
 }
@@ -959,6 +1060,7 @@ void vio_estimator_destroy(vio_estimator_t *e) {
   for (int g = 0; g < vio_estimator::kMaxGroups; g++)
     if (e->be[g]) vio_backend_destroy(e->be[g]);
   if (e->init_ba && vio_init_ba_destroy) vio_init_ba_destroy(e->init_ba);
+  if (e->init_sfm && vio_init_sfm_destroy) vio_init_sfm_destroy(e->init_sfm);
   delete e;
 }
 
@@ -970,8 +1072,8 @@ int vio_estimator_enable_initialization(vio_estimator_t *e, int32_t enable) {
 }
 
 int vio_estimator_set_init_device(vio_estimator_t *e, int32_t enable) {
-  if (!e) return VIO_EINVAL;
-  e->init_device = enable != 0;
+  if (!e || enable < 0 || enable > 2) return VIO_EINVAL;
+  e->init_device = enable;
   return VIO_OK;
 }
 
@@ -1135,6 +1237,7 @@ int vio_estimator_process_images(vio_estimator_t *e, const VioObs *obs, const in
   // with self-initialisation on, the synthetic replays the tests use never leave VIO_FRAME_INIT_FAILED at WINDOW_SIZE 16 or 20 on
   // EITHER route (seeds 1-8, 80 frames), so there is no solved window of a larger estimator to compare the two routes on.
   constexpr int kInitDeviceMaxFrames = 16;
+  const int sfm_max_extra = 4 * P;  // frames of all_image_frame outside the window a vio_init_sfm_solve problem may bring
   static_assert(kInitDeviceMaxFrames <= VIO_INIT_BA_MAX_FRAMES, "the context's own bound");
   auto phase_a = [&](int q) {
     VioFrameResult &res = results[q];
@@ -1200,7 +1303,16 @@ int vio_estimator_process_images(vio_estimator_t *e, const VioObs *obs, const in
           bool result = false;
           if (e->enable_init && headers[q] - s.initial_timestamp > 0.3) {  // VINS.cpp:413-417
             InitStage &st = e->init_stage[q];
-            if (e->init_device) {
+            if (e->init_device == 2 && P <= kInitDeviceMaxFrames) {
+              const bool staged = stage_sfm_problem(e, s, st);
+              s.initial_timestamp = headers[q];
+              if (staged && st.n_ok <= ba_max_points && staged_observations_seen_twice(st) <= ba_max_obs &&
+                  (int)st.ex_start.size() - 1 <= sfm_max_extra) {
+                e->sfm_wait[q] = 1;  // phase A continues in phase_a_after_sfm, after this call's vio_init_sfm_solve
+                return;
+              }
+              if (staged) result = solve_initial(e, s, st);  // beyond the context's capacity: the host route
+            } else if (e->init_device) {
               const bool head = solve_initial_head(e, s, st);
               s.initial_timestamp = headers[q];
               if (head && P <= kInitDeviceMaxFrames) {
@@ -1256,9 +1368,57 @@ int vio_estimator_process_images(vio_estimator_t *e, const VioObs *obs, const in
       results[q].action = VIO_FRAME_WAIT_INIT;
     }
   };
+  // the rest of phase A for a sequence whose start-up was part of this call's vio_init_sfm_solve
+  auto phase_a_after_sfm = [&](int q) {
+    Sequence &s = e->seq[q];
+    InitStage &st = e->init_stage[q];
+    bool result;
+    if (st.device_rc == VIO_OK) {
+      result = finish_sfm_problem(e, s, st);
+      e->init_device_count[q]++;
+    } else {  // (no device context, or the call failed: nothing was written, the host route takes over)
+      result = solve_initial(e, s, st);
+    }
+    st = InitStage();
+    if (result) {
+      stage_window(q);
+    } else {
+      slide_window(e, s);
+      results[q].action = VIO_FRAME_WAIT_INIT;
+    }
+  };
+  auto run_sfm_wait = [&](int q0, int q1) {
+    std::vector<int> wait;
+    for (int q = q0; q < q1; q++)
+      if (e->sfm_wait[q]) wait.push_back(q), e->sfm_wait[q] = 0;
+    if (wait.empty()) return;
+    int rcs = vio_init_sfm_create && vio_init_sfm_solve ? VIO_OK : VIO_ENODEV;
+    if (rcs == VIO_OK && !e->init_sfm) {
+      rcs = vio_init_sfm_create(e->n_seq, P, ba_max_points, ba_max_obs, sfm_max_extra, &e->init_sfm);
+      if (rcs != VIO_OK) fprintf(stderr, "vio_amd: no device context for the start-up structure from motion (%d): it runs on the host\n", rcs);
+    }
+    std::vector<VioInitSfmProblem> pr(wait.size());
+    for (size_t i = 0; i < wait.size(); i++) {
+      InitStage &st = e->init_stage[wait[i]];
+      VioInitSfmProblem &p = pr[i];
+      memset(&p, 0, sizeof(p));
+      p.frame_num = P, p.l = st.l, p.n_features = (int32_t)st.sfm_f.size();
+      p.feat_start = st.start.data(), p.obs_frame = st.frame.data(), p.obs_xy = st.xy.data();
+      p.relative_mode = st.mode, p.R_hint = st.hint;
+      memcpy(p.relative_R, st.relative_R, sizeof(p.relative_R)), memcpy(p.relative_T, st.relative_T, sizeof(p.relative_T));
+      p.n_extra = (int32_t)st.ex_start.size() - 1, p.extra_guess = st.ex_guess.data(), p.extra_start = st.ex_start.data();
+      p.extra_feature = st.ex_feature.data(), p.extra_xy = st.ex_xy.data();
+      p.q = st.q.data(), p.T = st.T.data(), p.points = st.points.data(), p.point_ok = st.ok.data();
+      p.extra_R = st.ex_R.data(), p.extra_T = st.ex_T.data();
+    }
+    if (rcs == VIO_OK) rcs = vio_init_sfm_solve(e->init_sfm, pr.data(), (int32_t)pr.size(), nullptr);
+    for (size_t i = 0; i < wait.size(); i++) e->init_stage[wait[i]].device_rc = rcs, e->init_stage[wait[i]].status = pr[i].status;
+    HostPool::get().parallel_for((int)wait.size(), [&](int i) { phase_a_after_sfm(wait[i]); });
+  };
   // phase A of sequences [q0, q1): the host pool, then one launch for the bundle adjustments that came up, then the pool again
   auto run_phase_a = [&](int q0, int q1) {
     HostPool::get().parallel_for(q1 - q0, [&](int i) { phase_a(q0 + i); });
+    run_sfm_wait(q0, q1);
     std::vector<int> wait;
     for (int q = q0; q < q1; q++)
       if (e->ba_wait[q]) wait.push_back(q), e->ba_wait[q] = 0;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "sfm_core.h"
+#include "sfm_launch.h"
 #include "sfm_pack.h"
 #include "vio_amd.h"
 #include "vio_device.h"
@@ -45,6 +46,24 @@ __global__ __launch_bounds__(sfm::Large::kThreads, 1) void sfm_ba_large_kernel(s
 }
 
 }  // namespace
+
+// The launch of sfm_launch.h in its two steps: the kernel's dynamic LDS limit (a host call, kept out of the timed interval),
+// then one workgroup per problem of B on stream st.
+static size_t ba_lds_bytes(const sfm::Batch &B, bool large, bool in_lds) {
+  return large ? sfm::large_lds_bytes(B.Fm) : sfm::lds_bytes(B.Fm, in_lds ? B.Pm : 0);
+}
+int vio::sfm::prepare_ba(const sfm::Batch &B, bool large, bool in_lds) {
+  const void *fn = large ? (const void *)sfm_ba_large_kernel : in_lds ? (const void *)sfm_ba_kernel<true> : (const void *)sfm_ba_kernel<false>;
+  HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ba_lds_bytes(B, large, in_lds)));
+  return VIO_OK;
+}
+int vio::sfm::launch_ba(const sfm::Batch &B, bool large, bool in_lds, hipStream_t st) {
+  const size_t lds = ba_lds_bytes(B, large, in_lds);
+  if (large) hipLaunchKernelGGL(sfm_ba_large_kernel, dim3(B.n), dim3(sfm::Large::kThreads), lds, st, B);
+  else if (in_lds) hipLaunchKernelGGL(sfm_ba_kernel<true>, dim3(B.n), dim3(sfm::kThreads), lds, st, B);
+  else hipLaunchKernelGGL(sfm_ba_kernel<false>, dim3(B.n), dim3(sfm::kThreads), lds, st, B);
+  return VIO_OK;
+}
 
 struct vio_init_ba {
   int device = -1;
@@ -107,14 +126,10 @@ static int solve_group(vio_init_ba *c, VioInitBaProblem *pr, const sfm::Shape *s
   B.n = n, B.Fm = hb.Fm, B.Pm = hb.Pm, B.Om = hb.Om;
   B.ints = c->d_ints.p, B.in = c->d_in.p, B.out = c->d_out.p, B.ob = c->d_ob.p, B.slab = in_lds ? nullptr : c->d_slab.p;
   B.stats_d = c->d_stats_d.p, B.stats_i = c->d_stats_i.p, B.hcc = large ? c->d_hcc.p : nullptr;
-  const size_t lds = large ? sfm::large_lds_bytes(hb.Fm) : sfm::lds_bytes(hb.Fm, in_lds ? hb.Pm : 0);
-  const void *fn = large ? (const void *)sfm_ba_large_kernel : in_lds ? (const void *)sfm_ba_kernel<true> : (const void *)sfm_ba_kernel<false>;
-  HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int rc = c->timer.begin(st);
+  int rc = sfm::prepare_ba(B, large, in_lds);
   if (rc != VIO_OK) return rc;
-  if (large) hipLaunchKernelGGL(sfm_ba_large_kernel, dim3(n), dim3(sfm::Large::kThreads), lds, st, B);
-  else if (in_lds) hipLaunchKernelGGL(sfm_ba_kernel<true>, dim3(n), dim3(sfm::kThreads), lds, st, B);
-  else hipLaunchKernelGGL(sfm_ba_kernel<false>, dim3(n), dim3(sfm::kThreads), lds, st, B);
+  if ((rc = c->timer.begin(st)) != VIO_OK) return rc;
+  if ((rc = sfm::launch_ba(B, large, in_lds, st)) != VIO_OK) return rc;
   if ((rc = c->timer.end(st)) != VIO_OK) return rc;
   HIP_OK(hipGetLastError());
   std::vector<double> out(out_doubles), sd(N * kStatsDoubles);

@@ -56,9 +56,10 @@ class Estimator:
         self._check(self.lib.vio_estimator_set_resident(self._h, 1 if on else 0), "set_resident")
 
     def set_init_device(self, on=True):
-        """The bundle adjustments of solveInitial of all sequences that reach it in one call in one device launch
-        (vio_estimator_set_init_device; include/vio_amd.h). status(seq).init_device_count counts them."""
-        self._check(self.lib.vio_estimator_set_init_device(self._h, 1 if on else 0), "set_init_device")
+        """False / 0: solveInitial on the host. True / 1: the bundle adjustments of solveInitial of all sequences that reach it
+        in one call in one device launch. 2: relative pose fit, construct and the PnP of the in-between frames as well, in one
+        vio_init_sfm_solve (vio_estimator_set_init_device; include/vio_amd.h). status(seq).init_device_count counts them."""
+        self._check(self.lib.vio_estimator_set_init_device(self._h, int(on)), "set_init_device")
 
     def clear(self, seq=0):
         self._check(self.lib.vio_estimator_clear(self._h, seq), "clear")
