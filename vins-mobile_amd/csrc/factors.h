@@ -84,10 +84,15 @@ VIO_DEV void projection_eval(double s_info, PA pose_i, PA pose_j, PE ex, double 
 // The same factor from rotation MATRICES prepared once per evaluation (w.rot: one per frame, then r_ic), for the
 // solver's inner loops: four mat-vecs for the residual and, with jac, (reduce A) chained through R_i and r_ic instead
 // of five dense 3x3 products. Equal to projection_eval up to rounding (different association of the same products).
+// Jex (marginalization: the extrinsic is a kept block of the next prior) from the same chains: with B = r_ic^T R_j^T R_i,
+//   d r / d t_ic     = reduce (B - r_ic^T)
+//   d r / d theta_ic = reduce (-B r_ic skew(pc_i) + skew(p_c_j))
+// (projection_facor.cpp:76-86 adds skew(B r_ic pc_i) and skew(r_ic^T (R_j^T (R_i t_ic + P_i - P_j) - t_ic)): the two vectors sum
+// to p_c_j).
 template <class PR, class PA, class PE>
 VIO_DEV void projection_eval_rot(double s_info, PR Ri_, PA pose_i, PR Rj_, PA pose_j, PR ric_, PE ex, double inv_dep,
                                  const double *pts_i, const double *pts_j, bool jac, double *r, double *Ji, double *Jj,
-                                 double *Jl) {
+                                 double *Jl, double *Jex = nullptr) {
   double Ri[9], Rj[9], ric[9];
 #pragma unroll
   for (int k = 0; k < 9; k++) Ri[k] = Ri_[k], Rj[k] = Rj_[k], ric[k] = ric_[k];
@@ -133,6 +138,14 @@ VIO_DEV void projection_eval_rot(double s_info, PR Ri_, PA pose_i, PR Rj_, PA po
     Jj[i * 6 + 4] = t[2] * p_imu_j[0] - t[0] * p_imu_j[2];
     Jj[i * 6 + 5] = t[0] * p_imu_j[1] - t[1] * p_imu_j[0];
     Jl[i] = -(RC[3 * i] * pi3[0] + RC[3 * i + 1] * pi3[1] + RC[3 * i + 2] * pi3[2]) * (dep_i * dep_i);
+    if (Jex) {
+      const double *c = RC + 3 * i;
+      const double q0 = i == 0 ? rz : 0.0, q1 = i == 0 ? 0.0 : rz, q2 = i == 0 ? rx : ry;  // row i of reduce
+      Jex[i * 6 + 0] = u[0] - t[0], Jex[i * 6 + 1] = u[1] - t[1], Jex[i * 6 + 2] = u[2] - t[2];
+      Jex[i * 6 + 3] = (q1 * p_c_j[2] - q2 * p_c_j[1]) - (c[1] * pc_i[2] - c[2] * pc_i[1]);
+      Jex[i * 6 + 4] = (q2 * p_c_j[0] - q0 * p_c_j[2]) - (c[2] * pc_i[0] - c[0] * pc_i[2]);
+      Jex[i * 6 + 5] = (q0 * p_c_j[1] - q1 * p_c_j[0]) - (c[0] * pc_i[1] - c[1] * pc_i[0]);
+    }
   }
 }
 

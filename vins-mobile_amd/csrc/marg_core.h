@@ -16,6 +16,27 @@
 // eigenvalue cut becomes a pivot cut: a pivot <= max(1e-8, 1e-12 * original diagonal) marks a direction without
 // information (gauge directions, blocks that no factor touches); its row of L is zeroed and skipped, which is what
 // the pseudo-inverse / zeroed eigenvalue does in the reference up to rounding noise.
+//
+// The factor pass (MARGIN_OLD: the projection factors hosted at frame 0, the slots [0, S0) of the solver's bucket order) and how its
+// work is dealt out:
+//   * chunks of MargWorkT::stage_slots slots -- whatever LDS the phase's vectors and the matrix leave -- at kMargSlot = 33 doubles per
+//     factor: two rows of 16 columns, Ji | rotation part of Jj | r | Jex. The translation part of Jj is the negated one of Ji and is
+//     not staged; the landmark column only feeds the per-landmark sums, which the factor's own work-item adds.
+//   * evaluation: one factor per work-item from rotation matrices formed once (projection_eval_rot with Jex); the slot records of
+//     chunk c + 1 are fetched while chunk c is evaluated (fetching those of chunk 0 ahead of the IMU factor cost m_imu more than it
+//     saved m_fact, and registers across the IMU part).
+//   * Gram products: ONE v_mfma_f64_16x16x4 per two-factor step gives every block of a bucket (0, t) at once -- host, target and
+//     extrinsic pose blocks, their couplings and J^T r; the not-staged columns are signed copies in the flush. Bucket p belongs to
+//     wave p mod (number of waves) with its tile in registers across chunk boundaries, so a bucket is flushed once: at most three
+//     matrix atomics and one right-hand-side atomic per accumulator element through a per-lane table formed in the flush.
+//     The matrix instructions of the four waves of a workgroup do not overlap (cutting every range four ways left the phase's time
+//     unchanged), so the count of instructions and of flushes is what the dealing minimizes.
+//   * the global-matrix instantiation (W > 12, 512 work-items, PASS = 1 / MargWorkT::wide) keeps the pass of rounds 3-9: slots of
+//     kWideSlot = 42 doubles (rows of 14 columns plus the 6 of Jex), three products per step, a bucket flushed per chunk, no rotation
+//     matrices. With the 16-column pass compiled in, that instantiation's register allocation came out with 418 instead of 312
+//     scratch reloads spread over the whole kernel and its W = 20 benchmark leg 0.3 % slower; six ways of trimming the new pass's
+//     live state (table in the flush, no prefetch, no tile kept across chunks, quaternion evaluation, shorter operand batches) left
+//     those counts where they were, so the instantiation is given the code it had.
 #pragma once
 
 #include "solver_core.h"
@@ -41,12 +62,14 @@ struct MargWorkT {
   ldsd ldinv;    // pos: 1 / L_jj (0 for a cut pivot)
   ldsd hff, gf, einv;  // F
   ldsd prdx, prr;      // prior_n
+  ldsd rot;            // [P + 1][9]: rotation matrices of the poses 0 .. P - 1 and, at P, of the extrinsic (projection_eval_rot)
   ldsi col_pose;  // [P+1]: first dense column of pose i (-1: not involved); entry P unused
   ldsi col_sb;    // [P]
   ldsi col_ex;    // [1]
   ldsi pcol;      // prior column -> dense column: prior_n
   ldsi meta;      // [4]: pos, m, n, nblocks
   ldsd stage;     // staging of robustified Jacobian rows for the Gram products: LDS in both variants (whatever the phase's
+  bool wide;      // the wide factor pass (matrix in global scratch): slots of kWideSlot doubles, no rotation matrices
   int stage_slots;  // vectors -- and the matrix, when it is in LDS -- leave of the workgroup's allocation)
 };
 
@@ -64,8 +87,10 @@ struct IntPtrOf<ldsd> {
 };
 #endif
 
-constexpr int kMargRowX = 6;                                   // extrinsic Jacobian row
-constexpr int kMargSlot = kSlotStride + 2 * kMargRowX + 1;     // [Ji Jj r Jl] x2 + pad, [Jex] x2 + pad = 42
+constexpr int kMargRow = 16;                 // staged Jacobian row: Ji (6) | rotation part of Jj (3) | r | Jex (6)
+constexpr int kMargSlot = 2 * kMargRow + 1;  // the two rows of a factor + 1 pad (odd stride: conflict-free LDS writes)
+// the wide pass: [Ji Jj r Jl] x2 + pad, [Jex] x2 + pad = 42 doubles per factor
+constexpr int kWideRow = 14, kWideStride = 2 * kWideRow + 1, kWideRowX = 6, kWideSlot = kWideStride + 2 * kWideRowX + 1;
 
 VIO_HD constexpr int kMargMaxPos(int W) { return 15 + 6 * W + 15; }
 
@@ -99,13 +124,16 @@ VIO_HD CarvedMarg<MP> carve_marg_all(const Dims &d, bool lds_matrix, ldsd base_a
   m.bm = take(pos + 16), m.tol = take(pos + 16), m.ldinv = take(pos + 16);  // (+16: whole 16-wide tiles)
   m.hff = take(F), m.gf = take(F), m.einv = take(F);
   m.prdx = take(d.Ncap), m.prr = take(d.Ncap);
+  m.wide = !lds_matrix;
+  m.rot = lds_matrix ? take(9 * ((size_t)d.Pcap + 1)) : base_after_state;
+  const size_t slot = lds_matrix ? kMargSlot : kWideSlot;
   ldsd ints = take(((size_t)(2 * d.Pcap + 2 + d.Ncap + 4) + 1) / 2 + 1);
   // whatever LDS is left (the solver's footprint is larger than the marginalization core) stages Jacobian rows -- also when
   // the matrix lives in global scratch (the staging area used to follow it there: two L2 round trips per operand batch)
   size_t stage_slots = 0;
-  if (avail_doubles > o + kMargSlot * 2) stage_slots = ((avail_doubles - o) / kMargSlot) & ~(size_t)1;
+  if (avail_doubles > o + slot * 2) stage_slots = ((avail_doubles - o) / slot) & ~(size_t)1;
   if (stage_slots > 1024) stage_slots = 1024;
-  ldsd stage = take(stage_slots * kMargSlot);
+  ldsd stage = take(stage_slots * slot);
   m.stage = stage, m.stage_slots = (int)stage_slots;
   m.Am = MatPick<MP>::get(lds_matrix, Am, am_global), m.ld = (int)pos;
   ldsi ip = reinterpret_cast<ldsi>(ints);
@@ -351,11 +379,14 @@ VIO_DEV void marg_cholesky_tiles(const Ctx &cx, MW &m, int pos) {
   }
 }
 
-template <class MW>
+// PASS: which factor pass runs (header comment): 0 the 16-column pass, 1 the wide pass of the global-matrix instantiation, -1 what the
+// carve says (m.wide; host builds).
+template <int PASS = -1, class MW>
 VIO_DEV void marginalize_window_impl(const Ctx &cx, const WinView &v, cldsd xpose, cldsd xsb, cldsd xfeat, cldsd ex,
                                      MW &m, const MargOut &out) {
   const int W = v.W, P = v.P, F = v.F;
   const int flag = v.marg_flag;
+  const bool wide = PASS < 0 ? m.wide : PASS == 1;
   const int pn = v.prior_n;
   // ---- which variant runs (uniform across the block) ---------------------------------------------------
   bool run = (flag == 0);
@@ -492,6 +523,17 @@ VIO_DEV void marginalize_window_impl(const Ctx &cx, const WinView &v, cldsd xpos
   }
   stamp(cx, ST_M_PRIOR);
   if (flag == 0) {
+    // rotation matrices of the poses and the extrinsic for the projection factors below, once (the last work-items: work-item 0
+    // runs the IMU factor); consumed behind the barrier ahead of the chunk loop
+    if (!wide) {
+      const int i = (int)cx.nt - 1 - VIO_TID(cx);
+      if (i <= P) {
+        double R[9];
+        if (i == P) qtoR(Quat{ex[3], ex[4], ex[5], ex[6]}, R);
+        else qtoR(Quat{xpose[7 * i + 3], xpose[7 * i + 4], xpose[7 * i + 5], xpose[7 * i + 6]}, R);
+        for (int k = 0; k < 9; k++) m.rot[9 * i + k] = R[k];
+      }
+    }
     // ---- IMUFactor(pre_integrations[1]) on (pose0, sb0, pose1, sb1) ------------------------------------
     if (cx.tid == 0)
       imu_eval_raw(v.gravity, v.preint, xpose, xsb, xpose + 7, xsb + 9, v.imu_r, v.imu_J);
@@ -529,129 +571,316 @@ VIO_DEV void marginalize_window_impl(const Ctx &cx, const WinView &v, cldsd xpos
     // ---- projections hosted at frame 0: blocks (pose0, pose_t, extrinsic, feature), Cauchy-corrected
     //      (ResidualBlockInfo::Evaluate, marginalization_factor.cpp:45-76, rho'' < 0 branch).
     //      Same scheme as the solver: rows staged in (0,t)-bucket order, one Gram product per bucket on the matrix
-    //      cores: [Ji Jj r Jl]^T [Ji Jj r Jl], Jex^T [Ji Jj r Jl] and Jex^T Jex.
-    const double cc = 1.0 / v.cauchy_b;
-    int S0 = 0, nb0 = 0;  // buckets (0, t < P) come first in the (host, target) order
-    for (int p = 0; p < v.npairs && v.pair_h[p] == 0; p++)
-      if (v.pair_t[p] != P) S0 = (v.pair_s1[p] + 1) & ~1, nb0 = p + 1;
-    auto G = m.stage;
-    const int CH = m.stage_slots;
-    if (CH < 2) {  // launcher guarantees staging space; never loop forever on a bad carve
-      if (cx.tid == 0) out.n[0] = -3, out.n[1] = 0;
-      return;
-    }
+    //      cores: G^T G with G = [Ji | rotation part of Jj | r | Jex], 16 columns (the flush table below).
     // dense-matrix add, lower triangle only
     auto add_lower = [&](int ra, int ca, double val) {
       if (ra >= ca) VIO_ATOMIC_ADD(m.Am + tri_at(ra, ca), val);
       else VIO_ATOMIC_ADD(m.Am + tri_at(ca, ra), val);
     };
-    // bucket descriptors (0, t): one per lane, fetched once (a dependent global round trip per Gram round otherwise)
-    const int lane_d = VIO_TID(cx) & 63;
-    const bool dv = lane_d < nb0;
-    const int d_s0 = dv ? v.pair_s0[lane_d] : 0, d_s1 = dv ? v.pair_s1[lane_d] : 0;
-    const int d_t = dv ? ((v.pair_h[lane_d] != 0 || v.pair_t[lane_d] == P) ? -1 : v.pair_t[lane_d]) : -1;
-    for (int c0 = 0; c0 < S0; c0 += CH) {
-      // The factors hosted at frame 0 occupy the staging slots [0, S0) of the solver's slot order: the slot records built
-      // at the start of the solve (srec_i / srec_d) give host | target | landmark and the observation pair in ONE global
-      // round trip per pass (factor index -> target / landmark / points were three dependent ones). The per-landmark sums
-      // (H_ff, g_f in LDS; the host and extrinsic coupling in the window's W) are gathered by the factor threads
-      // themselves with atomics, like in the solver: no second pass over the landmarks' factor lists.
-      VIO_PARFOR(slot, (S0 - c0 < CH ? S0 - c0 : CH)) {
-        const int rec = v.srec_i[c0 + slot];
-        double pij[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) pij[c] = v.srec_d[6 * (size_t)(c0 + slot) + c];
-        if (rec < 0) continue;
-        const int t = (rec >> 8) & 255, f = rec >> 16;
-        if ((rec & 255) != 0 || t == P) continue;
-        double r[2], Ji[12], Jj[12], Jex[12], Jl[2];
-        projection_eval(v.s_info, xpose, xpose + 7 * t, ex, xfeat[f], pij, pij + 3, true, r, Ji, Jj, Jex, Jl);
-        double sq = r[0] * r[0] + r[1] * r[1];
-        double sr = sqrt(1.0 / (1.0 + sq * cc));
-        auto g = G + slot * kMargSlot; auto gx = g + kSlotStride;
-#pragma unroll
-        for (int rr = 0; rr < 2; rr++) {
-#pragma unroll
+    // The global-matrix instantiation (W > 12, 512 work-items) keeps the pass of rounds 3-9 -- rows of 14 + 6 columns, three
+    // products per step, a bucket flushed per chunk: with the pass below its register allocation came out with a third more scratch
+    // reloads over the whole kernel and the W = 20 leg of the benchmark 0.3 % slower, for a phase that is a smaller share of those
+    // solves. wide: compile-time on the device (the launch says which), m.wide on the emulator.
+    if (wide) {
+      const double cc = 1.0 / v.cauchy_b;
+      int S0 = 0, nb0 = 0;  // buckets (0, t < P) come first in the (host, target) order
+      for (int p = 0; p < v.npairs && v.pair_h[p] == 0; p++)
+        if (v.pair_t[p] != P) S0 = (v.pair_s1[p] + 1) & ~1, nb0 = p + 1;
+      auto G = m.stage;
+      const int CH = m.stage_slots;
+      if (CH < 2) {  // launcher guarantees staging space; never loop forever on a bad carve
+        if (cx.tid == 0) out.n[0] = -3, out.n[1] = 0;
+        return;
+      }
+      // bucket descriptors (0, t): one per lane, fetched once (a dependent global round trip per Gram round otherwise)
+      const int lane_d = VIO_TID(cx) & 63;
+      const bool dv = lane_d < nb0;
+      const int d_s0 = dv ? v.pair_s0[lane_d] : 0, d_s1 = dv ? v.pair_s1[lane_d] : 0;
+      const int d_t = dv ? ((v.pair_h[lane_d] != 0 || v.pair_t[lane_d] == P) ? -1 : v.pair_t[lane_d]) : -1;
+      for (int c0 = 0; c0 < S0; c0 += CH) {
+        // The factors hosted at frame 0 occupy the staging slots [0, S0) of the solver's slot order: the slot records built
+        // at the start of the solve (srec_i / srec_d) give host | target | landmark and the observation pair in ONE global
+        // round trip per pass (factor index -> target / landmark / points were three dependent ones). The per-landmark sums
+        // (H_ff, g_f in LDS; the host and extrinsic coupling in the window's W) are gathered by the factor threads
+        // themselves with atomics, like in the solver: no second pass over the landmarks' factor lists.
+        VIO_PARFOR(slot, (S0 - c0 < CH ? S0 - c0 : CH)) {
+          const int rec = v.srec_i[c0 + slot];
+          double pij[6];
+  #pragma unroll
+          for (int c = 0; c < 6; c++) pij[c] = v.srec_d[6 * (size_t)(c0 + slot) + c];
+          if (rec < 0) continue;
+          const int t = (rec >> 8) & 255, f = rec >> 16;
+          if ((rec & 255) != 0 || t == P) continue;
+          double r[2], Ji[12], Jj[12], Jex[12], Jl[2];
+          projection_eval(v.s_info, xpose, xpose + 7 * t, ex, xfeat[f], pij, pij + 3, true, r, Ji, Jj, Jex, Jl);
+          double sq = r[0] * r[0] + r[1] * r[1];
+          double sr = sqrt(1.0 / (1.0 + sq * cc));
+          auto g = G + slot * kWideSlot; auto gx = g + kWideStride;
+  #pragma unroll
+          for (int rr = 0; rr < 2; rr++) {
+  #pragma unroll
+            for (int c = 0; c < 6; c++) {
+              g[rr * kWideRow + c] = Ji[rr * 6 + c] * sr, g[rr * kWideRow + 6 + c] = Jj[rr * 6 + c] * sr;
+              gx[rr * kWideRowX + c] = Jex[rr * 6 + c] * sr;
+            }
+            g[rr * kWideRow + 12] = r[rr] * sr, g[rr * kWideRow + 13] = Jl[rr] * sr;
+          }
+          const double s2 = sr * sr;
+          double *wf = v.WTf + (size_t)f * v.n6cap;
+  #pragma unroll
           for (int c = 0; c < 6; c++) {
-            g[rr * kRowLen + c] = Ji[rr * 6 + c] * sr, g[rr * kRowLen + 6 + c] = Jj[rr * 6 + c] * sr;
-            gx[rr * kMargRowX + c] = Jex[rr * 6 + c] * sr;
+            wf[6 * t + c] = (Jj[c] * Jl[0] + Jj[6 + c] * Jl[1]) * s2;  // target-frame coupling: one writer per (feature, frame)
+            VIO_ATOMIC_ADD(wf + c, (Ji[c] * Jl[0] + Ji[6 + c] * Jl[1]) * s2);
+            VIO_ATOMIC_ADD(wf + 6 * P + c, (Jex[c] * Jl[0] + Jex[6 + c] * Jl[1]) * s2);
           }
-          g[rr * kRowLen + 12] = r[rr] * sr, g[rr * kRowLen + 13] = Jl[rr] * sr;
+          VIO_ATOMIC_ADD(m.hff + f, (Jl[0] * Jl[0] + Jl[1] * Jl[1]) * s2);
+          VIO_ATOMIC_ADD(m.gf + f, (Jl[0] * r[0] + Jl[1] * r[1]) * s2);
         }
-        const double s2 = sr * sr;
-        double *wf = v.WTf + (size_t)f * v.n6cap;
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          wf[6 * t + c] = (Jj[c] * Jl[0] + Jj[6 + c] * Jl[1]) * s2;  // target-frame coupling: one writer per (feature, frame)
-          VIO_ATOMIC_ADD(wf + c, (Ji[c] * Jl[0] + Ji[6 + c] * Jl[1]) * s2);
-          VIO_ATOMIC_ADD(wf + 6 * P + c, (Jex[c] * Jl[0] + Jex[6 + c] * Jl[1]) * s2);
-        }
-        VIO_ATOMIC_ADD(m.hff + f, (Jl[0] * Jl[0] + Jl[1] * Jl[1]) * s2);
-        VIO_ATOMIC_ADD(m.gf + f, (Jl[0] * r[0] + Jl[1] * r[1]) * s2);
-      }
-      VIO_SYNC();
-      stamp(cx, ST_M_FACT);
-      // one element of the three Gram matrices of bucket (0, t)
-      auto flush1 = [&](int t, int row, int col, double val) {  // G1^T G1
-        const int c0p = m.col_pose[0], ctp = m.col_pose[t];
-        if (row < 6) {
-          if (col <= row) VIO_ATOMIC_ADD(m.Am + tri_at(c0p + row, c0p + col), val);
-        } else if (row < 12) {
-          if (col < 6) add_lower(ctp + row - 6, c0p + col, val);
-          else if (col < 12 && col <= row) VIO_ATOMIC_ADD(m.Am + tri_at(ctp + row - 6, ctp + col - 6), val);
-        } else if (row == 12) {
-          if (col < 6) VIO_ATOMIC_ADD(m.bm + c0p + col, val);
-          else if (col < 12) VIO_ATOMIC_ADD(m.bm + ctp + col - 6, val);
-        }
-      };
-      auto flush2 = [&](int t, int row, int col, double val) {  // Gx^T G1: rows = extrinsic components
-        if (row >= 6) return;
-        const int cx0 = m.col_ex[0];
-        if (col < 6) add_lower(cx0 + row, m.col_pose[0] + col, val);
-        else if (col < 12) add_lower(cx0 + row, m.col_pose[t] + col - 6, val);
-        else if (col == 12) VIO_ATOMIC_ADD(m.bm + cx0 + row, val);
-      };
-      auto flush3 = [&](int row, int col, double val) {  // Gx^T Gx
-        if (row < 6 && col <= row) VIO_ATOMIC_ADD(m.Am + tri_at(m.col_ex[0] + row, m.col_ex[0] + col), val);
-      };
-      {
-        const int tid_ = VIO_TID(cx), wave = __builtin_amdgcn_readfirstlane(tid_ >> 6), nw = cx.nt >> 6, lane = tid_ & 63;
-        const int li = lane & 15, kq = lane >> 4;
-        for (int p = wave; p < nb0 && p < 64; p += nw) {
-          const int b_s0 = __builtin_amdgcn_readlane(d_s0, p), b_s1 = __builtin_amdgcn_readlane(d_s1, p);
-          const int t = __builtin_amdgcn_readlane(d_t, p);
-          if (t < 0) continue;
-          const int s_lo = b_s0 > c0 ? b_s0 : c0, s_hi = b_s1 < c0 + CH ? b_s1 : c0 + CH;
-          if (s_lo >= s_hi) continue;
-          v4d a1 = {0.0, 0.0, 0.0, 0.0}, a2 = a1, a3 = a1;
-          const bool lv = li < kRowLen, lx = li < kMargRowX;
-          const int go = (s_lo - c0 + (kq >> 1)) * kMargSlot + (kq & 1) * kRowLen + (lv ? li : 0);
-          const int gxo = (s_lo - c0 + (kq >> 1)) * kMargSlot + kSlotStride + (kq & 1) * kMargRowX + (lx ? li : 0);
-          const int nsteps = (s_hi - s_lo + 1) >> 1;
-          constexpr int kB = 6;  // two-factor steps whose operands are fetched together
-          for (int st0 = 0; st0 < nsteps; st0 += kB) {
-            double av[kB], xv[kB];
-#pragma unroll
-            for (int j = 0; j < kB; j++) {
-              const bool in = st0 + j < nsteps && s_lo + 2 * (st0 + j) + (kq >> 1) < s_hi;  // odd tail: no second factor
-              av[j] = G[in ? go + 2 * (st0 + j) * kMargSlot : 0], xv[j] = G[in ? gxo + 2 * (st0 + j) * kMargSlot : 0];
+        VIO_SYNC();
+        stamp(cx, ST_M_FACT);
+        // one element of the three Gram matrices of bucket (0, t)
+        auto flush1 = [&](int t, int row, int col, double val) {  // G1^T G1
+          const int c0p = m.col_pose[0], ctp = m.col_pose[t];
+          if (row < 6) {
+            if (col <= row) VIO_ATOMIC_ADD(m.Am + tri_at(c0p + row, c0p + col), val);
+          } else if (row < 12) {
+            if (col < 6) add_lower(ctp + row - 6, c0p + col, val);
+            else if (col < 12 && col <= row) VIO_ATOMIC_ADD(m.Am + tri_at(ctp + row - 6, ctp + col - 6), val);
+          } else if (row == 12) {
+            if (col < 6) VIO_ATOMIC_ADD(m.bm + c0p + col, val);
+            else if (col < 12) VIO_ATOMIC_ADD(m.bm + ctp + col - 6, val);
+          }
+        };
+        auto flush2 = [&](int t, int row, int col, double val) {  // Gx^T G1: rows = extrinsic components
+          if (row >= 6) return;
+          const int cx0 = m.col_ex[0];
+          if (col < 6) add_lower(cx0 + row, m.col_pose[0] + col, val);
+          else if (col < 12) add_lower(cx0 + row, m.col_pose[t] + col - 6, val);
+          else if (col == 12) VIO_ATOMIC_ADD(m.bm + cx0 + row, val);
+        };
+        auto flush3 = [&](int row, int col, double val) {  // Gx^T Gx
+          if (row < 6 && col <= row) VIO_ATOMIC_ADD(m.Am + tri_at(m.col_ex[0] + row, m.col_ex[0] + col), val);
+        };
+        {
+          const int tid_ = VIO_TID(cx), wave = __builtin_amdgcn_readfirstlane(tid_ >> 6), nw = cx.nt >> 6, lane = tid_ & 63;
+          const int li = lane & 15, kq = lane >> 4;
+          for (int p = wave; p < nb0 && p < 64; p += nw) {
+            const int b_s0 = __builtin_amdgcn_readlane(d_s0, p), b_s1 = __builtin_amdgcn_readlane(d_s1, p);
+            const int t = __builtin_amdgcn_readlane(d_t, p);
+            if (t < 0) continue;
+            const int s_lo = b_s0 > c0 ? b_s0 : c0, s_hi = b_s1 < c0 + CH ? b_s1 : c0 + CH;
+            if (s_lo >= s_hi) continue;
+            v4d a1 = {0.0, 0.0, 0.0, 0.0}, a2 = a1, a3 = a1;
+            const bool lv = li < kWideRow, lx = li < kWideRowX;
+            const int go = (s_lo - c0 + (kq >> 1)) * kWideSlot + (kq & 1) * kWideRow + (lv ? li : 0);
+            const int gxo = (s_lo - c0 + (kq >> 1)) * kWideSlot + kWideStride + (kq & 1) * kWideRowX + (lx ? li : 0);
+            const int nsteps = (s_hi - s_lo + 1) >> 1;
+            constexpr int kB = 6;  // two-factor steps whose operands are fetched together
+            for (int st0 = 0; st0 < nsteps; st0 += kB) {
+              double av[kB], xv[kB];
+  #pragma unroll
+              for (int j = 0; j < kB; j++) {
+                const bool in = st0 + j < nsteps && s_lo + 2 * (st0 + j) + (kq >> 1) < s_hi;  // odd tail: no second factor
+                av[j] = G[in ? go + 2 * (st0 + j) * kWideSlot : 0], xv[j] = G[in ? gxo + 2 * (st0 + j) * kWideSlot : 0];
+              }
+              VIO_SCHED_FENCE();
+  #pragma unroll
+              for (int j = 0; j < kB; j++) {
+                const bool in = st0 + j < nsteps && s_lo + 2 * (st0 + j) + (kq >> 1) < s_hi;
+                const double a = (lv && in) ? av[j] : 0.0, x = (lx && in) ? xv[j] : 0.0;
+                if (st0 + j < nsteps) a1 = mfma_f64(a, a, a1), a2 = mfma_f64(x, a, a2), a3 = mfma_f64(x, x, a3);  // (uniform)
+              }
             }
-            VIO_SCHED_FENCE();
-#pragma unroll
-            for (int j = 0; j < kB; j++) {
-              const bool in = st0 + j < nsteps && s_lo + 2 * (st0 + j) + (kq >> 1) < s_hi;
-              const double a = (lv && in) ? av[j] : 0.0, x = (lx && in) ? xv[j] : 0.0;
-              if (st0 + j < nsteps) a1 = mfma_f64(a, a, a1), a2 = mfma_f64(x, a, a2), a3 = mfma_f64(x, x, a3);  // (uniform)
+  #pragma unroll
+            for (int r4 = 0; r4 < 4; r4++) {
+              flush1(t, kq + 4 * r4, li, a1[r4]), flush2(t, kq + 4 * r4, li, a2[r4]), flush3(kq + 4 * r4, li, a3[r4]);
             }
           }
-#pragma unroll
-          for (int r4 = 0; r4 < 4; r4++) {
-            flush1(t, kq + 4 * r4, li, a1[r4]), flush2(t, kq + 4 * r4, li, a2[r4]), flush3(kq + 4 * r4, li, a3[r4]);
-          }
+        }
+        VIO_SYNC();
+        stamp(cx, ST_M_GRAM);
+      }
+    } else {
+      const double cc = 1.0 / v.cauchy_b;
+      int S0 = 0, nb0 = 0;  // buckets (0, t < P) come first in the (host, target) order
+      for (int p = 0; p < v.npairs && v.pair_h[p] == 0; p++)
+        if (v.pair_t[p] != P) S0 = (v.pair_s1[p] + 1) & ~1, nb0 = p + 1;
+      auto G = m.stage;
+      const int CH = m.stage_slots;
+      if (CH < 2) {  // launcher guarantees staging space; never loop forever on a bad carve
+        if (cx.tid == 0) out.n[0] = -3, out.n[1] = 0;
+        return;
+      }
+      // bucket descriptors (0, t): one per lane, fetched once (a dependent global round trip per Gram round otherwise)
+      const int lane_d = VIO_TID(cx) & 63;
+      const bool dv = lane_d < nb0;
+      const int d_s0 = dv ? v.pair_s0[lane_d] : 0, d_s1 = dv ? v.pair_s1[lane_d] : 0;
+      const int d_t = dv ? ((v.pair_h[lane_d] != 0 || v.pair_t[lane_d] == P) ? -1 : v.pair_t[lane_d]) : -1;
+      // The slot records of a chunk (one global round trip) are fetched one chunk ahead, like in the solver (projections_jac): the
+      // fetch of chunk c + 1 travels behind the arithmetic of chunk c (one slot per work-item and chunk whenever a chunk is no larger
+      // than the workgroup).
+      const bool one_pass = CH <= (int)cx.nt;
+      int rec_n = -1;
+      double pij_n[6] = {0, 0, 0, 0, 0, 0};
+      if (one_pass) {
+        const int sl0 = VIO_TID(cx);
+        if (sl0 < S0 && sl0 < CH) {
+          rec_n = v.srec_i[sl0];
+  #pragma unroll
+          for (int c = 0; c < 6; c++) pij_n[c] = v.srec_d[6 * (size_t)sl0 + c];
         }
       }
-      VIO_SYNC();
-      stamp(cx, ST_M_GRAM);
+      // Flush table. A staged row has 16 columns (kMargRow): Ji (6: host translation, rotation) | rotation part of Jj (3) | r |
+      // Jex (6); the translation part of Jj is the negated translation part of Ji (projection_facor.cpp:52-73), so the Gram product
+      // of a bucket is ONE 16 x 16 tile G^T G per two-factor step. Staged column a stands for the Jacobian columns ("images")
+      //   a < 3: (pose 0, a, +) and (pose t, a, -);  a < 6: (pose 0, a, +);  a < 9: (pose t, a - 3, +);  a = 9: r;  else (extrinsic, a - 10, +)
+      // and element (a, b) of the tile goes, with the product of the signs, to the dense entry of every pair (image of a, image of b)
+      // that this lane owns: the pair whose first image comes later in (block, offset) order, or the diagonal. Element (b, a) owns the
+      // others, so every pair of Jacobian columns is added once. J^T r: element (a, 9) carries the first image of a, element (9, b) the
+      // second image of b. Which entries a lane's four elements (rows kq + 4 r4, column li) feed is a property of the lane up to the
+      // bucket's target frame: at most three matrix entries and one of the right-hand side per element. The table is worked out in the
+      // flush itself, from a lane index formed there: a bucket is flushed once, and sixteen table registers kept alive around the chunk
+      // loop cost the 512-work-item instantiation a hundred scratch reloads (its W = 20 leg ran 0.3 % slower with them).
+      // entry = row offset | col offset << 3 | row block << 6 | col block << 8 | negative << 10 | valid << 11; block 0 pose 0, 1 pose t,
+      // 2 extrinsic (the right-hand side uses the row part)
+      auto flush = [&](const v4d &acc, int ctp) {
+        const int lane_f = VIO_TID(cx) & 63, li = lane_f & 15, kq = lane_f >> 4;
+        const int c0p = m.col_pose[0], cx0 = m.col_ex[0];
+        // image k of staged column a: block, offset, sign; false if there is none
+        auto image = [](int a, int k, int &blk, int &off, int &neg) {
+          neg = 0;
+          if (a < 3) return blk = k, off = a, neg = k, true;
+          if (k != 0 || a == 9) return false;
+          if (a < 6) return blk = 0, off = a, true;
+          if (a < 9) return blk = 1, off = a - 3, true;
+          return blk = 2, off = a - 10, true;
+        };
+        auto base = [&](int blk) { return blk == 0 ? c0p : blk == 1 ? ctp : cx0; };
+  #pragma unroll
+        for (int r4 = 0; r4 < 4; r4++) {
+          const int a = kq + 4 * r4, b = li;
+          int em[3] = {0, 0, 0}, n = 0;
+  #pragma unroll
+          for (int ka = 0; ka < 2; ka++)
+  #pragma unroll
+            for (int kb = 0; kb < 2; kb++) {
+              int ba = 0, oa = 0, na = 0, bb = 0, ob = 0, nb = 0;
+              if (!image(a, ka, ba, oa, na) || !image(b, kb, bb, ob, nb)) continue;
+              const bool mine = ba > bb || (ba == bb && oa > ob) || (a == b && ka == kb);
+              if (!mine) continue;
+              const int e = oa | (ob << 3) | (ba << 6) | (bb << 8) | ((na ^ nb) << 10) | (1 << 11);
+              em[0] = n == 0 ? e : em[0], em[1] = n == 1 ? e : em[1], em[2] = n == 2 ? e : em[2];
+              n++;
+            }
+          int bv = 0, ov = 0, nv = 0, ev = 0;
+          if (b == 9 && image(a, 0, bv, ov, nv)) ev = ov | (bv << 6) | (nv << 10) | (1 << 11);
+          if (a == 9 && image(b, 1, bv, ov, nv)) ev = ov | (bv << 6) | (nv << 10) | (1 << 11);
+  #pragma unroll
+          for (int q = 0; q < 3; q++) {
+            const int e = em[q];
+            const int R = base((e >> 6) & 3) + (e & 7), C = base((e >> 8) & 3) + ((e >> 3) & 7);
+            if (e >> 11) VIO_ATOMIC_ADD(m.Am + tri_at(R >= C ? R : C, R >= C ? C : R), ((e >> 10) & 1) ? -acc[r4] : acc[r4]);
+          }
+          if (ev >> 11) VIO_ATOMIC_ADD(m.bm + base((ev >> 6) & 3) + (ev & 7), ((ev >> 10) & 1) ? -acc[r4] : acc[r4]);
+        }
+      };
+      // A wave owns the buckets wave, wave + nw, ... and keeps a bucket's tile in registers until the bucket ends: a bucket that
+      // continues in the next chunk is flushed once, behind its last slot.
+      v4d g_acc = {0.0, 0.0, 0.0, 0.0};
+      VIO_SYNC_LDS();  // m.rot (written ahead of the IMU factor) is read from here on: not left to the IMU part's own barriers
+      for (int c0 = 0; c0 < S0; c0 += CH) {
+        // The factors hosted at frame 0 occupy the staging slots [0, S0) of the solver's slot order: the slot records built
+        // at the start of the solve (srec_i / srec_d) give host | target | landmark and the observation pair in ONE global
+        // round trip per pass (factor index -> target / landmark / points were three dependent ones). The per-landmark sums
+        // (H_ff, g_f in LDS; the host and extrinsic coupling in the window's W) are gathered by the factor threads
+        // themselves with atomics, like in the solver: no second pass over the landmarks' factor lists.
+        VIO_PARFOR(slot, (S0 - c0 < CH ? S0 - c0 : CH)) {
+          int rec;
+          double pij[6];
+          if (one_pass) {
+            rec = rec_n;
+  #pragma unroll
+            for (int c = 0; c < 6; c++) pij[c] = pij_n[c];
+            const int sln = c0 + CH + slot;  // this work-item's slot of the next chunk
+            rec_n = -1;
+            if (sln < S0) {
+              rec_n = v.srec_i[sln];
+  #pragma unroll
+              for (int c = 0; c < 6; c++) pij_n[c] = v.srec_d[6 * (size_t)sln + c];
+            }
+          } else {
+            rec = v.srec_i[c0 + slot];
+  #pragma unroll
+            for (int c = 0; c < 6; c++) pij[c] = v.srec_d[6 * (size_t)(c0 + slot) + c];
+          }
+          if (rec < 0) continue;
+          const int t = (rec >> 8) & 255, f = rec >> 16;
+          if ((rec & 255) != 0 || t == P) continue;
+          double r[2], Ji[12], Jj[12], Jex[12], Jl[2];
+          projection_eval_rot(v.s_info, m.rot, xpose, m.rot + 9 * t, xpose + 7 * t, m.rot + 9 * P, ex, xfeat[f], pij, pij + 3, true, r, Ji, Jj,
+                              Jl, Jex);
+          double sq = r[0] * r[0] + r[1] * r[1];
+          double sr = rsqrt_f(1.0 + sq * cc);  // (>= 1)
+          auto g = G + slot * kMargSlot;
+  #pragma unroll
+          for (int rr = 0; rr < 2; rr++) {
+  #pragma unroll
+            for (int c = 0; c < 6; c++) g[rr * kMargRow + c] = Ji[rr * 6 + c] * sr, g[rr * kMargRow + 10 + c] = Jex[rr * 6 + c] * sr;
+  #pragma unroll
+            for (int c = 3; c < 6; c++) g[rr * kMargRow + 3 + c] = Jj[rr * 6 + c] * sr;
+            g[rr * kMargRow + 9] = r[rr] * sr;
+          }
+          const double s2 = sr * sr;
+          double *wf = v.WTf + (size_t)f * v.n6cap;
+  #pragma unroll
+          for (int c = 0; c < 6; c++) {
+            wf[6 * t + c] = (Jj[c] * Jl[0] + Jj[6 + c] * Jl[1]) * s2;  // target-frame coupling: one writer per (feature, frame)
+            VIO_ATOMIC_ADD(wf + c, (Ji[c] * Jl[0] + Ji[6 + c] * Jl[1]) * s2);
+            VIO_ATOMIC_ADD(wf + 6 * P + c, (Jex[c] * Jl[0] + Jex[6 + c] * Jl[1]) * s2);
+          }
+          VIO_ATOMIC_ADD(m.hff + f, (Jl[0] * Jl[0] + Jl[1] * Jl[1]) * s2);
+          VIO_ATOMIC_ADD(m.gf + f, (Jl[0] * r[0] + Jl[1] * r[1]) * s2);
+        }
+        VIO_SYNC();
+        stamp(cx, ST_M_FACT);
+        {
+          const int tid_ = VIO_TID(cx), wave = __builtin_amdgcn_readfirstlane(tid_ >> 6), nw = cx.nt >> 6, lane = tid_ & 63;
+          const int li = lane & 15, kq = lane >> 4;
+          for (int p = wave; p < nb0 && p < 64; p += nw) {
+            const int b_s0 = __builtin_amdgcn_readlane(d_s0, p), b_s1 = __builtin_amdgcn_readlane(d_s1, p);
+            const int t = __builtin_amdgcn_readlane(d_t, p);
+            if (t < 0) continue;
+            const int s_lo = b_s0 > c0 ? b_s0 : c0, s_hi = b_s1 < c0 + CH ? b_s1 : c0 + CH;
+            if (s_lo >= s_hi) continue;
+            // lane (li, kq): column li of row kq & 1 of the step's factor kq >> 1 -- 64 consecutive doubles of the staging area bar the pad
+            const int go = (s_lo - c0 + (kq >> 1)) * kMargSlot + (kq & 1) * kMargRow + li;
+            const int nsteps = (s_hi - s_lo + 1) >> 1;
+            constexpr int kB = 8;  // two-factor steps whose operands are fetched together
+            for (int st0 = 0; st0 < nsteps; st0 += kB) {
+              double av[kB];
+  #pragma unroll
+              for (int j = 0; j < kB; j++) {
+                const bool in = st0 + j < nsteps && s_lo + 2 * (st0 + j) + (kq >> 1) < s_hi;  // odd tail: no second factor
+                av[j] = G[in ? go + 2 * (st0 + j) * kMargSlot : 0];
+              }
+              VIO_SCHED_FENCE();
+  #pragma unroll
+              for (int j = 0; j < kB; j++) {
+                const bool in = st0 + j < nsteps && s_lo + 2 * (st0 + j) + (kq >> 1) < s_hi;
+                const double a = in ? av[j] : 0.0;
+                if (st0 + j < nsteps) g_acc = mfma_f64(a, a, g_acc);  // (uniform)
+              }
+            }
+            if (s_hi == b_s1) {  // the bucket ends in this chunk
+              flush(g_acc, m.col_pose[t]);
+              const v4d zero = {0.0, 0.0, 0.0, 0.0};
+              g_acc = zero;
+            }
+          }
+        }
+        VIO_SYNC();
+        stamp(cx, ST_M_GRAM);
+      }
     }
     // ---- eliminate the landmarks hosted at frame 0 (pseudo-inverse: e <= eps contributes nothing) --------
     VIO_PARFOR(f, F) {

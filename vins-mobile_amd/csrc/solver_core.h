@@ -583,8 +583,7 @@ VIO_DEV void setup_imu_info(const Ctx &cx, const WinView &v, MP mbox) {
 // Evaluation: cost, and (jac) H -> App / Dss / Css / Asp (unfactored reduced system), WTf, hff, gp, gf, dp
 // =====================================================================================================
 constexpr int kPanelTiles = 5;   // pose matrices of up to 80 rows (W <= 12) keep the fill tiles of the band in registers
-constexpr int kRowLen = 14;      // marginalization phase: staged Jacobian row Ji(6) Jj(6) r Jl
-constexpr int kSlotStride = 29;  // marginalization phase: two rows of 14 + 1 pad (odd stride: conflict-free LDS writes)
+// (the marginalization phase stages its own rows: kMargRow / kMargSlot, marg_core.h)
 // Solver: a staged row is [Ji(6) | Jj(3..5) | r]: the translation part of the target frame's Jacobian is the negated
 // translation part of the host's (projection_facor.cpp:52-73: both are reduce * r_ic^T R_j^T up to the sign) and is
 // rebuilt by the operand fetch of the Gram product; the landmark column only feeds per-landmark sums that the factor

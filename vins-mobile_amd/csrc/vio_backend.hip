@@ -277,7 +277,7 @@ static int plan_layout(vio_backend *be, BatchDims &d, int n, const int *nfeat, i
     const size_t bs = carve_work<double *>(dg, false, kThreadsGlb, nullptr, nullptr, nullptr, nullptr, &se, &tail);
     const size_t bm = (se + tail) * sizeof(double) + carve_marg<double *>(dg, false, nullptr, nullptr, nullptr, 0);
     // (the marginalization phase stages its Jacobian rows in LDS in this variant too: at least 64 slots behind its vectors)
-    const size_t bmm = bm + 64 * kMargSlot * sizeof(double);
+    const size_t bmm = bm + 64 * kWideSlot * sizeof(double);
     if (std::max(bs, bmm) > kLdsLimit) return VIO_ECAP;
     be->d_glb = dg, be->lds_bytes_glb = std::max(bs, bmm);
   }

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(NT, 2) void vio_window_kernel(BatchPtrs B_, MargPtr
     // FAILURE and returns VIO_ETIMEOUT from the download)
     if (cx.tid == 0 && coop_flags(v)[2]) v.stats_i[1] = -9;
   }
-  marginalize_window_impl(cx, fresh(), w.xpose, w.xsb, w.xfeat, w.ex, mw, mo);
+  marginalize_window_impl<LDS_MATRIX ? 0 : 1>(cx, fresh(), w.xpose, w.xsb, w.xfeat, w.ex, mw, mo);
   if (cx.prof && cx.tid == cx.prof_tid) {  // stage counters: LDS -> global
     cx.lprof[ST_TOTAL] += clock64();
     for (int q = 0; q < ST_COUNT; q++) cx.prof[q] = cx.lprof[q];
