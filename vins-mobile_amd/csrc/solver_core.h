@@ -418,12 +418,10 @@ VIO_DEV void setup_imu_info_gj(const Ctx &cx, const WinView &v, MP mbox) {
 //     J^T r = b0 + H0 dx,    cost = |r0|^2 / 2 + b0 . dx + dx . (H0 dx) / 2,    J^T J = H0,
 // so one symmetric mat-vec per evaluation serves the cost-only and the Jacobian evaluations alike (the first version
 // did r0 + J0 dx and J0^T r: two passes over two copies of J0). Here: the column map, H0 and b0, once per solve.
+//
+// The column map (behind a barrier that follows the -1 pass: the prior's blocks need not tile its columns)
 template <class WK>
-VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
-  const int n = v.prior_n;
-  if (n <= 0) return;
-  VIO_PARFOR(a, n) w.prcol[a] = -1;
-  VIO_SYNC();
+VIO_DEV void prior_column_map(const Ctx &cx, const WinView &v, WK &w) {
   VIO_PARFOR(b, v.prior_nb) {
     int kind = v.pr_kind[b], idx = v.pr_index[b], o = v.pr_offset[b];
     if (kind == 0)
@@ -431,13 +429,68 @@ VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
     else if (kind == 1)
       for (int k = 0; k < 9; k++) w.prcol[o + k] = (idx << 8) | (6 + k);
   }
+}
+
+// H0 in the layout of the reduced matrix, constant during the solve: pose x pose -> App, speed-bias x speed-bias -> Dss / Css
+// (copied into place by every linearization), speed-bias x pose -> Apri (read where it is needed). x = H0 at prior columns whose
+// reduced columns are pa >= pb >= 0.
+VIO_DEV void prior_place(const WinView &v, int napp, int pa, int pb, double x) {
+  const int fr = pa >> 8, cr = pa & 255, fc = pb >> 8, cc = pb & 255;
+  if (cr < 6 && cc < 6) v.AppPr[tri_at(6 * fr + cr, 6 * fc + cc)] = x;
+  else if (cr >= 6 && cc >= 6) {
+    if (fr == fc) v.AppPr[napp + fr * kSS + (cr - 6) * kSB + (cc - 6)] = x;
+    else if (fr - fc == 1) v.AppPr[napp + v.P * kSS + fr * kSS + (cc - 6) * kSB + (cr - 6)] = x;
+  } else if (cr >= 6) v.Apri[(cr - 6) * v.jp + 6 * fc + cc] = x;
+  else v.Apri[(cc - 6) * v.jp + 6 * fr + cr] = x;
+}
+
+// ACC (round 11, the LDS instantiations; solve_window's head has built the column map): no pass waits for one value at a time. The
+// constant part of the reduced matrix is zeroed first (stores only), J0 comes to LDS kU loads per work-item at a time, and an
+// element of H0 goes from the accumulator that holds it to prH0 AND to its place in AppPr / Apri -- the pass that read prH0 back,
+// n^2 / work-items dependent round trips behind a barrier, is gone. The values are the ones that pass copied: nothing is rounded
+// differently. !ACC (the global-matrix instantiation): the passes as they were, column map included -- that instantiation keeps
+// the old head of solve_window, which does not build the map (with the new head its register allocation came out with 130 more
+// scratch reloads, 312 -> 443, spread over evaluate() and the iteration loop: DESIGN section 0, round 11).
+template <bool ACC, class WK>
+VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
+  const int n = v.prior_n;
+  if (n <= 0) return;
+  const int napp = (int)tri_doubles(v.nrows), nband = 2 * v.P * kSS;
   // J0 goes through the (not yet assembled) matrix buffer when it fits: the n^2 dot products then read LDS
   const bool stage = (size_t)n * n <= (size_t)w.nstage;
   auto Js = w.stage;
-  if (stage) {
-    VIO_PARFOR(q, n * n) Js[q] = v.pr_J[q];
+  if constexpr (ACC) {
+    VIO_PARFOR(q, kSB * v.jp) v.Apri[q] = 0.0;
+    VIO_PARFOR(q, napp + nband) v.AppPr[q] = 0.0;
+    constexpr int kU = 12;
+    const int tid_ = VIO_TID(cx), nt_ = (int)cx.nt, nn = n * n;
+    if (stage) {
+      for (int q0 = tid_; q0 < nn; q0 += kU * nt_) {
+        double x[kU];
+#pragma unroll
+        for (int u = 0; u < kU; u++) {
+          const int q = q0 + u * nt_;
+          x[u] = v.pr_J[q < nn ? q : 0];
+        }
+        VIO_SCHED_FENCE();
+#pragma unroll
+        for (int u = 0; u < kU; u++) {
+          const int q = q0 + u * nt_;
+          if (q < nn) Js[q] = x[u];
+        }
+      }
+    }
     VIO_SYNC();
+  } else {
+    VIO_PARFOR(a, n) w.prcol[a] = -1;
+    VIO_SYNC();
+    prior_column_map(cx, v, w);
+    if (stage) {
+      VIO_PARFOR(q, n * n) Js[q] = v.pr_J[q];
+      VIO_SYNC();
+    }
   }
+  stamp(cx, ST_D5);  // J0 to LDS; ACC: and the zeroing, !ACC: and the column map
   // H0 = J0^T J0 on the matrix cores: one 16 x 16 tile of the lower triangle per wave visit (mirrored on store), the
   // k loop in chunks of 8 steps whose 16 operand fetches (4 row segments of 128 B each) are issued together
   {
@@ -467,20 +520,41 @@ VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
           const bool vk = 4 * (s0 + j) + kq < n;
           av[j] = (va && vk) ? av[j] : 0.0, bv[j] = (vb && vk) ? bv[j] : 0.0;
         }
+        if constexpr (ACC) {
+          // (the four waves' matrix instructions do not overlap -- DESIGN section 0, round 10 --, so the steps behind the last one
+          // of the final chunk, all zeros, are skipped: they were a fifth of the n = 75 product's time)
 #pragma unroll
-        for (int j = 0; j < kChunk; j += 2) acc0 = mfma_f64(av[j], bv[j], acc0), acc1 = mfma_f64(av[j + 1], bv[j + 1], acc1);
+          for (int j = 0; j < kChunk; j += 2) {
+            if (s0 + j < ksteps) acc0 = mfma_f64(av[j], bv[j], acc0);
+            if (s0 + j + 1 < ksteps) acc1 = mfma_f64(av[j + 1], bv[j + 1], acc1);
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < kChunk; j += 2) acc0 = mfma_f64(av[j], bv[j], acc0), acc1 = mfma_f64(av[j + 1], bv[j + 1], acc1);
+        }
       }
       acc0 += acc1;
+      // ACC: an entry of the reduced layout is the H0 element whose row comes behind its column in the reduced order (pa >= pb): in a
+      // tile off the diagonal the accumulator stands for both (a, b) and (b, a), in a diagonal tile each of the two has an
+      // accumulator element of its own.
+      const int pb0 = (ACC && vb) ? w.prcol[cb] : -1;
 #pragma unroll
       for (int r = 0; r < 4; r++) {  // element r: row 16 ti + kq + 4 r, column 16 tj + li
         const int a = 16 * ti + kq + 4 * r, b = cb;
         if (a < n && b < n) {
-          v.prH0[a * n + b] = acc0[r];
-          if (ti != tj) v.prH0[b * n + a] = acc0[r];
+          const double x = acc0[r];
+          v.prH0[a * n + b] = x;
+          if (ti != tj) v.prH0[b * n + a] = x;
+          if constexpr (ACC) {
+            int pa = w.prcol[a], pb = pb0;
+            if (ti != tj && pa < pb) pa = pb0, pb = w.prcol[a];
+            if (pb >= 0 && pa >= pb) prior_place(v, napp, pa, pb, x);
+          }
         }
       }
     }
   }
+  stamp(cx, ST_S0);  // Gram loop (ACC: and scatter), the clock's wave alone
   VIO_PARFOR(a, n) {
     double s = 0;
     if (stage) {
@@ -490,23 +564,17 @@ VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
     }
     v.prb0[a] = s;
   }
-  const int napp = (int)tri_doubles(v.nrows), nband = 2 * v.P * kSS;
-  VIO_PARFOR(q, kSB * v.jp) v.Apri[q] = 0.0;
-  VIO_PARFOR(q, napp + nband) v.AppPr[q] = 0.0;
-  VIO_SYNC();
-  // H0 in the layout of the reduced matrix, constant during the solve: pose x pose -> App, speed-bias x speed-bias ->
-  // Dss / Css (copied into place by every linearization), speed-bias x pose -> Apri (read where it is needed)
-  VIO_PARFOR(q, n * n) {
-    const int a = q / n, b = q - a * n, pa = w.prcol[a], pb = w.prcol[b];
-    if (pa < 0 || pb < 0 || pa < pb) continue;
-    const int fr = pa >> 8, cr = pa & 255, fc = pb >> 8, cc = pb & 255;
-    const double x = v.prH0[q];
-    if (cr < 6 && cc < 6) v.AppPr[tri_at(6 * fr + cr, 6 * fc + cc)] = x;
-    else if (cr >= 6 && cc >= 6) {
-      if (fr == fc) v.AppPr[napp + fr * kSS + (cr - 6) * kSB + (cc - 6)] = x;
-      else if (fr - fc == 1) v.AppPr[napp + v.P * kSS + fr * kSS + (cc - 6) * kSB + (cr - 6)] = x;
-    } else if (cr >= 6) v.Apri[(cr - 6) * v.jp + 6 * fc + cc] = x;
-    else v.Apri[(cc - 6) * v.jp + 6 * fr + cr] = x;
+  stamp(cx, ST_S1);  // b0
+  if constexpr (!ACC) {
+    VIO_PARFOR(q, kSB * v.jp) v.Apri[q] = 0.0;
+    VIO_PARFOR(q, napp + nband) v.AppPr[q] = 0.0;
+    VIO_SYNC();
+    stamp(cx, ST_S2);  // zeroing + the barrier that ends the Gram loop and b0 of every wave
+    VIO_PARFOR(q, n * n) {
+      const int a = q / n, b = q - a * n, pa = w.prcol[a], pb = w.prcol[b];
+      if (pa < 0 || pb < 0 || pa < pb) continue;
+      prior_place(v, napp, pa, pb, v.prH0[q]);
+    }
   }
   VIO_SYNC();
 }
@@ -530,6 +598,7 @@ VIO_DEV void setup_imu_info(const Ctx &cx, const WinView &v, MP mbox) {
   bool all_good = true;
   if (cx.tid == 0) mbox[nw * kTile] = 0.0;  // (fallback flag)
   VIO_SYNC();
+  stamp(cx, ST_S3);  // the zeroing passes (fh, PP, imu_J) and their barrier; ST_SETUP_IMU is then cov^-1 alone
   for (int f = wave; f < W; f += nw) {
     const double *cov = v.preint + f * kPreintDoubles + 242;
     double c4[4];
@@ -3002,8 +3071,19 @@ template <class WK>
 VIO_DEV void init_band_reach(const Ctx &cx, const WinView &v, WK &w) {
   VIO_PARFOR(k, v.P) {
     int lo = 6 * (k > 0 ? k - 1 : 0), pr = 0;
-    for (int b = 0; b < v.prior_nb; b++)
-      if (v.pr_kind[b] == 1 && v.pr_index[b] == k) lo = 0, pr = 1;
+    constexpr int kB = 8;  // (blocks per round trip: the header was read one value at a time)
+    for (int b0 = 0; b0 < v.prior_nb; b0 += kB) {
+      int kind[kB], idx[kB];
+#pragma unroll
+      for (int j = 0; j < kB; j++) {
+        const int b = b0 + j < v.prior_nb ? b0 + j : b0;
+        kind[j] = v.pr_kind[b], idx[j] = v.pr_index[b];
+      }
+      VIO_SCHED_FENCE();
+#pragma unroll
+      for (int j = 0; j < kB; j++)
+        if (kind[j] == 1 && idx[j] == k) lo = 0, pr = 1;
+    }
     w.sbr[2 * k] = lo, w.sbr[2 * k + 1] = pr;
   }
 }
@@ -3072,37 +3152,93 @@ VIO_DEV void coop_helper(const Ctx &cx, const WinView &v, WK &w) {
 template <bool REGS, int NW, class WK, class VP, class WP>
 VIO_DEV void solve_window(const Ctx &cx, const WinView &v, WK &w, const VP &fresh, const WP &fresh_work) {
   const int P = v.P, F = v.F;
-  VIO_PARFOR(q, P * 7) w.xpose[q] = v.pose0[q];
-  VIO_PARFOR(q, P * 9) w.xsb[q] = v.sb0[q];
-  VIO_PARFOR(q, F) w.xfeat[q] = v.feat0[q];
-  VIO_PARFOR(q, 7) w.ex[q] = v.ex[q];
-  if (v.has_loop) VIO_PARFOR(q, 7) w.xpose[7 * P + q] = v.pose0[7 * v.loop_frame + q];  // VINS.cpp:590-591
-  VIO_PARFOR(q, v.nblk * kBS) w.t1[q] = 0.0, w.t2[q] = 0.0;
-  if (cx.tid == 0) w.flag[0] = w.flag[1] = w.flag[2] = w.flag[3] = 0;
-  init_band_reach(cx, v, w);
-  VIO_SYNC();
-  if (cx.prof && cx.tid == cx.prof_tid) {
+  if (cx.prof && cx.tid == cx.prof_tid) {  // (the clock starts ahead of the state load: round 11 times the whole set-up)
     for (int q = 0; q < ST_COUNT; q++) cx.lprof[q] = 0;
     cx.lprof[ST_COUNT - 1] = clock64();
     cx.lprof[ST_TOTAL] = -cx.lprof[ST_COUNT - 1];
   }
-  VIO_PARFOR(q, v.nslots) v.sfact[q] = -1;
-  VIO_SYNC();
-  VIO_PARFOR(q, v.nslots) v.srec_i[q] = -1;
-  VIO_SYNC();
-  VIO_PARFOR(k, v.M) {
-    const int sl = v.fslot[k];
-    v.sfact[sl] = k;
-    v.srec_i[sl] = v.fhost[k] | (v.ftarget[k] << 8) | (v.ffeat[k] << 16);
-    double *d = v.srec_d + 6 * (size_t)sl;
-    for (int c = 0; c < 3; c++) d[c] = v.pts_i[3 * k + c], d[3 + c] = v.pts_j[3 * k + c];
+  if constexpr (REGS) {
+    // Round 11, the LDS instantiations: the fetches of a phase are issued together. The state: a work-item's first element of
+    // every array is fetched before any of them is stored (one round trip, not four).
+    const int t = VIO_TID(cx), nt_ = (int)cx.nt;
+    const double xp = v.pose0[t < P * 7 ? t : 0], xs = v.sb0[t < P * 9 ? t : 0], xe = v.ex[t < 7 ? t : 0];
+    const double xf = *(t < F ? v.feat0 + t : v.pose0);  // (a window may have no landmark at all)
+    const double xl = v.pose0[(v.has_loop ? 7 * v.loop_frame : 0) + (t < 7 ? t : 0)];  // VINS.cpp:590-591
+    VIO_SCHED_FENCE();
+    if (t < P * 7) w.xpose[t] = xp;
+    if (t < P * 9) w.xsb[t] = xs;
+    if (t < F) w.xfeat[t] = xf;
+    if (t < 7) w.ex[t] = xe;
+    if (v.has_loop && t < 7) w.xpose[7 * P + t] = xl;
+    for (int q = t + nt_; q < P * 7; q += nt_) w.xpose[q] = v.pose0[q];
+    for (int q = t + nt_; q < P * 9; q += nt_) w.xsb[q] = v.sb0[q];
+    for (int q = t + nt_; q < F; q += nt_) w.xfeat[q] = v.feat0[q];
+  } else {  // (the global-matrix instantiation keeps the head it had: the batched state load alone costs it 130 scratch reloads elsewhere)
+    VIO_PARFOR(q, P * 7) w.xpose[q] = v.pose0[q];
+    VIO_PARFOR(q, P * 9) w.xsb[q] = v.sb0[q];
+    VIO_PARFOR(q, F) w.xfeat[q] = v.feat0[q];
+    VIO_PARFOR(q, 7) w.ex[q] = v.ex[q];
+    if (v.has_loop) VIO_PARFOR(q, 7) w.xpose[7 * P + q] = v.pose0[7 * v.loop_frame + q];  // VINS.cpp:590-591
   }
+  VIO_PARFOR(q, v.nblk * kBS) w.t1[q] = 0.0, w.t2[q] = 0.0;
+  if (cx.tid == 0) w.flag[0] = w.flag[1] = w.flag[2] = w.flag[3] = 0;
+  init_band_reach(cx, v, w);
+  if constexpr (REGS) {
+    VIO_PARFOR(a, v.prior_n) w.prcol[a] = -1;  // (the prior's column map, filled behind the barrier: setup_prior<true> expects it)
+    VIO_PARFOR(q, v.nslots) v.sfact[q] = -1, v.srec_i[q] = -1;
+    VIO_SYNC();
+    stamp(cx, ST_X1);  // state load, cleared slot and column maps
+    prior_column_map(cx, v, w);
+    // slot records: the index and point fetches of kT factors per work-item in flight together, then the stores
+    constexpr int kT = 4;
+    const int t = VIO_TID(cx), nt_ = (int)cx.nt, M = v.M;
+    for (int k0 = t; k0 < M; k0 += kT * nt_) {
+      int sl[kT], rec[kT];
+      double pt[kT][6];
+#pragma unroll
+      for (int u = 0; u < kT; u++) {
+        const int k = k0 + u * nt_, kc = k < M ? k : 0;
+        sl[u] = v.fslot[kc];
+        rec[u] = v.fhost[kc] | (v.ftarget[kc] << 8) | (v.ffeat[kc] << 16);
+#pragma unroll
+        for (int c = 0; c < 3; c++) pt[u][c] = v.pts_i[3 * kc + c], pt[u][3 + c] = v.pts_j[3 * kc + c];
+      }
+      VIO_SCHED_FENCE();
+#pragma unroll
+      for (int u = 0; u < kT; u++) {
+        const int k = k0 + u * nt_;
+        if (k < M) {
+          v.sfact[sl[u]] = k;
+          v.srec_i[sl[u]] = rec[u];
+          double *d = v.srec_d + 6 * (size_t)sl[u];
+#pragma unroll
+          for (int c = 0; c < 6; c++) d[c] = pt[u][c];
+        }
+      }
+    }
+  } else {
+    VIO_SYNC();
+    stamp(cx, ST_X1);  // state load
+    VIO_PARFOR(q, v.nslots) v.sfact[q] = -1;
+    VIO_SYNC();
+    VIO_PARFOR(q, v.nslots) v.srec_i[q] = -1;
+    VIO_SYNC();
+    VIO_PARFOR(k, v.M) {
+      const int sl = v.fslot[k];
+      v.sfact[sl] = k;
+      v.srec_i[sl] = v.fhost[k] | (v.ftarget[k] << 8) | (v.ffeat[k] << 16);
+      double *d = v.srec_d + 6 * (size_t)sl;
+      for (int c = 0; c < 3; c++) d[c] = v.pts_i[3 * k + c], d[3 + c] = v.pts_j[3 * k + c];
+    }
+  }
+  stamp(cx, ST_X2);  // slot records (the clock's wave alone: the barrier behind them is build_gram_pieces' first)
   build_gram_pieces(cx, v, w);
+  stamp(cx, ST_X3);
   VIO_PARFOR(f, F) w.fh[f] = v.fstart[f + 1] > v.fstart[f] ? v.fhost[v.fstart[f]] : -1;
   VIO_PARFOR(q, (int)tri_doubles(v.nrows)) v.PP[q] = 0.0;  // (blocks without a (host, target) bucket stay zero for the whole solve)
   setup_imu_info(cx, fresh(), w.stage);
   stamp(cx, ST_SETUP_IMU);
-  setup_prior(cx, fresh(), w);
+  setup_prior<REGS>(cx, fresh(), w);
   stamp(cx, ST_SETUP_PRIOR);
 
   minimize<REGS, NW>(cx, v, w, fresh, fresh_work);

@@ -128,6 +128,7 @@ enum Stage {
   ST_B_INIT, ST_B_POSE, ST_B_ASP, ST_B_BAND, ST_B_GN,  // backsolve: copies; pose tiles; A_sp z_p; band chains (+ landmarks); GN step
   ST_E_HEAD, ST_E_COPY, ST_E_H0DX, ST_E_TAIL,      // evaluate(jac): rotations + zeroing; AppPr + PP copy (+ raw IMU); H0 dx + diagonal blocks; diag / scaling tail
   ST_X0, ST_X1, ST_X2, ST_X3,
+  ST_S0, ST_S1, ST_S2, ST_S3,                       // round 11: the set-up's inner intervals together with D5 and X1 .. X3 (solve_window, setup_prior)
   ST_COUNT = 64                                    // (last slot = time of the previous stamp)
 };
 
