@@ -125,7 +125,9 @@ typedef struct VioPrior {
 
 /* One sliding window as solve_ceres sees it after old2new() (VINS.cpp:505).  */
 typedef struct VioWindow {
-  int32_t window_size; /* W */
+  int32_t window_size; /* W, 1 <= W <= cfg.window_size (VIO_EINVAL below, VIO_ECAP
+                          above); the windows of one batch may differ in W: the batch
+                          is laid out for its largest, every window solved at its own */
   int32_t n_features;  /* rows of inv_depth in use = getFeatureCount()        */
   int32_t n_factors;   /* M projection factors, grouped by feature in
                           ascending feature order as VINS.cpp:528-567 emits

@@ -20,14 +20,28 @@ using namespace vio;
 // how many cooperative shares the band's trailing product is dealt out to (run one after the other by the one emulated workgroup)
 extern "C" void simt_set_syrk_shares(int n) { vio::simt_syrk_shares() = n < 1 ? 1 : n; }
 
-extern "C" int simt_solve_window(const VioConfig *cfg, VioWindow *win, VioSolveStats *stats, int nthreads, int variant,
-                                 int order) {
+// caps = {Wcap, Fcap, Mcap, Ncap, Flds, loop_cap}: the capacities of the batch the window is laid out in, as the launcher
+// (vio_backend.hip backend_upload_impl / plan_layout) sizes them for the largest window of a batch -- 0: the window's own, what
+// simt_solve_window passes. loop_cap: the layout has room for a relocalization pose although this window has none (another
+// window of the batch carries one). Ncap > 0: max(6 Wcap + 15, Ncap), the launcher's prior capacity. VIO_EINVAL for a
+// capacity below the window's own size.
+extern "C" int simt_solve_window_caps(const VioConfig *cfg, VioWindow *win, VioSolveStats *stats, int nthreads, int variant,
+                                      int order, const int caps[6]) {
   if (nthreads != 256 && nthreads != 512) return VIO_EINVAL;
   bool any_loop = false;
   for (int k = 0; k < win->n_factors; k++)
     if (win->factor_target[k] == win->window_size + 1) any_loop = true;
+  const int Wcap = caps[0] ? caps[0] : win->window_size, Fcap = caps[1] ? caps[1] : win->n_features;
+  const int Mcap = caps[2] ? caps[2] : win->n_factors, Flds = caps[4] ? caps[4] : std::max(1, win->n_features);
+  if (Wcap < win->window_size || Fcap < win->n_features || Mcap < win->n_factors || Flds < win->n_features || Flds > std::max(1, Fcap))
+    return VIO_EINVAL;
   HostBatch hb;
-  hb.resize(make_dims(*cfg, win->window_size, win->n_features, win->n_factors, any_loop), 1);
+  {
+    BatchDims d = make_dims(*cfg, Wcap, Fcap, Mcap, any_loop || caps[5]);
+    if (caps[3]) d.Ncap = std::max(6 * Wcap + 15, caps[3]);
+    if (win->prior && win->prior->n > d.Ncap) return VIO_EINVAL;
+    hb.resize(d, 1);
+  }
   hb.d.lds_asp = variant == 2 ? 0 : 1;
   const bool lds_shape = pose_jp(hb.d) <= 16 * kPanelTiles && variant != 0;
   int rc = pack_window(hb, 0, *win, false, order % 2 ? 0 : stage_chunk_slots(hb.d, lds_shape, nthreads));  // (with and without bucket alignment)
@@ -54,7 +68,7 @@ extern "C" int simt_solve_window(const VioConfig *cfg, VioWindow *win, VioSolveS
   B.out_pose = out_pose.data(), B.out_sb = out_sb.data(), B.out_feat = out_feat.data();
   B.raw_pose = raw_pose.data(), B.raw_sb = raw_sb.data(), B.raw_feat = raw_feat.data(), B.out_loop = out_loop.data();
   B.stats_d = stats_d.data(), B.stats_i = stats_i.data();
-  B.d.Flds = std::max(1, win->n_features);
+  B.d.Flds = Flds;
   B.d.lds_asp = variant == 2 ? 0 : 1;  // variant 2: the LDS matrix with the IMU coupling in global scratch
 
   // LDS or global matrix: the launcher's rule (vio_backend.hip backend_upload_impl)
@@ -100,4 +114,10 @@ extern "C" int simt_solve_window(const VioConfig *cfg, VioWindow *win, VioSolveS
                 raw_feat.data(), out_loop.data(), stats_d.data(), stats_i.data(), *win, stats);
   if (win->next_prior) unpack_prior(mo, *win->next_prior);
   return VIO_OK;
+}
+
+extern "C" int simt_solve_window(const VioConfig *cfg, VioWindow *win, VioSolveStats *stats, int nthreads, int variant,
+                                 int order) {
+  const int own[6] = {0, 0, 0, 0, 0, 0};
+  return simt_solve_window_caps(cfg, win, stats, nthreads, variant, order, own);
 }

@@ -49,8 +49,8 @@ def test_runtime_w_lds_variant_with_loop(w10):
 
 
 def test_runtime_w_lds_variant_w6():
-    """W = 6 (a configuration of its own, as every batch of the suite has one window size): window size, strides and the staging chunk
-    are run-time values."""
+    """W = 6 in a configuration of its own (batches that mix window sizes: tests/test_window_capacities_gpu.py): window size, strides
+    and the staging chunk are run-time values."""
     cfg = abi.default_config(window_size=6)
     osolve, _ = H.oracle_backend()
     w6 = MW.build_windows(cfg, lambda *a: pkg.backend.preintegrate(cfg, *a), osolve, W=6, seed=43, full=False)

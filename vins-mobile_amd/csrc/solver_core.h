@@ -433,13 +433,15 @@ VIO_DEV void prior_column_map(const Ctx &cx, const WinView &v, WK &w) {
 
 // H0 in the layout of the reduced matrix, constant during the solve: pose x pose -> App, speed-bias x speed-bias -> Dss / Css
 // (copied into place by every linearization), speed-bias x pose -> Apri (read where it is needed). x = H0 at prior columns whose
-// reduced columns are pa >= pb >= 0.
+// reduced columns are pa >= pb >= 0. The band in AppPr is the layout's Dss | Css, Pcap blocks each (carve_work puts Css
+// Pcap blocks behind Dss): a window below its batch's largest has P < Pcap, and with P blocks per half the copy's second half
+// landed between the two arrays while Css kept what LDS held. At a compile-time window size P == Pcap: the same code as before.
 VIO_DEV void prior_place(const WinView &v, int napp, int pa, int pb, double x) {
   const int fr = pa >> 8, cr = pa & 255, fc = pb >> 8, cc = pb & 255;
   if (cr < 6 && cc < 6) v.AppPr[tri_at(6 * fr + cr, 6 * fc + cc)] = x;
   else if (cr >= 6 && cc >= 6) {
     if (fr == fc) v.AppPr[napp + fr * kSS + (cr - 6) * kSB + (cc - 6)] = x;
-    else if (fr - fc == 1) v.AppPr[napp + v.P * kSS + fr * kSS + (cc - 6) * kSB + (cr - 6)] = x;
+    else if (fr - fc == 1) v.AppPr[napp + v.Pcap * kSS + fr * kSS + (cc - 6) * kSB + (cr - 6)] = x;
   } else if (cr >= 6) v.Apri[(cr - 6) * v.jp + 6 * fc + cc] = x;
   else v.Apri[(cc - 6) * v.jp + 6 * fr + cr] = x;
 }
@@ -455,7 +457,7 @@ template <bool ACC, class WK>
 VIO_DEV void setup_prior(const Ctx &cx, const WinView &v, WK &w) {
   const int n = v.prior_n;
   if (n <= 0) return;
-  const int napp = (int)tri_doubles(v.nrows), nband = 2 * v.P * kSS;
+  const int napp = (int)tri_doubles(v.nrows), nband = 2 * v.Pcap * kSS;
   // J0 goes through the (not yet assembled) matrix buffer when it fits: the n^2 dot products then read LDS
   const bool stage = (size_t)n * n <= (size_t)w.nstage;
   auto Js = w.stage;
@@ -1047,7 +1049,7 @@ VIO_DEV double evaluate(const Ctx &cx, const WinView &v, WK &w, cldsd pose, clds
     //     (one lane per factor, ~1.5 k dependent operations: they run beside the copy instead of in a phase of their own)
     //  2  prr = b0 + H0 dx (MarginalizationFactor::Evaluate as J^T r); diagonal pose blocks of the projection factors -> App
     //  3  prior cost and gradient; IMU factors on the matrix cores (Gram products, gradient, cost)
-    const int napp = (int)tri_doubles(v.nrows), nband = 2 * v.P * kSS;
+    const int napp = (int)tri_doubles(v.nrows), nband = 2 * v.Pcap * kSS;  // (the band's halves: Pcap blocks each, prior_place)
     const int n = v.prior_n, nt_ = (int)cx.nt;
     const bool do_prior = n > 0 && !reuse_aux;
     {
@@ -1083,7 +1085,7 @@ VIO_DEV double evaluate(const Ctx &cx, const WinView &v, WK &w, cldsd pose, clds
 #pragma unroll
           for (int u = 0; u < kU; u++) {
             const int q = q0 + u * nt_;
-            if (q < nband) w.Dss[q] = x[u];  // (Css follows Dss)
+            if (q < nband) w.Dss[q] = x[u];  // (Css follows Dss: both halves Pcap blocks long, in AppPr as in the layout)
           }
         }
       }
