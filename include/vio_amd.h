@@ -614,6 +614,62 @@ int vio_brief_extract(vio_brief_t *b, const uint8_t *gray /* [n_frames][rows*col
                       float *keypoints /* [n_frames][max_keypoints][2] */,
                       uint64_t *descriptors /* [n_frames][max_keypoints][4] */, int32_t *n_fast,
                       int32_t *n_keypoints);
+/* The same extraction from frames that are on the device already (extractBrief, loop/keyframe.cpp:61-71, on the image
+ * the front end holds): d_frames is a packed device buffer of rows*cols bytes per slot that the caller owns (a ring,
+ * e.g. what vio_preprocess_run_resident writes); frame f of the call is slot frame_index[f] (f when NULL; slots may
+ * repeat and come in any order). The kernels read the slots in place: no copy of an image is made, slots that follow
+ * each other in the call are one launch. window_pts / n_window are host arrays as above. keypoints / descriptors may be
+ * NULL: then only the two count arrays come back. Results and return codes are those of vio_brief_extract on the same
+ * pixels, bit for bit, the capacity cut and its VIO_ECAP included. VIO_EINVAL, with nothing launched: d_frames is not
+ * device memory of the extractor's device (hipPointerGetAttributes) or its allocation does not hold every slot named;
+ * a negative slot.
+ * One vio_brief_t serves one call at a time (its device arrays hold the results of the last launch): never give the
+ * same one to two calls that can overlap, vio_loop_detector_keyframes included.                                    */
+int vio_brief_extract_device(vio_brief_t *b, const void *d_frames, const int32_t *frame_index, int32_t n_frames,
+                             const float *window_pts, const int32_t *n_window, int32_t window_stride,
+                             int32_t fast_threshold, float *keypoints /* or NULL */,
+                             uint64_t *descriptors /* or NULL */, int32_t *n_fast, int32_t *n_keypoints);
+
+/* The loop thread's keyframe step in one call (VINS_ios/ViewController.mm:913-975: extractBrief loop/keyframe.cpp:61-71
+ * + BriefExtractor :395-409, startLoopClosure, findConnectionWithOldFrame :267-273) for the newest keyframe of n
+ * sessions. It does exactly what this sequence does:
+ *   1. vio_brief_extract on the n frames (frame i = slot frame_index[i] of `frames`, i when NULL);
+ *   2. vio_loop_detector_detect with n_keys = n_keypoints, the keys and descriptors packed back to back;
+ *   3. for the sessions with detection.status == VIO_LOOP_DETECTED one vio_loop_detector_connect with cur_entry =
+ *      detection.query, old_entry = detection.match and the session's n_window and ids;
+ * every field of out[i], every row i of status / matched_old_pts / kept_* ([n][stride]) and cur_pts / old_pts
+ * ([n][pts_stride][2]) and the detector's state afterwards are bit for bit that sequence's. Rows of sessions that did not
+ * detect are not written. A FAST list that had to be cut is no error here: the cut list is used, fast_cut says so.
+ * Data movement: with frames_on_device = 1 no image, key or descriptor crosses the bus in either direction (frames as
+ * in vio_brief_extract_device); with 0 `frames` is host memory and goes up once (by DMA from where it lies when the
+ * range is registered, vio_host_register). Up go the window points, n_window, ids and the detector's item records;
+ * down come the per-frame counts and what detect and connect download. The host waits once for the counts between
+ * extraction and detection; the two contexts' streams are ordered by an event.
+ * Refused before anything is launched, nothing changed: VIO_EINVAL for b and d on different devices, b's max_keypoints
+ * above the detector's, cfg->image_rows / image_cols other than b's rows / cols or a zero fx / fy, a session twice or
+ * out of range, n_window[i] > stride, pts_stride < max_keypoints with cur_pts / old_pts given, a frames pointer that
+ * fails the device-memory check; VIO_ECAP for n above b's max_frames, n_window above b's max_keypoints, a session
+ * that already holds max_entries. A keyframe without corners and window points (n_keys 0) is legal.
+ * Measured on one MI355X (tools/loop_keyframes_timing.py, profiles/loop_keyframes_timing.txt; wall time per call, median
+ * of 5 with the minimum in brackets; 640x480 keyframes of ~1700 descriptors and ~147 window points, a loop detected and
+ * connected in every session), 1 / 64 / 512 sessions per call: device frames 1.39 (1.21) / 2.15 (2.06) / 7.72 (7.32) ms,
+ * host frames 1.38 (1.20) / 2.44 (2.38) / 10.46 (10.14) ms, the three calls it replaces 1.50 (1.30) / 2.80 (2.73) /
+ * 11.96 (11.62) ms (inside the C calls; the caller's packing between them not counted).                             */
+typedef struct VioLoopKeyframe {
+  VioLoopDetection  detection;   /* as vio_loop_detector_detect                                                      */
+  VioLoopConnection connection;  /* as vio_loop_detector_connect; zeroed unless detection.status == VIO_LOOP_DETECTED */
+  int32_t n_fast, n_keys;        /* FAST corners found; descriptors stored (the kept corners + n_window)             */
+  int32_t fast_cut;              /* 1: n_fast > max_keypoints - n_window, the cut list was used                      */
+} VioLoopKeyframe;
+int vio_loop_detector_keyframes(vio_loop_detector_t *d, vio_brief_t *b, const VioConfig *cfg /* fx fy cx cy, image size */,
+                                int32_t min_loop_num /* MIN_LOOP_NUM = 22 */, int32_t n, const int32_t *session,
+                                const void *frames, int32_t frames_on_device, const int32_t *frame_index /* or NULL */,
+                                const float *window_pts /* [n][stride][2] */, const int32_t *n_window,
+                                const int32_t *ids /* [n][stride] or NULL */, int32_t stride, int32_t fast_threshold,
+                                VioLoopKeyframe *out, uint8_t *status /* [n][stride] */,
+                                float *matched_old_pts /* [n][stride][2] or NULL */, int32_t *kept_index /* [n][stride] */,
+                                int32_t *kept_ids /* [n][stride], with ids */, double *kept_old_norm /* [n][stride][2] */,
+                                float *cur_pts, float *old_pts /* [n][pts_stride][2] or NULL */, int32_t pts_stride);
 
 /* 4-DoF loop pose graph: KeyFrameDatabase::optimize4DoFLoopPoseGraph
  * (VINS_ios/loop/keyfame_database.cpp:140-353). Per keyframe the unknowns are

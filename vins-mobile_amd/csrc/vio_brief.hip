@@ -13,6 +13,8 @@
 //                      window points are appended behind them
 //   brief_kernel       one wave per keypoint: lane l makes tests l, l + 64, l + 128, l + 192; four ballots are the
 //                      four descriptor words
+// The launch sequence is vio::brief_launch (vio_brief_launch.h): vio_brief_extract uploads host frames first,
+// vio_brief_extract_device and the loop detector's keyframe step read frames that are on the device where they lie.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -23,6 +25,7 @@
 #include <vector>
 
 #include "vio_amd.h"
+#include "vio_brief_launch.h"
 #include "vio_device.h"
 
 namespace {
@@ -226,14 +229,132 @@ struct vio_brief {
   int rows = 0, cols = 0, max_frames = 0, cap = 0, n_bits = 0;
   Taps9 taps;
   hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;  // behind the last kernel of a launch: what another stream waits for
   vio::DevBuf<uint8_t> d_img, d_blur, d_score;
   vio::DevBuf<float> d_kp, d_wpts;
   vio::DevBuf<unsigned long long> d_desc;
   vio::DevBuf<int> d_nw, d_nfast, d_nkp, d_pat;
   ~vio_brief() {
     if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+    if (done) (void)hipEventDestroy(done);
   }
 };
+
+namespace vio {
+
+BriefShape brief_shape(const vio_brief *b) { return BriefShape{b->device, b->rows, b->cols, b->max_frames, b->cap}; }
+
+int brief_check(const vio_brief *b, const void *frames, bool on_device, const int32_t *frame_index, int n_frames, const float *window_pts,
+                const int32_t *n_window, int window_stride) {
+  if (!b || !frames || n_frames < 1 || !n_window || window_stride < 0) return VIO_EINVAL;
+  int max_w = 0, max_slot = n_frames - 1;
+  if (frame_index) {
+    max_slot = 0;
+    for (int f = 0; f < n_frames; f++) {
+      if (frame_index[f] < 0) return VIO_EINVAL;
+      max_slot = frame_index[f] > max_slot ? frame_index[f] : max_slot;
+    }
+  }
+  if (on_device) {  // before every other answer: a pointer that cannot be read on the device is never a question of capacity
+    DeviceScope scope(b->device);
+    if (!scope.ok()) return VIO_ENODEV;
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    if (hipPointerGetAttributes(&attr, frames) != hipSuccess) {  // (what the runtime has never seen: plain host memory)
+      (void)hipGetLastError();
+      return VIO_EINVAL;
+    }
+    if (attr.type != hipMemoryTypeDevice || attr.device != b->device) return VIO_EINVAL;
+    // the allocation around the pointer holds every slot named (where the runtime knows the allocation)
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)frames) == hipSuccess) {
+      const size_t at = (size_t)((const char *)frames - (const char *)base), need = ((size_t)max_slot + 1) * b->rows * b->cols;
+      if (at > size || need > size - at) return VIO_EINVAL;
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  if (n_frames > b->max_frames) return VIO_ECAP;
+  for (int f = 0; f < n_frames; f++) {
+    if (n_window[f] < 0 || n_window[f] > window_stride || (n_window[f] > 0 && !window_pts)) return VIO_EINVAL;
+    if (n_window[f] > b->cap) return VIO_ECAP;
+    max_w = n_window[f] > max_w ? n_window[f] : max_w;
+  }
+  if (max_w > 0 && window_stride > b->cap) return VIO_ECAP;  // (the caller's stride is kept on the device)
+  return VIO_OK;
+}
+
+int brief_launch(vio_brief *b, const void *frames, bool on_device, const int32_t *frame_index, int n_frames, const float *window_pts,
+                 const int32_t *n_window, int window_stride, int fast_threshold, BriefResult *out) {
+  hipStream_t st = b->stream;
+  const int rows = b->rows, cols = b->cols, cap = b->cap;
+  const size_t px = (size_t)rows * cols;
+  const uint8_t *src = (const uint8_t *)frames;
+  auto slot = [&](int f) { return frame_index ? frame_index[f] : f; };
+  // [f0, f1): frames of the call whose slots follow each other in the buffer
+  auto run_end = [&](int f0) {
+    int f1 = f0 + 1;
+    while (f1 < n_frames && slot(f1) == slot(f1 - 1) + 1) f1++;
+    return f1;
+  };
+  if (!on_device)
+    for (int f0 = 0, f1; f0 < n_frames; f0 = f1) {
+      f1 = run_end(f0);
+      HIP_OK(hipMemcpyAsync(b->d_img.p + f0 * px, src + slot(f0) * px, px * (f1 - f0), hipMemcpyHostToDevice, st));
+    }
+  int max_w = 0;
+  for (int f = 0; f < n_frames; f++) max_w = n_window[f] > max_w ? n_window[f] : max_w;
+  HIP_OK(hipMemcpyAsync(b->d_nw.p, n_window, n_frames * sizeof(int), hipMemcpyHostToDevice, st));
+  if (max_w > 0) {
+    HIP_OK(hipMemcpyAsync(b->d_wpts.p, window_pts, (size_t)n_frames * window_stride * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+  }
+  const int thr = fast_threshold < 0 ? 0 : (fast_threshold > 255 ? 255 : fast_threshold);
+  // blockIdx.z walks source and destination alike: a run of slots is one launch, frame f0 of the call at its head
+  auto blur_score = [&](const uint8_t *img, int f0, int nf) {
+    hipLaunchKernelGGL(blur9_kernel, dim3((cols + kBlW - 1) / kBlW, (rows + kBlH - 1) / kBlH, nf), dim3(256), 0, st, img, b->d_blur.p + f0 * px, rows,
+                       cols, b->taps);
+    hipLaunchKernelGGL(fast_score_kernel, dim3((cols + 63) / 64, (rows + 3) / 4, nf), dim3(256), 0, st, img, b->d_score.p + f0 * px, rows, cols, thr);
+  };
+  if (!on_device) {
+    blur_score(b->d_img.p, 0, n_frames);
+  } else {
+    for (int f0 = 0, f1; f0 < n_frames; f0 = f1) {
+      f1 = run_end(f0);
+      blur_score(src + slot(f0) * px, f0, f1 - f0);
+    }
+  }
+  hipLaunchKernelGGL(fast_collect_kernel, dim3(n_frames), dim3(kColThreads), 0, st, b->d_score.p, rows, cols, b->d_wpts.p, b->d_nw.p,
+                     window_stride, cap, b->d_kp.p, b->d_nfast.p, b->d_nkp.p);
+  Pattern P = {b->d_pat.p, b->d_pat.p + 256, b->d_pat.p + 512, b->d_pat.p + 768, b->n_bits};
+  hipLaunchKernelGGL(brief_kernel, dim3((cap + 3) / 4, n_frames), dim3(256), 0, st, b->d_blur.p, rows, cols, b->d_kp.p, b->d_nkp.p, cap, P,
+                     b->d_desc.p);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(b->done, st));
+  *out = BriefResult{b->d_kp.p, b->d_desc.p, b->d_nfast.p, b->d_nkp.p, cap, st, b->done};
+  return VIO_OK;
+}
+
+}  // namespace vio
+
+namespace {
+
+// what an extraction brings back: the counts always, the rows when asked for; VIO_ECAP when a FAST list was cut
+int brief_download(const vio::BriefResult &r, int n_frames, const int32_t *n_window, float *keypoints, uint64_t *descriptors,
+                   int32_t *n_fast, int32_t *n_keypoints) {
+  hipStream_t st = r.stream;
+  const int cap = r.cap;
+  HIP_OK(hipMemcpyAsync(n_fast, r.n_fast, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(n_keypoints, r.n_keypoints, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (keypoints) HIP_OK(hipMemcpyAsync(keypoints, r.keypoints, (size_t)n_frames * cap * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (descriptors) HIP_OK(hipMemcpyAsync(descriptors, r.desc, (size_t)n_frames * cap * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (int f = 0; f < n_frames; f++)
+    if (n_fast[f] > cap - n_window[f]) return VIO_ECAP;  // (what fitted is valid; the FAST list is cut at the capacity)
+  return VIO_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -308,7 +429,8 @@ int vio_brief_create(int32_t rows, int32_t cols, int32_t max_frames, int32_t max
   memset(pat, 0, sizeof(pat));
   memcpy(pat, x1, n_bits * sizeof(int)), memcpy(pat + 256, y1, n_bits * sizeof(int));
   memcpy(pat + 512, x2, n_bits * sizeof(int)), memcpy(pat + 768, y2, n_bits * sizeof(int));
-  if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess || b->d_img.ensure(px) != VIO_OK ||
+  if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&b->done, hipEventDisableTiming) != hipSuccess || b->d_img.ensure(px) != VIO_OK ||
       b->d_blur.ensure(px) != VIO_OK || b->d_score.ensure(px) != VIO_OK || b->d_kp.ensure(kp * 2) != VIO_OK ||
       b->d_wpts.ensure(kp * 2) != VIO_OK || b->d_desc.ensure(kp * 4) != VIO_OK || b->d_nw.ensure(max_frames) != VIO_OK ||
       b->d_nfast.ensure(max_frames) != VIO_OK || b->d_nkp.ensure(max_frames) != VIO_OK || b->d_pat.ensure(4 * 256) != VIO_OK ||
@@ -337,41 +459,26 @@ int vio_brief_extract(vio_brief_t *b, const uint8_t *gray, int32_t n_frames, con
                       int32_t *n_keypoints) {
   if (!b || !gray || n_frames < 1 || !n_window || !keypoints || !descriptors || !n_fast || !n_keypoints || window_stride < 0)
     return VIO_EINVAL;
-  if (n_frames > b->max_frames) return VIO_ECAP;
-  int max_w = 0;
-  for (int f = 0; f < n_frames; f++) {
-    if (n_window[f] < 0 || n_window[f] > window_stride || (n_window[f] > 0 && !window_pts)) return VIO_EINVAL;
-    if (n_window[f] > b->cap) return VIO_ECAP;
-    max_w = n_window[f] > max_w ? n_window[f] : max_w;
-  }
-  if (max_w > 0 && window_stride > b->cap) return VIO_ECAP;  // (the caller's stride is kept on the device)
+  int rc = vio::brief_check(b, gray, false, nullptr, n_frames, window_pts, n_window, window_stride);
+  if (rc != VIO_OK) return rc;
   VIO_ON_DEVICE_OF(b);
-  hipStream_t st = b->stream;
-  const int rows = b->rows, cols = b->cols, cap = b->cap;
-  const size_t px = (size_t)rows * cols;
-  HIP_OK(hipMemcpyAsync(b->d_img.p, gray, px * n_frames, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(b->d_nw.p, n_window, n_frames * sizeof(int), hipMemcpyHostToDevice, st));
-  if (max_w > 0) {
-    HIP_OK(hipMemcpyAsync(b->d_wpts.p, window_pts, (size_t)n_frames * window_stride * 2 * sizeof(float), hipMemcpyHostToDevice, st));
-  }
-  const int thr = fast_threshold < 0 ? 0 : (fast_threshold > 255 ? 255 : fast_threshold);
-  hipLaunchKernelGGL(blur9_kernel, dim3((cols + kBlW - 1) / kBlW, (rows + kBlH - 1) / kBlH, n_frames), dim3(256), 0, st, b->d_img.p, b->d_blur.p,
-                     rows, cols, b->taps);
-  hipLaunchKernelGGL(fast_score_kernel, dim3((cols + 63) / 64, (rows + 3) / 4, n_frames), dim3(256), 0, st, b->d_img.p, b->d_score.p, rows, cols, thr);
-  hipLaunchKernelGGL(fast_collect_kernel, dim3(n_frames), dim3(kColThreads), 0, st, b->d_score.p, rows, cols, b->d_wpts.p, b->d_nw.p,
-                     window_stride, cap, b->d_kp.p, b->d_nfast.p, b->d_nkp.p);
-  Pattern P = {b->d_pat.p, b->d_pat.p + 256, b->d_pat.p + 512, b->d_pat.p + 768, b->n_bits};
-  hipLaunchKernelGGL(brief_kernel, dim3((cap + 3) / 4, n_frames), dim3(256), 0, st, b->d_blur.p, rows, cols, b->d_kp.p, b->d_nkp.p, cap, P,
-                     b->d_desc.p);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(n_fast, b->d_nfast.p, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(n_keypoints, b->d_nkp.p, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(keypoints, b->d_kp.p, (size_t)n_frames * cap * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(descriptors, b->d_desc.p, (size_t)n_frames * cap * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  for (int f = 0; f < n_frames; f++)
-    if (n_fast[f] > cap - n_window[f]) return VIO_ECAP;  // (what fitted is valid; the FAST list is cut at the capacity)
-  return VIO_OK;
+  vio::BriefResult r;
+  rc = vio::brief_launch(b, gray, false, nullptr, n_frames, window_pts, n_window, window_stride, fast_threshold, &r);
+  if (rc != VIO_OK) return rc;
+  return brief_download(r,n_frames, n_window, keypoints, descriptors, n_fast, n_keypoints);
+}
+
+int vio_brief_extract_device(vio_brief_t *b, const void *d_frames, const int32_t *frame_index, int32_t n_frames, const float *window_pts,
+                             const int32_t *n_window, int32_t window_stride, int32_t fast_threshold, float *keypoints, uint64_t *descriptors,
+                             int32_t *n_fast, int32_t *n_keypoints) {
+  if (!b || !d_frames || n_frames < 1 || !n_window || !n_fast || !n_keypoints || window_stride < 0) return VIO_EINVAL;
+  int rc = vio::brief_check(b, d_frames, true, frame_index, n_frames, window_pts, n_window, window_stride);
+  if (rc != VIO_OK) return rc;
+  VIO_ON_DEVICE_OF(b);
+  vio::BriefResult r;
+  rc = vio::brief_launch(b, d_frames, true, frame_index, n_frames, window_pts, n_window, window_stride, fast_threshold, &r);
+  if (rc != VIO_OK) return rc;
+  return brief_download(r,n_frames, n_window, keypoints, descriptors, n_fast, n_keypoints);
 }
 
 }  // extern "C"

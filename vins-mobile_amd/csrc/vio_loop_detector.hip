@@ -30,6 +30,9 @@
 //   ld_connect_search_kernel   searchByDes :161-190 (search_by_des_kernel of vio_loop.hip on slab offsets)
 //   ld_connect_count_kernel    the pairs whose queries all found a match go to the RANSAC
 //   vio::fundamental_ransac_batch, ld_connect_keep_kernel   rejectWithF :35-58 and its reduceVector calls, one download
+// vio_loop_detector_keyframes is the loop thread's whole keyframe step (ViewController.mm:913-975): the extraction of
+// vio_brief.hip launched through vio_brief_launch.h, its rows packed into in_keys / in_desc on the device
+// (vio_brief_pack.hip) where detect has its two uploads, then detect and, for the sessions that detected, connect.
 // There is no CPU path: without a device vio_loop_detector_create answers VIO_ENODEV.
 #include <hip/hip_runtime.h>
 
@@ -42,6 +45,7 @@
 
 #include "vio_amd.h"
 #include "vio_bow_core.h"
+#include "vio_brief_launch.h"
 #include "vio_device.h"
 #include "vio_ransac.h"
 
@@ -562,6 +566,9 @@ struct vio_loop_detector {
   vio::PinnedBuf<unsigned char> cn_host;  // (page-locked: the one download of a call)
   std::vector<LdPair> cn_hpairs;
   std::vector<char> cn_seen;
+  std::vector<int> cn_hids;  // the ids of the pairs of a call whose rows do not lie behind each other (the keyframe step)
+  // vio_loop_detector_keyframes: n_fast | n_keypoints of the call's extraction (page-locked, sized at its first call)
+  vio::PinnedBuf<int> kf_counts;
   // host mirror of every session
   struct Session {
     int n_entries = 0, n_post = 0, cur = 0;
@@ -615,6 +622,20 @@ void compute_islands(const VioLoopDetectorParams &P, std::vector<std::pair<int, 
     }
   }
   close_island();
+}
+
+// what vio_loop_detector_detect refuses about its sessions, on the host mirror: a session out of range or twice
+// (VIO_EINVAL), a session that already holds max_entries (VIO_ECAP)
+int check_sessions(const vio_loop_detector *d, int n, const int32_t *session) {
+  if (n > d->S) return VIO_EINVAL;  // (some session would be named twice)
+  std::vector<char> seen(d->S, 0);
+  for (int q = 0; q < n; q++) {
+    if (session[q] < 0 || session[q] >= d->S || seen[session[q]]) return VIO_EINVAL;
+    seen[session[q]] = 1;
+  }
+  for (int q = 0; q < n; q++)
+    if (d->sess[session[q]].n_entries >= d->E) return VIO_ECAP;
+  return VIO_OK;
 }
 
 }  // namespace
@@ -757,8 +778,14 @@ int vio_loop_detector_erase(vio_loop_detector_t *d, int32_t session, int32_t n, 
   return VIO_OK;
 }
 
-int vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *session, const int32_t *n_keys, const float *keys,
-                             const uint64_t *desc, VioLoopDetection *out, float *cur_pts, float *old_pts, int32_t pts_stride) {
+}  // extern "C"
+
+namespace {
+
+// vio_loop_detector_detect. from_device: the keyframes are the rows of an extraction that has been launched (its counts
+// are n_keys); they are packed into in_keys / in_desc on the device behind its `done` event, keys / desc are not read.
+int detect_run(vio_loop_detector *d, int32_t n, const int32_t *session, const int32_t *n_keys, const float *keys, const uint64_t *desc,
+               const vio::BriefResult *from_device, VioLoopDetection *out, float *cur_pts, float *old_pts, int32_t pts_stride) {
   if (!d || n < 1 || !session || !n_keys || !out) return VIO_EINVAL;
   if ((cur_pts || old_pts) && pts_stride < d->K) return VIO_EINVAL;
   if (n > d->S) return VIO_EINVAL;  // (some session would be named twice)
@@ -785,7 +812,7 @@ int vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *s
       max_post = std::max(max_post, s.n_post), any_query = any_query || it.do_query;
     }
     const int total = off[n];
-    if (total > 0 && (!keys || !desc)) return VIO_EINVAL;
+    if (total > 0 && !from_device && (!keys || !desc)) return VIO_EINVAL;
     VIO_ON_DEVICE_OF(d);
     hipStream_t st = d->stream;
     const LdStore S = d->store();
@@ -793,7 +820,10 @@ int vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *s
     // ---- round A: transform, query, ns_factor, add
     HIP_OK(hipMemcpyAsync(d->items.p, items.data(), sizeof(LdItem) * (size_t)n, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d->t_off.p, off.data(), 4 * (size_t)(n + 1), hipMemcpyHostToDevice, st));
-    if (total > 0) {
+    if (total > 0 && from_device) {  // the extractor's stream is ordered before this one by its event, not by the host
+      HIP_OK(hipStreamWaitEvent(st, from_device->done, 0));
+      HIP_OK(vio::launch_brief_pack(*from_device, n, d->t_off.p, d->in_keys.p, d->in_desc.p, st));
+    } else if (total > 0) {
       HIP_OK(hipMemcpyAsync(d->in_desc.p, desc, 32 * (size_t)total, hipMemcpyHostToDevice, st));
       HIP_OK(hipMemcpyAsync(d->in_keys.p, keys, 8 * (size_t)total, hipMemcpyHostToDevice, st));
     }
@@ -962,10 +992,13 @@ int vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *s
   }
 }
 
-int vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg, int32_t min_loop_num, int32_t n, const int32_t *session,
-                              const int32_t *cur_entry, const int32_t *old_entry, const int32_t *n_window, const int32_t *ids, int32_t stride,
-                              VioLoopConnection *out, uint8_t *status, float *matched_old_pts, int32_t *kept_index, int32_t *kept_ids,
-                              double *kept_old_norm) {
+// vio_loop_detector_connect. row: pair i reads row row[i] of ids and writes row row[i] of every output (NULL: row i);
+// its VioLoopConnection is the one at (char *)out + row * out_step.
+int connect_run(vio_loop_detector *d, const VioConfig *cfg, int32_t min_loop_num, int32_t n, const int32_t *session, const int32_t *cur_entry,
+                const int32_t *old_entry, const int32_t *n_window, const int32_t *ids, int32_t stride, const int32_t *row, void *out,
+                size_t out_step, uint8_t *status, float *matched_old_pts, int32_t *kept_index, int32_t *kept_ids, double *kept_old_norm) {
+  auto row_of = [row](int i) { return row ? row[i] : i; };
+  auto result = [&](int i) -> VioLoopConnection & { return *(VioLoopConnection *)((char *)out + (size_t)row_of(i) * out_step); };
   if (!d || !cfg || n < 1 || !session || !cur_entry || !old_entry || !n_window || stride < 0 || !out || !status || !kept_index || !kept_old_norm)
     return VIO_EINVAL;
   if (ids && !kept_ids) return VIO_EINVAL;
@@ -984,7 +1017,7 @@ int vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg, int3
       d->cn_hpairs[i] = LdPair{session[i], nw, s.off[o + 1] - s.off[o], s.off[c + 1] - nw, s.off[o]};
       wmax = std::max(wmax, nw);
     }
-    for (int i = 0; i < n; i++) memset(&out[i], 0, sizeof(out[i])), out[i].n_window = n_window[i];
+    for (int i = 0; i < n; i++) memset(&result(i), 0, sizeof(VioLoopConnection)), result(i).n_window = n_window[i];
     if (wmax == 0) return VIO_OK;  // (no queries anywhere: nothing kept, nothing connected)
     VIO_ON_DEVICE_OF(d);
     hipStream_t st = d->stream;
@@ -1002,8 +1035,13 @@ int vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg, int3
     const size_t bytes = o_status + T;
     unsigned char *D = d->cn_out.p, *Hb = d->cn_host.p;
     HIP_OK(hipMemcpyAsync(d->cn_pairs.p, d->cn_hpairs.data(), sizeof(LdPair) * (size_t)n, hipMemcpyHostToDevice, st));
-    if (ids)
+    if (ids && row) {  // the rows of the pairs do not lie behind each other: gathered on the host, one upload
+      d->cn_hids.resize(T);
+      for (int i = 0; i < n; i++) memcpy(d->cn_hids.data() + (size_t)i * wmax, ids + (size_t)row[i] * stride, 4 * (size_t)n_window[i]);
+      HIP_OK(hipMemcpyAsync(d->cn_ids.p, d->cn_hids.data(), 4 * T, hipMemcpyHostToDevice, st));
+    } else if (ids) {
       HIP_OK(hipMemcpy2DAsync(d->cn_ids.p, 4 * (size_t)wmax, ids, 4 * (size_t)stride, 4 * (size_t)wmax, n, hipMemcpyHostToDevice, st));
+    }
     const LdStore S = d->store();
     hipLaunchKernelGGL(ld_connect_search_kernel, dim3((wmax + kCnWaves - 1) / kCnWaves, n), dim3(64 * kCnWaves), 0, st, d->cn_pairs.p, S, wmax,
                        d->p_cur.p, (float *)(D + o_pts), d->cn_unmatched.p);
@@ -1021,8 +1059,9 @@ int vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg, int3
     const int *hdr = (const int *)(Hb + o_hdr);
     for (int i = 0; i < n; i++) {
       const int nw = n_window[i], nk = hdr[2 * i], ran = hdr[2 * i + 1];
-      const size_t src = (size_t)i * wmax, dst = (size_t)i * stride;
-      out[i].ransac_ran = ran, out[i].n_kept = nk, out[i].connected = ran && nk > min_loop_num ? 1 : 0;
+      const size_t src = (size_t)i * wmax, dst = (size_t)row_of(i) * stride;
+      VioLoopConnection &r = result(i);
+      r.ransac_ran = ran, r.n_kept = nk, r.connected = ran && nk > min_loop_num ? 1 : 0;
       memcpy(status + dst, Hb + o_status + src, (size_t)nw);
       const bool matched = nw < 8 ? nk == nw : ran != 0;  // (with an unmatched query the old points mean nothing: not written)
       if (matched_old_pts && matched) memcpy(matched_old_pts + 2 * dst, Hb + o_pts + 8 * src, 8 * (size_t)nw);
@@ -1031,6 +1070,78 @@ int vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg, int3
       if (ran) memcpy(kept_old_norm + 2 * dst, Hb + o_norm + 16 * src, 16 * (size_t)nk);
     }
     return VIO_OK;
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *session, const int32_t *n_keys, const float *keys,
+                             const uint64_t *desc, VioLoopDetection *out, float *cur_pts, float *old_pts, int32_t pts_stride) {
+  return detect_run(d, n, session, n_keys, keys, desc, nullptr, out, cur_pts, old_pts, pts_stride);
+}
+
+int vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg, int32_t min_loop_num, int32_t n, const int32_t *session,
+                              const int32_t *cur_entry, const int32_t *old_entry, const int32_t *n_window, const int32_t *ids, int32_t stride,
+                              VioLoopConnection *out, uint8_t *status, float *matched_old_pts, int32_t *kept_index, int32_t *kept_ids,
+                              double *kept_old_norm) {
+  return connect_run(d, cfg, min_loop_num, n, session, cur_entry, old_entry, n_window, ids, stride, nullptr, out, sizeof(VioLoopConnection), status,
+                     matched_old_pts, kept_index, kept_ids, kept_old_norm);
+}
+
+// The loop thread's keyframe step (VINS_ios/ViewController.mm:913-975: extractBrief, startLoopClosure,
+// findConnectionWithOldFrame) = vio_brief_extract, vio_loop_detector_detect, vio_loop_detector_connect for the sessions
+// that detected, with the keys and descriptors handed over on the device (vio_brief_pack.hip). The host waits once for
+// the per-frame counts (its mirror of the slab offsets needs them); the detector's stream waits for the extractor's by
+// its event.
+int vio_loop_detector_keyframes(vio_loop_detector_t *d, vio_brief_t *b, const VioConfig *cfg, int32_t min_loop_num, int32_t n,
+                                const int32_t *session, const void *frames, int32_t frames_on_device, const int32_t *frame_index,
+                                const float *window_pts, const int32_t *n_window, const int32_t *ids, int32_t stride, int32_t fast_threshold,
+                                VioLoopKeyframe *out, uint8_t *status, float *matched_old_pts, int32_t *kept_index, int32_t *kept_ids,
+                                double *kept_old_norm, float *cur_pts, float *old_pts, int32_t pts_stride) {
+  if (!d || !b || !cfg || n < 1 || !session || !frames || !n_window || stride < 0 || !out || !status || !kept_index || !kept_old_norm)
+    return VIO_EINVAL;
+  if (ids && !kept_ids) return VIO_EINVAL;
+  if ((cur_pts || old_pts) && pts_stride < d->K) return VIO_EINVAL;
+  // every refusal is decided here, on the host, before anything is launched or written
+  const vio::BriefShape shape = vio::brief_shape(b);
+  if (shape.device != d->device || shape.cap > d->K) return VIO_EINVAL;
+  // (the intrinsics normalise the old frame's pixels: they belong to the image size the extractor was made for)
+  if (cfg->image_rows != shape.rows || cfg->image_cols != shape.cols || !(cfg->fx != 0.0) || !(cfg->fy != 0.0)) return VIO_EINVAL;
+  int rc = check_sessions(d, n, session);
+  if (rc == VIO_EINVAL) return rc;
+  const int rc_brief = vio::brief_check(b, frames, frames_on_device != 0, frame_index, n, window_pts, n_window, stride);
+  if (rc_brief == VIO_EINVAL) return rc_brief;
+  if (rc != VIO_OK) return rc;
+  if (rc_brief != VIO_OK) return rc_brief;
+  try {
+    VIO_ON_DEVICE_OF(d);
+    rc = d->kf_counts.ensure(2 * (size_t)d->S);
+    if (rc != VIO_OK) return rc;
+    vio::BriefResult ex;
+    rc = vio::brief_launch(b, frames, frames_on_device != 0, frame_index, n, window_pts, n_window, stride, fast_threshold, &ex);
+    if (rc != VIO_OK) return rc;
+    int *n_fast = d->kf_counts.p, *n_keys = d->kf_counts.p + d->S;
+    HIP_OK(hipMemcpyAsync(n_fast, ex.n_fast, 4 * (size_t)n, hipMemcpyDeviceToHost, ex.stream));
+    HIP_OK(hipMemcpyAsync(n_keys, ex.n_keypoints, 4 * (size_t)n, hipMemcpyDeviceToHost, ex.stream));
+    HIP_OK(hipStreamSynchronize(ex.stream));
+    std::vector<VioLoopDetection> det(n);
+    rc = detect_run(d, n, session, n_keys, nullptr, nullptr, &ex, det.data(), cur_pts, old_pts, pts_stride);
+    if (rc != VIO_OK) return rc;
+    std::vector<int> row, ses, cur, old, nw;
+    for (int q = 0; q < n; q++) {
+      memset(&out[q], 0, sizeof(out[q]));
+      out[q].detection = det[q];
+      out[q].n_fast = n_fast[q], out[q].n_keys = n_keys[q], out[q].fast_cut = n_fast[q] > shape.cap - n_window[q] ? 1 : 0;
+      if (det[q].status != VIO_LOOP_DETECTED) continue;
+      row.push_back(q), ses.push_back(session[q]), cur.push_back(det[q].query), old.push_back(det[q].match), nw.push_back(n_window[q]);
+    }
+    if (row.empty()) return VIO_OK;
+    return connect_run(d, cfg, min_loop_num, (int)row.size(), ses.data(), cur.data(), old.data(), nw.data(), ids, stride, row.data(),
+                       &out[0].connection, sizeof(VioLoopKeyframe), status, matched_old_pts, kept_index, kept_ids, kept_old_norm);
   } catch (const std::bad_alloc &) {
     return VIO_ENOMEM;
   }

@@ -76,7 +76,45 @@ def bind_brief(lib):
     lib.vio_brief_destroy.argtypes = [C.c_void_p]
     lib.vio_brief_get_device.argtypes = [C.c_void_p, _i32p]
     lib.vio_brief_extract.argtypes = [C.c_void_p, _u8p, C.c_int32, _fp, _i32p, C.c_int32, C.c_int32, _fp, _u64p, _i32p, _i32p]
+    lib.vio_brief_extract_device.argtypes = [C.c_void_p, C.c_void_p, _i32p, C.c_int32, _fp, _i32p, C.c_int32, C.c_int32, _fp, _u64p, _i32p,
+                                             _i32p]
     return lib
+
+
+class DeviceFrames:
+    """A caller-owned device buffer of packed frames (what vio_preprocess_run_resident leaves behind): hipMalloc + one
+    upload, through the HIP runtime the library is linked against. `.ptr` is what the *_device entries take."""
+
+    def __init__(self, frames):
+        frames = np.ascontiguousarray(frames, np.uint8)
+        hip = self.hip = C.CDLL("libamdhip64.so")
+        hip.hipMalloc.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p]
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        p = C.c_void_p()
+        if hip.hipMalloc(C.byref(p), max(1, frames.nbytes)) != 0:
+            raise RuntimeError("hipMalloc failed")
+        self.ptr, self.nbytes = p.value, frames.nbytes
+        if frames.nbytes and hip.hipMemcpy(p, frames.ctypes.data, frames.nbytes, 1) != 0:   # hipMemcpyHostToDevice
+            self.close()
+            raise RuntimeError("hipMemcpy failed")
+
+    def close(self):
+        if self.ptr:
+            self.hip.hipFree(C.c_void_p(self.ptr))
+            self.ptr = None
+
+
+def _window_arrays(window_pts, n, stride=None):
+    """per frame float [k][2] -> (n_window [n], points [n][stride][2], stride)"""
+    nw = np.array([len(w) for w in window_pts], np.int32)
+    assert len(nw) == n
+    if stride is None:
+        stride = max(1, int(nw.max()) if n else 1)
+    wp = np.zeros((n, stride, 2), np.float32)
+    for f, w in enumerate(window_pts):
+        if len(w):   # (a given stride below a frame's count is the library's to refuse: n_window says what was asked)
+            wp[f, :min(len(w), stride)] = np.asarray(w, np.float32).reshape(-1, 2)[:stride]
+    return nw, wp, stride
 
 
 def load_pattern(path, cap=256):
@@ -128,6 +166,23 @@ class BriefExtractor:
         if rc != abi.VIO_OK and not (allow_cut and rc == abi.VIO_ECAP):
             raise RuntimeError("vio_brief_extract failed rc=%d" % rc)
         return [(kp[f, :nk[f]].copy(), desc[f, :nk[f]].copy(), int(nf[f])) for f in range(n)]
+
+    def extract_device(self, d_frames, n, window_pts, frame_index=None, fast_threshold=20, counts_only=False):
+        """vio_brief_extract_device: d_frames = device pointer (int) of packed frames, frame f = slot frame_index[f].
+        -> (rc, per frame (keypoints, descriptors, n_fast)), or (rc, n_fast [n], n_keypoints [n]) with counts_only."""
+        nw, wp, stride = _window_arrays(window_pts, n)
+        fi = None if frame_index is None else np.ascontiguousarray(frame_index, np.int32)
+        kp = None if counts_only else np.zeros((n, self.cap, 2), np.float32)
+        desc = None if counts_only else np.zeros((n, self.cap, 4), np.uint64)
+        nf, nk = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        rc = self.lib.vio_brief_extract_device(self._h, C.c_void_p(d_frames), None if fi is None else fi.ctypes.data_as(_i32p), n,
+                                               wp.ctypes.data_as(_fp), nw.ctypes.data_as(_i32p), stride, fast_threshold,
+                                               None if counts_only else kp.ctypes.data_as(_fp),
+                                               None if counts_only else desc.ctypes.data_as(_u64p), nf.ctypes.data_as(_i32p),
+                                               nk.ctypes.data_as(_i32p))
+        if counts_only or rc not in (abi.VIO_OK, abi.VIO_ECAP):
+            return rc, nf, nk
+        return rc, [(kp[f, :nk[f]].copy(), desc[f, :nk[f]].copy(), int(nf[f])) for f in range(n)]
 
 
 # ---- bag-of-words query (DBoW2: csrc/vio_bow.hip) ---------------------------------------------------------------------
@@ -272,6 +327,11 @@ class VioLoopConnection(C.Structure):
     _fields_ = [("n_window", C.c_int32), ("ransac_ran", C.c_int32), ("n_kept", C.c_int32), ("connected", C.c_int32)]
 
 
+class VioLoopKeyframe(C.Structure):
+    _fields_ = [("detection", VioLoopDetection), ("connection", VioLoopConnection), ("n_fast", C.c_int32), ("n_keys", C.c_int32),
+                ("fast_cut", C.c_int32)]
+
+
 LOOP_STATUS = ("LOOP_DETECTED", "CLOSE_MATCHES_ONLY", "NO_DB_RESULTS", "LOW_NSS_FACTOR", "LOW_SCORES", "NO_GROUPS",
                "NO_TEMPORAL_CONSISTENCY", "NO_GEOMETRICAL_CONSISTENCY")   # DetectionStatus, TemplatedLoopDetector.h:46-64
 
@@ -291,6 +351,9 @@ def bind_loop_detector(lib):
     lib.vio_loop_detector_kernel_ms.argtypes = [vp, _fp]
     lib.vio_loop_detector_connect.argtypes = [vp, C.POINTER(abi.VioConfig), C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int32,
                                               C.POINTER(VioLoopConnection), _u8p, _fp, _i32p, _i32p, C.POINTER(C.c_double)]
+    lib.vio_loop_detector_keyframes.argtypes = [vp, vp, C.POINTER(abi.VioConfig), C.c_int32, C.c_int32, _i32p, vp, C.c_int32, _i32p, _fp, _i32p,
+                                                _i32p, C.c_int32, C.c_int32, C.POINTER(VioLoopKeyframe), _u8p, _fp, _i32p, _i32p,
+                                                C.POINTER(C.c_double), _fp, _fp, C.c_int32]
     return lib
 
 
@@ -389,6 +452,58 @@ class LoopDetector:
             r["kept_ids"] = kids[i, :k].copy() if ids is not None else None
             r["kept_old_norm"] = norm[i, :k].copy() if r["ransac_ran"] else np.zeros((0, 2))
             got.append(r)
+        return got
+
+    def keyframes(self, brief, cfg, sessions, frames, window_pts, ids=None, frame_index=None, on_device=False, min_loop_num=22,
+                  fast_threshold=20, stride=None):
+        """vio_loop_detector_keyframes: extraction (brief: a BriefExtractor), detect and connect for the newest keyframe of
+        `sessions`. frames: a device pointer (int) with on_device, else a uint8 array of packed frames; frame i of the
+        call is slot frame_index[i]. -> per keyframe a dict: detection (as detect()'s dict), cur_pts, old_pts, connection
+        (as connect()'s dict; None unless the loop was detected), n_fast, n_keys, fast_cut, rows_written (the call wrote
+        the keyframe's connection struct or its status / matched / kept rows)."""
+        n = len(sessions)
+        ses = np.ascontiguousarray(sessions, np.int32)
+        nw, wp, stride = _window_arrays(window_pts, n, stride)
+        fi = None if frame_index is None else np.ascontiguousarray(frame_index, np.int32)
+        idp = None
+        if ids is not None:
+            idp = np.zeros((n, stride), np.int32)
+            for i, a in enumerate(ids):
+                idp[i, :min(len(a), stride)] = np.asarray(a, np.int32)[:stride]
+        out = (VioLoopKeyframe * max(n, 1))()
+        status, pts = np.zeros((n, stride), np.uint8), np.zeros((n, stride, 2), np.float32)
+        kidx, kids, norm = np.zeros((n, stride), np.int32), np.zeros((n, stride), np.int32), np.zeros((n, stride, 2), np.float64)
+        ps = self.max_keypoints
+        cur, old = np.zeros((n, ps, 2), np.float32), np.zeros((n, ps, 2), np.float32)
+        fptr = C.c_void_p(frames) if on_device else C.c_void_p(frames.ctypes.data)
+        rc = self.lib.vio_loop_detector_keyframes(self._h, brief._h, C.byref(cfg), min_loop_num, n, ses.ctypes.data_as(_i32p), fptr,
+                                                  1 if on_device else 0, None if fi is None else fi.ctypes.data_as(_i32p),
+                                                  wp.ctypes.data_as(_fp), nw.ctypes.data_as(_i32p),
+                                                  idp.ctypes.data_as(_i32p) if idp is not None else None, stride, fast_threshold, out,
+                                                  status.ctypes.data_as(_u8p), pts.ctypes.data_as(_fp), kidx.ctypes.data_as(_i32p),
+                                                  kids.ctypes.data_as(_i32p), norm.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  cur.ctypes.data_as(_fp), old.ctypes.data_as(_fp), ps)
+        if rc != abi.VIO_OK:
+            raise LoopDetectorError("vio_loop_detector_keyframes", rc)
+        got = []
+        for q in range(n):
+            r = {f: getattr(out[q].detection, f) for f, _ in VioLoopDetection._fields_}
+            m = r["n_inliers"] if r["status"] == 0 else 0
+            k = dict(detection=r, cur_pts=cur[q, :m].copy(), old_pts=old[q, :m].copy(), connection=None, n_fast=out[q].n_fast,
+                     n_keys=out[q].n_keys, fast_cut=out[q].fast_cut)
+            c = {f: getattr(out[q].connection, f) for f, _ in VioLoopConnection._fields_}
+            if r["status"] == 0:
+                mw, nk = c["n_window"], c["n_kept"]
+                c["status"] = status[q, :mw].copy()
+                c["matched_old_pts"] = pts[q, :mw].copy() if (c["ransac_ran"] or (mw < 8 and nk == mw)) else None
+                c["kept_index"] = kidx[q, :nk].copy()
+                c["kept_ids"] = kids[q, :nk].copy() if ids is not None else None
+                c["kept_old_norm"] = norm[q, :nk].copy() if c["ransac_ran"] else np.zeros((0, 2))
+                k["connection"] = c
+            # (the rows went in zeroed: a call that leaves a row alone leaves it zero)
+            k["rows_written"] = bool(any(c[f] for f, _ in VioLoopConnection._fields_) or status[q].any() or kidx[q].any() or kids[q].any()
+                                     or norm[q].any() or pts[q].any())
+            got.append(k)
         return got
 
     def erase(self, session, entries):
