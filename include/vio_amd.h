@@ -323,6 +323,62 @@ int vio_frontend_submit_images_async(vio_frontend_t *fe, const uint8_t *gray, in
 int vio_frontend_collect(vio_frontend_t *fe, VioObs *out_obs /* [n_seq][max_corners] */,
                          int32_t *n_obs /* [n_seq] */);
 
+/* Frames for a SUBSET of the context's sequences, each with its own publish flag
+ * (feature_tracker.cpp:162-310 per sequence): cameras of a server have their own
+ * clocks, lose frames and keep their own img_cnt phase (ViewController.mm:467,494).
+ * One frame for n of the sequences, any n in 0..n_seq, seq[] in any order without
+ * duplicates: sequence seq[i] takes frame i and publish[i]; every other sequence is
+ * not touched in any way (its images, points, ids and counters stay as they are).
+ * A sequence's first frame after create or reset is the reference's `first image`
+ * (pre = cur = forw, :166-167).
+ *   frames, frames_on_device = 0: host memory, n images back to back in call order,
+ *     rows * stride bytes each (frame_index must be NULL). Frames inside a range
+ *     registered with vio_host_register (stride == cols) go to the device by DMA from
+ *     where they lie, others through the gather of read_images.
+ *   frames_on_device = 1: a packed [slots][rows][cols] device buffer the caller owns
+ *     (stride == cols; what vio_preprocess_run_resident writes); frame_index[i] names
+ *     the slot of seq[i], NULL = slot i. The caller guarantees the frames are complete
+ *     (its producer has finished) before the call.
+ * On EVERY route -- pageable host memory, a registered host range, device memory --
+ * the frames must stay valid and unchanged until vio_frontend_collect_subset returns.
+ * One frame in flight per context, shared with the lock-step submit: a second submit
+ * of either kind before the collect is VIO_ESTATE; vio_frontend_collect after
+ * submit_subset and vio_frontend_collect_subset after submit_images are VIO_ESTATE
+ * (the frame stays in flight). Duplicates or out-of-range entries of seq[], a wrong
+ * image size, a negative frame_index or publish == NULL with n > 0 are VIO_EINVAL and
+ * change no sequence. n == 0 is VIO_OK and launches nothing.
+ * collect_subset: out_obs [n][max_corners] and n_obs [n] in the CALL's order (row i
+ * belongs to seq[i]; 0 observations for a sequence that did not publish); the bytes
+ * that travel back scale with n, not with n_seq.
+ * vio_frontend_kernel_ms also averages the device time of subset calls made with
+ * frames_on_device = 1; the counters of vio_frontend_lk_iterations cover the
+ * lock-step entry points only.                                                      */
+int vio_frontend_submit_subset(vio_frontend_t *fe, int32_t n, const int32_t *seq, const void *frames,
+                               int32_t frames_on_device, const int32_t *frame_index /* [n], NULL = i */,
+                               int32_t rows, int32_t cols, int32_t stride, const uint8_t *publish /* [n] */);
+int vio_frontend_collect_subset(vio_frontend_t *fe, VioObs *out_obs /* [n][max_corners], call order */,
+                                int32_t *n_obs /* [n] */);
+/* submit_subset + collect_subset */
+int vio_frontend_read_subset(vio_frontend_t *fe, int32_t n, const int32_t *seq, const void *frames,
+                             int32_t frames_on_device, const int32_t *frame_index, int32_t rows, int32_t cols,
+                             int32_t stride, const uint8_t *publish, VioObs *out_obs, int32_t *n_obs);
+/* A fresh FeatureTracker (feature_tracker.cpp:162-310: first image, no points, n_id = 0,
+ * empty track_cnt) for the n sequences of seq[]; seq == NULL: for all of them. Other
+ * sequences are not touched. VIO_ESTATE while a frame is in flight, VIO_EINVAL for
+ * duplicates or entries out of range. Waits for the device. The estimator's
+ * counterpart is vio_estimator_clear.                                                */
+int vio_frontend_reset(vio_frontend_t *fe, int32_t n, const int32_t *seq);
+/* *in_step = 1 while every sequence of the context is in the same phase (same pyramid
+ * bank, all with or all without an image). The lock-step entry points --
+ * read_image(s), submit_images(_async), step_resident -- need that: after subset calls
+ * or resets have put the sequences out of phase they return VIO_ESTATE until the
+ * sequences are in phase again, which vio_frontend_reset(fe, 0, NULL) always brings
+ * about. A context that never calls the subset entries is always in step. The
+ * context's resident ring (upload_frames / step_resident) stays lock-step; a subset
+ * call on a context whose current image is still read in place from the ring first
+ * moves that image into the pyramid's own storage.                                    */
+int vio_frontend_in_step(vio_frontend_t *fe, int32_t *in_step);
+
 /* Host frame buffers registered once (camera / decoder ring buffers, the cv::Mat
  * storage behind `_img` in FeatureTracker::readImage, feature_tracker.cpp:162):
  * the range is page-locked in place, and read_images / submit_images(_async)

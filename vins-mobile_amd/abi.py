@@ -490,6 +490,12 @@ def load_product():
     lib.vio_frontend_submit_images.argtypes = [vp, u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.vio_frontend_submit_images_async.argtypes = [vp, u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.vio_frontend_collect.argtypes = [vp, C.POINTER(VioObs), _ip]
+    lib.vio_frontend_submit_subset.argtypes = [vp, C.c_int32, _ip, vp, C.c_int32, _ip, C.c_int32, C.c_int32, C.c_int32, u8p]
+    lib.vio_frontend_collect_subset.argtypes = [vp, C.POINTER(VioObs), _ip]
+    lib.vio_frontend_read_subset.argtypes = [vp, C.c_int32, _ip, vp, C.c_int32, _ip, C.c_int32, C.c_int32, C.c_int32, u8p,
+                                             C.POINTER(VioObs), _ip]
+    lib.vio_frontend_reset.argtypes = [vp, C.c_int32, _ip]
+    lib.vio_frontend_in_step.argtypes = [vp, _ip]
     lib.vio_host_register.argtypes = [vp, C.c_size_t]
     lib.vio_host_unregister.argtypes = [vp]
     lib.vio_frontend_upload_frames.argtypes = [vp, u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
+#include <stdint.h>
 
 namespace {
 
@@ -28,6 +29,21 @@ __device__ __forceinline__ int reflect101(int p, int len) {
   return p;
 }
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// What the subset instantiations of the step's kernels (vio_frontend_submit_subset) take in place of "sequence = block index, one
+// pyramid bank for all": the call's plan (fe_subset.h) on the device, n entries per row, and the context's two banks. Call
+// position i = a block index; everything read through it is uniform over the workgroup and is kept in scalar registers.
+struct SubsetArgs {
+  const int *seq;        // [n] sequence of call position i
+  const int *slot;       // [n] frame slot
+  const int *prev_bank;  // [n] bank LK tracks from, < 0: the sequence's first frame
+  const int *forw_bank;  // [n] bank the frame's pyramid goes to
+  const int *publish;    // [n]
+  const int *pub;        // [n_pub] call positions that publish
+  uint8_t *pyr[2];       // the banks, [n_seq][pyr_bytes] each
+};
+__device__ __forceinline__ int subset_at(const int *row, int i) { return __builtin_amdgcn_readfirstlane(row[i]); }
+__device__ __forceinline__ uint8_t *subset_bank(const SubsetArgs &M, int bank) { return bank ? M.pyr[1] : M.pyr[0]; }
 
 typedef short lk_s2 __attribute__((ext_vector_type(2)));
 typedef unsigned short lk_us2 __attribute__((ext_vector_type(2)));

@@ -275,6 +275,19 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t *img_base, si
                                           blockIdx.y, gridDim.y);
 }
 
+// Subset instantiation (the step's form: setMask discs, no mask image): blockIdx.z counts the PUBLISHED sequences of the call;
+// the image is level 0 of the sequence's forw bank (M.pyr, img_stride apart).
+__global__ __launch_bounds__(256) void detect_subset_kernel(SubsetArgs M, size_t img_stride, const int *kept_xy, const int *n_kept, int cap,
+                                                            const int *hw, int radius, unsigned *max_bits, int rows, int cols,
+                                                            unsigned long long *cand_base, int seg_cap, int *n_cand, int *ovf, int epoch,
+                                                            const int *n_have, int max_corners) {
+  const int i = subset_at(M.pub, blockIdx.z), seq = subset_at(M.seq, i);
+  if (n_have && n_have[seq] >= max_corners) return;
+  detect_tile<false, false, kDetWaves>(subset_bank(M, subset_at(M.forw_bank, i)), img_stride, (const uint8_t *)nullptr, (size_t)0, kept_xy,
+                                       n_kept, cap, hw, radius, max_bits, rows, cols, cand_base, seg_cap, n_cand, ovf, epoch,
+                                       (unsigned long long *)nullptr, seq, blockIdx.x, blockIdx.y, gridDim.y);
+}
+
 #undef LANE_LEFT
 #undef LANE_RIGHT
 

@@ -334,4 +334,67 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
   }
 }
 
+// Subset instantiation (the step's form: no mask image): the same two kinds of workgroup over the n_pub PUBLISHED sequences of a
+// call. Workgroup k < n_pub takes call position pub[k]; the redo workgroups behind them find the flagged sequences among those
+// n_pub through ovf[] == epoch as above (a sequence outside the call keeps an older stamp or, after a reset, none). The image
+// of a redo is level 0 of the sequence's forw bank (M.pyr, R.img_stride apart; R.img_base, R.mask_base and R.n_seq are not used).
+// select_sequence is the lock-step kernel's, untouched: image_msg lands in the sequence's own row of obs / n_obs, and
+// gather_obs_subset_kernel below packs the call's rows.
+__global__ __launch_bounds__(kSelThreads) void corner_select_subset_kernel(SubsetArgs M, int n_pub, unsigned long long *cand_base,
+                                                                           int seg_cap, int nseg, int *n_cand, unsigned *max_bits,
+                                                                           RedoParams R, double quality, SelectParams P, float *forw_pts,
+                                                                           float *cur_pts, float *pre_pts, int *ids, int *track_cnt,
+                                                                           int *n_forw, int *n_pts, int *n_id, VioObs *obs, int *n_obs) {
+  const bool redo = (int)blockIdx.x >= n_pub;
+  const int slot = (int)blockIdx.x - n_pub, n_slots = R.n_wg;
+  if (redo) {
+    int any = 0;
+    for (int k = slot + n_slots * (int)threadIdx.x; k < n_pub; k += n_slots * kSelThreads) any |= R.ovf[M.seq[M.pub[k]]] == R.epoch;
+    if (!__syncthreads_or(any)) return;
+  }
+  for (int k = redo ? slot : (int)blockIdx.x; k < n_pub; k += redo ? n_slots : n_pub) {
+    const int i = subset_at(M.pub, k), seq = subset_at(M.seq, i);
+    const bool flagged = R.ovf[seq] == R.epoch;  // (uniform)
+    if (redo && !flagged) continue;
+    unsigned long long *cand = cand_base + (size_t)seq * nseg * seg_cap;
+    int cand_seg = seg_cap;
+    if (redo) {
+      cand = R.full + (size_t)slot * P.rows * P.cols, cand_seg = kDetR * P.cols;
+      constexpr int NW = kSelThreads / 64;
+      const int nbx = (P.cols + NW * kDetW - 1) / (NW * kDetW);
+      const uint8_t *img = subset_bank(M, subset_at(M.forw_bank, i));
+      for (int by = 0; by < nseg; by++)
+        for (int bx = 0; bx < nbx; bx++) {
+          detect_tile<false, true, NW>(img, R.img_stride, (const uint8_t *)nullptr, (size_t)0, R.kept_xy, R.n_kept, P.cap, R.hw, R.radius,
+                                       (unsigned *)nullptr, P.rows, P.cols, (unsigned long long *)nullptr, 0, (int *)nullptr, (int *)nullptr, 0,
+                                       cand, seq, bx, by, nseg);
+          __syncthreads();  // (the next tile clears the mask words this one reads; behind the last tile: the list is written)
+        }
+      if (threadIdx.x == 0) atomicAdd(R.n_redo, 1);
+    }
+    select_sequence(cand, cand_seg, nseg, n_cand, max_bits, quality, P, forw_pts, cur_pts, pre_pts, ids, track_cnt, n_forw, n_pts, n_id, obs,
+                    n_obs, (long long *)nullptr, seq, redo, !redo && flagged);
+    if (redo) __syncthreads();  // (the next sequence reuses the selection's LDS)
+  }
+}
+
+// image_msg of a subset call in the call's order: row i of obs_out / n_out = the observations of sequence seq[i] if it published,
+// none otherwise -- the rows that travel back to the host are the call's n, not the context's n_seq. One workgroup per call position.
+__global__ __launch_bounds__(256) void gather_obs_subset_kernel(SubsetArgs M, int cap, const VioObs *obs, const int *n_obs, VioObs *obs_out,
+                                                                int *n_out) {
+  const int i = blockIdx.x, seq = subset_at(M.seq, i);
+  const int m = subset_at(M.publish, i) ? min(subset_at(n_obs, seq), cap) : 0;
+  if (threadIdx.x == 0) n_out[i] = m;
+  for (int k = threadIdx.x; k < m; k += blockDim.x) obs_out[(size_t)i * cap + k] = obs[(size_t)seq * cap + k];
+}
+
+// vio_frontend_reset: a fresh FeatureTracker for the listed sequences -- no points, ids from 0 again (n_id, feature_tracker.cpp:311),
+// and no overflow stamp, so that a stamp from before the reset can never match a later detection pass.
+__global__ void reset_sequences_kernel(const int *seq, int n, int *n_pts, int *n_forw, int *n_id, int *n_pnp, int *n_kept, int *ovf) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = seq[i];
+  n_pts[s] = 0, n_forw[s] = 0, n_id[s] = 0, n_pnp[s] = 0, n_kept[s] = 0, ovf[s] = 0;
+}
+
 }  // namespace

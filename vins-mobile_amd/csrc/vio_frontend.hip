@@ -3,6 +3,8 @@
 // Drop-in for FeatureTracker::readImage (VINS_ios/feature_tracker.cpp:162-321) over a batch of independent sequences:
 // every kernel takes (sequence, item) grids so one set of launches advances all trackers by one frame.
 //   fe_common.h        limits, LevelDims, reflect101, descale: what the headers below share
+//   fe_subset.h        (host only) the plan of a subset call: per-sequence phase bits -> launch lists; every kernel below has a
+//                      subset instantiation next to it that takes the plan (SubsetArgs) in place of "sequence = block index"
 //   fe_pyramid.h       pyr_down_kernel        cv::pyrDown levels of calcOpticalFlowPyrLK                  (feature_tracker.cpp:181)
 //                      pyr_down4_kernel       the same for rows of whole dwords; the level-1 launch can also write level 0
 //                                                                                      (feature_tracker.cpp:165-170,181)
@@ -40,6 +42,7 @@
 #include "vio_device.h"
 #include "vio_pool.h"
 
+#include "fe_subset.h"
 #include "fe_common.h"
 #include "fe_pyramid.h"
 #include "fe_lk.h"
@@ -128,6 +131,19 @@ struct vio_frontend {
     const uint8_t *gray = nullptr;
     int rows = 0, cols = 0, stride = 0, publish = 0, rc = VIO_OK;
   } *async = nullptr;
+  // Subset calls (vio_frontend_submit_subset / vio_frontend_reset, fe_subset.h): every sequence has its own phase. While all of them
+  // are in the same one (in_step) cur_idx / have_img above are the record, the lock-step entry points are allowed and keep it;
+  // the vectors are filled from it at the head of a subset call. Out of step the vectors are the record.
+  std::vector<uint8_t> ph_bank, ph_have, ph_seen;
+  bool in_step = true;
+  bool foreign_stream = false;  // a lock-step step was queued on a caller's stream: a subset call waits for the device once
+  PinnedBuf<int32_t> p_arena;   // the call's plan: seq | slot | prev bank | forw bank | publish | published list
+  DevBuf<int> d_arena;
+  DevBuf<VioObs> obs_sub;  // [n][cap] image_msg of a subset call in the call's order, and their counts
+  DevBuf<int> n_obs_sub;
+  bool pending_subset = false;  // the frame in flight came from submit_subset (pending_n sequences, pending_pub of them published)
+  int pending_n = 0, pending_pub = 0;
+  bool attr_set_subset = false;
   // host staging
   std::vector<VioObs> h_obs;
   std::vector<int> h_nobs;
@@ -184,7 +200,7 @@ SelectParams select_params(const VioConfig &cfg) {
 }
 
 // feature_tracker.cpp:183-205 (+ :235-255, :50-87 on publish frames) for every sequence: one workgroup each
-int launch_track_update(vio_frontend *fe, int publish, hipStream_t st) {
+TrackerArrays tracker_arrays(vio_frontend *fe) {
   TrackerArrays A;
   A.cap = fe->cap, A.rows = fe->cfg.image_rows, A.cols = fe->cfg.image_cols;
   A.cur_pts = fe->cur_pts.p, A.pre_pts = fe->pre_pts.p, A.forw_pts = fe->forw_pts.p, A.ids = fe->ids.p, A.track_cnt = fe->track_cnt.p;
@@ -192,6 +208,12 @@ int launch_track_update(vio_frontend *fe, int publish, hipStream_t st) {
   A.n_kept = fe->n_kept.p, A.hw = fe->hw.p, A.radius = fe->cfg.min_dist, A.f_thresh = (float)fe->cfg.f_threshold;
   A.pnp_pts = fe->pnp_pts.p, A.pnp_ids = fe->pnp_ids.p, A.n_pnp = fe->n_pnp.p;
   A.f_conf = fe->cfg.f_confidence;
+  A.prof = nullptr;
+  return A;
+}
+
+int launch_track_update(vio_frontend *fe, int publish, hipStream_t st) {
+  TrackerArrays A = tracker_arrays(fe);
   static const bool tu_prof = vio::env_flag("VIO_AMD_TU_PROF");
   if (tu_prof) (void)fe->d_prof.ensure(32);
   A.prof = tu_prof ? fe->d_prof.p : nullptr;
@@ -308,6 +330,103 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
   return VIO_OK;
 }
 
+// An image that is still read in place from the context's ring (fe->lvl0) moves into its pyramid: the ring is about to go
+// (upload_frames), or the sequences are about to leave the lock-step phase the aliasing relies on (subset calls, reset).
+int own_level0(vio_frontend *fe) {
+  if (!fe->lvl0[0] && !fe->lvl0[1]) return VIO_OK;
+  const size_t px = (size_t)fe->cfg.image_rows * fe->cfg.image_cols;
+  HIP_OK(hipDeviceSynchronize());
+  for (int k = 0; k < 2; k++) {
+    if (fe->lvl0[k]) HIP_OK(hipMemcpy2D(fe->pyr[k].p, fe->ld.pyr_bytes, fe->lvl0[k], px, px, fe->n_seq, hipMemcpyDeviceToDevice));
+    fe->lvl0[k] = nullptr;
+  }
+  return VIO_OK;
+}
+
+// The phase vectors as the lock-step record says (in step), ready for a subset call or a reset to change them.
+void phase_from_lockstep(vio_frontend *fe) {
+  if (!fe->in_step && !fe->ph_bank.empty()) return;
+  fe->ph_bank.assign(fe->n_seq, fe->have_img ? (uint8_t)fe->cur_idx : 0), fe->ph_have.assign(fe->n_seq, fe->have_img ? 1 : 0);
+  fe->ph_seen.assign(fe->n_seq, 0);
+  if (!fe->have_img) fe->cur_idx = 0;
+}
+// ... and back: a call that leaves every sequence in the same phase hands the record to the lock-step entry points again.
+void phase_to_lockstep(vio_frontend *fe) {
+  fe->in_step = fe_subset::in_step(fe->n_seq, fe->ph_bank.data(), fe->ph_have.data());
+  if (fe->in_step) fe->cur_idx = fe->ph_bank[0], fe->have_img = fe->ph_have[0] != 0;
+}
+
+// readImage for the n sequences of a plan (feature_tracker.cpp:162-310): the subset instantiations of fe_step's kernels, every one
+// launched once over the call's sequences (detection and selection: over the n_pub that publish). d_frames: packed frame slots
+// on the device; M: the plan on the device. Level 0 always becomes the pyramid's own copy.
+int fe_step_subset(vio_frontend *fe, const SubsetArgs &M, int n, int n_pub, const uint8_t *d_frames, hipStream_t st) {
+  const int rows = fe->cfg.image_rows, cols = fe->cfg.image_cols, cap = fe->cap;
+  const size_t img_bytes = (size_t)rows * cols;
+  const LevelDims &ld = fe->ld;
+  const bool fused0 = ld.levels >= 2 && cols % 4 == 0 && ld.cols[1] % 4 == 0 && cols >= 8 && ld.pyr_bytes % 4 == 0 && img_bytes % 4 == 0 &&
+                      (uintptr_t)d_frames % 4 == 0 && (uintptr_t)M.pyr[0] % 4 == 0 && (uintptr_t)M.pyr[1] % 4 == 0 && ld.off[1] % 4 == 0;
+  if (!fused0) {
+    const int vec_ok = img_bytes % 16 == 0 && ld.pyr_bytes % 16 == 0 && (uintptr_t)d_frames % 16 == 0 && (uintptr_t)M.pyr[0] % 16 == 0 &&
+                       (uintptr_t)M.pyr[1] % 16 == 0;
+    dim3 grd((unsigned)((img_bytes + 16 * 256 - 1) / (16 * 256)), n);
+    hipLaunchKernelGGL(copy_frames_subset_kernel, grd, dim3(256), 0, st, M, d_frames, img_bytes, ld.pyr_bytes, img_bytes, vec_ok);
+  }
+  for (int l = 1; l < ld.levels; l++) {
+    const int sc = ld.cols[l - 1], dc = ld.cols[l];
+    if (l == 1 && fused0) {
+      dim3 grd((dc + kPdW - 1) / kPdW, (ld.rows[1] + kPd4H * kPd4T - 1) / (kPd4H * kPd4T), n);
+      hipLaunchKernelGGL(pyr_down4_subset_kernel<true>, grd, dim3(256), 0, st, M, d_frames, img_bytes, (size_t)0, ld.off[1], ld.pyr_bytes, rows,
+                         cols, ld.rows[1], dc);
+      continue;
+    }
+    const bool dwords = sc % 4 == 0 && dc % 4 == 0 && sc >= 8 && ld.pyr_bytes % 4 == 0 && ld.off[l - 1] % 4 == 0 && ld.off[l] % 4 == 0 &&
+                        (uintptr_t)M.pyr[0] % 4 == 0 && (uintptr_t)M.pyr[1] % 4 == 0;
+    if (dwords) {
+      dim3 grd((dc + kPdW - 1) / kPdW, (ld.rows[l] + kPd4H * kPd4T - 1) / (kPd4H * kPd4T), n);
+      hipLaunchKernelGGL(pyr_down4_subset_kernel<false>, grd, dim3(256), 0, st, M, (const uint8_t *)nullptr, (size_t)0, ld.off[l - 1], ld.off[l],
+                         ld.pyr_bytes, ld.rows[l - 1], sc, ld.rows[l], dc);
+    } else {
+      dim3 grd((dc + kPdW - 1) / kPdW, (ld.rows[l] + kPdH - 1) / kPdH, n);
+      hipLaunchKernelGGL(pyr_down_subset_kernel, grd, dim3(256), 0, st, M, ld.off[l - 1], ld.off[l], ld.pyr_bytes, ld.rows[l - 1], sc,
+                         ld.rows[l], dc);
+    }
+  }
+  {  // (a sequence on its first frame leaves at once: pre_img = cur_img = forw_img, :166-167)
+    LkParams P = lk_params(fe->cfg, ld);
+    P.prev0 = P.next0 = nullptr, P.stride0 = 0;
+    hipLaunchKernelGGL(lk_track_subset_kernel, dim3((cap + 3) / 4, n), dim3(256), 0, st, M, P, fe->n_pts.p, fe->cur_pts.p, fe->forw_pts.p,
+                       fe->lk_status.p);
+  }
+  {
+    const TrackerArrays A = tracker_arrays(fe);
+    const bool small = cap <= 256;
+    const size_t shm = ((small ? sizeof(TrackShared<256>) : sizeof(TrackShared<kMaxCap>)) + 15 & ~(size_t)15) + sizeof(RansacShared);
+    if (!fe->attr_set_subset) {
+      const void *kern = small ? (const void *)track_update_subset_kernel<256> : (const void *)track_update_subset_kernel<kMaxCap>;
+      HIP_OK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+      fe->attr_set_subset = true;
+    }
+    if (small) hipLaunchKernelGGL(track_update_subset_kernel<256>, dim3(n), dim3(256), shm, st, A, M);
+    else hipLaunchKernelGGL(track_update_subset_kernel<kMaxCap>, dim3(n), dim3(256), shm, st, A, M);
+  }
+  if (n_pub > 0) {
+    dim3 tg((cols + kDetWaves * kDetW - 1) / (kDetWaves * kDetW), fe->nseg, n_pub);
+    hipLaunchKernelGGL(detect_subset_kernel, tg, dim3(256), 0, st, M, ld.pyr_bytes, fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist,
+                       fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, fe->ovf.p, next_epoch(fe),
+                       fe->detect_always ? (const int *)nullptr : fe->n_forw.p, fe->cfg.max_corners);
+    const SelectParams SP = select_params(fe->cfg);
+    RedoParams RP = redo_params(fe, nullptr, ld.pyr_bytes, nullptr, 0, fe->cfg.min_dist);
+    RP.n_wg = std::min(fe->n_redo_wg, n_pub);
+    hipLaunchKernelGGL(corner_select_subset_kernel, dim3(n_pub + RP.n_wg), dim3(kSelThreads), 0, st, M, n_pub, fe->cand.p, fe->seg_cap, fe->nseg,
+                       fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
+                       fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p);
+  }
+  // image_msg in the call's order: only these rows travel back
+  hipLaunchKernelGGL(gather_obs_subset_kernel, dim3(n), dim3(256), 0, st, M, cap, fe->obs.p, fe->n_obs.p, fe->obs_sub.p, fe->n_obs_sub.p);
+  HIP_OK(hipGetLastError());
+  return VIO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -399,11 +518,8 @@ int vio_frontend_upload_frames(vio_frontend_t *fe, const uint8_t *gray, int32_t 
   if (fe->pending) return VIO_ESTATE;
   // the current image may still be read in place from the ring that is about to go: it moves into its pyramid first
   HIP_OK(hipDeviceSynchronize());
-  for (int k = 0; k < 2; k++) {
-    if (fe->lvl0[k])
-      HIP_OK(hipMemcpy2D(fe->pyr[k].p, fe->ld.pyr_bytes, fe->lvl0[k], px, px, fe->n_seq, hipMemcpyDeviceToDevice));
-    fe->lvl0[k] = nullptr;
-  }
+  const int rco = own_level0(fe);
+  if (rco != VIO_OK) return rco;
   fe->frames.release();  // (exactly the new size)
   if (fe->frames.ensure(total * px) != VIO_OK) return VIO_ENOMEM;
   HIP_OK(hipMemcpy2D(fe->frames.p, cols, gray, stride, cols, total * rows, hipMemcpyHostToDevice));
@@ -415,8 +531,10 @@ int vio_frontend_step_resident(vio_frontend_t *fe, int32_t frame_index, int32_t 
   if (!fe) return VIO_EINVAL;
   if (!fe->frames.p || frame_index < 0 || frame_index >= fe->n_frames) return VIO_ESTATE;
   if (fe->pending) return VIO_ESTATE;  // a submitted frame owns the tracker state and the observation staging until it is collected
+  if (!fe->in_step) return VIO_ESTATE;  // subset calls or resets left the sequences in different phases (vio_frontend_in_step)
   VIO_ON_DEVICE_OF(fe);
   hipStream_t st = stream ? (hipStream_t)stream : fe->stream;
+  if (st != fe->stream) fe->foreign_stream = true;
   int rc = fe->timer.begin(st);
   if (rc != VIO_OK) return rc;
   const size_t px = (size_t)fe->cfg.image_rows * fe->cfg.image_cols;
@@ -540,6 +658,7 @@ int vio_frontend_submit_images(vio_frontend_t *fe, const uint8_t *gray, int32_t 
   if (!fe || !gray) return VIO_EINVAL;
   if (rows != fe->cfg.image_rows || cols != fe->cfg.image_cols || stride < cols) return VIO_EINVAL;
   if (fe->pending) return VIO_ESTATE;  // one frame in flight per context: collect it first
+  if (!fe->in_step) return VIO_ESTATE;  // (vio_frontend_in_step)
   const int rc = submit_body(fe, gray, rows, cols, stride, publish);
   if (rc != VIO_OK) return rc;
   fe->pending = true, fe->pending_publish = publish != 0, fe->pending_async = false;
@@ -553,6 +672,7 @@ int vio_frontend_submit_images_async(vio_frontend_t *fe, const uint8_t *gray, in
   if (!fe || !gray) return VIO_EINVAL;
   if (rows != fe->cfg.image_rows || cols != fe->cfg.image_cols || stride < cols) return VIO_EINVAL;
   if (fe->pending) return VIO_ESTATE;
+  if (!fe->in_step) return VIO_ESTATE;
   try {
     if (!fe->async) {
       fe->async = new vio_frontend::Async();
@@ -588,7 +708,7 @@ int vio_frontend_submit_images_async(vio_frontend_t *fe, const uint8_t *gray, in
 
 int vio_frontend_collect(vio_frontend_t *fe, VioObs *out_obs, int32_t *n_obs) {
   if (!fe || !n_obs) return VIO_EINVAL;
-  if (!fe->pending) return VIO_ESTATE;
+  if (!fe->pending || fe->pending_subset) return VIO_ESTATE;  // (a subset submit is collected by vio_frontend_collect_subset)
   if (fe->pending_publish && !out_obs) return VIO_EINVAL;
   if (fe->async && fe->pending_async) {  // an asynchronous submit finishes queueing first (a->rc belongs to THAT submit only)
     vio_frontend::Async *a = fe->async;
@@ -626,6 +746,141 @@ int vio_frontend_read_image(vio_frontend_t *fe, int32_t seq, const uint8_t *gray
   (void)seq, (void)viz;
   if (!fe || fe->n_seq != 1 || seq != 0) return VIO_EINVAL;  // single-sequence contexts only; batches use read_images
   return vio_frontend_read_images(fe, gray, rows, cols, stride, &header, publish, out_obs, n_obs);
+}
+
+// ---- frames for a subset of the sequences, per-sequence publish, reset (fe_subset.h plans, fe_step_subset launches) -----------
+int vio_frontend_submit_subset(vio_frontend_t *fe, int32_t n, const int32_t *seq, const void *frames, int32_t frames_on_device,
+                               const int32_t *frame_index, int32_t rows, int32_t cols, int32_t stride, const uint8_t *publish) {
+  if (!fe || n < 0 || n > fe->n_seq) return VIO_EINVAL;
+  if (rows != fe->cfg.image_rows || cols != fe->cfg.image_cols || stride < cols) return VIO_EINVAL;
+  if (n > 0 && (!seq || !frames || !publish)) return VIO_EINVAL;
+  if (frames_on_device ? stride != cols : frame_index != nullptr) return VIO_EINVAL;  // (packed slots; host frames lie in call order)
+  if (fe->pending) return VIO_ESTATE;  // one frame in flight per context, lock-step or subset
+  VIO_ON_DEVICE_OF(fe);
+  phase_from_lockstep(fe);
+  const size_t S = fe->n_seq, px = (size_t)rows * cols;
+  if (fe->p_arena.ensure(fe_subset::arena_ints((int)S)) != VIO_OK || fe->d_arena.ensure(fe_subset::arena_ints((int)S)) != VIO_OK) return VIO_ENOMEM;
+  const fe_subset::Arena H = fe_subset::carve(fe->p_arena.p, n);
+  int n_pub = 0;
+  if (!fe_subset::plan((int)S, fe->ph_bank.data(), fe->ph_have.data(), n, seq, frame_index, -1, publish, fe->ph_seen.data(), H, &n_pub))
+    return VIO_EINVAL;  // (nothing was changed)
+  fe->pending = true, fe->pending_subset = true, fe->pending_async = false, fe->pending_publish = n_pub > 0;
+  fe->pending_n = n, fe->pending_pub = n_pub;
+  if (n == 0) return VIO_OK;  // nothing to launch: collect_subset hands back nothing
+  auto fail = [&](int rc) {
+    fe->pending = fe->pending_subset = false;
+    return rc;
+  };
+  hipStream_t st = fe->stream;
+  if (fe->foreign_stream) {  // (a lock-step step on a caller's stream may still be running)
+    if (hipDeviceSynchronize() != hipSuccess) return fail(VIO_ENODEV);
+    fe->foreign_stream = false;
+  }
+  int rc = own_level0(fe);
+  if (rc != VIO_OK) return fail(rc);
+  if (fe->p_obs.ensure(S * fe->cap) != VIO_OK || fe->p_nobs.ensure(S) != VIO_OK || fe->obs_sub.ensure(S * fe->cap) != VIO_OK ||
+      fe->n_obs_sub.ensure(S) != VIO_OK)
+    return fail(VIO_ENOMEM);
+  const uint8_t *d_frames = static_cast<const uint8_t *>(frames);
+  if (!frames_on_device) {
+    const uint8_t *gray = static_cast<const uint8_t *>(frames);
+    if (fe->d_stage.ensure(S * px) != VIO_OK) return fail(VIO_ENOMEM);
+    if (stride == cols && host_range_registered(gray, (size_t)n * px)) {
+      if (hipMemcpyAsync(fe->d_stage.p, gray, (size_t)n * px, hipMemcpyHostToDevice, st) != hipSuccess) return fail(VIO_ENODEV);
+    } else {  // the gather of read_images, over the call's n frames
+      if (fe->p_frames.ensure(S * px) != VIO_OK) return fail(VIO_ENOMEM);
+      const size_t N = n, n_chunks = N >= 32 ? 8 : 1, per = (N + n_chunks - 1) / n_chunks;
+      for (size_t c0 = 0; c0 < N; c0 += per) {
+        const size_t c1 = std::min(N, c0 + per);
+        vio::HostPool::get().parallel_for((int)(c1 - c0), [&](int i) {
+          const size_t s = c0 + i;
+          const uint8_t *src = gray + s * (size_t)rows * stride;
+          uint8_t *dst = fe->p_frames.p + s * px;
+          if (stride == cols) memcpy(dst, src, px);
+          else
+            for (int r = 0; r < rows; r++) memcpy(dst + (size_t)r * cols, src + (size_t)r * stride, cols);
+        });
+        if (hipMemcpyAsync(fe->d_stage.p + c0 * px, fe->p_frames.p + c0 * px, (c1 - c0) * px, hipMemcpyHostToDevice, st) != hipSuccess)
+          return fail(VIO_ENODEV);
+      }
+    }
+    d_frames = fe->d_stage.p;
+  }
+  if (frames_on_device && (rc = fe->timer.begin(st)) != VIO_OK) return fail(rc);  // (vio_frontend_kernel_ms, as step_resident)
+  if (hipMemcpyAsync(fe->d_arena.p, fe->p_arena.p, sizeof(int32_t) * fe_subset::arena_ints(n), hipMemcpyHostToDevice, st) != hipSuccess)
+    return fail(VIO_ENODEV);
+  const fe_subset::Arena D = fe_subset::carve(fe->d_arena.p, n);
+  SubsetArgs M;
+  M.seq = D.seq, M.slot = D.slot, M.prev_bank = D.prev_bank, M.forw_bank = D.forw_bank, M.publish = D.publish, M.pub = D.pub;
+  M.pyr[0] = fe->pyr[0].p, M.pyr[1] = fe->pyr[1].p;
+  if ((rc = fe_step_subset(fe, M, n, n_pub, d_frames, st)) != VIO_OK) return fail(rc);
+  if (frames_on_device && (rc = fe->timer.end(st)) != VIO_OK) return fail(rc);
+  if (hipMemcpyAsync(fe->p_nobs.p, fe->n_obs_sub.p, sizeof(int) * n, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(VIO_ENODEV);
+  if (n_pub > 0 && hipMemcpyAsync(fe->p_obs.p, fe->obs_sub.p, sizeof(VioObs) * (size_t)n * fe->cap, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return fail(VIO_ENODEV);
+  fe_subset::commit(fe->ph_bank.data(), fe->ph_have.data(), n, H);
+  phase_to_lockstep(fe);
+  return VIO_OK;
+}
+
+int vio_frontend_collect_subset(vio_frontend_t *fe, VioObs *out_obs, int32_t *n_obs) {
+  if (!fe) return VIO_EINVAL;
+  if (!fe->pending || !fe->pending_subset) return VIO_ESTATE;  // (a lock-step submit is collected by vio_frontend_collect)
+  const size_t n = fe->pending_n;
+  if (n > 0 && (!n_obs || (fe->pending_pub > 0 && !out_obs))) return VIO_EINVAL;
+  VIO_ON_DEVICE_OF(fe);
+  fe->pending = fe->pending_subset = false;
+  if (n == 0) return VIO_OK;
+  HIP_OK(hipStreamSynchronize(fe->stream));
+  for (size_t i = 0; i < n; i++) {
+    n_obs[i] = fe->p_nobs.p[i];
+    if (n_obs[i] > 0) memcpy(out_obs + i * fe->cap, fe->p_obs.p + i * fe->cap, sizeof(VioObs) * n_obs[i]);
+  }
+  return VIO_OK;
+}
+
+int vio_frontend_read_subset(vio_frontend_t *fe, int32_t n, const int32_t *seq, const void *frames, int32_t frames_on_device,
+                             const int32_t *frame_index, int32_t rows, int32_t cols, int32_t stride, const uint8_t *publish,
+                             VioObs *out_obs, int32_t *n_obs) {
+  if (n > 0 && (!n_obs || !out_obs)) return VIO_EINVAL;
+  const int rc = vio_frontend_submit_subset(fe, n, seq, frames, frames_on_device, frame_index, rows, cols, stride, publish);
+  if (rc != VIO_OK) return rc;
+  return vio_frontend_collect_subset(fe, out_obs, n_obs);
+}
+
+int vio_frontend_reset(vio_frontend_t *fe, int32_t n, const int32_t *seq) {
+  if (!fe) return VIO_EINVAL;
+  if (fe->pending) return VIO_ESTATE;
+  VIO_ON_DEVICE_OF(fe);
+  phase_from_lockstep(fe);
+  const int S = fe->n_seq;
+  if (seq && !fe_subset::valid_list(S, n, seq, fe->ph_seen.data())) return VIO_EINVAL;
+  if (seq && n == 0) return VIO_OK;
+  HIP_OK(hipDeviceSynchronize());  // (rare: whatever stream the last step ran on)
+  fe->foreign_stream = false;
+  int rc = VIO_OK;
+  if (!seq) {  // all of them: the aliased images go with their sequences
+    fe->lvl0[0] = fe->lvl0[1] = nullptr;
+    for (int *p : {fe->n_pts.p, fe->n_forw.p, fe->n_id.p, fe->n_pnp.p, fe->n_kept.p, fe->ovf.p}) HIP_OK(hipMemsetAsync(p, 0, sizeof(int) * S, fe->stream));
+  } else {
+    if ((rc = own_level0(fe)) != VIO_OK) return rc;
+    if (fe->p_arena.ensure(fe_subset::arena_ints(S)) != VIO_OK || fe->d_arena.ensure(fe_subset::arena_ints(S)) != VIO_OK) return VIO_ENOMEM;
+    memcpy(fe->p_arena.p, seq, sizeof(int32_t) * n);
+    HIP_OK(hipMemcpyAsync(fe->d_arena.p, fe->p_arena.p, sizeof(int32_t) * n, hipMemcpyHostToDevice, fe->stream));
+    hipLaunchKernelGGL(reset_sequences_kernel, dim3((n + 255) / 256), dim3(256), 0, fe->stream, fe->d_arena.p, n, fe->n_pts.p, fe->n_forw.p,
+                       fe->n_id.p, fe->n_pnp.p, fe->n_kept.p, fe->ovf.p);
+    HIP_OK(hipGetLastError());
+  }
+  HIP_OK(hipStreamSynchronize(fe->stream));
+  fe_subset::reset(S, fe->ph_bank.data(), fe->ph_have.data(), n, seq);
+  phase_to_lockstep(fe);
+  return VIO_OK;
+}
+
+int vio_frontend_in_step(vio_frontend_t *fe, int32_t *in_step) {
+  if (!fe || !in_step) return VIO_EINVAL;
+  *in_step = fe->in_step ? 1 : 0;
+  return VIO_OK;
 }
 
 int vio_frontend_get_state(vio_frontend_t *fe, int32_t seq, float *cur_pts, int32_t *ids, int32_t *track_cnt, int32_t cap,

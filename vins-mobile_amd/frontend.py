@@ -21,6 +21,14 @@ _OBS_DTYPE = np.dtype({"names": ["id", "x", "y", "z"], "formats": ["<i4", "<f8",
 assert C.sizeof(abi.VioObs) == 32
 
 
+class TrackerError(RuntimeError):
+    """A front-end call that did not return VIO_OK; `rc` is the code (abi.VIO_EINVAL, abi.VIO_ESTATE, ...)."""
+
+    def __init__(self, what, rc):
+        super().__init__("%s failed rc=%d" % (what, rc))
+        self.rc = rc
+
+
 class FeatureTracker:
     def __init__(self, cfg=None, n_seq=1):
         self.lib = abi.load_product()
@@ -46,7 +54,7 @@ class FeatureTracker:
     @staticmethod
     def _check(rc, what):
         if rc != abi.VIO_OK:
-            raise RuntimeError("%s failed rc=%d" % (what, rc))
+            raise TrackerError(what, rc)
 
     def device(self):
         """HIP device the tracker's contexts live on (vio_frontend_get_device)."""
@@ -106,6 +114,72 @@ class FeatureTracker:
             o = obs[s, :int(n_obs[s])]
             out.append((o["id"].copy(), np.stack([o["x"], o["y"], o["z"]], axis=1)))
         return out
+
+    # ---- frames for a subset of the sequences (asynchronous cameras): per-sequence publish, reset ----------------------
+    def _subset_args(self, seqs, frames, publish, frame_index):
+        seqs = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        n = len(seqs)
+        publish = np.ascontiguousarray(np.broadcast_to(np.asarray(publish, np.uint8), (n,)))
+        fi = None if frame_index is None else np.ascontiguousarray(frame_index, np.int32).reshape(-1)
+        assert fi is None or len(fi) == n
+        if isinstance(frames, int):  # a device pointer: packed [slots][rows][cols]
+            ptr, on_dev, rows, cols, keep = C.c_void_p(frames), 1, self.cfg.image_rows, self.cfg.image_cols, None
+        else:
+            keep = frames if (isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags["C_CONTIGUOUS"]) \
+                else np.ascontiguousarray(frames, np.uint8)
+            assert keep.ndim == 3 and keep.shape[0] >= n, keep.shape
+            ptr, on_dev, rows, cols = C.c_void_p(keep.ctypes.data), 0, keep.shape[1], keep.shape[2]
+        return (n, seqs, publish, fi, keep), (self._h, n, seqs.ctypes.data_as(_ip), ptr, on_dev,
+                                              fi.ctypes.data_as(_ip) if fi is not None else None, rows, cols, cols,
+                                              publish.ctypes.data_as(_u8p))
+
+    def submit_subset(self, seqs, frames, publish, frame_index=None):
+        """vio_frontend_submit_subset: frame i for sequence seqs[i] with publish[i] (one flag or one per sequence). frames:
+        uint8 [n, rows, cols] on the host (taken where it lies when C-contiguous, so a registered range is used in place), or
+        an int device pointer to packed [slots, rows, cols] frames, frame_index naming the slots. Kept alive until collect."""
+        keep, args = self._subset_args(seqs, frames, publish, frame_index)
+        rc = self.lib.vio_frontend_submit_subset(*args)
+        if rc == abi.VIO_OK:
+            self._pending_subset = keep
+        self._check(rc, "submit_subset")
+
+    def collect_subset(self):
+        """vio_frontend_collect_subset -> [(ids, xyz)] in the order of the submit's seqs (empty for a sequence that did not
+        publish)."""
+        n = self._pending_subset[0] if getattr(self, "_pending_subset", None) else 0
+        cap = self.cfg.max_corners
+        obs = np.zeros(max(n, 1) * cap, _OBS_DTYPE)
+        n_obs = np.zeros(max(n, 1), np.int32)
+        rc = self.lib.vio_frontend_collect_subset(self._h, C.cast(obs.ctypes.data, C.POINTER(abi.VioObs)), n_obs.ctypes.data_as(_ip))
+        if rc != abi.VIO_ESTATE:
+            self._pending_subset = None
+        self._check(rc, "collect_subset")
+        obs = obs.reshape(max(n, 1), cap)
+        out = []
+        for i in range(n):
+            o = obs[i, :int(n_obs[i])]
+            out.append((o["id"].copy(), np.stack([o["x"], o["y"], o["z"]], axis=1)))
+        return out
+
+    def read_subset(self, seqs, frames, publish, frame_index=None):
+        """readImage for the sequences of `seqs` only (vio_frontend_read_subset): submit_subset + collect_subset."""
+        self.submit_subset(seqs, frames, publish, frame_index)
+        return self.collect_subset()
+
+    def reset(self, seqs=None):
+        """vio_frontend_reset: a fresh FeatureTracker for the sequences of `seqs` (None: all of them)."""
+        if seqs is None:
+            rc = self.lib.vio_frontend_reset(self._h, 0, None)
+        else:
+            seqs = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+            rc = self.lib.vio_frontend_reset(self._h, len(seqs), seqs.ctypes.data_as(_ip))
+        self._check(rc, "reset")
+
+    def in_step(self):
+        """True while every sequence is in the same phase, i.e. while the lock-step calls (read_images, submit, step) are allowed."""
+        v = C.c_int32()
+        self._check(self.lib.vio_frontend_in_step(self._h, C.byref(v)), "in_step")
+        return bool(v.value)
 
     def state(self, seq=0):
         cap = self.cfg.max_corners
