@@ -1,7 +1,9 @@
 // tests/fuzz/host_sanity.cpp — TEST-ONLY driver that walks the host-side C++ of the library (landmark store, estimator state
 // machine incl. solveInitial, initialisation pieces, PnP tracker bookkeeping, measurement queue) under
-// -fsanitize=address,undefined (built and run by tests/test_abi_cpu.py). The device entry points those files call are
-// stubbed HERE to return VIO_ENODEV: this binary never solves anything, it only has to finish without a sanitizer report.
+// -fsanitize=address,undefined and -fsanitize=thread (built and run by tests/test_host_sanitizers.py). The device entry
+// points those files call are stubbed HERE to return VIO_ENODEV: this binary never solves anything, it has to finish without
+// a sanitizer report, and the estimator's three start-up routes (vio_estimator_set_init_device 0 / 1 / 2), which all end on
+// the host route without a device, have to walk the same states.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -56,8 +58,8 @@ static double nrand() { return sqrt(-2 * log(urand() + 1e-300)) * cos(6.28318530
 
 struct Scene {  // camera looking along +z of the body (ric = I), moving mostly sideways, slowly yawing
   std::vector<double> lm;
-  Scene() {
-    for (int i = 0; i < 400; i++) lm.push_back(-6 + 12 * urand()), lm.push_back(-4 + 8 * urand()), lm.push_back(4 + 6 * urand());
+  explicit Scene(bool fill = true) {  // (false: empty, no random draws; a walk of the estimator fills it)
+    for (int i = 0; fill && i < 400; i++) lm.push_back(-6 + 12 * urand()), lm.push_back(-4 + 8 * urand()), lm.push_back(4 + 6 * urand());
   }
   void pose(double t, double P[3], double R[9]) const {
     P[0] = 0.6 * t + 0.1 * sin(2 * t), P[1] = 0.15 * sin(1.3 * t), P[2] = 0.1 * cos(0.7 * t);
@@ -87,21 +89,36 @@ struct Scene {  // camera looking along +z of the body (ric = I), moving mostly 
     }                                                            \
   } while (0)
 
-int main(int argc, char **argv) {
-  const int NS = argc > 1 ? atoi(argv[1]) : 3;  // sequences in the estimator (>= 32 engages the host thread pool)
-  VioConfig cfg;
-  vio_config_default(&cfg);
-  cfg.window_size = 6;
-  const int W = cfg.window_size;
-  const double tic[3] = {0, 0.05, 0.01}, ric[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  Scene sc;
-  // ---- estimator: three sequences at different phases, own initialisation switched on for sequence 0's sake
+// One walk of the estimator: what every frame of every sequence answered and the windows it left behind, folded.
+struct Walk {
+  unsigned long long fold = 0xCBF29CE484222325ULL;
+  int actions[8] = {0, 0, 0, 0, 0, 0, 0, 0}, solve_attempts = 0;
+  void mix(unsigned long long v) {
+    fold = (fold ^ v) * 0x100000001B3ULL;
+    fold ^= fold >> 29;
+  }
+  void mix_bits(const double *x, int n) {
+    for (int i = 0; i < n; i++) {
+      unsigned long long b;
+      memcpy(&b, &x[i], sizeof(b));
+      mix(b);
+    }
+  }
+};
+
+// ---- estimator: three sequences at different phases, own initialisation switched on for sequence 0's sake. Every walk
+// starts from the same seed and leaves `sc` as the scene of that seed. Without the vio_init_* symbols, levels 1 and 2 send
+// every start-up out through the waiting path and bring it back on the host route.
+static int walk_estimator(const VioConfig &cfg, int NS, int level, const double tic[3], const double ric[9], Scene &sc, Walk &wk) {
+  st = 0x9E3779B97F4A7C15ULL;
+  sc = Scene();
+  const int P = cfg.window_size + 1;
   vio_estimator_t *est = nullptr;
   REQUIRE(NS >= 3 && vio_estimator_create(&cfg, NS, tic, ric, &est) == VIO_OK);
   REQUIRE(vio_estimator_enable_initialization(est, 1) == VIO_OK);
+  REQUIRE(vio_estimator_set_init_device(est, level) == VIO_OK);
   std::vector<VioObs> obs((size_t)NS * 160);
   std::vector<VioFrameResult> res(NS);
-  int solve_attempts = 0;
   for (int k = 0; k < 40; k++) {
     const double t = 0.1 * k;
     std::vector<int32_t> n_imu(NS);
@@ -127,16 +144,50 @@ int main(int argc, char **argv) {
       REQUIRE(vio_estimator_set_relocalization(est, 1, headers[2], P_old, Q_old, ids, xy, 4) == VIO_OK);
     }
     const int rc = vio_estimator_process_images(est, obs.data(), n_obs.data(), 160, hdr.data(), active.data(), res.data());
-    if (rc == VIO_ENODEV) solve_attempts++;  // solveInitial went through and wanted the device: stubbed here
+    if (rc == VIO_ENODEV) wk.solve_attempts++;  // solveInitial went through and wanted the device: stubbed here
     else REQUIRE(rc == VIO_OK || rc == VIO_ESTATE);  // (sequence 2 is fed IMU irregularly: a window without an interval)
+    for (int q = 0; q < NS; q++) {
+      const VioFrameResult &r = res[q];
+      REQUIRE(r.action >= 0 && r.action < 8);
+      wk.actions[r.action]++;
+      wk.mix((unsigned long long)(uint32_t)r.action), wk.mix((unsigned long long)(uint32_t)r.error);
+      wk.mix((unsigned long long)(uint32_t)r.marginalization_flag), wk.mix((unsigned long long)(uint32_t)r.track_num);
+    }
     VioEstimatorStatus stt;
     REQUIRE(vio_estimator_get_status(est, 0, &stt) == VIO_OK);
     if (k == 30) REQUIRE(vio_estimator_clear(est, 1) == VIO_OK);
   }
-  printf("host_sanity: estimator walked, %d frames reached the (stubbed) solve after solveInitial\n", solve_attempts);
+  for (int q = 0; q < NS; q++) {
+    double Ps[3 * 16], Rs[9 * 16], Vs[3 * 16], Bas[3 * 16], Bgs[3 * 16], headers[16];
+    REQUIRE(vio_estimator_get_window(est, q, Ps, Rs, Vs, Bas, Bgs, headers) == VIO_OK);
+    wk.mix_bits(Ps, 3 * P), wk.mix_bits(Rs, 9 * P), wk.mix_bits(Vs, 3 * P), wk.mix_bits(Bas, 3 * P), wk.mix_bits(Bgs, 3 * P);
+    wk.mix_bits(headers, P);
+  }
   double cP[3 * 16], cR[9 * 16];
   REQUIRE(vio_estimator_get_corrected_window(est, 0, cP, cR) == VIO_OK);
   vio_estimator_destroy(est);
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  const int NS = argc > 1 ? atoi(argv[1]) : 3;  // sequences in the estimator (>= 32 engages the host thread pool)
+  VioConfig cfg;
+  vio_config_default(&cfg);
+  cfg.window_size = 6;
+  const int W = cfg.window_size;
+  const double tic[3] = {0, 0.05, 0.01}, ric[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  Scene sc(false);
+  // ---- estimator: the same walk on each start-up route; they are one computation where there is no device
+  Walk wk[3];
+  for (int level = 0; level < 3; level++) REQUIRE(walk_estimator(cfg, NS, level, tic, ric, sc, wk[level]) == 0);
+  printf("host_sanity: estimator walked, %d frames reached the (stubbed) solve after solveInitial\n", wk[0].solve_attempts);
+  for (int level = 1; level < 3; level++) {
+    REQUIRE(wk[level].fold == wk[0].fold && wk[level].solve_attempts == wk[0].solve_attempts);
+    REQUIRE(memcmp(wk[level].actions, wk[0].actions, sizeof(wk[0].actions)) == 0);
+  }
+  printf("host_sanity: levels 0/1/2 agree, fold %016llx, actions", wk[0].fold);
+  for (int a = 0; a < 8; a++) printf(" %d", wk[0].actions[a]);
+  printf("\n");
 
   // ---- initialisation pieces on the same scene
   {
