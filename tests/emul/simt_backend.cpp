@@ -9,8 +9,7 @@
 #include <limits>
 #include <vector>
 
-#include "batch.h"
-#include "marg_core.h"
+#include "wk_plan.h"
 
 using namespace vio;
 
@@ -21,7 +20,7 @@ using namespace vio;
 extern "C" void simt_set_syrk_shares(int n) { vio::simt_syrk_shares() = n < 1 ? 1 : n; }
 
 // caps = {Wcap, Fcap, Mcap, Ncap, Flds, loop_cap}: the capacities of the batch the window is laid out in, as the launcher
-// (vio_backend.hip backend_upload_impl / plan_layout) sizes them for the largest window of a batch -- 0: the window's own, what
+// (vio_backend.hip backend_upload_impl, wk_plan.h) sizes them for the largest window of a batch -- 0: the window's own, what
 // simt_solve_window passes. loop_cap: the layout has room for a relocalization pose although this window has none (another
 // window of the batch carries one). Ncap > 0: max(6 Wcap + 15, Ncap), the launcher's prior capacity. VIO_EINVAL for a
 // capacity below the window's own size.
@@ -53,7 +52,7 @@ extern "C" int simt_solve_window_caps(const VioConfig *cfg, VioWindow *win, VioS
   std::vector<int> stats_i(s.stats_i);
   std::vector<double> m_scratch(marg_scratch_doubles(hb.d.Wcap), kNaN), m_x0(9 * kMaxPriorBlocks), m_J((size_t)hb.d.Ncap * hb.d.Ncap),
       m_r(hb.d.Ncap);
-  std::vector<int> m_int(4 + 3 * kMaxPriorBlocks);
+  std::vector<int> m_int(kMargInts);
   BatchPtrs B;
   B.n = 1, B.d = hb.d, B.s = s, B.order = nullptr, B.ptab = nullptr;
   B.hdr = hb.hdr.data(), B.hdr_d = hb.hdr_d.data();
@@ -71,25 +70,18 @@ extern "C" int simt_solve_window_caps(const VioConfig *cfg, VioWindow *win, VioS
   B.d.Flds = Flds;
   B.d.lds_asp = variant == 2 ? 0 : 1;  // variant 2: the LDS matrix with the IMU coupling in global scratch
 
-  // LDS or global matrix: the launcher's rule (vio_backend.hip backend_upload_impl)
-  auto lds_need = [&](bool lds_matrix) {
-    size_t se = 0, tail = 0;
-    const size_t bs = carve_work<double *>(B.d, lds_matrix, nthreads, nullptr, nullptr, nullptr, nullptr, &se, &tail);
-    const size_t bm = (se + tail) * sizeof(double) + carve_marg<double *>(B.d, lds_matrix, nullptr, nullptr, nullptr, 0);
-    return std::max(bs, bm + 64 * kMargSlot * sizeof(double));
-  };
-  bool lds_matrix = pose_jp(B.d) <= 16 * kPanelTiles && lds_need(true) <= kLdsBytes;
+  // LDS or global matrix: the launcher's rule for one window (wk_plan.h)
+  bool lds_matrix = vio_wk::lds_eligible(B.d, nthreads, B.d.lds_asp != 0);
   if ((variant == 1 || variant == 2) && !lds_matrix) return VIO_ECAP;
   if (variant == 0) lds_matrix = false;
-  if (!lds_matrix && lds_need(false) > kLdsBytes) return VIO_ECAP;
-  // (the launcher gives an LDS-variant workgroup half a CU whenever its layout fits there: two windows per CU)
-  const size_t lds_bytes = lds_matrix ? (lds_need(true) <= kLdsBytes / 2 ? kLdsBytes / 2 : kLdsBytes) : lds_need(false);
+  const size_t need = vio_wk::lds_need(B.d, lds_matrix, nthreads, B.d.lds_asp != 0);
+  if (need > kLdsBytes) return VIO_ECAP;
+  const size_t lds_bytes = lds_matrix ? vio_wk::lds_grant(need) : need;
   const size_t lds_doubles = lds_bytes / sizeof(double);
   std::vector<double> lds(lds_doubles + 2, kNaN);
 
-  MargOut mo;
-  mo.n = m_int.data(), mo.kind = m_int.data() + 4, mo.index = mo.kind + kMaxPriorBlocks, mo.offset = mo.index + kMaxPriorBlocks;
-  mo.x0 = m_x0.data(), mo.J = m_J.data(), mo.r = m_r.data(), mo.scratch = lds_matrix ? nullptr : m_scratch.data(), mo.ncap = hb.d.Ncap;
+  MargOut mo = marg_header(m_int.data(), hb.d.Ncap);
+  mo.x0 = m_x0.data(), mo.J = m_J.data(), mo.r = m_r.data(), mo.scratch = lds_matrix ? nullptr : m_scratch.data();
 
   // the body of vio_window_kernel (vio_backend.hip), one fiber per work-item
   simt::launch(nthreads, [&](int tid) {

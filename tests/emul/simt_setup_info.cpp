@@ -8,8 +8,7 @@
 
 #include <algorithm>
 
-#include "batch.h"
-#include "marg_core.h"
+#include "wk_plan.h"
 
 using namespace vio;
 
@@ -31,17 +30,13 @@ extern "C" int simt_setup_info(const VioConfig *cfg, const VioWindow *win, int n
   BatchDims d = hb.d;
   d.Flds = std::max(1, win->n_features);
   d.lds_asp = variant == 2 ? 0 : 1;
-  auto lds_need = [&](bool lds_matrix) {
-    size_t se = 0, tail = 0;
-    const size_t bs = carve_work<double *>(d, lds_matrix, nthreads, nullptr, nullptr, nullptr, nullptr, &se, &tail);
-    const size_t bm = (se + tail) * sizeof(double) + carve_marg<double *>(d, lds_matrix, nullptr, nullptr, nullptr, 0);
-    return std::max(bs, bm + 64 * kMargSlot * sizeof(double));
-  };
-  bool lds_matrix = pose_jp(d) <= 16 * kPanelTiles && lds_need(true) <= kLdsBytes;
+  // LDS or global matrix: the launcher's rule for one window (wk_plan.h)
+  bool lds_matrix = vio_wk::lds_eligible(d, nthreads, d.lds_asp != 0);
   if ((variant == 1 || variant == 2) && !lds_matrix) return VIO_ECAP;
   if (variant == 0) lds_matrix = false;
-  if (!lds_matrix && lds_need(false) > kLdsBytes) return VIO_ECAP;
-  const size_t lds_bytes = lds_matrix ? (lds_need(true) <= kLdsBytes / 2 ? kLdsBytes / 2 : kLdsBytes) : lds_need(false);
+  const size_t need = vio_wk::lds_need(d, lds_matrix, nthreads, d.lds_asp != 0);
+  if (need > kLdsBytes) return VIO_ECAP;
+  const size_t lds_bytes = lds_matrix ? vio_wk::lds_grant(need) : need;
   const Carved<double *> cw = carve_all<double *>(d, lds_matrix, nthreads, nullptr, nullptr, nullptr, lds_bytes / sizeof(double));
   const int *h = hb.hdr.data();
   out[0] = h[H_M], out[1] = h[H_NSLOTS], out[2] = h[H_NPAIRS], out[3] = h[H_PRIOR_N], out[4] = h[H_PRIOR_NB];

@@ -1,64 +1,8 @@
-// vio_backend_resident.inc — the device-resident path of the back-end (vio_resident.h); included at the end of
-// vio_backend.hip, which owns the context struct, the window kernels and the layout rules this path shares with the
-// host-window path (plan_layout, ensure_work_buffers, bind_work_buffers, vio_backend_launch).
-
-#include <atomic>
-
-#include "vio_resident.h"
-#include "vio_store.h"
-
-constexpr int kResidentLoopIds = 256;  // matched ids of a relocalization frame a slot takes (vio_resident.h)
-
-struct vio_resident {
-  int n_slots = 0, W = 0, P = 0;
-  vio::store::Dims sd;
-  // the store: two banks per slot, control blocks, pre-integration blocks, the extrinsic
-  DevBuf<int> fid, start, nobs, flag, ctl;
-  DevBuf<double> depth, obs, ctld, preint, consts;  // consts: ex_pose 7 | tic 3 | ric 9
-  double ex_pose[7];
-  // per-frame inputs: page-locked arena and its device mirror (same offsets)
-  HostVec<unsigned char> h_in;
-  DevBuf<unsigned char> d_in;
-  size_t o_active = 0, o_nobs = 0, o_hdr = 0, o_prk = 0, o_pri = 0, o_pro = 0, o_preidx = 0, o_hdrd = 0, o_pose = 0, o_sb = 0, o_ex = 0,
-         o_Ps = 0, o_Rs = 0, o_obs = 0, o_preblk = 0, total_bytes = 0;
-  std::atomic<int> n_pre{0};
-  // IMU samples integrated on the device: job records (16 doubles) and samples (7 doubles), both behind the fixed part
-  size_t o_jobs = 0, o_samples = 0;
-  int cap_jobs = 0, cap_samples = 0;
-  std::atomic<int> n_jobs{0}, n_samples{0}, n_obs_total{0};
-  size_t o_obsoff = 0;  // per slot: where its observations start in the packed observation region
-  // relocalization frames: per slot frame / count / offset (fixed part), packed ids and observations (variable)
-  size_t o_loopf = 0, o_loopn = 0, o_loopoff = 0, o_loopids = 0, o_loopxy = 0;
-  int cap_loop = 0;
-  std::atomic<int> n_loop_total{0};
-  bool any_loop = false;
-  HostVec<double> h_raw_pose, h_out_loop;
-  DevBuf<double> pre_side;  // [n_slots][W][preint::kSide]
-  // landmark side of the batch (written by store_pack), sized by the sticky dims
-  BatchDims d;
-  BatchStrides s;
-  bool bound = false;
-  DevBuf<int> b_fhost, b_ftarget, b_ffeat, b_fslot, b_fstart, b_pair_h, b_pair_t, b_pair_s0, b_pair_s1;
-  DevBuf<double> b_feat, b_pts_i, b_pts_j, b_dummy;
-  DevBuf<long long> prof;
-  // results
-  HostVec<int> h_ctl, h_stats_i, h_m_ints;
-  HostVec<double> h_out_pose, h_out_sb, h_stats_d;
-  std::vector<int> active_list;  // slots whose window was solved in this frame
-  std::vector<char> solved;
-  int phase = 0;  // 0 idle / collected, 1 begun, 2 ingested, 3 launched
-  // vio_backend_resident_keyframe: the jobs and their window states up, the sections of one download back
-  DevBuf<int> kf_jobs;
-  DevBuf<double> kf_states;
-  DevBuf<unsigned char> kf_out;
-  std::vector<int> kf_hjobs;
-  std::vector<double> kf_hstates;
-  HostVec<unsigned char> kf_hout;  // (page-locked: the download is a few MB at 512 slots)
-  template <class T>
-  T *hp(size_t off) { return reinterpret_cast<T *>(h_in.data() + off); }
-  template <class T>
-  T *dp(size_t off) { return reinterpret_cast<T *>(d_in.p + off); }
-};
+// be_resident.h — part of vio_backend.hip: the entry points of the device-resident path (vio_resident.h). The store kernels
+// (vio_store.h) ingest, pack and finish a frame of every slot on the device; the windows they pack run through the plan, the
+// work buffers and the launch function that the host-window path uses (wk_plan.h, be_work.h).
+#pragma once
+#include "be_work.h"
 
 static vio::StoreDev resident_store_dev(vio_backend *be) {
   vio_resident *r = be->res.get();
@@ -92,7 +36,7 @@ int vio_backend_resident_reserve(vio_backend_t *be, int32_t n_slots, int32_t lis
   {  // the store kernels keep a sequence's scan arrays in LDS: the whole of it must fit one CU at the largest factor capacity
     vio::store::Dims sd;
     sd.W = W, sd.Lcap = list_cap, sd.Ocap = obs_cap;
-    if (list_cap > 65535 || vio::store_pack_lds_bytes(sd, be->cfg.max_factors) > kLdsLimit) return VIO_ECAP;
+    if (list_cap > 65535 || vio::store_pack_lds_bytes(sd, be->cfg.max_factors) > vio_wk::kLdsLimit) return VIO_ECAP;
   }
   VIO_ON_DEVICE_OF(be);
   HIP_OK(hipStreamSynchronize(be->last_stream ? be->last_stream : be->stream));
@@ -511,19 +455,8 @@ int vio_backend_resident_ingest(vio_backend_t *be) {
     const int n = r->n_slots;
     if (be->d_ptab.ensure(n) != VIO_OK) return VIO_ENOMEM;
     be->h_ptab.resize(n);
-    const size_t sx = 9 * kMaxPriorBlocks, sJ = (size_t)be->st_ncap * be->st_ncap, sr = be->st_ncap;
     const int *hdr = r->hp<int>(r->o_hdr), *act = r->hp<int>(r->o_active);
-    for (int k = 0; k < n; k++) {
-      PriorTab t = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-      if (act[k]) {
-        const int cur = be->st_bank[k], nxt = 1 - cur;
-        if (hdr[(size_t)k * kHdrInts + H_PRIOR_N] > 0)
-          t.x0 = be->d_st_x0[cur].p + k * sx, t.J = be->d_st_J[cur].p + k * sJ, t.r = be->d_st_r[cur].p + k * sr;
-        t.mx0 = be->d_st_x0[nxt].p + k * sx, t.mJ = be->d_st_J[nxt].p + k * sJ, t.mr = be->d_st_r[nxt].p + k * sr;
-        t.ncap = be->st_ncap;
-      }
-      be->h_ptab[k] = t;
-    }
+    for (int k = 0; k < n; k++) be->h_ptab[k] = act[k] ? prior_tab(be, k, hdr[(size_t)k * kHdrInts + H_PRIOR_N] > 0, be->st_ncap) : PriorTab{};
     HIP_OK(hipMemcpyAsync(be->d_ptab.p, be->h_ptab.data(), sizeof(PriorTab) * n, hipMemcpyHostToDevice, st));
   }
   const vio::StoreDev S = resident_store_dev(be);
@@ -574,16 +507,10 @@ int vio_backend_resident_launch(vio_backend_t *be) {
   }
   if (r->active_list.empty()) return VIO_OK;
   try {
-    // sticky capacities, the growth rule of the host-window path (backend_upload_impl)
-    const bool want_loop = r->any_loop;  // a loop pose is one more 6-dof block: other strides, another LDS layout
-    if (!r->bound || Fmax > r->d.Fcap || Mmax > r->d.Mcap || (want_loop && r->d.nblk_cap != r->d.Pcap + 1)) {
-      // (nothing here travels over the bus: generous steps, every growth is a round of hipFree / hipMalloc that stalls the
-      // device for ~10 ms)
-      const int Fr = std::min(be->cfg.max_features, std::max(384, (Fmax + Fmax / 2 + 63) / 64 * 64)),
-                Mr = std::min(be->cfg.max_factors, std::max(3072, (Mmax + Mmax / 2 + 127) / 128 * 128));
-      BatchDims d = make_dims(be->cfg, r->W, std::max({Fr, Fmax, r->bound ? r->d.Fcap : 1}), std::max({Mr, Mmax, r->bound ? r->d.Mcap : 1}),
-                              want_loop || (r->bound && r->d.nblk_cap == r->d.Pcap + 1));
-      d.Ncap = 6 * r->W + 15;
+    // sticky capacities. (A loop pose is one more 6-dof block: other strides, another LDS layout.)
+    const vio_wk::Need need = {r->W, Fmax, Mmax, 0, r->any_loop};
+    if (!r->bound || !vio_wk::fits(r->d, need)) {
+      const BatchDims d = vio_wk::grow_dims(be->cfg, need, vio_wk::kResidentGrowth, r->bound ? &r->d : nullptr);
       const BatchStrides s = make_strides(d);
       const size_t N = n;
       int rc = VIO_OK;
@@ -604,18 +531,17 @@ int vio_backend_resident_launch(vio_backend_t *be) {
       }
       r->d = d, r->s = s, r->bound = true;
     }
-    BatchDims d = r->d;
     const BatchStrides &s = r->s;
-    std::vector<int> order;
-    int rc = plan_layout(be, d, n, nfeat.data(), Fmax, order, &r->active_list);
-    if (rc != VIO_OK) return rc;
-    be->static_w = static_launch_ok(d, r->W == vio_wk::kStaticW);  // (every resident window has the store's window size)
-    const BatchDims dl = be->d_lds;
-    rc = ensure_work_buffers(be, d, s, n);
+    be->uploaded = false;  // the context's plan and bindings are this path's from here on: nothing for vio_backend_launch / _download
+    // (every resident window has the store's window size)
+    be->plan = vio_wk::plan_layout(r->d, n, nfeat.data(), &r->active_list, r->W == vio_wk::kStaticW, be->n_cus, be->peers, be->profile);
+    if (be->plan.rc != VIO_OK) return be->plan.rc;
+    const BatchDims &d = be->plan.d;
+    int rc = bind_work_buffers(be, s, n);
     if (rc != VIO_OK) return rc;
     if (be->d_order.ensure(n) != VIO_OK) return VIO_ENOMEM;
-    be->h_order.assign(order.begin(), order.end());
-    HIP_OK(hipMemcpyAsync(be->d_order.p, be->h_order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, st));
+    be->h_order.assign(be->plan.order.begin(), be->plan.order.end());
+    HIP_OK(hipMemcpyAsync(be->d_order.p, be->h_order.data(), sizeof(int) * be->h_order.size(), hipMemcpyHostToDevice, st));
     BatchPtrs &B = be->B;
     B.n = n, B.d = d, B.s = s;
     B.hdr = r->dp<int>(r->o_hdr), B.hdr_d = r->dp<double>(r->o_hdrd);
@@ -626,26 +552,17 @@ int vio_backend_resident_launch(vio_backend_t *be) {
     B.pts_i = r->b_pts_i.p, B.pts_j = r->b_pts_j.p, B.preint = r->preint.p;
     B.pr_x0 = r->b_dummy.p, B.pr_J = r->b_dummy.p, B.pr_r = r->b_dummy.p;  // (every prior of this path sits in the store: ptab)
     B.ptab = be->d_ptab.p;
-    rc = bind_work_buffers(be, d, s, n);
-    if (rc != VIO_OK) return rc;
-    const bool lds_shape = pose_jp(d) <= 16 * kPanelTiles;
-    const int chunk = stage_chunk_slots(dl, lds_shape, lds_shape ? kThreadsLds : kThreadsGlb);
     const vio::StoreDev S = resident_store_dev(be);
-    rc = vio::store_launch_pack(S, B, chunk, st);
+    rc = vio::store_launch_pack(S, B, be->plan.chunk, st);
     if (rc != VIO_OK) return rc;
-    if (!be->upload_done) HIP_OK(hipEventCreateWithFlags(&be->upload_done, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(be->upload_done, st));
-    be->n = n, be->uploaded = true, be->slots_advanced = true;  // (the banks of this path advance in collect)
-    be->slot_of.assign(n, -1);
-    rc = vio_backend_launch(be, nullptr);
-    be->uploaded = false;  // nothing here for vio_backend_download
+    rc = launch_windows(be, st, B);  // (on the stream of the pack: nothing to wait for)
     if (rc != VIO_OK) return rc;
     rc = vio::store_launch_finish(S, B, st);
     if (rc != VIO_OK) return rc;
     for (int k : r->active_list) r->solved[k] = 1;
     if (host_timing())
       fprintf(stderr, "resident_launch: wait for the counts %.3f ms, layout + launches %.3f ms (%zu windows, F <= %d, M <= %d, %d LDS / %d global)\n",
-              t1 - t0, now_ms() - t1, r->active_list.size(), Fmax, Mmax, be->n_lds, be->n_glb);
+              t1 - t0, now_ms() - t1, r->active_list.size(), Fmax, Mmax, be->plan.n_lds, be->plan.n_glb);
   } catch (const std::bad_alloc &) {
     return VIO_ENOMEM;
   }
@@ -663,22 +580,16 @@ int vio_backend_resident_collect(vio_backend_t *be) {
   // would start only after this kernel: measured, two groups ran one after the other).
   if (r->phase == 3 && !r->active_list.empty()) {
     hipStream_t st = be->stream;
-#define D2H(dst, src)                                                                                          \
-do {                                                                                                         \
-  if ((dst).size() != (src).n) (dst).resize((src).n);                                                        \
-  HIP_OK(hipMemcpyAsync((dst).data(), (src).p, (src).n * sizeof((dst)[0]), hipMemcpyDeviceToHost, st));      \
-} while (0)
-  HIP_OK(hipMemcpyAsync(r->h_ctl.data(), r->ctl.p, sizeof(int) * r->h_ctl.size(), hipMemcpyDeviceToHost, st));
-  D2H(r->h_out_pose, be->d_out_pose);
-  D2H(r->h_out_sb, be->d_out_sb);
-  D2H(r->h_stats_d, be->d_stats_d);
-  D2H(r->h_stats_i, be->d_stats_i);
-  D2H(r->h_m_ints, be->d_m_ints);
-  if (r->any_loop) {
-    D2H(r->h_raw_pose, be->d_raw_pose);
-    D2H(r->h_out_loop, be->d_out_loop);
-  }
-#undef D2H
+    HIP_OK(hipMemcpyAsync(r->h_ctl.data(), r->ctl.p, sizeof(int) * r->h_ctl.size(), hipMemcpyDeviceToHost, st));
+    HIP_OK(d2h(r->h_out_pose, be->d_out_pose, st));
+    HIP_OK(d2h(r->h_out_sb, be->d_out_sb, st));
+    HIP_OK(d2h(r->h_stats_d, be->d_stats_d, st));
+    HIP_OK(d2h(r->h_stats_i, be->d_stats_i, st));
+    HIP_OK(d2h(r->h_m_ints, be->d_m_ints, st));
+    if (r->any_loop) {
+      HIP_OK(d2h(r->h_raw_pose, be->d_raw_pose, st));
+      HIP_OK(d2h(r->h_out_loop, be->d_out_loop, st));
+    }
   }
   HIP_OK(hipStreamSynchronize(be->stream));
   if (host_timing()) fprintf(stderr, "resident_collect: wait %.3f ms\n", now_ms() - t0);
@@ -720,10 +631,7 @@ int vio_backend_resident_result(vio_backend_t *be, int32_t slot, VioResidentResu
   out->speed_bias = r->h_out_sb.data() + (size_t)slot * s.out_sb;
   unpack_solve_stats(r->h_stats_d.data() + (size_t)slot * s.stats_d, r->h_stats_i.data() + (size_t)slot * s.stats_i, &out->stats);
   if (next_prior_header) {
-    MargOut mo;
-    int *mi = r->h_m_ints.data() + (size_t)slot * be->MP.s_ints;
-    mo.n = mi, mo.kind = mi + 4, mo.index = mo.kind + kMaxPriorBlocks, mo.offset = mo.index + kMaxPriorBlocks;
-    mo.x0 = nullptr, mo.J = nullptr, mo.r = nullptr, mo.scratch = nullptr, mo.ncap = be->B.d.Ncap;
+    const MargOut mo = marg_header(r->h_m_ints.data() + (size_t)slot * be->MP.s_ints, be->B.d.Ncap);
     unpack_prior(mo, *next_prior_header, false);
   }
   return VIO_OK;

@@ -941,6 +941,15 @@ VIO_DEV void marginalize_window_impl(const Ctx &cx, const WinView &v, cldsd xpos
   stamp(cx, ST_MARG_CHOL);
 }
 
+// Host side: a window's header of the next prior, kMargInts ints (n[4] | kind | index | offset), as a MargOut without data.
+constexpr size_t kMargInts = 4 + 3 * VIO_MAX_PRIOR_BLOCKS;
+inline MargOut marg_header(int *ints, int ncap) {
+  MargOut mo;
+  mo.n = ints, mo.kind = ints + 4, mo.index = mo.kind + VIO_MAX_PRIOR_BLOCKS, mo.offset = mo.index + VIO_MAX_PRIOR_BLOCKS;
+  mo.x0 = nullptr, mo.J = nullptr, mo.r = nullptr, mo.scratch = nullptr, mo.ncap = ncap;
+  return mo;
+}
+
 // data = false: header only (the data stays in the device-resident store; mo.x0 / J / r are not read).
 inline void unpack_prior(const MargOut &mo, VioPrior &p, bool data = true) {
   p.n = mo.n[0];

@@ -1,4 +1,5 @@
-// vio_window_variants.h -- the instantiations of the window kernel (vio_window_kernel.inc) and how the launcher reaches them.
+// vio_window_variants.h -- the instantiations of the window kernel (vio_window_kernel.inc) and how the launcher reaches them. The table
+// of variants (kTraits) is host-only and lives with the launcher's plan, wk_plan.h.
 // Every (variant, stage clock on / off) pair is a translation unit of its own (vio_wk_unit.hip compiled once per pair, csrc/Makefile):
 // the kernel is ~70 k instructions per instantiation and the units build in parallel.
 #pragma once
@@ -6,29 +7,9 @@
 
 #include <stddef.h>
 
-namespace vio {
-struct BatchPtrs;
-struct MargPtrs;
-}  // namespace vio
+#include "wk_plan.h"
 
 namespace vio_wk {
-
-constexpr int kThreadsLds = 256, kThreadsGlb = 512;
-
-// variant: pose matrix in LDS?, IMU coupling in LDS?, work-items, compile-time window size (0: run-time)
-//   0  LDS, LDS, 256, 0     the fat layout, two windows per CU (F <= 160 at W = 10)
-//   1  LDS, scratch, 256, 0 the lean layout (F <= 310)
-//   2  scratch, scratch, 512, 0   W > 12 (cooperative windows)
-//   3  = 0 with W = 10 at compile time (the reference's WINDOW_SIZE, global_param.hpp:28), no relocalization pose in the batch
-//   4  = 1 with W = 10 at compile time
-constexpr int kVariants = 5;
-constexpr int kStaticW = 10;
-struct VariantTraits {
-  bool lds_matrix, lds_asp;
-  int threads, ws;
-};
-constexpr VariantTraits kTraits[kVariants] = {{true, true, kThreadsLds, 0},        {true, false, kThreadsLds, 0}, {false, false, kThreadsGlb, 0},
-                                              {true, true, kThreadsLds, kStaticW}, {true, false, kThreadsLds, kStaticW}};
 
 struct VariantFns {
   const void *fn;  // the kernel (hipFuncSetAttribute, occupancy queries)
