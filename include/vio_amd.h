@@ -532,6 +532,84 @@ int vio_vocabulary_get_device(const vio_vocabulary_t *v, int32_t *device);
 int vio_vocabulary_transform(vio_vocabulary_t *v, int32_t n_keyframes, const int32_t *n_desc, const uint64_t *desc,
                              int32_t *word_id, double *word_weight, int32_t *bow_count, int32_t *bow_word,
                              double *bow_value, int32_t bow_stride);
+/* Vocabulary training: TemplatedVocabulary::create(training_features, k, L, weighting, L1_NORM) for FBrief
+ * (ThirdParty/DBoW/TemplatedVocabulary.h:551-580), node by node:
+ *   HKmeansStep            :635-812  on a node's descriptor list (original order: image after image, inside an image
+ *                          the given order): an empty list makes nothing; n <= k makes one child per descriptor, in
+ *                          order; otherwise k-means++ seeds, every descriptor goes to the nearest centre (Hamming
+ *                          distance, FIRST centre on ties, :727-738), then centres = meanValue(groups), associate,
+ *                          until the association equals the previous one (:748-765). A child is made for every centre,
+ *                          empty groups included, and split further while level < L and its group has more than one
+ *                          member (:789-811); groups keep their members in list order.
+ *   FBrief::meanValue      ThirdParty/DBoW/FBrief.cpp:22-49: bit i is set iff more than floor(N/2) members have it; an
+ *                          EMPTY group gives the all-zero descriptor (the reference's comment says it cannot happen; it
+ *                          can, after a re-association; the cluster stays and may be re-populated).
+ *   initiateClustersKMpp   :827-908: first centre = a uniform index; after each new centre min_dists is updated and
+ *                          summed (integers 0..256: the 64-bit sum is exact), cut = random * sum, the next centre is the
+ *                          first index whose running sum reaches cut; seeding ends early, with fewer than k centres,
+ *                          when the sum is 0.
+ *   createWords / setNodeWeights  :913-933, :938-991: node ids in the order the recursion creates them (all children
+ *                          of a node consecutively, then the first child's subtree, ...), word ids in node-id order
+ *                          over the leaves; weight 1 for TF / BINARY, log(NDocs / Ni) for IDF / TF_IDF where Ni = the
+ *                          images in which at least one descriptor TRANSFORMS to the word (the ordinary descent, counted
+ *                          on the device; std::log on the host), NDocs counts images without descriptors too, a word
+ *                          with Ni = 0 keeps weight 0; inner nodes have weight 0.
+ * Two departures from the reference:
+ *  1. Random stream. The reference draws from rand() seeded by the clock, in recursion order. Here every draw is a pure
+ *     function of `seed` and the node's PATH, so the result does not depend on the order in which nodes are processed:
+ *       mix(x)            = splitmix64's step: x += 0x9E3779B97F4A7C15; z = x; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                           z = (z ^ z >> 27) * 0x94D049BB133111EB; result z ^ z >> 31          (64-bit wrap-around)
+ *       key(root)         = mix(seed);   key(child c of p) = mix(key(p) ^ (c + 1))             c = 0 .. the child's place
+ *       h_j               = mix(key(node) + j * 0x9E3779B97F4A7C15)                             draw j of a node
+ *       first centre      = min(n - 1, floor(((h_0 >> 11) * 2^-53) * n))                       one fp64 multiply
+ *       centre m >= 1     : cut = (((h_m >> 11) + 1) * 2^-53) * (double)sum                    factor in (0, 1], one fp64
+ *                           multiply; the pick is the first index with (double)prefix >= cut
+ *  2. Iteration cap. The reference loops without bound, and a deterministic tie rule does not exclude a cycle of
+ *     equal-cost states. max_iterations caps the meanValue passes of a node; a node stopped by the cap (its association
+ *     after the last allowed pass still differs from the one before; with max_iterations = 0: every node that runs
+ *     k-means) keeps its last centres and its last association, which is always computed with those centres, and is
+ *     counted in capped_nodes. max_iterations = 0 is seeds plus one association. Default 128: Lloyd passes on binary
+ *     descriptors settle within a few tens of passes at every size measured (profiles/vocabulary_train_timing.txt: at
+ *     most 32 at 10^6 descriptors), a pass over 10^6 descriptors costs well under a millisecond, so 128 leaves a factor
+ *     of four and still bounds a cycle. Values below 0 or above 4096 are refused.
+ * Limits: 2 <= k <= 32, 1 <= L <= 10, at most 4 194 304 descriptors and 65 536 per image (VIO_ECAP beyond). VIO_EINVAL
+ * for k / L / weighting / max_iterations outside their ranges, a negative count, no descriptor at all; VIO_ENODEV
+ * without a device (no CPU fallback). Only L1_NORM scoring.
+ * Level-synchronous (csrc/voc_train_core.h): all nodes of a tree level are processed by the same launches.
+ * stats.launches counts kernel launches: at most 3 k + 2 iterations_max[level] + 4 per level and 2 for the weights, so
+ *   launches <= c0 + c1 * sum over levels of (k + iterations_max[level])       with c0 = 2, c1 = 5.
+ * stats: n_nodes without the root (= the file's nNodes); capped_nodes as above; short_nodes = nodes whose k-means++
+ * ended below k centres; empty_clusters = children whose final group is empty; iterations_max[l] = most meanValue passes
+ * of a node whose children are on level l + 1; kernel_ms = the sum of pass_ms, the time on the stream between the first
+ * launch of a pass and the first of the next (seeding, iterations, regrouping, weights), host round trips included.
+ * Measured on one MI355X (profiles/vocabulary_train_timing.txt; k = 10, the whole call against the same semantics in plain
+ * C++, tools/vocabulary_train_host_route.cpp, on one host thread / on 16): L = 4, 10^5 descriptors 6.1 ms against 245 / 139 ms;
+ * L = 6, 10^6 descriptors in 2 000 images 94 ms against 6 587 / 2 145 ms (54 ms of the 94 pass between a level's regrouping and
+ * the next pass's first launch: the level's centres come back, the host lays out the tables of 674 k nodes and, after the
+ * last level, makes the vocabulary from the file). The device route wins at both sizes: no break-even in that range.
+ * The vocabulary that comes back is an ordinary one, bound to the current device.                                   */
+typedef struct VioVocabularyTrainParams {
+  int32_t k, L;
+  int32_t weighting;       /* 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY (WeightingType, as in the file) */
+  int32_t max_iterations;
+  uint64_t seed;
+} VioVocabularyTrainParams;
+typedef struct VioVocabularyTrainStats {
+  int32_t n_descriptors, n_nodes, n_words, capped_nodes, empty_clusters, short_nodes, launches;
+  int32_t iterations_max[16];
+  double kernel_ms;
+  double pass_ms[4];       /* seeding, iterations, regrouping, weights */
+} VioVocabularyTrainStats;
+void vio_vocabulary_train_params_default(VioVocabularyTrainParams *p);  /* k 10, L 6, TF_IDF, 128 passes, seed 0 */
+/* desc: the images' descriptors back to back, 4 words each (vio_brief_extract's layout); n_desc [n_images].       */
+int vio_vocabulary_train(const VioVocabularyTrainParams *p, int32_t n_images, const int32_t *n_desc,
+                         const uint64_t *desc, vio_vocabulary_t **out, VioVocabularyTrainStats *stats /* or NULL */);
+/* The vocabulary's file (loop/VocabularyBinary.hpp:17-50, what the app's loadBin reads, TemplatedVocabulary.h:
+ * 1505-1554). A trained vocabulary gives canonical bytes (nodes in id order, words in id order); a loaded one gives
+ * back the bytes it was made from. vio_vocabulary_create(serialize(v)) transforms identically to v. blob == NULL
+ * reports the size in *bytes; VIO_ECAP (with the size) when cap is too small.                                        */
+int vio_vocabulary_serialize(const vio_vocabulary_t *v, void *blob, size_t cap, size_t *bytes);
+int vio_vocabulary_save(const vio_vocabulary_t *v, const char *path);
 typedef struct vio_bow_database vio_bow_database_t;
 /* The database takes what it needs from the vocabulary (device, word count) at create and
  * owns its stream: it stays valid after vio_vocabulary_destroy, and a vocabulary and its

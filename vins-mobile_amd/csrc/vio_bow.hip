@@ -23,6 +23,8 @@
 //                       entries that share a word with a query, one wave per such entry sums |q - d| - |q| - |d| over the
 //                       common words in ascending word order (= the order in which queryL1 meets them: bit-identical sums)
 //                       from the entry's BowVector in the direct file; see the comment above bow_insert_kernel
+// A vocabulary keeps the bytes of its file on the host (vio_vocabulary_serialize / _save; 48 bytes per node). Training
+// (vio_voc_train.hip) makes a vocabulary through vio_vocabulary_create and uses the lookup kernel for the words' Ni.
 // The final sort / cut / scaling of queryL1 (a few hundred candidates) runs on the host inside the ABI call.
 // Scoring other than L1_NORM is refused (the app's vocabulary is TF_IDF / L1_NORM, DBoW2's defaults).
 #include <hip/hip_runtime.h>
@@ -210,6 +212,38 @@ struct vio_bow_database {
   }
 };
 
+int vio::bow_lookup_words(vio_vocabulary *v, const unsigned long long *d_desc, int n, int *d_word) {
+  if (n < 1) return VIO_OK;
+  if (v->t_weight.ensure((size_t)n) != VIO_OK) return VIO_ENOMEM;
+  hipLaunchKernelGGL(bow_lookup_kernel, dim3(((size_t)n * 16 + 255) / 256), dim3(256), 0, v->stream, v->d_desc.p, v->d_weight.p, v->d_word.p,
+                     v->d_child_off.p, v->d_child.p, d_desc, n, v->height + 1, d_word, v->t_weight.p);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(v->stream));
+  return VIO_OK;
+}
+
+int vio::bow_set_word_weights(vio_vocabulary *v, const double *word_weight) {
+  const size_t nn = (size_t)v->n_nodes - 1, nw = (size_t)v->n_words;
+  try {
+    std::vector<double> weight(nn + 1, 0.0);
+    for (size_t i = 0; i < nw; i++) {  // struct Word { int32 nodeId, wordId; }
+      int32_t rec[2];
+      memcpy(rec, v->blob.data() + 24 + nn * 48 + i * 8, 8);
+      weight[rec[0]] = word_weight[rec[1]];
+    }
+    for (size_t i = 0; i < nn; i++) {  // struct Node { int32 nodeId, parentId; double weight; ... }
+      int32_t nid;
+      memcpy(&nid, v->blob.data() + 24 + i * 48, 4);
+      memcpy(v->blob.data() + 24 + i * 48 + 8, &weight[nid], 8);
+    }
+    HIP_OK(hipMemcpy(v->d_weight.p, weight.data(), 8 * (nn + 1), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(v->d_wweight.p, word_weight, 8 * nw, hipMemcpyHostToDevice));
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+  return VIO_OK;
+}
+
 extern "C" {
 
 int vio_vocabulary_create(const void *blob, size_t bytes, vio_vocabulary_t **out) {
@@ -289,6 +323,12 @@ int vio_vocabulary_create(const void *blob, size_t bytes, vio_vocabulary_t **out
       delete v;
       return VIO_ENOMEM;
     }
+    try {
+      v->blob.assign(p, p + 24 + (size_t)nNodes * 48 + (size_t)nWords * 8);
+    } catch (const std::bad_alloc &) {
+      delete v;
+      return VIO_ENOMEM;
+    }
     *out = v;
     return VIO_OK;
   } catch (const std::bad_alloc &) {
@@ -318,6 +358,23 @@ int vio_vocabulary_load(const char *path, vio_vocabulary_t **out) {
     return VIO_ENOMEM;
   }
   return vio_vocabulary_create(blob.data(), blob.size(), out);
+}
+
+int vio_vocabulary_serialize(const vio_vocabulary_t *v, void *blob, size_t cap, size_t *bytes) {
+  if (!v || !bytes) return VIO_EINVAL;
+  *bytes = v->blob.size();
+  if (!blob) return VIO_OK;
+  if (cap < v->blob.size()) return VIO_ECAP;
+  memcpy(blob, v->blob.data(), v->blob.size());
+  return VIO_OK;
+}
+
+int vio_vocabulary_save(const vio_vocabulary_t *v, const char *path) {
+  if (!v || !path) return VIO_EINVAL;
+  FILE *f = fopen(path, "wb");
+  if (!f) return VIO_EINVAL;
+  const size_t put = fwrite(v->blob.data(), 1, v->blob.size(), f);
+  return (fclose(f) == 0 && put == v->blob.size()) ? VIO_OK : VIO_EINVAL;
 }
 
 void vio_vocabulary_destroy(vio_vocabulary_t *v) {

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "vio_amd.h"
 #include "vio_device.h"
 
@@ -107,7 +109,16 @@ struct vio_vocabulary {
   vio::DevBuf<unsigned long long> t_desc;
   vio::DevBuf<int> t_word, t_off, t_bcount, t_bword;
   vio::DevBuf<double> t_weight, t_bvalue;
+  std::vector<unsigned char> blob;  // the file the vocabulary was made from (vio_vocabulary_serialize / _save)
   ~vio_vocabulary() {
     if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
   }
 };
+
+namespace vio {
+// what vocabulary training (vio_voc_train.hip) needs from vio_bow.hip: the descent of bow_lookup_kernel for n descriptors
+// that are on the device already (word [n] on the device; the call returns after the kernel has run), and the word
+// weights of a vocabulary made with weights 0 (nodes, words, and the weight fields of v->blob)
+int bow_lookup_words(vio_vocabulary *v, const unsigned long long *d_desc, int n, int *d_word);
+int bow_set_word_weights(vio_vocabulary *v, const double *word_weight);
+}  // namespace vio

@@ -202,8 +202,23 @@ def make_vocabulary_blob(k, L, scoring, weighting, nodes, words):
     return b"".join(out)
 
 
+class VioVocabularyTrainParams(C.Structure):  # include/vio_amd.h
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("max_iterations", C.c_int32), ("seed", C.c_uint64)]
+
+
+class VioVocabularyTrainStats(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("n_descriptors", "n_nodes", "n_words", "capped_nodes", "empty_clusters", "short_nodes", "launches")] + \
+               [("iterations_max", C.c_int32 * 16), ("kernel_ms", C.c_double), ("pass_ms", C.c_double * 4)]
+
+
 def bind_bow(lib):
     vp = C.c_void_p
+    lib.vio_vocabulary_train_params_default.argtypes = [C.POINTER(VioVocabularyTrainParams)]
+    lib.vio_vocabulary_train_params_default.restype = None
+    lib.vio_vocabulary_train.argtypes = [C.POINTER(VioVocabularyTrainParams), C.c_int32, _i32p, _u64p, C.POINTER(vp),
+                                         C.POINTER(VioVocabularyTrainStats)]
+    lib.vio_vocabulary_serialize.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.vio_vocabulary_save.argtypes = [vp, C.c_char_p]
     lib.vio_vocabulary_create.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp)]
     lib.vio_vocabulary_load.argtypes = [C.c_char_p, C.POINTER(vp)]
     lib.vio_vocabulary_destroy.argtypes = [vp]
@@ -221,11 +236,15 @@ def bind_bow(lib):
 
 
 class BowVocabulary:
-    """TemplatedVocabulary<FBrief> on the device: transform() for batches of keyframes."""
+    """TemplatedVocabulary<FBrief> on the device: transform() for batches of keyframes; train() makes one from descriptors
+    (TemplatedVocabulary::create), serialize() / save() write the app's file."""
 
-    def __init__(self, blob=None, path=None):
+    def __init__(self, blob=None, path=None, _handle=None):
         self.lib = bind_bow(abi.load_product())
         self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+            return
         rc = self.lib.vio_vocabulary_load(path.encode(), C.byref(self._h)) if path else \
             self.lib.vio_vocabulary_create(blob, len(blob), C.byref(self._h))
         if rc != abi.VIO_OK:
@@ -235,6 +254,42 @@ class BowVocabulary:
         if self._h:
             self.lib.vio_vocabulary_destroy(self._h)
             self._h = C.c_void_p()
+
+    @classmethod
+    def train(cls, desc_list, k=None, L=None, weighting=None, max_iterations=None, seed=None):
+        """vio_vocabulary_train on per image uint64 [n][4] descriptors -> (vocabulary, stats dict). Arguments left None keep
+        vio_vocabulary_train_params_default's values."""
+        lib = bind_bow(abi.load_product())
+        p = VioVocabularyTrainParams()
+        lib.vio_vocabulary_train_params_default(C.byref(p))
+        for name, val in (("k", k), ("L", L), ("weighting", weighting), ("max_iterations", max_iterations), ("seed", seed)):
+            if val is not None:
+                setattr(p, name, val)
+        n_desc = np.array([len(d) for d in desc_list], np.int32)
+        desc = np.ascontiguousarray(np.concatenate([np.asarray(d, np.uint64).reshape(-1, 4) for d in desc_list] + [np.zeros((0, 4), np.uint64)]))
+        h, st = C.c_void_p(), VioVocabularyTrainStats()
+        rc = lib.vio_vocabulary_train(C.byref(p), len(desc_list), n_desc.ctypes.data_as(_i32p), desc.ctypes.data_as(_u64p), C.byref(h),
+                                      C.byref(st))
+        if rc != abi.VIO_OK:
+            raise RuntimeError("vio_vocabulary_train failed rc=%d" % rc)
+        stats = {f: getattr(st, f) for f, _ in VioVocabularyTrainStats._fields_}
+        stats["iterations_max"], stats["pass_ms"] = list(st.iterations_max), list(st.pass_ms)
+        return cls(_handle=h), stats
+
+    def serialize(self):
+        """The vocabulary's file (loop/VocabularyBinary.hpp) as bytes."""
+        n = C.c_size_t(0)
+        rc = self.lib.vio_vocabulary_serialize(self._h, None, 0, C.byref(n))
+        buf = C.create_string_buffer(max(1, n.value))
+        rc = rc or self.lib.vio_vocabulary_serialize(self._h, buf, n.value, C.byref(n))
+        if rc != abi.VIO_OK:
+            raise RuntimeError("vio_vocabulary_serialize failed rc=%d" % rc)
+        return buf.raw[:n.value]
+
+    def save(self, path):
+        rc = self.lib.vio_vocabulary_save(self._h, str(path).encode())
+        if rc != abi.VIO_OK:
+            raise RuntimeError("vio_vocabulary_save failed rc=%d" % rc)
 
     def info(self):
         a = np.zeros(6, np.int32)
