@@ -86,6 +86,21 @@ typedef struct VioConfig {
  * (global_param.cpp:27-42, feature_tracker.hpp:24-29).                       */
 void vio_config_default(VioConfig *cfg);
 
+/* The camera of ONE sequence: the per-device globals setGlobalParam switches
+ * by phone model (global_param.cpp:24-131). cfg.fx .. cfg.cy, and the tic / ric
+ * a context is created with, are what a sequence uses until a camera is set for
+ * it: a context whose sequences set none computes exactly what it always did.
+ * Pinhole only. Lens distortion is NOT modelled, as in the reference, whose
+ * rejectWithF works on raw pixels (feature_tracker.cpp:95,198); a distorted
+ * lens has to be undistorted by the caller ahead of the front end.           */
+typedef struct VioCamera {
+  double fx, fy, cx, cy;   /* FOCUS_LENGTH_X/Y, PX, PY  global_param.cpp:24-131 */
+  double tic[3], ric[9];   /* camera -> body, ric row-major (TIC_*, RIC_*)      */
+} VioCamera;
+/* The camera a context's configuration stands for: cfg's intrinsics with the
+ * given extrinsic (NULL: tic = 0, ric = identity).                            */
+void vio_camera_from_config(const VioConfig *cfg, const double tic[3], const double ric[9], VioCamera *out);
+
 /* ------------------------------------------------------------------------- */
 /* IMU pre-integration between two frames: the public state of
  * IntegrationBase (integration_base.h:200-221) after the last push_back.     */
@@ -219,6 +234,15 @@ int vio_preintegrate(const VioConfig *cfg, const double acc_0[3], const double g
  * results are deterministic).                                                */
 int vio_backend_solve_windows(vio_backend_t *be, VioWindow *windows, int32_t n,
                               int32_t buf_num, VioSolveStats *stats /* [n] or NULL */);
+/* The same for windows of DIFFERENT cameras in one launch: sqrt_info[b] is
+ * window b's ProjectionFactor::sqrt_info = FOCUS_LENGTH_X / 1.5 of ITS camera
+ * (VINS.cpp:31; setGlobalParam switches the focal length by device,
+ * global_param.cpp:24-131), ex_pose is per window already. sqrt_info == NULL:
+ * cfg.fx / 1.5 for every window, which is what vio_backend_solve_windows calls
+ * this with. An entry that is not finite and > 0 is VIO_EINVAL.               */
+int vio_backend_solve_windows_cam(vio_backend_t *be, VioWindow *windows, int32_t n,
+                                  const double *sqrt_info /* [n] or NULL */,
+                                  VioSolveStats *stats /* [n] or NULL */);
 
 /* Device-resident prior chain. The prior a window leaves behind (the output of
  * marginalize(), VINS.cpp:697-831) is the next window's
@@ -234,6 +258,10 @@ int vio_backend_reserve_priors(vio_backend_t *be, int32_t n_slots);
  * times from the same initial state, download when wanted. `stream` is a
  * hipStream_t (or NULL for the library's own stream).                        */
 int vio_backend_upload(vio_backend_t *be, const VioWindow *windows, int32_t n);
+/* vio_backend_upload with a sqrt_info per window, as vio_backend_solve_windows_cam
+ * (VINS.cpp:31 per camera); NULL is vio_backend_upload.                       */
+int vio_backend_upload_cam(vio_backend_t *be, const VioWindow *windows, int32_t n,
+                           const double *sqrt_info /* [n] or NULL */);
 int vio_backend_launch(vio_backend_t *be, void *stream);
 int vio_backend_sync(vio_backend_t *be);
 int vio_backend_download(vio_backend_t *be, VioWindow *windows, int32_t n, VioSolveStats *stats);
@@ -378,6 +406,16 @@ int vio_frontend_reset(vio_frontend_t *fe, int32_t n, const int32_t *seq);
  * call on a context whose current image is still read in place from the ring first
  * moves that image into the pyramid's own storage.                                    */
 int vio_frontend_in_step(vio_frontend_t *fe, int32_t *in_step);
+/* The camera of sequence seq[i] becomes cam[i]: what image_msg divides by,
+ * ((u - PX) / FOCUS_LENGTH_X, (v - PY) / FOCUS_LENGTH_Y, 1) (feature_tracker.cpp:300-306),
+ * the per-device globals of setGlobalParam (global_param.cpp:24-131). Only fx, fy, cx, cy
+ * are used; a sequence without one uses cfg's. It takes effect at the next publish,
+ * changes nothing of the tracker's pixel state and survives vio_frontend_reset.
+ * VIO_ESTATE between a submit and its collect; VIO_EINVAL for an entry of seq[] out of
+ * range or named twice, for fx or fy zero, and for a value that is not finite (no camera
+ * is changed then). Waits for the device. get_camera: tic = 0, ric = identity.          */
+int vio_frontend_set_cameras(vio_frontend_t *fe, int32_t n, const int32_t *seq /* [n] */, const VioCamera *cam /* [n] */);
+int vio_frontend_get_camera(vio_frontend_t *fe, int32_t seq, VioCamera *out);
 
 /* Host frame buffers registered once (camera / decoder ring buffers, the cv::Mat
  * storage behind `_img` in FeatureTracker::readImage, feature_tracker.cpp:162):
@@ -500,7 +538,8 @@ int vio_matcher_search_by_des(vio_matcher_t *m, int32_t n_pairs, const int32_t *
  * best old descriptor (pixels), then, from 8 matches on, rejectWithF =
  * findFundamentalMat(cur_pts, matched_old_pts, FM_RANSAC, 2.0, 0.99) ->
  * status[i] (1 = kept), matched_old_norm = (pt - (cx, cy)) / (fx, fy)
- * (optional). Fewer than 8 matches keep everything.                            */
+ * (optional). Fewer than 8 matches keep everything. cfg is read per call:
+ * pass the intrinsics of THAT session's camera (VioCamera).                    */
 int vio_loop_find_connection(vio_matcher_t *m, const VioConfig *cfg, int32_t n_cur,
                              const uint64_t *cur_desc, const float *cur_pts /* [n_cur][2] */,
                              int32_t n_old, const uint64_t *old_desc,
@@ -724,6 +763,14 @@ int  vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg /* f
                                uint8_t *status /* [n][stride] */, float *matched_old_pts /* [n][stride][2] or NULL */,
                                int32_t *kept_index /* [n][stride] */, int32_t *kept_ids /* [n][stride], with ids */,
                                double *kept_old_norm /* [n][stride][2] */);
+/* The camera of session[i] becomes cam[i] (only fx, fy, cx, cy are used): what findConnectionWithOldFrame normalises
+ * the old keyframe's pixels with, (pt - (PX, PY)) / (FOCUS_LENGTH_X, FOCUS_LENGTH_Y) in float (loop/keyframe.cpp:45-46;
+ * per device in the reference, global_param.cpp:24-131). A session with a camera uses it in vio_loop_detector_connect
+ * and vio_loop_detector_keyframes in place of the cfg passed to the call; a session without one keeps using that cfg.
+ * VIO_EINVAL: a session out of range or named twice, fx or fy zero, a value that is not finite (nothing is changed).
+ * get_camera: VIO_ESTATE for a session that has none. The camera outlives vio_loop_detector_clear.                */
+int  vio_loop_detector_set_cameras(vio_loop_detector_t *d, int32_t n, const int32_t *session /* [n] */, const VioCamera *cam /* [n] */);
+int  vio_loop_detector_get_camera(vio_loop_detector_t *d, int32_t session, VioCamera *out);
 
 /* Keyframe descriptor extraction: BriefExtractor::operator() (loop/keyframe.cpp:395-409) =
  * cv::FAST(im, keys, 20, true); keys += window_pts; DVision::BRIEF::compute
@@ -994,7 +1041,8 @@ int vio_features_load(vio_features_t *fm, const VioFeatureInfo *info, int32_t n,
  * p.z) (pts_normalize); ids = feature_id; cloud = Rs[start] (ric (obs[0] estimated_depth) + tic) + Ps[start]
  * (point_clouds). No test of the depth's sign or of solve_flag: the reference has none. Ps [W+1][3], Rs [W+1][9] are
  * the states of the moment (vio_estimator_get_window). The call writes used_num and nothing else of the list.
- * VIO_ECAP with *n = -(needed) when more than cap landmarks qualify (the first cap are written).                   */
+ * VIO_ECAP with *n = -(needed) when more than cap landmarks qualify (the first cap are written).
+ * cfg, tic and ric are read per call: pass the camera of THAT sequence (VioCamera).                                  */
 int vio_features_keyframe(vio_features_t *fm, const VioConfig *cfg /* fx fy cx cy */, const double *Ps, const double *Rs,
                           const double tic[3], const double ric[9], int32_t cap, int32_t *ids, float *px /* [cap][2] */,
                           float *norm /* [cap][2] */, double *cloud /* [cap][3] */, int32_t *n);
@@ -1058,6 +1106,15 @@ int vio_estimator_create(const VioConfig *cfg, int32_t n_seq, const double tic[3
                          vio_estimator_t **out);
 void vio_estimator_destroy(vio_estimator_t *est);
 int vio_estimator_clear(vio_estimator_t *est, int32_t seq);   /* clearState + the constructor's r_drift / t_drift */
+/* The camera of ONE sequence: what setGlobalParam switches per device model (FOCUS_LENGTH_X/Y, PX, PY, TIC_*, RIC_*:
+ * global_param.cpp:24-131) and VINS reads as globals (VINS.cpp:31 sqrt_info, :36-81 clearState, the triangulation, the
+ * start-up's gyroscope hint and alignment, slideWindowOld, buildKeyFrameFeatures). A sequence uses cfg.fx .. cfg.cy and
+ * the tic / ric of vio_estimator_create until one is set; get returns what it uses. Allowed only while the sequence holds
+ * no frame -- after create or vio_estimator_clear, frame_count == 0 -- VIO_ESTATE otherwise: a window is built with one
+ * camera. VIO_EINVAL for a value that is not finite, fx <= 0 (sqrt_info = fx / 1.5 is a weight), fy zero, or a ric that
+ * is not orthonormal to 1e-6 with determinant +1. The camera survives vio_estimator_clear and every clearState inside process_images.                 */
+int vio_estimator_set_camera(vio_estimator_t *est, int32_t seq, const VioCamera *cam);
+int vio_estimator_get_camera(vio_estimator_t *est, int32_t seq, VioCamera *out);
 /* solveInitial (VINS.cpp:833-1145) inside process_image when the window is full and no
  * state was handed over: relative pose, global SfM, PnP of the in-between frames,
  * visual-inertial alignment. Off by default (0): the caller hands states over.
@@ -1172,6 +1229,12 @@ int vio_pnp_create(const VioConfig *cfg, int32_t max_batch, vio_pnp_t **out);
 void vio_pnp_destroy(vio_pnp_t *p);
 /* n independent windows in one device launch (one workgroup each).              */
 int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSolveStats *stats /* [n] or NULL */);
+/* The same for windows of different cameras in one launch: sqrt_info[b] is window b's
+ * PerspectiveFactor::sqrt_info = FOCUS_LENGTH_X / 1.5 of its camera (vins_pnp.cpp:19,
+ * global_param.cpp:24-131); ex_pose is per window already. NULL: cfg.fx / 1.5 for all,
+ * which is vio_pnp_solve_windows. An entry that is not finite and > 0 is VIO_EINVAL. */
+int vio_pnp_solve_windows_cam(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, const double *sqrt_info /* [n] or NULL */,
+                              VioSolveStats *stats /* [n] or NULL */);
 int vio_pnp_kernel_ms(vio_pnp_t *p, double *ms_avg, int32_t *launches);
 
 /* The vinsPnP object around that solve (vins_pnp.cpp:16-382), n_seq sequences sharing one launch; what
@@ -1191,6 +1254,11 @@ int vio_pnp_tracker_create(const VioConfig *cfg, int32_t n_seq, int32_t pnp_size
                            const double ric[9], vio_pnp_tracker_t **out);
 void vio_pnp_tracker_destroy(vio_pnp_tracker_t *t);
 int vio_pnp_tracker_clear(vio_pnp_tracker_t *t, int32_t seq);                                       /* clearState */
+/* The camera of one sequence, as vio_estimator_set_camera: the extrinsic of its windows (para_Ex_Pose, vins_pnp.cpp:94-135)
+ * and the focal length of PerspectiveFactor::sqrt_info (vins_pnp.cpp:19; global_param.cpp:24-131). Only on a cleared
+ * sequence (frame_count == 0), VIO_ESTATE otherwise; the same argument checks; it survives vio_pnp_tracker_clear.   */
+int vio_pnp_tracker_set_camera(vio_pnp_tracker_t *t, int32_t seq, const VioCamera *cam);
+int vio_pnp_tracker_get_camera(vio_pnp_tracker_t *t, int32_t seq, VioCamera *out);
 int vio_pnp_tracker_set_init(vio_pnp_tracker_t *t, int32_t seq, const VioVinsResult *r);           /* setInit    */
 int vio_pnp_tracker_process_imu(vio_pnp_tracker_t *t, int32_t seq, double dt, const double acc[3], const double gyr[3]);
 /* processImage(feature_msg, header, use_pnp) for every active sequence; P_out [n_seq][3] / R_out [n_seq][9] =
@@ -1200,7 +1268,7 @@ int vio_pnp_tracker_process_images(vio_pnp_tracker_t *t, const VioPnpFeature *fe
                                    double *P_out, double *R_out, int32_t *solved);
 /* feature_msg of solveVinsPnP (feature_tracker.cpp:121-134): solved landmarks (id, position, track_num; ascending id)
  * joined by id with the tracker's current ids / pixel positions (vio_frontend_get_state); observation =
- * ((x - PX) / fx, (y - PY) / fy).                                                                            */
+ * ((x - PX) / fx, (y - PY) / fy). cfg is read per call: pass the intrinsics of THAT sequence's camera.       */
 int vio_pnp_match_features(const VioConfig *cfg, const int32_t *ids, const float *forw_pts /* [n_pts][2] */, int32_t n_pts,
                            const VioPnpFeature *solved, int32_t n_solved, VioPnpFeature *out, int32_t cap, int32_t *n_out);
 int vio_pnp_tracker_get_window(vio_pnp_tracker_t *t, int32_t seq, double *Ps, double *Rs, double *Vs, double *headers,

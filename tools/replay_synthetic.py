@@ -32,13 +32,15 @@ abi, synth, window = pkg.abi, pkg.synth, pkg.window
 class SyntheticWorld:
     """Ground-truth trajectory, IMU samples and landmark observations."""
 
-    def __init__(self, cfg, seed, n_landmarks=4000, frame_dt=0.1, imu_per_frame=10, pix_noise=0.5):
+    def __init__(self, cfg, seed, n_landmarks=4000, frame_dt=0.1, imu_per_frame=10, pix_noise=0.5, ex=None):
+        """ex: the camera -> body extrinsic as para_Ex_Pose [7] (tic, then ric as x y z w); None: synth.ex_pose_default().
+        The intrinsics are cfg's: a world for another camera takes a cfg that carries that camera's fx .. cy."""
         self.cfg, self.rng = cfg, np.random.default_rng(seed)
         rng = self.rng
         self.traj = synth.Trajectory(rng)
         self.t0 = rng.uniform(0, 20)
         self.frame_dt, self.imu_per_frame, self.dt = frame_dt, imu_per_frame, frame_dt / imu_per_frame
-        self.ex = synth.ex_pose_default()
+        self.ex = synth.ex_pose_default() if ex is None else np.asarray(ex, np.float64).copy()
         self.ric, self.tic = synth.quat_to_rot(self.ex[3:]), self.ex[:3]
         self.ba, self.bg = rng.normal(0, 0.02, 3), rng.normal(0, 0.002, 3)
         self.g = np.array([0, 0, synth.GRAVITY])

@@ -74,6 +74,34 @@ def default_config(**kw):
     return c
 
 
+class VioCamera(C.Structure):
+    """The camera of one sequence (vio_amd.h): pinhole intrinsics, camera -> body extrinsic (ric row-major). No distortion."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("tic", C.c_double * 3), ("ric", C.c_double * 9)]
+
+
+def make_camera(fx, fy, cx, cy, tic=(0, 0, 0), ric=(1, 0, 0, 0, 1, 0, 0, 0, 1)):
+    c = VioCamera(fx=fx, fy=fy, cx=cx, cy=cy)
+    c.tic[:] = [float(x) for x in np.asarray(tic, np.float64).ravel()]
+    c.ric[:] = [float(x) for x in np.asarray(ric, np.float64).ravel()]
+    return c
+
+
+def camera_from_config(cfg, tic=None, ric=None):
+    """vio_camera_from_config: cfg's intrinsics with the given extrinsic (None: tic = 0, ric = identity)."""
+    out = VioCamera()
+    t = None if tic is None else np.ascontiguousarray(tic, np.float64).ravel()
+    r = None if ric is None else np.ascontiguousarray(ric, np.float64).ravel()
+    load_product().vio_camera_from_config(C.byref(cfg), _ptr(t) if t is not None else None, _ptr(r) if r is not None else None,
+                                          C.byref(out))
+    return out
+
+
+def camera_fields(c):
+    """-> (fx, fy, cx, cy, tic [3], ric [3, 3]) of a VioCamera."""
+    return c.fx, c.fy, c.cx, c.cy, np.array(c.tic[:]), np.array(c.ric[:]).reshape(3, 3)
+
+
 class VioPreintegration(C.Structure):
     _fields_ = [
         ("sum_dt", C.c_double), ("delta_p", C.c_double * 3), ("delta_q", C.c_double * 4),
@@ -468,6 +496,20 @@ def load_product():
     lib.vio_backend_solve_windows.argtypes = [vp, C.POINTER(VioWindow), C.c_int32, C.c_int32,
                                               C.POINTER(VioSolveStats)]
     lib.vio_backend_reserve_priors.argtypes = [vp, C.c_int32]
+    camp = C.POINTER(VioCamera)
+    lib.vio_camera_from_config.argtypes = [C.POINTER(VioConfig), _dp, _dp, camp]
+    lib.vio_camera_from_config.restype = None
+    lib.vio_backend_solve_windows_cam.argtypes = [vp, C.POINTER(VioWindow), C.c_int32, _dp, C.POINTER(VioSolveStats)]
+    lib.vio_backend_upload_cam.argtypes = [vp, C.POINTER(VioWindow), C.c_int32, _dp]
+    lib.vio_frontend_set_cameras.argtypes = [vp, C.c_int32, _ip, camp]
+    lib.vio_frontend_get_camera.argtypes = [vp, C.c_int32, camp]
+    lib.vio_estimator_set_camera.argtypes = [vp, C.c_int32, camp]
+    lib.vio_estimator_get_camera.argtypes = [vp, C.c_int32, camp]
+    lib.vio_pnp_tracker_set_camera.argtypes = [vp, C.c_int32, camp]
+    lib.vio_pnp_tracker_get_camera.argtypes = [vp, C.c_int32, camp]
+    lib.vio_pnp_solve_windows_cam.argtypes = [vp, C.POINTER(VioPnpWindow), C.c_int32, _dp, C.POINTER(VioSolveStats)]
+    lib.vio_loop_detector_set_cameras.argtypes = [vp, C.c_int32, _ip, camp]
+    lib.vio_loop_detector_get_camera.argtypes = [vp, C.c_int32, camp]
     lib.vio_backend_get_device.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.vio_frontend_get_device.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.vio_backend_upload.argtypes = [vp, C.POINTER(VioWindow), C.c_int32]

@@ -54,6 +54,28 @@ class WindowSolver:
         self._check(self.lib.vio_backend_solve_windows(self._h, arr, len(windows), buf_num, stats), "solve_windows")
         return [abi.stats_to_dict(s) for s in stats]
 
+    @staticmethod
+    def _sqrt_info(sqrt_info, n):
+        if sqrt_info is None:
+            return None, None
+        a = np.ascontiguousarray(sqrt_info, np.float64)
+        assert a.shape == (n,)
+        return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+    def solve_cam(self, windows, sqrt_info=None):
+        """solve() for windows of different cameras: sqrt_info[b] = fx / 1.5 of window b's camera (None: cfg.fx / 1.5 for
+        all); ex_pose is per window already (vio_backend_solve_windows_cam). Returns the rc, stats dicts."""
+        arr = self._array(windows)
+        stats = (abi.VioSolveStats * len(windows))()
+        keep, p = self._sqrt_info(sqrt_info, len(windows))
+        rc = self.lib.vio_backend_solve_windows_cam(self._h, arr, len(windows), p, stats)
+        return rc, [abi.stats_to_dict(s) for s in stats]
+
+    def upload_cam(self, windows, sqrt_info=None):
+        self._structs = self._array(windows)
+        keep, p = self._sqrt_info(sqrt_info, len(windows))
+        return self.lib.vio_backend_upload_cam(self._h, self._structs, len(windows), p)
+
     def device(self):
         """HIP device ordinal the context is bound to (the device current on the creating thread)."""
         d = C.c_int32(-1)

@@ -21,7 +21,7 @@ namespace vio {
 
 constexpr int kHdrInts = 12;
 enum { H_W = 0, H_F, H_M, H_HAS_LOOP, H_LOOP_FRAME, H_MARG, H_PRIOR_N, H_PRIOR_NB, H_USE_ORIGIN, H_NPAIRS, H_NSLOTS, H_NREV };
-constexpr int kHdrDoubles = 4;
+constexpr int kHdrDoubles = 5;  // origin yaw | origin p (3) | sqrt_info of the window's camera
 constexpr int kMaxPriorBlocks = VIO_MAX_PRIOR_BLOCKS;
 
 struct BatchDims {
@@ -31,7 +31,7 @@ struct BatchDims {
                 // or in global scratch (0: leaves the room to windows with many landmarks, two of which then share a CU)
   int prof_stages;  // LDS slots of the stage clock: ST_COUNT for the launches of vio_backend_set_profile, 0 for the product's
   int max_iter;
-  double s_info, gravity, cauchy_b;
+  double s_info, gravity, cauchy_b;  // s_info: what the pack writes for a window that names no camera of its own (hdr_d[4])
 };
 
 // Wcap/Fcap/Mcap: largest window / feature / factor count in the batch; any_loop: some window carries a loop pose
@@ -186,7 +186,7 @@ VIO_HD WinView make_view(const BatchPtrs &B, int b) {
   v.Fpad = B.d.Fpad;
   v.npose6 = 6 * (v.P + (v.has_loop ? 1 : 0));
   v.n6 = v.npose6, v.nrows = v.n6 + 1, v.nT = (v.nrows + 15) >> 4, v.jp = (6 * B.d.nblk_cap + 1 + 15) / 16 * 16;
-  v.s_info = B.d.s_info, v.gravity = B.d.gravity, v.cauchy_b = B.d.cauchy_b;
+  v.gravity = B.d.gravity, v.cauchy_b = B.d.cauchy_b;
   v.pose0 = B.pose + b * B.s.pose, v.sb0 = B.sb + b * B.s.sb, v.ex = B.ex + b * B.s.ex, v.feat0 = B.feat + b * B.s.feat;
   v.fhost = B.fhost + b * B.s.fint, v.ftarget = B.ftarget + b * B.s.fint, v.ffeat = B.ffeat + b * B.s.fint;
   v.fslot = B.fslot + b * B.s.fint, v.fstart = B.fstart + b * B.s.fstart;
@@ -201,6 +201,7 @@ VIO_HD WinView make_view(const BatchPtrs &B, int b) {
   if (B.ptab && B.ptab[b].J) v.pr_x0 = B.ptab[b].x0, v.pr_J = B.ptab[b].J, v.pr_r = B.ptab[b].r;
   v.use_origin = h[H_USE_ORIGIN];
   v.origin_yaw = hd[0], v.origin_p[0] = hd[1], v.origin_p[1] = hd[2], v.origin_p[2] = hd[3];
+  v.s_info = hd[4];  // ProjectionFactor::sqrt_info of the window's camera (VINS.cpp:31)
   double *sc = B.scratch + b * B.s.scratch;
   v.imu_info = sc + B.s.s_info, v.imu_aug = sc + B.s.s_aug, v.imu_J = sc + B.s.s_J, v.imu_M = sc + B.s.s_M;
   v.imu_r = sc + B.s.s_r, v.imu_Mr = sc + B.s.s_Mr, v.prb0 = sc + B.s.s_prJT, v.prH0 = sc + B.s.s_prH0;
@@ -527,6 +528,7 @@ inline int pack_window(HostBatch &hb, int b, const VioWindow &w, bool store_ok =
   h[H_MARG] = w.marginalization_flag, h[H_USE_ORIGIN] = w.use_origin_override, h[H_NREV] = nrev;
   double *hd = &hb.hdr_d[(size_t)b * kHdrDoubles];
   hd[0] = w.origin_yaw_deg, hd[1] = w.origin_p[0], hd[2] = w.origin_p[1], hd[3] = w.origin_p[2];
+  hd[4] = d.s_info;  // (the context's camera; vio_backend_upload_cam overwrites it with the window's own)
   memcpy(&hb.pose[b * s.pose], w.pose, sizeof(double) * 7 * P);
   memcpy(&hb.sb[b * s.sb], w.speed_bias, sizeof(double) * 9 * P);
   memcpy(&hb.ex[b * s.ex], w.ex_pose, sizeof(double) * 7);

@@ -14,11 +14,11 @@ static vio::StoreDev resident_store_dev(vio_backend *be) {
   S.loop_frame = r->dp<int>(r->o_loopf), S.loop_n = r->dp<int>(r->o_loopn), S.loop_off = r->dp<int>(r->o_loopoff);
   S.loop_ids = r->dp<int>(r->o_loopids), S.loop_xy = r->dp<double>(r->o_loopxy);
   S.Ps = r->dp<double>(r->o_Ps), S.Rs = r->dp<double>(r->o_Rs);
-  S.tic = r->consts.p + 7, S.ric = r->consts.p + 10;
+  S.tic = r->consts.p + 7, S.ric = r->consts.p + 10, S.cam_stride = vio_resident::kCamDev;  // one record per slot
   S.preint = r->preint.p, S.pre_idx = r->dp<int>(r->o_preidx), S.pre_blk = r->dp<double>(r->o_preblk);
   S.n_pre = r->n_pre.load();
   S.imu_jobs = r->dp<double>(r->o_jobs), S.imu_samples = r->dp<double>(r->o_samples), S.n_imu_jobs = r->n_jobs.load();
-  S.pre_side = r->pre_side.p, S.noise = r->consts.p + 19;
+  S.pre_side = r->pre_side.p, S.noise = r->consts.p + (size_t)r->n_slots * vio_resident::kCamDev;
   S.prof = nullptr;
   static const bool prof = vio::env_flag("VIO_AMD_STORE_PROF");
   if (prof && r->prof.ensure(32) == VIO_OK) S.prof = r->prof.p;
@@ -62,22 +62,30 @@ int vio_backend_resident_reserve(vio_backend_t *be, int32_t n_slots, int32_t lis
     if (rc == VIO_OK) rc = r->ctl.ensure(N * vio::store::C_COUNT);
     if (rc == VIO_OK) rc = r->ctld.ensure(N * vio::store::kCtlDoubles);
     if (rc == VIO_OK) rc = r->preint.ensure(N * W * kPreintDoubles);
-    if (rc == VIO_OK) rc = r->consts.ensure(19 + 18);
+    if (rc == VIO_OK) rc = r->consts.ensure(N * vio_resident::kCamDev + 18);
     if (rc == VIO_OK) rc = r->pre_side.ensure(N * W * vio::preint::kSide);
     if (rc == VIO_OK) rc = r->b_dummy.ensure(16);
     if (rc != VIO_OK) return rc;
     HIP_OK(hipMemset(r->ctl.p, 0, N * vio::store::C_COUNT * sizeof(int)));
     HIP_OK(hipMemset(r->preint.p, 0, N * W * kPreintDoubles * sizeof(double)));
-    double c[19 + 18];
-    memcpy(c, ex_pose, 56), memcpy(c + 7, tic, 24), memcpy(c + 10, ric, 72);
+    // every slot starts with the context's camera; a sequence with its own brings it along (vio_backend_resident_set_cameras)
+    r->cam_rec.assign(N * vio_resident::kCamRec, 0.0);
+    for (size_t b = 0; b < N; b++) {
+      double *rec = &r->cam_rec[b * vio_resident::kCamRec];
+      memcpy(rec, ex_pose, 56), memcpy(rec + 7, tic, 24), memcpy(rec + 10, ric, 72);
+      rec[19] = be->cfg.fx / 1.5;  // ProjectionFactor::sqrt_info (VINS.cpp:31)
+    }
+    std::vector<double> cv(N * vio_resident::kCamDev + 18);
+    for (size_t b = 0; b < N; b++) memcpy(&cv[b * vio_resident::kCamDev], &r->cam_rec[b * vio_resident::kCamRec], sizeof(double) * vio_resident::kCamDev);
     {  // noise diagonal of the pre-integration, integration_base.h:30-36 (vio_preint.h preint_init)
       const VioConfig &cf = be->cfg;
       const double an = cf.acc_n * cf.acc_n, gn = cf.gyr_n * cf.gyr_n, aw = cf.acc_w * cf.acc_w, gw = cf.gyr_w * cf.gyr_w;
-      for (int k = 0; k < 3; k++) c[19 + k] = an, c[22 + k] = gn, c[25 + k] = an, c[28 + k] = gn, c[31 + k] = aw, c[34 + k] = gw;
+      double *c = &cv[N * vio_resident::kCamDev];
+      for (int k = 0; k < 3; k++) c[k] = an, c[3 + k] = gn, c[6 + k] = an, c[9 + k] = gn, c[12 + k] = aw, c[15 + k] = gw;
     }
     HIP_OK(hipMemset(r->pre_side.p, 0, N * W * vio::preint::kSide * sizeof(double)));
     memcpy(r->ex_pose, ex_pose, 56);
-    HIP_OK(hipMemcpy(r->consts.p, c, sizeof(c), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(r->consts.p, cv.data(), sizeof(double) * cv.size(), hipMemcpyHostToDevice));
     // staging layout: ints, doubles, observations, then the pre-integration blocks (only the ones in use travel)
     size_t o = 0;
     auto place = [&](size_t bytes) {
@@ -119,6 +127,36 @@ int vio_backend_resident_reserve(vio_backend_t *be, int32_t n_slots, int32_t lis
 int vio_backend_set_peers(vio_backend_t *be, int32_t peers) {
   if (!be || peers < 1) return VIO_EINVAL;
   be->peers = peers;
+  return VIO_OK;
+}
+
+// The cameras of n slots (any order, distinct): rec[k] = ex_pose 7 | tic 3 | ric 9 | sqrt_info of slot slots[k]. Between two frames
+// only. The extrinsic the window kernel reads is staged per slot with every frame; the store kernels' records go up here.
+int vio_backend_resident_set_cameras(vio_backend_t *be, int32_t n, const int32_t *slots, const double *rec) {
+  if (!be || !be->res) return VIO_ESTATE;
+  vio_resident *r = be->res.get();
+  if (n < 0 || (n > 0 && (!slots || !rec))) return VIO_EINVAL;
+  if (r->phase != 0) return VIO_ESTATE;
+  if (n == 0) return VIO_OK;
+  constexpr int R = vio_resident::kCamRec, D = vio_resident::kCamDev;
+  for (int k = 0; k < n; k++) {
+    if (slots[k] < 0 || slots[k] >= r->n_slots) return VIO_EINVAL;
+    for (int i = 0; i < R; i++)
+      if (!std::isfinite(rec[(size_t)k * R + i])) return VIO_EINVAL;
+    if (!(rec[(size_t)k * R + 19] > 0)) return VIO_EINVAL;
+  }
+  VIO_ON_DEVICE_OF(be);
+  HIP_OK(hipStreamSynchronize(be->last_stream ? be->last_stream : be->stream));  // (a keyframe pass may still read the records)
+  HIP_OK(hipStreamSynchronize(be->stream));
+  for (int k = 0; k < n; k++) {
+    const size_t b = slots[k];
+    memcpy(&r->cam_rec[b * R], rec + (size_t)k * R, sizeof(double) * R);
+    memcpy(r->hp<double>(r->o_ex) + 7 * b, rec + (size_t)k * R, 56);
+  }
+  // one copy of the whole table of records (19 doubles per slot; the IMU noise behind it stays)
+  std::vector<double> dev((size_t)r->n_slots * D);
+  for (size_t b = 0; b < (size_t)r->n_slots; b++) memcpy(&dev[b * D], &r->cam_rec[b * R], sizeof(double) * D);
+  HIP_OK(hipMemcpy(r->consts.p, dev.data(), sizeof(double) * dev.size(), hipMemcpyHostToDevice));
   return VIO_OK;
 }
 
@@ -252,7 +290,15 @@ int vio_backend_resident_fetch(vio_backend_t *be, int32_t slot, VioFeatureInfo *
 int vio_backend_resident_keyframe(vio_backend_t *be, int32_t n, const int32_t *slots, const int32_t *rows, const double *const *Ps,
                                   const double *const *Rs, const double intr[4], int32_t stride, int32_t *ids, float *px, float *norm,
                                   double *cloud, int32_t *count) {
+  return vio_backend_resident_keyframe_cam(be, n, slots, rows, Ps, Rs, intr, 0, stride, ids, px, norm, cloud, count);
+}
+
+// intr_stride: doubles between the intrinsics of two slots of the call (4: one camera per slot, 0: one for all)
+int vio_backend_resident_keyframe_cam(vio_backend_t *be, int32_t n, const int32_t *slots, const int32_t *rows, const double *const *Ps,
+                                      const double *const *Rs, const double *intr, int32_t intr_stride, int32_t stride, int32_t *ids,
+                                      float *px, float *norm, double *cloud, int32_t *count) {
   if (!be || !be->res) return VIO_ESTATE;
+  if (intr_stride != 0 && intr_stride != 4) return VIO_EINVAL;
   vio_resident *r = be->res.get();
   if (n < 0 || stride < 0 || (n > 0 && (!slots || !rows || !Ps || !Rs || !intr || !count)) || (n > 0 && stride > 0 && (!ids || !px || !norm || !cloud)))
     return VIO_EINVAL;
@@ -272,23 +318,26 @@ int vio_backend_resident_keyframe(vio_backend_t *be, int32_t n, const int32_t *s
     const int cap = std::max(1, std::min((int)stride, r->sd.Lcap));
     const size_t N = r->n_slots, T = (size_t)n * cap;
     int rc = r->kf_jobs.ensure(N);
-    if (rc == VIO_OK) rc = r->kf_states.ensure(N * 12 * P);
+    if (rc == VIO_OK) rc = r->kf_states.ensure(N * (12 * P + 4));  // (behind the states: fx fy cx cy of every job)
     if (rc == VIO_OK) rc = r->kf_out.ensure(44 * N * (size_t)r->sd.Lcap + 4 * N);
     if (rc != VIO_OK) return rc;
     r->kf_hjobs.assign(slots, slots + n);
-    r->kf_hstates.resize((size_t)n * 12 * P);
+    const size_t o_intr = (size_t)n * 12 * P;
+    r->kf_hstates.resize(o_intr + (intr_stride ? 4 * (size_t)n : 0));
     for (int k = 0; k < n; k++) {
       memcpy(&r->kf_hstates[(size_t)k * 12 * P], Ps[k], sizeof(double) * 3 * P);
       memcpy(&r->kf_hstates[(size_t)k * 12 * P + 3 * P], Rs[k], sizeof(double) * 9 * P);
+      if (intr_stride) memcpy(&r->kf_hstates[o_intr + 4 * (size_t)k], intr + (size_t)k * intr_stride, sizeof(double) * 4);
     }
     // the sections of the download: cloud | px | norm | ids | count
     const size_t o_cloud = 0, o_px = 24 * T, o_norm = 32 * T, o_ids = 40 * T, o_count = 44 * T, bytes = 44 * T + 4 * (size_t)n;
     if (r->kf_hout.size() < bytes) r->kf_hout.resize(bytes);
     unsigned char *D = r->kf_out.p, *Hb = r->kf_hout.data();
     HIP_OK(hipMemcpyAsync(r->kf_jobs.p, r->kf_hjobs.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(r->kf_states.p, r->kf_hstates.data(), sizeof(double) * (size_t)n * 12 * P, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(r->kf_states.p, r->kf_hstates.data(), sizeof(double) * r->kf_hstates.size(), hipMemcpyHostToDevice, st));
     vio::StoreKeyframe K;
     K.jobs = r->kf_jobs.p, K.states = r->kf_states.p, K.fx = intr[0], K.fy = intr[1], K.cx = intr[2], K.cy = intr[3], K.cap = cap;
+    K.intr = intr_stride ? r->kf_states.p + o_intr : nullptr;
     K.cloud = (double *)(D + o_cloud), K.px = (float *)(D + o_px), K.norm = (float *)(D + o_norm), K.ids = (int *)(D + o_ids);
     K.count = (int *)(D + o_count);
     rc = vio::store_launch_keyframe(resident_store_dev(be), K, n, st);
@@ -364,6 +413,7 @@ int vio_backend_resident_stage(vio_backend_t *be, int32_t slot, const VioObs *ob
     h[H_PRIOR_N] = prior->n, h[H_PRIOR_NB] = prior->n_blocks;
   }
   memset(r->hp<double>(r->o_hdrd) + (size_t)slot * kHdrDoubles, 0, sizeof(double) * kHdrDoubles);
+  r->hp<double>(r->o_hdrd)[(size_t)slot * kHdrDoubles + 4] = r->cam_rec[(size_t)slot * vio_resident::kCamRec + 19];  // sqrt_info of the slot's camera
   memcpy(r->hp<double>(r->o_pose) + (size_t)slot * 7 * P, pose, sizeof(double) * 7 * P);
   memcpy(r->hp<double>(r->o_sb) + (size_t)slot * 9 * P, speed_bias, sizeof(double) * 9 * P);
   memcpy(r->hp<double>(r->o_Ps) + (size_t)slot * 3 * P, Ps, sizeof(double) * 3 * P);

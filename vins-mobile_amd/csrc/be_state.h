@@ -36,8 +36,12 @@ struct vio_resident {
   vio::store::Dims sd;
   // the store: two banks per slot, control blocks, pre-integration blocks, the extrinsic
   DevBuf<int> fid, start, nobs, flag, ctl;
-  DevBuf<double> depth, obs, ctld, preint, consts;  // consts: ex_pose 7 | tic 3 | ric 9
+  DevBuf<double> depth, obs, ctld, preint, consts;  // consts: [n_slots] x (ex_pose 7 | tic 3 | ric 9), then the IMU noise 18
   double ex_pose[7];
+  // the camera of every slot (vio_backend_resident_set_cameras; the one of reserve until then): kCamRec doubles per slot,
+  // ex_pose 7 | tic 3 | ric 9 as in consts, then sqrt_info = FOCUS_LENGTH_X / 1.5 (VINS.cpp:31)
+  static constexpr int kCamRec = 20, kCamDev = 19;
+  std::vector<double> cam_rec;
   // per-frame inputs: page-locked arena and its device mirror (same offsets)
   HostVec<unsigned char> h_in;
   DevBuf<unsigned char> d_in;

@@ -9,6 +9,12 @@
 __attribute__((weak)) int vio_backend_resident_keyframe(vio_backend_t *, int32_t, const int32_t *, const int32_t *, const double *const *,
                                                         const double *const *, const double *, int32_t, int32_t *, float *, float *, double *,
                                                         int32_t *);
+__attribute__((weak)) int vio_backend_resident_keyframe_cam(vio_backend_t *, int32_t, const int32_t *, const int32_t *, const double *const *,
+                                                            const double *const *, const double *, int32_t, int32_t, int32_t *, float *, float *,
+                                                            double *, int32_t *);
+// (weak as well: only an estimator some sequence of which was given a camera of its own calls these)
+__attribute__((weak)) int vio_backend_resident_set_cameras(vio_backend_t *, int32_t, const int32_t *, const double *);
+extern "C" __attribute__((weak)) int vio_backend_upload_cam(vio_backend_t *, const VioWindow *, int32_t, const double *);
 
 namespace {
 // ---- device-resident sequences (vio_resident.h) --------------------------------------------------------------------------
@@ -34,7 +40,7 @@ int ensure_store(vio_estimator *e, int g) {
   // (the last term: store_pack scans its (W + 2)^2 bucket keys through a landmark-sized array, vio_backend_resident_reserve)
   e->res_list_cap = std::max({1024, (e->W + 2) * e->cfg.max_corners, e->res_obs_cap, (e->W + 2) * (e->W + 2)});
   double ex[7];
-  extrinsic_pose(e, ex);
+  extrinsic_pose(e->tic, e->ric, ex);  // (every slot starts with the context's camera: promote_group brings a sequence's own)
   const int rc = vio_backend_resident_reserve(e->be[g], e->group_size, e->res_list_cap, e->res_obs_cap, ex, e->tic, e->ric);
   if (rc != VIO_OK) e->resident = false;  // (a window size the store does not take, or no memory: every sequence stays on the host-side lists)
   return rc;
@@ -70,6 +76,17 @@ void promote_group(vio_estimator *e, int g, const std::vector<int> &seqs) {
     who.push_back(seqs[k]);
   }
   if (who.empty()) return;
+  if (e->any_camera) {  // the slots' cameras first: the store kernels of the next frame read them
+    std::vector<double> rec;
+    for (int q : who) {
+      const Sequence &s = e->seq[q];
+      double ex[7];
+      extrinsic_pose(s.cam.tic, s.cam.ric, ex);
+      rec.insert(rec.end(), ex, ex + 7), rec.insert(rec.end(), s.cam.tic, s.cam.tic + 3), rec.insert(rec.end(), s.cam.ric, s.cam.ric + 9);
+      rec.push_back(s.cam.fx / 1.5);  // ProjectionFactor::sqrt_info of the sequence's camera (VINS.cpp:31)
+    }
+    if (!vio_backend_resident_set_cameras || vio_backend_resident_set_cameras(e->be[g], (int)who.size(), slots.data(), rec.data()) != VIO_OK) return;
+  }
   if (vio_backend_resident_load_batch(e->be[g], (int)who.size(), slots.data(), ip.data(), counts.data(), pp.data(), lp.data(), lr.data()) != VIO_OK)
     return;
   for (int q : who) {

@@ -91,8 +91,8 @@ bool solve_initial_scan(vio_estimator *e, Sequence &s, InitStage &st, std::vecto
       for (int k = i + 1; k <= W; k++) dq = qmul(dq, s.pre[k].dq);
       double Rb[9], Rt[9], ricT[9];
       qtoR(qnormalized(dq), Rb);
-      mat3T(e->ric, ricT);
-      mat3mul(ricT, Rb, Rt), mat3mul(Rt, e->ric, hint);
+      mat3T(s.cam.ric, ricT);
+      mat3mul(ricT, Rb, Rt), mat3mul(Rt, s.cam.ric, hint);
       st.l = i;
       return true;
     }
@@ -171,7 +171,7 @@ bool solve_initial_align(vio_estimator *e, Sequence &s) {
   frames.reserve(s.all_image_frame.size());
   for (auto &kv : s.all_image_frame) frames.push_back(kv.second);
   std::vector<double> x;
-  if (!init::visual_imu_alignment(e->cfg, e->tic, frames, W, s.Bgs.data(), s.g, x)) return false;  // FAIL_ALIGN
+  if (!init::visual_imu_alignment(e->cfg, s.cam.tic, frames, W, s.Bgs.data(), s.g, x)) return false;  // FAIL_ALIGN
   {
     size_t k = 0;
     for (auto &kv : s.all_image_frame) kv.second = frames[k++];  // the re-integrated intervals
@@ -188,11 +188,11 @@ bool solve_initial_align(vio_estimator *e, Sequence &s) {
   for (int k = 0; k <= W; k++) repropagate(e, s, k, zero, &s.Bgs[3 * k]);
   {
     double r0t[3], base[3];
-    mat3vec(&s.Rs[0], e->tic, r0t);
+    mat3vec(&s.Rs[0], s.cam.tic, r0t);
     for (int k = 0; k < 3; k++) base[k] = sc * s.Ps[k] - r0t[k];
     for (int k = s.frame_count; k >= 0; k--) {
       double rt[3];
-      mat3vec(&s.Rs[9 * k], e->tic, rt);
+      mat3vec(&s.Rs[9 * k], s.cam.tic, rt);
       for (int c = 0; c < 3; c++) s.Ps[3 * k + c] = sc * s.Ps[3 * k + c] - rt[c] - base[c];
     }
   }
@@ -234,7 +234,7 @@ bool solve_initial_tail(vio_estimator *e, Sequence &s, InitStage &st, bool ba_ok
   init::sfm_construct_after_ba(P, st.cq, st.tc, st.sfm_f, Q.data(), T.data(), tracked);
   // PnP for every frame of all_image_frame (VINS.cpp:926-1003)
   double ricT[9];
-  mat3T(e->ric, ricT);
+  mat3T(s.cam.ric, ricT);
   const bool posed = for_each_startup_frame(
       s, P, [&](init::Frame &f, int i) { window_frame_pose(f, &Q[4 * i], &T[3 * i], ricT); },
       [&](init::Frame &f, int ii, int) {
@@ -310,7 +310,7 @@ bool finish_sfm_problem(vio_estimator *e, Sequence &s, InitStage &st) {
   if (st.verdict == VIO_INIT_SFM_FAIL_CHAIN || st.verdict == VIO_INIT_SFM_FAIL_BA) s.marginalization_flag = VIO_MARGIN_OLD;  // FAIL_SFM (VINS.cpp:915-917)
   if (st.verdict != VIO_INIT_SFM_OK) return false;
   double ricT[9];
-  mat3T(e->ric, ricT);
+  mat3T(s.cam.ric, ricT);
   for_each_startup_frame(
       s, P, [&](init::Frame &f, int i) { window_frame_pose(f, &st.q[4 * i], &st.T[3 * i], ricT); },
       [&](init::Frame &f, int, int x) {
@@ -333,7 +333,7 @@ bool take_initial_state(vio_estimator *e, Sequence &s) {
   s.init_pending = false;
   // visualInitialAlign re-integrates every interval from the biases it found (VINS.cpp:1057-1060, with ba = 0 there)
   for (int i = 1; i < P; i++) repropagate(e, s, i, &s.Bas[3 * i], &s.Bgs[3 * i]);
-  retriangulate(e, s, e->tic);
+  retriangulate(e, s, s.cam.tic);
   return true;
 }
 

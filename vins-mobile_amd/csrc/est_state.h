@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "vio_amd.h"
+#include "vio_camera.h"
 #include "vio_env.h"
 #include "vio_resident.h"
 #include "vio_math.h"
@@ -49,6 +50,9 @@ struct PriorBuf {
 
 struct Sequence {
   int index = 0;  // position in the estimator = slot of the device-resident prior store
+  // the sequence's camera (vio_estimator_set_camera): the context's cfg.fx .. cy and creation tic / ric until one is set.
+  // Outlives clearState: the reference reads the same per-device globals again there (VINS.cpp:36-81, global_param.cpp:24-131)
+  VioCamera cam;
   int frame_count = 0, solver_flag = VIO_SOLVER_INITIAL, marginalization_flag = VIO_MARGIN_OLD;
   bool first_imu = false;
   int failure_occur = 0;
@@ -121,7 +125,8 @@ using namespace est;
 struct vio_estimator {
   VioConfig cfg;
   int W = 10, n_seq = 0;
-  double tic[3], ric[9];
+  double tic[3], ric[9];  // of the context: what a sequence without a camera of its own uses
+  bool any_camera = false;  // some sequence has been given a camera (vio_estimator_set_camera): the back ends are told per slot / window
   std::vector<Sequence> seq;
   // Created at the first solve: IMU propagation and window filling need no device. The sequences are split into
   // n_groups contiguous groups with one back-end context (own stream, own resident batch, own prior store) each: while
@@ -236,10 +241,10 @@ void slide_window(vio_estimator *e, Sequence &s) {
     // for a resident sequence, together with the shift of the pre-integration blocks)
     if (!s.on_device && s.solver_flag == VIO_SOLVER_NON_LINEAR) {
       double R0[9], R1[9], P0[3], P1[3], t[3];
-      mat3mul(back_R0, e->ric, R0), mat3mul(&s.Rs[0], e->ric, R1);
-      mat3vec(back_R0, e->tic, t);
+      mat3mul(back_R0, s.cam.ric, R0), mat3mul(&s.Rs[0], s.cam.ric, R1);
+      mat3vec(back_R0, s.cam.tic, t);
       for (int k = 0; k < 3; k++) P0[k] = back_P0[k] + t[k];
-      mat3vec(&s.Rs[0], e->tic, t);
+      mat3vec(&s.Rs[0], s.cam.tic, t);
       for (int k = 0; k < 3; k++) P1[k] = s.Ps[k] + t[k];
       vio_features_remove_back_shift_depth(s.fm, R0, P0, R1, P1);
     } else if (!s.on_device) {

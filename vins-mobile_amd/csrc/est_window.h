@@ -32,9 +32,9 @@ int first_error_of(const VioFrameResult *results, int q0, int q1, int first) {
     if (results[q].action == VIO_FRAME_ERROR) first = results[q].error;
   return first;
 }
-void extrinsic_pose(const vio_estimator *e, double out7[7]) {  // para_Ex_Pose: tic, then ric as x y z w
-  const Quat q = RtoQ(e->ric);
-  out7[0] = e->tic[0], out7[1] = e->tic[1], out7[2] = e->tic[2], out7[3] = q.x, out7[4] = q.y, out7[5] = q.z, out7[6] = q.w;
+void extrinsic_pose(const double tic[3], const double ric[9], double out7[7]) {  // para_Ex_Pose: tic, then ric as x y z w
+  const Quat q = RtoQ(ric);
+  out7[0] = tic[0], out7[1] = tic[1], out7[2] = tic[2], out7[3] = q.x, out7[4] = q.y, out7[5] = q.z, out7[6] = q.w;
 }
 
 // Relocalization constraint: front_pose follows retrive_pose_data; it enters when its frame is still in the window. The sweep at
@@ -54,14 +54,14 @@ void retriangulate(vio_estimator *e, Sequence &s, const double tic[3]) {
   vio_features_count(s.fm, &nfe);
   std::vector<double> minus1(nfe > 0 ? nfe : 1, -1.0);
   vio_features_clear_depth(s.fm, minus1.data(), nfe);
-  vio_features_triangulate(s.fm, s.Ps.data(), s.Rs.data(), tic, e->ric);
+  vio_features_triangulate(s.fm, s.Ps.data(), s.Rs.data(), tic, s.cam.ric);
 }
 
 // old2new + the factor list + the loop pose: everything solve_ceres hands to the solver (VINS.cpp:89-129, 505-637)
 int build_window(vio_estimator *e, Sequence &s, VioWindow *w) {
   const int W = e->W;
   fill_pose_arrays(e, s);
-  extrinsic_pose(e, s.ex_pose);
+  extrinsic_pose(s.cam.tic, s.cam.ric, s.ex_pose);
   int nf = 0;
   int rc = vio_features_get_depth_vector(s.fm, s.inv_depth.data(), e->cfg.max_features, &nf);
   if (rc != VIO_OK) return rc;

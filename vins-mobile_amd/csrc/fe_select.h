@@ -15,7 +15,7 @@ namespace {
 struct SelectParams {
   int cap, rows, cols, max_corners;
   float min_dist;
-  double fx, fy, cx, cy;
+  const double *cam;  // [n_seq][4] fx, fy, cx, cy of every sequence's camera (vio_frontend_set_cameras)
 };
 
 constexpr int kSelThreads = 512;
@@ -240,6 +240,10 @@ __device__ __forceinline__ void select_sequence(unsigned long long *cand, int se
   // corner taken above has none (-1). The features without an id are numbered from n_id in index order, like the serial loop
   // (which was up to n dependent trips to global memory on one lane): rank = exclusive count of the -1 entries before i,
   // from a ballot per wave and the waves' counts through LDS.
+  // the sequence's camera for image_msg below: one uniform load per workgroup, asked for ahead of the barrier of the id pass (the
+  // selection rounds above do not carry it)
+  const double *cam = P.cam + 4 * (size_t)seq;
+  const double cam_fx = cam[0], cam_fy = cam[1], cam_cx = cam[2], cam_cy = cam[3];
   const bool is_new = tid >= n_old && tid < n;
   if (is_new) {
     const unsigned bidx = s_pick[tid];
@@ -268,7 +272,7 @@ __device__ __forceinline__ void select_sequence(unsigned long long *cand, int se
     pre_pts[(base + i) * 2] = x, pre_pts[(base + i) * 2 + 1] = y;
     VioObs o;
     o.id = my_id;
-    o.x = ((double)x - P.cx) / P.fx, o.y = ((double)y - P.cy) / P.fy, o.z = 1.0;
+    o.x = ((double)x - cam_cx) / cam_fx, o.y = ((double)y - cam_cy) / cam_fy, o.z = 1.0;
     obs[base + i] = o;
   }
   CS_STAMP(4);

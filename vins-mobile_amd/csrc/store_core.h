@@ -52,6 +52,25 @@ struct Dims {
   int W, Lcap, Ocap;  // window size; list capacity; observations per frame
 };
 
+// The camera of a slot: where its camera -> body record lies. The records of the slots are cam_stride doubles apart, tic and ric
+// at the same place in each (0: one record shared by every slot), and the passes below take the two pointers.
+struct SlotCamera {
+  const double *tic, *ric;
+};
+VIO_HD SlotCamera slot_camera(const double *tic0, const double *ric0, int cam_stride, int slot) {
+  const size_t o = (size_t)slot * (size_t)cam_stride;
+  return SlotCamera{tic0 + o, ric0 + o};
+}
+// The intrinsics of job j of a keyframe launch: row j of intr ([jobs][4] fx fy cx cy), or the launch's own four when intr is null.
+struct Intrinsics {
+  double fx, fy, cx, cy;
+};
+VIO_HD Intrinsics job_intrinsics(const double *intr, int j, double fx, double fy, double cx, double cy) {
+  if (!intr) return Intrinsics{fx, fy, cx, cy};
+  const double *in = intr + 4 * (size_t)j;
+  return Intrinsics{in[0], in[1], in[2], in[3]};
+}
+
 // One bank of one sequence.
 struct Bank {
   int *fid, *start, *nobs, *flag;  // [Lcap] feature_id, start_frame, feature_per_frame.size(), solve_flag

@@ -8,6 +8,8 @@
 // Larger windows keep the pose matrix in global scratch and take a CU each (512 threads).
 // This file: the table of instantiations and the entry points of the host-window path. The contexts are in be_state.h, what both
 // paths share once a batch is planned in be_work.h, the launch policy in wk_plan.h, the device-resident path in be_resident.h.
+#include <cmath>
+
 #include "be_state.h"
 #include "be_work.h"
 #include "be_resident.h"
@@ -115,9 +117,13 @@ int vio_backend_reserve_priors(vio_backend_t *be, int32_t n_slots) {
   return VIO_OK;
 }
 
-int vio_backend_upload(vio_backend_t *be, const VioWindow *windows, int32_t n) try {  // (the staging vectors and the packers allocate: no exception crosses the ABI)
+int vio_backend_upload(vio_backend_t *be, const VioWindow *windows, int32_t n) { return vio_backend_upload_cam(be, windows, n, nullptr); }
+
+int vio_backend_upload_cam(vio_backend_t *be, const VioWindow *windows, int32_t n, const double *sqrt_info) try {  // (the staging vectors and the packers allocate: no exception crosses the ABI)
   if (!be || !windows || n < 1) return VIO_EINVAL;
   if (n > be->max_batch) return VIO_ECAP;
+  for (int b = 0; sqrt_info && b < n; b++)
+    if (!(std::isfinite(sqrt_info[b]) && sqrt_info[b] > 0)) return VIO_EINVAL;
   VIO_ON_DEVICE_OF(be);
   be->uploaded = false;  // a failed upload leaves nothing to launch or download
   be->coop_ok = false;  // (set again below once every global-matrix window is known to be packed for a cooperative launch)
@@ -180,6 +186,7 @@ int vio_backend_upload(vio_backend_t *be, const VioWindow *windows, int32_t n) t
       try {
         bool st_ = false;
         rcs[b] = pack_window(be->hb, b, windows[b], be->slot_of[b] >= 0, glb[b] ? P.chunk_glb : P.chunk, &st_);
+        if (sqrt_info) be->hb.hdr_d[(size_t)b * kHdrDoubles + 4] = sqrt_info[b];  // the window's own camera (VINS.cpp:31)
         strad[b] = st_ ? 1 : 0;
       } catch (const std::bad_alloc &) {  // (worker thread: must not unwind out of the pool)
         rcs[b] = VIO_ENOMEM;
@@ -355,8 +362,12 @@ int vio_backend_download(vio_backend_t *be, VioWindow *windows, int32_t n, VioSo
 
 int vio_backend_solve_windows(vio_backend_t *be, VioWindow *windows, int32_t n, int32_t buf_num, VioSolveStats *stats) {
   (void)buf_num;  // wall-clock budget selector in the reference (VINS.cpp:648-653); no time limit here
+  return vio_backend_solve_windows_cam(be, windows, n, nullptr, stats);
+}
+
+int vio_backend_solve_windows_cam(vio_backend_t *be, VioWindow *windows, int32_t n, const double *sqrt_info, VioSolveStats *stats) {
   const double t0 = now_ms();
-  int rc = vio_backend_upload(be, windows, n);
+  int rc = vio_backend_upload_cam(be, windows, n, sqrt_info);
   if (rc != VIO_OK) return rc;
   const double t1 = now_ms();
   rc = vio_backend_launch(be, nullptr);

@@ -93,7 +93,7 @@ void phase_a(const FrameCall &fc, int q) {
   vio_features_count(s.fm, &res.n_features);
   s.Headers[s.frame_count] = fc.headers[q];
   if (s.solver_flag == VIO_SOLVER_INITIAL) return phase_a_initial(fc, q);
-  vio_features_triangulate(s.fm, s.Ps.data(), s.Rs.data(), e->tic, e->ric);
+  vio_features_triangulate(s.fm, s.Ps.data(), s.Rs.data(), s.cam.tic, s.cam.ric);
   stage_window(fc, q);
 }
 
@@ -160,7 +160,13 @@ void launch_group(const FrameCall &fc, int g, GroupRun &run) {
     if (rc == VIO_OK) rc = vio_backend_set_peers(e->be[g], e->n_groups);
     if (rc == VIO_OK && e->resident_priors) rc = vio_backend_reserve_priors(e->be[g], e->group_size);
   }
-  if (rc == VIO_OK) rc = vio_backend_upload(e->be[g], e->windows.data() + run.g0[g], ng);
+  if (rc == VIO_OK && e->any_camera) {  // ProjectionFactor::sqrt_info of every window's own camera (VINS.cpp:31)
+    std::vector<double> si(ng);
+    for (int k = 0; k < ng; k++) si[k] = e->seq[e->solving[run.g0[g] + k]].cam.fx / 1.5;
+    rc = vio_backend_upload_cam ? vio_backend_upload_cam(e->be[g], e->windows.data() + run.g0[g], ng, si.data()) : VIO_ENODEV;
+  } else if (rc == VIO_OK) {
+    rc = vio_backend_upload(e->be[g], e->windows.data() + run.g0[g], ng);
+  }
   if (rc == VIO_OK) rc = vio_backend_launch(e->be[g], nullptr);
   run.launched[g] = rc == VIO_OK;
   run.rc = rc;
@@ -191,6 +197,7 @@ int vio_estimator_create(const VioConfig *cfg, int32_t n_seq, const double tic[3
       return VIO_ENOMEM;
     }
     s.index = (int)(&s - e->seq.data());
+    vio_camera_from_config(cfg, tic, ric, &s.cam);
     s.prior[0].init(cap, e->resident_priors), s.prior[1].init(cap, e->resident_priors);
     memcpy(s.last_R, kI3, 72), memcpy(s.last_R_old, kI3, 72), memcpy(s.r_drift, kI3, 72);
     for (int k = 0; k < 3; k++) s.last_P[k] = s.last_P_old[k] = s.t_drift[k] = 0;
@@ -253,6 +260,25 @@ int vio_estimator_clear(vio_estimator_t *e, int32_t seq) {
   // clearState of a failure inside process_image keeps the drift, as in the reference.
   memcpy(s.r_drift, kI3, 72);
   for (int k = 0; k < 3; k++) s.t_drift[k] = 0;
+  return VIO_OK;
+}
+
+// The per-device globals of setGlobalParam (global_param.cpp:24-131) for ONE sequence. Only while the sequence holds no frame:
+// every landmark, pre-integration and prior of a window was made with one camera.
+int vio_estimator_set_camera(vio_estimator_t *e, int32_t seq, const VioCamera *cam) {
+  if (!e || seq < 0 || seq >= e->n_seq || !cam) return VIO_EINVAL;
+  // (fx > 0: ProjectionFactor::sqrt_info = fx / 1.5 weighs the residuals, VINS.cpp:31; the back end takes no other)
+  if (!camera_valid(*cam, true) || !(cam->fx > 0)) return VIO_EINVAL;
+  Sequence &s = e->seq[seq];
+  if (s.frame_count != 0 || s.on_device) return VIO_ESTATE;
+  s.cam = *cam;
+  e->any_camera = true;
+  return VIO_OK;
+}
+
+int vio_estimator_get_camera(vio_estimator_t *e, int32_t seq, VioCamera *out) {
+  if (!e || seq < 0 || seq >= e->n_seq || !out) return VIO_EINVAL;
+  *out = e->seq[seq].cam;
   return VIO_OK;
 }
 
@@ -522,11 +548,14 @@ int vio_estimator_keyframe_features(vio_estimator_t *e, int32_t n, const int32_t
     const int i = host_rows[k];
     Sequence &s = e->seq[seq[i]];
     const size_t o = (size_t)i * stride;
-    host_rc[k] = vio_features_keyframe(s.fm, &e->cfg, s.Ps.data(), s.Rs.data(), e->tic, e->ric, stride, ids + o, px + 2 * o, norm + 2 * o, cloud + 3 * o,
+    VioConfig cf = e->cfg;  // (the sequence's intrinsics: vio_features_keyframe takes them per call)
+    cf.fx = s.cam.fx, cf.fy = s.cam.fy, cf.cx = s.cam.cx, cf.cy = s.cam.cy;
+    host_rc[k] = vio_features_keyframe(s.fm, &cf, s.Ps.data(), s.Rs.data(), s.cam.tic, s.cam.ric, stride, ids + o, px + 2 * o, norm + 2 * o, cloud + 3 * o,
                                        &count[i]);
   });
   for (int rc : host_rc) note(rc);
   const double intr[4] = {e->cfg.fx, e->cfg.fy, e->cfg.cx, e->cfg.cy};
+  std::vector<double> intr_of;  // [slots of the call][4], when some sequence has a camera of its own
   for (int g = 0; g < e->n_groups; g++) {
     const std::vector<int> &rows = dev_rows[g];
     if (rows.empty()) continue;
@@ -536,12 +565,20 @@ int vio_estimator_keyframe_features(vio_estimator_t *e, int32_t n, const int32_t
     }
     std::vector<int32_t> slots;
     std::vector<const double *> pp, rr;
+    intr_of.clear();
     for (int i : rows) {
       const Sequence &s = e->seq[seq[i]];
       slots.push_back(slot_of(e, s)), pp.push_back(s.Ps.data()), rr.push_back(s.Rs.data());
+      if (e->any_camera) intr_of.insert(intr_of.end(), {s.cam.fx, s.cam.fy, s.cam.cx, s.cam.cy});
     }
-    note(vio_backend_resident_keyframe(e->be[g], (int)rows.size(), slots.data(), rows.data(), pp.data(), rr.data(), intr, stride, ids, px, norm, cloud,
-                                       count));
+    if (!e->any_camera)
+      note(vio_backend_resident_keyframe(e->be[g], (int)rows.size(), slots.data(), rows.data(), pp.data(), rr.data(), intr, stride, ids, px, norm,
+                                         cloud, count));
+    else
+      note(vio_backend_resident_keyframe_cam
+               ? vio_backend_resident_keyframe_cam(e->be[g], (int)rows.size(), slots.data(), rows.data(), pp.data(), rr.data(), intr_of.data(), 4,
+                                                   stride, ids, px, norm, cloud, count)
+               : VIO_ENODEV);
   }
   return first_error;
 }

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "vio_amd.h"
+#include "vio_camera.h"
 #include "vio_device.h"
 #include "vio_pool.h"
 
@@ -105,6 +106,9 @@ struct vio_frontend {
   DevBuf<float> pnp_pts;
   DevBuf<uint8_t> lk_status;
   DevBuf<VioObs> obs;
+  // the camera of every sequence (vio_frontend_set_cameras): cfg's until one is set; image_msg reads the device table
+  DevBuf<double> cam;       // [n_seq][4] fx, fy, cx, cy
+  std::vector<double> h_cam;  // the same on the host (vio_frontend_get_camera)
   DevBuf<long long> d_prof;  // stage clock of track_update_kernel (VIO_AMD_TU_PROF=1)
   DevBuf<long long> d_cs_prof;  // stage clock of corner_select_kernel (VIO_AMD_CS_PROF=1, read at create)
   bool cs_prof = false;
@@ -192,10 +196,11 @@ LkParams lk_params(const VioConfig &cfg, const LevelDims &ld) {
   return P;
 }
 
-SelectParams select_params(const VioConfig &cfg) {
+SelectParams select_params(const vio_frontend *fe) {
+  const VioConfig &cfg = fe->cfg;
   SelectParams SP;
   SP.cap = cfg.max_corners, SP.rows = cfg.image_rows, SP.cols = cfg.image_cols, SP.max_corners = cfg.max_corners, SP.min_dist = (float)cfg.min_dist;
-  SP.fx = cfg.fx, SP.fy = cfg.fy, SP.cx = cfg.cx, SP.cy = cfg.cy;
+  SP.cam = fe->cam.p;
   return SP;
 }
 
@@ -313,7 +318,7 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
                        fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist, fe->max_bits.p, rows, cols, fe->cand.p,
                        fe->seg_cap, fe->n_cand.p, fe->ovf.p, next_epoch(fe), fe->detect_always ? (const int *)nullptr : fe->n_forw.p,
                        fe->cfg.max_corners);
-    const SelectParams SP = select_params(fe->cfg);
+    const SelectParams SP = select_params(fe);
     const RedoParams RP = redo_params(fe, alias0 ? d_frames : forw, alias0 ? img_bytes : fe->ld.pyr_bytes, nullptr, 0, fe->cfg.min_dist);
     hipLaunchKernelGGL(corner_select_kernel<false>, dim3(S + fe->n_redo_wg), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg,
                        fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
@@ -414,7 +419,7 @@ int fe_step_subset(vio_frontend *fe, const SubsetArgs &M, int n, int n_pub, cons
     hipLaunchKernelGGL(detect_subset_kernel, tg, dim3(256), 0, st, M, ld.pyr_bytes, fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist,
                        fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, fe->ovf.p, next_epoch(fe),
                        fe->detect_always ? (const int *)nullptr : fe->n_forw.p, fe->cfg.max_corners);
-    const SelectParams SP = select_params(fe->cfg);
+    const SelectParams SP = select_params(fe);
     RedoParams RP = redo_params(fe, nullptr, ld.pyr_bytes, nullptr, 0, fe->cfg.min_dist);
     RP.n_wg = std::min(fe->n_redo_wg, n_pub);
     hipLaunchKernelGGL(corner_select_subset_kernel, dim3(n_pub + RP.n_wg), dim3(kSelThreads), 0, st, M, n_pub, fe->cand.p, fe->seg_cap, fe->nseg,
@@ -477,13 +482,16 @@ int vio_frontend_create(const VioConfig *cfg, int32_t n_seq, vio_frontend_t **ou
       fe->n_forw.ensure(S) != VIO_OK || fe->n_id.ensure(S) != VIO_OK || fe->kept_xy.ensure(S * cap * 2) != VIO_OK ||
       fe->n_kept.ensure(S) != VIO_OK || fe->pnp_pts.ensure(S * cap * 2) != VIO_OK || fe->pnp_ids.ensure(S * cap) != VIO_OK ||
       fe->n_pnp.ensure(S) != VIO_OK || fe->n_obs.ensure(S) != VIO_OK || fe->lk_status.ensure(S * cap) != VIO_OK ||
-      fe->obs.ensure(S * cap) != VIO_OK || fe->hw.ensure((size_t)2 * cfg->min_dist + 1) != VIO_OK) {
+      fe->obs.ensure(S * cap) != VIO_OK || fe->hw.ensure((size_t)2 * cfg->min_dist + 1) != VIO_OK || fe->cam.ensure(S * 4) != VIO_OK) {
     delete fe;
     return VIO_ENOMEM;
   }
   std::vector<int> hw;
   circle_halfwidths(cfg->min_dist, hw);
+  fe->h_cam.resize(S * 4);
+  for (size_t q = 0; q < S; q++) fe->h_cam[4 * q] = cfg->fx, fe->h_cam[4 * q + 1] = cfg->fy, fe->h_cam[4 * q + 2] = cfg->cx, fe->h_cam[4 * q + 3] = cfg->cy;
   if (hipMemcpy(fe->hw.p, hw.data(), hw.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(fe->cam.p, fe->h_cam.data(), fe->h_cam.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(fe->max_bits.p, 0, sizeof(unsigned) * S * fe->nseg) != hipSuccess ||
       hipMemset(fe->n_cand.p, 0, sizeof(int) * S * fe->nseg) != hipSuccess || hipMemset(fe->n_pts.p, 0, sizeof(int) * S) != hipSuccess ||
       hipMemset(fe->ovf.p, 0, sizeof(int) * S) != hipSuccess || hipMemset(fe->n_redo.p, 0, sizeof(int)) != hipSuccess ||
@@ -877,6 +885,43 @@ int vio_frontend_reset(vio_frontend_t *fe, int32_t n, const int32_t *seq) {
   return VIO_OK;
 }
 
+// The camera of a sequence is what image_msg divides by (feature_tracker.cpp:300-306; FOCUS_LENGTH_X/Y, PX, PY are per device,
+// global_param.cpp:24-131). The table is rewritten between steps only: every launch that reads it has been collected.
+int vio_frontend_set_cameras(vio_frontend_t *fe, int32_t n, const int32_t *seq, const VioCamera *cam) {
+  if (!fe || n < 0 || (n > 0 && (!seq || !cam))) return VIO_EINVAL;
+  if (fe->pending) return VIO_ESTATE;
+  const int S = fe->n_seq;
+  std::vector<uint8_t> seen(S, 0);
+  if (!fe_subset::valid_list(S, n, seq, seen.data())) return VIO_EINVAL;
+  for (int i = 0; i < n; i++)
+    if (!vio::camera_valid(cam[i], false)) return VIO_EINVAL;
+  if (n == 0) return VIO_OK;
+  VIO_ON_DEVICE_OF(fe);
+  // a step that is not collected through this context may still read the table: vio_frontend_step_resident on the context's
+  // stream, or on a caller's (only then the whole device is waited for: sessions that join one by one must not stall the others)
+  if (fe->foreign_stream) {
+    HIP_OK(hipDeviceSynchronize());
+    fe->foreign_stream = false;
+  } else {
+    HIP_OK(hipStreamSynchronize(fe->stream));
+  }
+  for (int i = 0; i < n; i++) {
+    double *row = &fe->h_cam[4 * (size_t)seq[i]];
+    row[0] = cam[i].fx, row[1] = cam[i].fy, row[2] = cam[i].cx, row[3] = cam[i].cy;
+  }
+  HIP_OK(hipMemcpy(fe->cam.p, fe->h_cam.data(), fe->h_cam.size() * sizeof(double), hipMemcpyHostToDevice));
+  return VIO_OK;
+}
+
+int vio_frontend_get_camera(vio_frontend_t *fe, int32_t seq, VioCamera *out) {
+  if (!fe || seq < 0 || seq >= fe->n_seq || !out) return VIO_EINVAL;
+  const double *row = &fe->h_cam[4 * (size_t)seq];
+  memset(out, 0, sizeof(*out));
+  out->fx = row[0], out->fy = row[1], out->cx = row[2], out->cy = row[3];
+  out->ric[0] = out->ric[4] = out->ric[8] = 1.0;  // (the front end has no use for the extrinsic)
+  return VIO_OK;
+}
+
 int vio_frontend_in_step(vio_frontend_t *fe, int32_t *in_step) {
   if (!fe || !in_step) return VIO_EINVAL;
   *in_step = fe->in_step ? 1 : 0;
@@ -1068,7 +1113,7 @@ int vio_good_features(const VioConfig *cfg, const uint8_t *img, const uint8_t *m
   hipLaunchKernelGGL(detect_kernel<true>, tg, tb, 0, st, fe->pyr[0].p, fe->ld.pyr_bytes, fe->mask.p, px, fe->kept_xy.p, fe->n_kept.p,
                      fe->cap, fe->hw.p, c.min_dist, fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, fe->ovf.p,
                      next_epoch(fe.get()), (const int *)nullptr, 0);
-  const SelectParams SP = select_params(fe->cfg);
+  const SelectParams SP = select_params(fe.get());
   const RedoParams RP = redo_params(fe.get(), fe->pyr[0].p, fe->ld.pyr_bytes, fe->mask.p, px, c.min_dist);
   hipLaunchKernelGGL(corner_select_kernel<true>, dim3(1 + fe->n_redo_wg), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg,
                      fe->n_cand.p, fe->max_bits.p, RP, c.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p, fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p,

@@ -12,6 +12,16 @@
 
 using namespace vio;
 
+// The camera a configuration and an extrinsic stand for (FOCUS_LENGTH_X/Y, PX, PY, TIC_*, RIC_*: global_param.cpp:24-131)
+extern "C" void vio_camera_from_config(const VioConfig *cfg, const double tic[3], const double ric[9], VioCamera *out) {
+  if (!cfg || !out) return;
+  memset(out, 0, sizeof(*out));
+  out->fx = cfg->fx, out->fy = cfg->fy, out->cx = cfg->cx, out->cy = cfg->cy;
+  out->ric[0] = out->ric[4] = out->ric[8] = 1.0;
+  if (tic) memcpy(out->tic, tic, sizeof(out->tic));
+  if (ric) memcpy(out->ric, ric, sizeof(out->ric));
+}
+
 extern "C" int vio_preintegrate(const VioConfig *cfg, const double acc_0[3], const double gyr_0[3], const double ba[3],
                                 const double bg[3], int32_t n, const double *dt, const double *acc, const double *gyr,
                                 VioPreintegration *out) {

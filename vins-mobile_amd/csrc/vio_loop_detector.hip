@@ -46,6 +46,7 @@
 #include "vio_amd.h"
 #include "vio_bow_core.h"
 #include "vio_brief_launch.h"
+#include "vio_camera.h"
 #include "vio_device.h"
 #include "vio_ransac.h"
 
@@ -497,11 +498,13 @@ __global__ __launch_bounds__(64) void ld_connect_count_kernel(const LdPair *pair
 // rejectWithF :35-58 behind the RANSAC, one wave per pair: status, and the reduceVector calls as one ballot compaction in
 // window order. The batch RANSAC leaves the mask of a problem below 8 pairs unwritten: fewer than 8 keep everything (and
 // have no normalised points, measurements_old_norm stays empty), an unmatched query keeps nothing.
-// hdr [n][2] = n_kept, ransac_ran.
+// hdr [n][2] = n_kept, ransac_ran. intr [sessions][4] = cx cy fx fy of every session's camera, in float.
 __global__ __launch_bounds__(64) void ld_connect_keep_kernel(const LdPair *pairs, int stride, const int *count, const unsigned char *mask,
-                                                              const float *p_old, const int *ids, float cx, float cy, float fx, float fy,
+                                                              const float *p_old, const int *ids, const float *intr,
                                                               unsigned char *status, int *kept_index, int *kept_ids, double *kept_norm, int *hdr) {
   const int p = blockIdx.x, lane = threadIdx.x, n = pairs[p].n_window;
+  const float *in = intr + 4 * (size_t)pairs[p].session;  // (uniform)
+  const float cx = in[0], cy = in[1], fx = in[2], fy = in[3];
   const size_t o = (size_t)p * stride;
   const bool matched = count[p] == n, ran = matched && n >= 8;
   int cnt = 0;
@@ -562,6 +565,12 @@ struct vio_loop_detector {
   // sections of one download (kept_old_norm | matched old points | kept_index | kept_ids | hdr | status)
   DevBuf<LdPair> cn_pairs;
   DevBuf<int> cn_ids, cn_unmatched;
+  // the camera of every session (vio_loop_detector_set_cameras), and what a call's connect kernel reads: cx cy fx fy in
+  // float per session, a session's own camera or the call's cfg
+  std::vector<VioCamera> cam;
+  std::vector<char> has_cam;
+  DevBuf<float> cn_intr;
+  vio::PinnedBuf<float> cn_hintr;
   DevBuf<unsigned char> cn_out;
   vio::PinnedBuf<unsigned char> cn_host;  // (page-locked: the one download of a call)
   std::vector<LdPair> cn_hpairs;
@@ -672,6 +681,7 @@ int vio_loop_detector_create(vio_vocabulary_t *v, const VioLoopDetectorParams *p
   d->height = v->height, d->nid_level = v->L - p->di_levels, d->accumulate = v->weighting == 0 || v->weighting == 1;
   try {
     d->sess.resize(n_sessions);
+    d->cam.resize(n_sessions), d->has_cam.assign(n_sessions, 0);
     for (auto &s : d->sess) s.off.assign((size_t)max_entries + 1, 0), s.bow.assign(max_entries, 0), s.erased.assign(max_entries, 0);
   } catch (const std::bad_alloc &) {
     delete d;
@@ -1025,6 +1035,11 @@ int connect_run(vio_loop_detector *d, const VioConfig *cfg, int32_t min_loop_num
     const size_t full = 33 * SK + 8 * (size_t)d->S;
     int rc = d->cn_pairs.ensure(d->S);
     if (rc == VIO_OK) rc = d->cn_ids.ensure(SK);
+    if (rc == VIO_OK) rc = d->cn_intr.ensure(4 * (size_t)d->S);
+    if (rc == VIO_OK && !d->cn_hintr.p) {  // (first call: the rows of sessions no call has named yet travel too, as zeros)
+      rc = d->cn_hintr.ensure(4 * (size_t)d->S);
+      if (rc == VIO_OK) memset(d->cn_hintr.p, 0, sizeof(float) * 4 * (size_t)d->S);
+    }
     if (rc == VIO_OK) rc = d->cn_unmatched.ensure(SK);
     if (rc == VIO_OK) rc = d->cn_out.ensure(full);
     // (page-locked memory for what this call brings back; it grows to the largest call seen and stays)
@@ -1035,6 +1050,13 @@ int connect_run(vio_loop_detector *d, const VioConfig *cfg, int32_t min_loop_num
     const size_t bytes = o_status + T;
     unsigned char *D = d->cn_out.p, *Hb = d->cn_host.p;
     HIP_OK(hipMemcpyAsync(d->cn_pairs.p, d->cn_hpairs.data(), sizeof(LdPair) * (size_t)n, hipMemcpyHostToDevice, st));
+    for (int i = 0; i < n; i++) {  // the rows of the call's sessions (the other rows are not read)
+      const int q = session[i];
+      float *in = d->cn_hintr.p + 4 * (size_t)q;
+      if (d->has_cam[q]) in[0] = (float)d->cam[q].cx, in[1] = (float)d->cam[q].cy, in[2] = (float)d->cam[q].fx, in[3] = (float)d->cam[q].fy;
+      else in[0] = (float)cfg->cx, in[1] = (float)cfg->cy, in[2] = (float)cfg->fx, in[3] = (float)cfg->fy;
+    }
+    HIP_OK(hipMemcpyAsync(d->cn_intr.p, d->cn_hintr.p, sizeof(float) * 4 * (size_t)d->S, hipMemcpyHostToDevice, st));
     if (ids && row) {  // the rows of the pairs do not lie behind each other: gathered on the host, one upload
       d->cn_hids.resize(T);
       for (int i = 0; i < n; i++) memcpy(d->cn_hids.data() + (size_t)i * wmax, ids + (size_t)row[i] * stride, 4 * (size_t)n_window[i]);
@@ -1051,7 +1073,7 @@ int connect_run(vio_loop_detector *d, const VioConfig *cfg, int32_t min_loop_num
     rc = vio::fundamental_ransac_batch(st, d->p_cur.p, (const float *)(D + o_pts), d->n_pairs.p, n, wmax, 8, 2.0f, 0.99, d->mask.p);
     if (rc != VIO_OK) return rc;
     hipLaunchKernelGGL(ld_connect_keep_kernel, dim3(n), dim3(64), 0, st, d->cn_pairs.p, wmax, d->n_pairs.p, d->mask.p, (const float *)(D + o_pts),
-                       ids ? d->cn_ids.p : nullptr, (float)cfg->cx, (float)cfg->cy, (float)cfg->fx, (float)cfg->fy, D + o_status,
+                       ids ? d->cn_ids.p : nullptr, d->cn_intr.p, D + o_status,
                        (int *)(D + o_kidx), (int *)(D + o_kids), (double *)(D + o_norm), (int *)(D + o_hdr));
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(Hb, D, bytes, hipMemcpyDeviceToHost, st));
@@ -1082,6 +1104,26 @@ extern "C" {
 int vio_loop_detector_detect(vio_loop_detector_t *d, int32_t n, const int32_t *session, const int32_t *n_keys, const float *keys,
                              const uint64_t *desc, VioLoopDetection *out, float *cur_pts, float *old_pts, int32_t pts_stride) {
   return detect_run(d, n, session, n_keys, keys, desc, nullptr, out, cur_pts, old_pts, pts_stride);
+}
+
+// The intrinsics findConnectionWithOldFrame normalises the old keyframe's pixels with (loop/keyframe.cpp:45-46; FOCUS_LENGTH_X/Y,
+// PX, PY per device: global_param.cpp:24-131), per session.
+int vio_loop_detector_set_cameras(vio_loop_detector_t *d, int32_t n, const int32_t *session, const VioCamera *cam) {
+  if (!d || n < 0 || (n > 0 && (!session || !cam)) || n > d->S) return VIO_EINVAL;
+  std::vector<char> seen(d->S, 0);
+  for (int i = 0; i < n; i++) {
+    if (session[i] < 0 || session[i] >= d->S || seen[session[i]] || !vio::camera_valid(cam[i], false)) return VIO_EINVAL;
+    seen[session[i]] = 1;
+  }
+  for (int i = 0; i < n; i++) d->cam[session[i]] = cam[i], d->has_cam[session[i]] = 1;
+  return VIO_OK;
+}
+
+int vio_loop_detector_get_camera(vio_loop_detector_t *d, int32_t session, VioCamera *out) {
+  if (!d || session < 0 || session >= d->S || !out) return VIO_EINVAL;
+  if (!d->has_cam[session]) return VIO_ESTATE;  // (none set: the session uses the cfg of every call)
+  *out = d->cam[session];
+  return VIO_OK;
 }
 
 int vio_loop_detector_connect(vio_loop_detector_t *d, const VioConfig *cfg, int32_t min_loop_num, int32_t n, const int32_t *session,

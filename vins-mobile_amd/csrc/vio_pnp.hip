@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -20,11 +21,11 @@ constexpr int kThreads = 256;
 struct PnpBatch {  // device pointers, per-window strides in elements
   int n_windows, max_frames, max_factors;
   const int *hdr;  // [N][4 + 2*max_frames + 1]: n, M, max_iter, -, fixed[max_frames], feat_start[max_frames+1]
-  const double *pose, *speed, *bias, *ex, *preint, *obs, *pos;
+  const double *pose, *speed, *bias, *ex, *preint, *obs, *pos;  // ex: [N][8] = ex_pose (7) | sqrt_info of the window's camera
   const int *track;
   double *out_pose, *out_speed, *stats_d, *Jraw;
   int *stats_i;
-  double s_info, gravity, cauchy_b;
+  double gravity, cauchy_b;
 };
 
 __global__ __launch_bounds__(kThreads) void pnp_window_kernel(PnpBatch B) {
@@ -35,14 +36,14 @@ __global__ __launch_bounds__(kThreads) void pnp_window_kernel(PnpBatch B) {
   v.n = h[0], v.M = h[1], v.max_iter = h[2];
   v.fixed = h + 4, v.feat_start = h + 4 + F;
   v.pose0 = B.pose + (size_t)b * 7 * F, v.speed0 = B.speed + (size_t)b * 3 * F, v.bias = B.bias + (size_t)b * 6 * F;
-  v.ex = B.ex + (size_t)b * 7;
+  v.ex = B.ex + (size_t)b * 8;
   v.preint = B.preint + (size_t)b * (F - 1) * kPreintDoubles;
   v.obs = B.obs + (size_t)b * 2 * B.max_factors, v.pos = B.pos + (size_t)b * 3 * B.max_factors;
   v.track = B.track + (size_t)b * B.max_factors;
   v.out_pose = B.out_pose + (size_t)b * 7 * F, v.out_speed = B.out_speed + (size_t)b * 3 * F;
   v.stats_d = B.stats_d + (size_t)b * kStatsDoubles, v.stats_i = B.stats_i + (size_t)b * kStatsInts;
   v.Jraw = B.Jraw + (size_t)b * (F - 1) * 450;
-  v.s_info = B.s_info, v.gravity = B.gravity, v.cauchy_b = B.cauchy_b;
+  v.s_info = v.ex[7], v.gravity = B.gravity, v.cauchy_b = B.cauchy_b;
   Ctx cx;
   cx.wave64 = __builtin_amdgcn_readfirstlane((int)threadIdx.x & ~63);
   cx.tid = threadIdx.x, cx.nt = blockDim.x, cx.prof = nullptr, cx.lprof = nullptr;
@@ -90,8 +91,14 @@ void vio_pnp_destroy(vio_pnp_t *p) {
 }
 
 int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSolveStats *stats) {
+  return vio_pnp_solve_windows_cam(p, windows, n, nullptr, stats);
+}
+
+int vio_pnp_solve_windows_cam(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, const double *sqrt_info, VioSolveStats *stats) {
   if (!p || !windows || n < 1) return VIO_EINVAL;
   if (n > p->max_batch) return VIO_ECAP;
+  for (int b = 0; sqrt_info && b < n; b++)
+    if (!(std::isfinite(sqrt_info[b]) && sqrt_info[b] > 0)) return VIO_EINVAL;
   VIO_ON_DEVICE_OF(p);
   int F = 2, Mmax = 1;
   for (int b = 0; b < n; b++) {
@@ -107,7 +114,7 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
   }
   const size_t N = n, hs = 4 + 2 * (size_t)F + 1;
   std::vector<int> hdr(N * hs, 0), track(N * Mmax, 1);
-  std::vector<double> pose(N * 7 * F, 0.0), speed(N * 3 * F, 0.0), bias(N * 6 * F, 0.0), ex(N * 7, 0.0),
+  std::vector<double> pose(N * 7 * F, 0.0), speed(N * 3 * F, 0.0), bias(N * 6 * F, 0.0), ex(N * 8, 0.0),
       pre(N * (F - 1) * kPreintDoubles, 0.0), obs(N * 2 * Mmax, 0.0), pos(N * 3 * Mmax, 1.0);
   static_assert(sizeof(VioPreintegration) == kPreintDoubles * sizeof(double), "VioPreintegration layout");
   for (int b = 0; b < n; b++) {
@@ -120,7 +127,9 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
     memcpy(&pose[(size_t)b * 7 * F], w.pose, sizeof(double) * 7 * nf);
     memcpy(&speed[(size_t)b * 3 * F], w.speed, sizeof(double) * 3 * nf);
     memcpy(&bias[(size_t)b * 6 * F], w.bias, sizeof(double) * 6 * nf);
-    memcpy(&ex[(size_t)b * 7], w.ex_pose, sizeof(double) * 7);
+    memcpy(&ex[(size_t)b * 8], w.ex_pose, sizeof(double) * 7);
+    // PerspectiveFactor::sqrt_info = FOCUS_LENGTH_X / 1.5 (vins_pnp.cpp:19) of the window's camera
+    ex[(size_t)b * 8 + 7] = sqrt_info ? sqrt_info[b] : p->cfg.fx / 1.5;
     memcpy(&pre[(size_t)b * (F - 1) * kPreintDoubles], w.preint, sizeof(VioPreintegration) * (nf - 1));
     if (M) {
       memcpy(&obs[(size_t)b * 2 * Mmax], w.observation, sizeof(double) * 2 * M);
@@ -153,7 +162,6 @@ int vio_pnp_solve_windows(vio_pnp_t *p, VioPnpWindow *windows, int32_t n, VioSol
   B.preint = p->d_preint.p, B.obs = p->d_obs.p, B.pos = p->d_pos.p, B.track = p->d_track.p;
   B.out_pose = p->d_out_pose.p, B.out_speed = p->d_out_speed.p, B.stats_d = p->d_stats_d.p, B.stats_i = p->d_stats_i.p;
   B.Jraw = p->d_Jraw.p;
-  B.s_info = p->cfg.fx / 1.5;  // PerspectiveFactor::sqrt_info = FOCUS_LENGTH_X / 1.5 (vins_pnp.cpp:19)
   B.gravity = p->cfg.gravity, B.cauchy_b = p->cfg.cauchy_a * p->cfg.cauchy_a;
   const size_t lds = pnp::carve<ldsd>(F, kThreads, nullptr, nullptr, nullptr);
   HIP_OK(hipFuncSetAttribute((const void *)pnp_window_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "vio_amd.h"
+#include "vio_camera.h"
 #include "vio_math.h"
 #include "vio_preint.h"
 
@@ -22,6 +23,9 @@ namespace {
 
 struct Seq {
   int n = 0;  // PNP_SIZE
+  // the sequence's camera (vio_pnp_tracker_set_camera; the context's until then) and its para_Ex_Pose. Outlives clearState.
+  VioCamera cam;
+  double ex_pose[7];
   int frame_count = 0;
   bool first_imu = false;
   double acc_0[3] = {0, 0, 0}, gyr_0[3] = {0, 0, 0};
@@ -38,12 +42,22 @@ struct Seq {
 
 const double kI3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 
+void set_seq_camera(Seq &s, const VioCamera &c) {  // para_Ex_Pose: tic, then ric as x y z w
+  s.cam = c;
+  const Quat q = RtoQ(c.ric);
+  s.ex_pose[0] = c.tic[0], s.ex_pose[1] = c.tic[1], s.ex_pose[2] = c.tic[2];
+  s.ex_pose[3] = q.x, s.ex_pose[4] = q.y, s.ex_pose[5] = q.z, s.ex_pose[6] = q.w;
+}
+
 }  // namespace
+
+// (weak: only a tracker some sequence of which was given a camera of its own calls it; a host-only build has no device side)
+extern "C" __attribute__((weak)) int vio_pnp_solve_windows_cam(vio_pnp_t *, VioPnpWindow *, int32_t, const double *, VioSolveStats *);
 
 struct vio_pnp_tracker {
   VioConfig cfg;
   int n_seq = 0, size = 6;  // PNP_SIZE (global_param.hpp:29)
-  double ex_pose[7];
+  bool any_camera = false;  // some sequence has a camera of its own: the solve is told every window's sqrt_info
   std::vector<Seq> seq;
   vio_pnp_t *solver = nullptr;  // created at the first solve
   std::vector<VioPnpWindow> windows;
@@ -127,7 +141,7 @@ void build_window(vio_pnp_tracker *t, Seq &s, VioPnpWindow *w) {  // old2new (:9
   }
   memset(w, 0, sizeof(*w));
   w->n_frames = P, w->pose = s.pose.data(), w->speed = s.speed.data(), w->bias = s.bias.data(), w->fixed = s.fixed.data();
-  w->ex_pose = t->ex_pose, w->preint = s.preint.data(), w->feat_start = s.feat_start.data();
+  w->ex_pose = s.ex_pose, w->preint = s.preint.data(), w->feat_start = s.feat_start.data();
   w->observation = s.obs.data(), w->position = s.pos.data(), w->track_num = s.track.data();
 }
 
@@ -141,11 +155,10 @@ int vio_pnp_tracker_create(const VioConfig *cfg, int32_t n_seq, int32_t pnp_size
   vio_pnp_tracker *t = new (std::nothrow) vio_pnp_tracker();
   if (!t) return VIO_ENOMEM;
   t->cfg = *cfg, t->n_seq = n_seq, t->size = pnp_size;
-  const Quat q = RtoQ(ric);
-  t->ex_pose[0] = tic[0], t->ex_pose[1] = tic[1], t->ex_pose[2] = tic[2];
-  t->ex_pose[3] = q.x, t->ex_pose[4] = q.y, t->ex_pose[5] = q.z, t->ex_pose[6] = q.w;
+  VioCamera cam;
+  vio_camera_from_config(cfg, tic, ric, &cam);
   t->seq.resize(n_seq);
-  for (Seq &s : t->seq) clear_state(t, s);
+  for (Seq &s : t->seq) set_seq_camera(s, cam), clear_state(t, s);
   t->windows.resize(n_seq);
   *out = t;
   return VIO_OK;
@@ -160,6 +173,24 @@ void vio_pnp_tracker_destroy(vio_pnp_tracker_t *t) {
 int vio_pnp_tracker_clear(vio_pnp_tracker_t *t, int32_t seq) {
   if (!t || seq < 0 || seq >= t->n_seq) return VIO_EINVAL;
   clear_state(t, t->seq[seq]);
+  return VIO_OK;
+}
+
+// The per-device globals of setGlobalParam (global_param.cpp:24-131) for ONE sequence: the extrinsic of its windows and the
+// focal length in PerspectiveFactor::sqrt_info (vins_pnp.cpp:19). Only on a cleared sequence.
+int vio_pnp_tracker_set_camera(vio_pnp_tracker_t *t, int32_t seq, const VioCamera *cam) {
+  // (fx > 0: PerspectiveFactor::sqrt_info = fx / 1.5 weighs the residuals, vins_pnp.cpp:19)
+  if (!t || seq < 0 || seq >= t->n_seq || !cam || !camera_valid(*cam, true) || !(cam->fx > 0)) return VIO_EINVAL;
+  Seq &s = t->seq[seq];
+  if (s.frame_count != 0) return VIO_ESTATE;
+  set_seq_camera(s, *cam);
+  t->any_camera = true;
+  return VIO_OK;
+}
+
+int vio_pnp_tracker_get_camera(vio_pnp_tracker_t *t, int32_t seq, VioCamera *out) {
+  if (!t || seq < 0 || seq >= t->n_seq || !out) return VIO_EINVAL;
+  *out = t->seq[seq].cam;
   return VIO_OK;
 }
 
@@ -246,7 +277,14 @@ int vio_pnp_tracker_process_images(vio_pnp_tracker_t *t, const VioPnpFeature *fe
       int rc = vio_pnp_create(&t->cfg, t->n_seq, &t->solver);
       if (rc != VIO_OK) return rc;
     }
-    int rc = vio_pnp_solve_windows(t->solver, t->windows.data(), n, nullptr);
+    int rc;
+    if (t->any_camera) {
+      std::vector<double> si(n);
+      for (int k = 0; k < n; k++) si[k] = t->seq[t->solving[k]].cam.fx / 1.5;
+      rc = vio_pnp_solve_windows_cam ? vio_pnp_solve_windows_cam(t->solver, t->windows.data(), n, si.data(), nullptr) : VIO_ENODEV;
+    } else {
+      rc = vio_pnp_solve_windows(t->solver, t->windows.data(), n, nullptr);
+    }
     if (rc != VIO_OK) return rc;
     for (int k = 0; k < n; k++) {
       Seq &s = t->seq[t->solving[k]];

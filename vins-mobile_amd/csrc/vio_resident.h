@@ -53,6 +53,15 @@ int vio_backend_resident_fetch(vio_backend_t *be, int32_t slot, VioFeatureInfo *
 int vio_backend_resident_keyframe(vio_backend_t *be, int32_t n, const int32_t *slots, const int32_t *rows, const double *const *Ps,
                                   const double *const *Rs, const double intr[4], int32_t stride, int32_t *ids, float *px, float *norm,
                                   double *cloud, int32_t *count);
+// The same with a camera per slot of the call: intr + k * intr_stride is slot k's fx fy cx cy (intr_stride 4; 0: one for all,
+// which is what vio_backend_resident_keyframe calls this with).
+int vio_backend_resident_keyframe_cam(vio_backend_t *be, int32_t n, const int32_t *slots, const int32_t *rows, const double *const *Ps,
+                                      const double *const *Rs, const double *intr, int32_t intr_stride, int32_t stride, int32_t *ids,
+                                      float *px, float *norm, double *cloud, int32_t *count);
+// The cameras of n slots (distinct), between two frames (VIO_ESTATE otherwise): rec + 20 k = ex_pose 7 | tic 3 | ric 9 | sqrt_info
+// of slot slots[k], in place of what reserve gave every slot. A slot keeps its camera until the next call names it: a sequence
+// with a camera of its own brings it along when it moves into the slot, before the first store kernel reads the record.
+int vio_backend_resident_set_cameras(vio_backend_t *be, int32_t n, const int32_t *slots, const double *rec);
 int vio_backend_resident_begin(vio_backend_t *be);
 // prior: the header of the slot's prior (n, blocks) or null; its data is in the slot of the prior store.
 // loop_frame >= 0: the window frame a relocalization frame is matched to, with the matched landmark ids (ascending, at

@@ -23,8 +23,9 @@ struct StoreDev {
   const VioObs *obs_in;            // the frames' observations, packed; slot s starts at obs_off[s]
   const int *obs_off;              // [n_slots]
   const double *Ps, *Rs;           // [n_slots][P][3], [n_slots][P][9]: the window states triangulate reads
-  const double *tic, *ric;         // camera -> body
-  double *preint;                  // [n_slots][W][kPreintDoubles] the pre-integration blocks of the window, kept across frames
+  const double *tic, *ric;         // camera -> body: slot s reads tic + s * cam_stride, ric + s * cam_stride
+  int cam_stride;                  // doubles between the records of two slots; 0: one record shared by every slot
+  double *preint;                 // [n_slots][W][kPreintDoubles] the pre-integration blocks of the window, kept across frames
   const int *pre_idx;              // [n_pre] slot * W + interval of every block that arrives with this frame
   const double *pre_blk;           // [n_pre][kPreintDoubles]
   int n_pre;
@@ -48,6 +49,7 @@ struct StoreKeyframe {
   const int *jobs;       // [n_jobs]
   const double *states;  // [n_jobs][12 P]: Ps [P][3] | Rs [P][9]
   double fx, fy, cx, cy;
+  const double *intr;    // [n_jobs][4] fx fy cx cy of every job's camera; null: the four above for all jobs
   int cap;
   int *ids, *count;      // [n_jobs][cap], [n_jobs]
   float *px, *norm;      // [n_jobs][cap][2]

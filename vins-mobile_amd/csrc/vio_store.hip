@@ -58,8 +58,9 @@ __global__ __launch_bounds__(st::kThreads) void store_ingest_kernel(StoreDev S) 
   if (slot == 0) l.prof = S.prof;
   int *ctl = S.ctl + (size_t)slot * st::C_COUNT;
   const int P = S.d.W + 1;
+  const st::SlotCamera cam = st::slot_camera(S.tic, S.ric, S.cam_stride, slot);
   st::store_ingest(cx, S.d, bank_of(S, slot, ctl[st::C_BANK]), ctl, l, S.obs_in + S.obs_off[slot], S.n_obs[slot],
-                   S.Ps + (size_t)slot * 3 * P, S.Rs + (size_t)slot * 9 * P, S.tic, S.ric);
+                   S.Ps + (size_t)slot * 3 * P, S.Rs + (size_t)slot * 9 * P, cam.tic, cam.ric);
 }
 
 __global__ __launch_bounds__(st::kThreads) void store_pack_kernel(StoreDev S, BatchPtrs B, int chunk) {
@@ -104,9 +105,10 @@ __global__ __launch_bounds__(st::kThreads) void store_finish_kernel(StoreDev S, 
   int *ctl = S.ctl + (size_t)slot * st::C_COUNT;
   const BatchStrides &s = B.s;
   const int bank = ctl[st::C_BANK];
+  const st::SlotCamera cam = st::slot_camera(S.tic, S.ric, S.cam_stride, slot);
   st::store_finish(cx, S.d, bank_of(S, slot, bank), bank_of(S, slot, 1 - bank), ctl, S.ctld + (size_t)slot * st::kCtlDoubles, l,
                    B.out_feat + (size_t)slot * s.out_feat, B.out_pose + (size_t)slot * s.out_pose, B.out_sb + (size_t)slot * s.out_sb,
-                   S.tic, S.ric);
+                   cam.tic, cam.ric);
   __syncthreads();
   // slideWindow, MARGIN_OLD: the pre-integration of interval i + 1 becomes that of interval i (VINS.cpp:1160-1187); the
   // newest interval arrives with the next frame
@@ -159,7 +161,9 @@ __global__ __launch_bounds__(st::kThreads) void store_keyframe_kernel(StoreDev S
   const double *Ps = K.states + (size_t)j * 12 * P, *Rs = Ps + 3 * P;
   const size_t r = (size_t)j * K.cap;
   const st::KeyOut o{K.ids + r, K.px + 2 * r, K.norm + 2 * r, K.cloud + 3 * r, K.count + j, K.cap};
-  st::store_keyframe(cx, S.d, bank_of(S, slot, ctl[st::C_BANK] & 1), ctl, (ldsi)part, Ps, Rs, S.tic, S.ric, K.fx, K.fy, K.cx, K.cy, o);
+  const st::SlotCamera cam = st::slot_camera(S.tic, S.ric, S.cam_stride, slot);
+  const st::Intrinsics in = st::job_intrinsics(K.intr, j, K.fx, K.fy, K.cx, K.cy);  // the job's own camera (uniform)
+  st::store_keyframe(cx, S.d, bank_of(S, slot, ctl[st::C_BANK] & 1), ctl, (ldsi)part, Ps, Rs, cam.tic, cam.ric, in.fx, in.fy, in.cx, in.cy, o);
 }
 
 }  // namespace

@@ -110,6 +110,7 @@ __global__ __launch_bounds__(NT, 2) void vio_window_kernel(BatchPtrs B_, MargPtr
     WinView f = static_view<WS>(make_view(B, bb));
     f.F = v.F, f.M = v.M, f.marg_flag = v.marg_flag, f.prior_n = v.prior_n, f.prior_nb = v.prior_nb, f.npairs = v.npairs;
     f.nslots = v.nslots, f.nrev = v.nrev, f.use_origin = v.use_origin, f.loop_frame = v.loop_frame;
+    f.s_info = v.s_info;  // (the same for the window's sqrt_info, a header double: every phase with projection factors reads it)
     if (WS == 0) f.W = v.W, f.P = v.P, f.has_loop = v.has_loop, f.np = v.np, f.nblk = v.nblk, f.npose6 = v.npose6, f.n6 = v.n6, f.nrows = v.nrows, f.nT = v.nT;
     return f;
   };

@@ -64,6 +64,15 @@ class Estimator:
     def clear(self, seq=0):
         self._check(self.lib.vio_estimator_clear(self._h, seq), "clear")
 
+    def set_camera(self, cam, seq=0):
+        """The sequence's own camera (abi.VioCamera), while it holds no frame (vio_estimator_set_camera). -> rc."""
+        return self.lib.vio_estimator_set_camera(self._h, seq, C.byref(cam))
+
+    def get_camera(self, seq=0):
+        out = abi.VioCamera()
+        self._check(self.lib.vio_estimator_get_camera(self._h, seq, C.byref(out)), "get_camera")
+        return out
+
     def process_imu(self, dt, acc, gyr, seq=0):
         acc, gyr = _d(acc), _d(gyr)
         self._check(self.lib.vio_estimator_process_imu(self._h, seq, float(dt), _p(acc), _p(gyr)), "process_imu")

@@ -175,6 +175,18 @@ class FeatureTracker:
             rc = self.lib.vio_frontend_reset(self._h, len(seqs), seqs.ctypes.data_as(_ip))
         self._check(rc, "reset")
 
+    def set_cameras(self, seqs, cams):
+        """vio_frontend_set_cameras: sequence seqs[i] publishes with the intrinsics of cams[i] (abi.VioCamera) from its next
+        published frame on. -> rc."""
+        seqs = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        arr = (abi.VioCamera * max(len(cams), 1))(*cams)
+        return self.lib.vio_frontend_set_cameras(self._h, len(seqs), seqs.ctypes.data_as(_ip), arr)
+
+    def get_camera(self, seq=0):
+        out = abi.VioCamera()
+        self._check(self.lib.vio_frontend_get_camera(self._h, seq, C.byref(out)), "get_camera")
+        return out
+
     def in_step(self):
         """True while every sequence is in the same phase, i.e. while the lock-step calls (read_images, submit, step) are allowed."""
         v = C.c_int32()

@@ -409,6 +409,8 @@ def bind_loop_detector(lib):
     lib.vio_loop_detector_keyframes.argtypes = [vp, vp, C.POINTER(abi.VioConfig), C.c_int32, C.c_int32, _i32p, vp, C.c_int32, _i32p, _fp, _i32p,
                                                 _i32p, C.c_int32, C.c_int32, C.POINTER(VioLoopKeyframe), _u8p, _fp, _i32p, _i32p,
                                                 C.POINTER(C.c_double), _fp, _fp, C.c_int32]
+    lib.vio_loop_detector_set_cameras.argtypes = [vp, C.c_int32, _i32p, C.POINTER(abi.VioCamera)]
+    lib.vio_loop_detector_get_camera.argtypes = [vp, C.c_int32, C.POINTER(abi.VioCamera)]
     return lib
 
 
@@ -469,6 +471,18 @@ class LoopDetector:
             m = r["n_inliers"] if r["status"] == 0 else 0
             res.append((r, cur[q, :m].copy(), old[q, :m].copy()))
         return res
+
+    def set_cameras(self, sessions, cams):
+        """vio_loop_detector_set_cameras: session sessions[i] normalises with the intrinsics of cams[i] (abi.VioCamera) in
+        connect() and keyframes(), in place of the cfg of the call. -> rc."""
+        ses = np.ascontiguousarray(sessions, np.int32).reshape(-1)
+        arr = (abi.VioCamera * max(len(cams), 1))(*cams)
+        return self.lib.vio_loop_detector_set_cameras(self._h, len(ses), ses.ctypes.data_as(_i32p), arr)
+
+    def get_camera(self, session):
+        """-> (rc, abi.VioCamera); rc VIO_ESTATE: the session has none and uses the cfg of every call."""
+        out = abi.VioCamera()
+        return self.lib.vio_loop_detector_get_camera(self._h, session, C.byref(out)), out
 
     def connect(self, cfg, sessions, cur_entries, old_entries, n_window, ids=None, min_loop_num=22, stride=None, out=None):
         """findConnectionWithOldFrame for one (current, old) pair of entries per session, read from the detector's slabs.

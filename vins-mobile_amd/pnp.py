@@ -81,6 +81,17 @@ class PnpSolver:
             raise RuntimeError("vio_pnp_solve_windows failed: %d" % rc)
         return [stats_dict(s) for s in st]
 
+    def solve_cam(self, windows, sqrt_info=None):
+        """solve() for windows of different cameras: sqrt_info[b] = fx / 1.5 of window b's camera, None = cfg.fx / 1.5 for
+        all (vio_pnp_solve_windows_cam). -> (rc, stats dicts)."""
+        n = len(windows)
+        arr, st = (abi.VioPnpWindow * n)(), (abi.VioSolveStats * n)()
+        for a, w in zip(arr, windows):
+            w.fill_struct(a)
+        si = None if sqrt_info is None else np.ascontiguousarray(sqrt_info, np.float64)
+        rc = self.lib.vio_pnp_solve_windows_cam(self._h, arr, n, None if si is None else si.ctypes.data_as(_dp), st)
+        return rc, [stats_dict(s) for s in st]
+
     def kernel_ms(self):
         ms, k = C.c_double(), C.c_int32()
         self.lib.vio_pnp_kernel_ms(self._h, C.byref(ms), C.byref(k))
@@ -108,6 +119,18 @@ class PnpTracker:
     def _check(self, rc, what):
         if rc != 0:
             raise RuntimeError("vio_pnp_tracker_%s failed: %d" % (what, rc))
+
+    def set_camera(self, cam, seq=0):
+        """The sequence's own camera (abi.VioCamera), on a cleared sequence (vio_pnp_tracker_set_camera). -> rc."""
+        return self.lib.vio_pnp_tracker_set_camera(self._h, seq, C.byref(cam))
+
+    def get_camera(self, seq=0):
+        out = abi.VioCamera()
+        self._check(self.lib.vio_pnp_tracker_get_camera(self._h, seq, C.byref(out)), "get_camera")
+        return out
+
+    def clear(self, seq=0):
+        self._check(self.lib.vio_pnp_tracker_clear(self._h, seq), "clear")
 
     def set_init(self, header, Ba, Bg, P, R, V, seq=0):
         r = abi.VioVinsResult()
