@@ -91,8 +91,10 @@ void vio_config_default(VioConfig *cfg);
  * a context is created with, are what a sequence uses until a camera is set for
  * it: a context whose sequences set none computes exactly what it always did.
  * Pinhole only. Lens distortion is NOT modelled, as in the reference, whose
- * rejectWithF works on raw pixels (feature_tracker.cpp:95,198); a distorted
- * lens has to be undistorted by the caller ahead of the front end.           */
+ * rejectWithF works on raw pixels (feature_tracker.cpp:95,198); the frames of
+ * a distorted lens are rectified to a pinhole by the image pre-step, on the
+ * device (VioLens, vio_preprocess_set_lenses), and the intrinsics given here
+ * are then those of the rectified image (VioLens.rect_*).                     */
 typedef struct VioCamera {
   double fx, fy, cx, cy;   /* FOCUS_LENGTH_X/Y, PX, PY  global_param.cpp:24-131 */
   double tic[3], ric[9];   /* camera -> body, ric row-major (TIC_*, RIC_*)      */
@@ -458,6 +460,47 @@ int vio_preprocess_run_resident(vio_preprocess_t *p, const void *d_pixels, int32
                                 int32_t stride, void *d_equalized, void *stream);
 int vio_preprocess_sync(vio_preprocess_t *p);
 int vio_preprocess_kernel_ms(vio_preprocess_t *p, double *ms_avg, int32_t *launches);
+
+/* Lens rectification inside the pre-step. A frame slot that holds a lens is
+ * rectified to the pinhole rect_* while it is converted to gray: gray_out of
+ * vio_preprocess_run is then the RECTIFIED gray, CLAHE runs on it, and
+ * everything downstream sees a pinhole image. Per output pixel (x, y), in IEEE
+ * doubles, every operation rounded on its own (no fused multiply-add):
+ *   xn = (x - rect_cx) / rect_fx,  yn = (y - rect_cy) / rect_fy,  r2 = xn*xn + yn*yn
+ *   radial = 1 + r2*(k1 + r2*(k2 + r2*k3))
+ *   xd = (xn*radial + (2*p1)*xn*yn) + p2*(r2 + (2*xn)*xn)
+ *   yd = (yn*radial + p1*(r2 + (2*yn)*yn)) + ((2*p2)*xn)*yn
+ *   u = fx*xd + cx, v = fy*yd + cy, clamped to the raw image (replicate border)
+ *   U = rint(32 u), V = rint(32 v)   (ties to even: 1/32-pixel fixed point)
+ *   out = integer bilinear blend of the four raw grays around (U, V) / 32,
+ *         (top*(32-ay) + bot*ay + 512) >> 10; RGBA is converted at each neighbour.
+ * The rectified image has the size of the raw one.                            */
+typedef struct VioLens {            /* Brown-Conrady, OpenCV's coefficient order */
+  double fx, fy, cx, cy;            /* intrinsics of the RAW image                */
+  double k1, k2, p1, p2, k3;
+  double rect_fx, rect_fy, rect_cx, rect_cy;  /* pinhole of the rectified image: what VioCamera / cfg take */
+} VioLens;
+/* slot = position of a frame inside a vio_preprocess_run / _run_resident call,
+ * 0 .. max_frames-1 (the sequence, in the throughput deployments). lens[i]
+ * goes to slot[i]; lens = NULL clears the named slots. A lens stays until it
+ * is replaced or cleared. The call waits for the context's last launch and
+ * returns with the lenses in device memory: a later run on any stream sees
+ * them. VIO_EINVAL, and nothing changed, for a slot out of range or named
+ * twice, a non-finite field, or fx, fy, rect_fx, rect_fy <= 0. Slots without a
+ * lens, and a context that never sets one, compute what they always did.      */
+int vio_preprocess_set_lenses(vio_preprocess_t *p, int32_t n, const int32_t *slot /* [n] */, const VioLens *lens /* [n] or NULL: clear */);
+int vio_preprocess_get_lens(vio_preprocess_t *p, int32_t slot, VioLens *out, int32_t *is_set);
+/* The forward model on the host: normalized undistorted points -> raw pixels
+ * (not clamped), and its inverse by fixed-point iteration x <- x + (x_d - D(x))
+ * from x_d = ((u-cx)/fx, (v-cy)/fy), until a step is below 1e-12 in both
+ * coordinates (converged[i] = 1) or 50 rounds have passed (converged[i] = 0). */
+int vio_lens_distort_points(const VioLens *lens, const double *xn /* [n][2] normalized */, int32_t n, double *uv /* [n][2] raw px */);
+int vio_lens_undistort_points(const VioLens *lens, const double *uv /* [n][2] */, int32_t n, double *xn /* [n][2] */,
+                              uint8_t *converged /* [n] or NULL */);
+/* Output pixels of a rows x cols frame whose source lies outside the raw image
+ * (u outside [0, cols-1] or v outside [0, rows-1]; the kernel clamps these):
+ * what a caller looks at when choosing rect_*.                                */
+int vio_lens_coverage(const VioLens *lens, int32_t rows, int32_t cols, int64_t *n_outside);
 
 /* Introspection of tracker state (cur_pts / ids / track_cnt,
  * feature_tracker.hpp:72-75) for parity tests.                               */

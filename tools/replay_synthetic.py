@@ -97,9 +97,11 @@ class SyntheticWorld:
 
 class ImageWorld(SyntheticWorld):
     """The same trajectory and IMU, but the camera films a textured plane: frames are rendered by intersecting every
-    pixel's ray with the plane z = z0, and the observations come from the KLT front-end run on those frames."""
+    pixel's ray with the plane z = z0, and the observations come from the KLT front-end run on those frames.
+    lens (abi.VioLens whose rect_* are cfg's intrinsics): the camera films through that lens (raw pixel ->
+    vio_lens_undistort_points -> ray) and every frame is rectified on the device by the image pre-step before it is returned."""
 
-    def __init__(self, cfg, seed, z0=-6.0, px_per_m=77.0, **kw):
+    def __init__(self, cfg, seed, z0=-6.0, px_per_m=77.0, lens=None, **kw):
         super().__init__(cfg, seed, n_landmarks=1, **kw)
         self.z0, self.s = z0, px_per_m
         self.tex_half = 9.0  # metres covered by the texture around the origin
@@ -108,8 +110,21 @@ class ImageWorld(SyntheticWorld):
         rows, cols = cfg.image_rows, cfg.image_cols
         v, u = np.mgrid[0:rows, 0:cols].astype(np.float64)
         self.rays = np.stack([(u - cfg.cx) / cfg.fx, (v - cfg.cy) / cfg.fy, np.ones_like(u)], axis=-1)
+        self.pre = None
+        if lens is not None:
+            assert (lens.rect_fx, lens.rect_fy, lens.rect_cx, lens.rect_cy) == (cfg.fx, cfg.fy, cfg.cx, cfg.cy)
+            xn, ok = abi.lens_undistort_points(lens, np.stack([u.ravel(), v.ravel()], axis=1))
+            assert ok.all(), "the lens model does not invert over the raw image"
+            self.rays = np.concatenate([xn.reshape(rows, cols, 2), np.ones((rows, cols, 1))], axis=-1)
+            self.pre = pkg.frontend.Preprocessor(rows, cols, max_frames=1)
+            assert self.pre.set_lenses([0], [lens]) == abi.VIO_OK
+            self.clamped = abi.lens_coverage(lens, rows, cols)
 
     def render(self, k):
+        raw = self.render_raw(k)
+        return raw if self.pre is None else self.pre.run(raw[None])[0][0]   # gray_out: the rectified gray, ahead of CLAHE
+
+    def render_raw(self, k):
         P, R, _ = self.truth(k)
         Rc, Pc = R @ self.ric, P + R @ self.tic
         d = self.rays @ Rc.T
@@ -125,11 +140,11 @@ class ClosedLoop:
     With `tracker` (a frontend.FeatureTracker for one sequence) the observations are what the KLT front-end publishes
     on frames rendered by an ImageWorld; without, they are noisy projections of a landmark cloud."""
 
-    def __init__(self, cfg, solve, preintegrate, seed=1, init_noise=0.0, tracker=None):
+    def __init__(self, cfg, solve, preintegrate, seed=1, init_noise=0.0, tracker=None, world=None):
         self.cfg, self.solve, self.pre = cfg, solve, preintegrate
         self.W = cfg.window_size
         self.tracker = tracker
-        self.world = ImageWorld(cfg, seed) if tracker is not None else SyntheticWorld(cfg, seed)
+        self.world = world or (ImageWorld(cfg, seed) if tracker is not None else SyntheticWorld(cfg, seed))
         self.fm = window.FeatureManager(self.W)
         self.Ps, self.Rs, self.Vs, self.Bas, self.Bgs = [], [], [], [], []
         self.pre_arr, self.pre_samples = [], []   # per interval (i-1, i): packed pre-integration and its raw samples
@@ -326,16 +341,26 @@ def main():
     ap.add_argument("--frames", type=int, default=150)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--images", action="store_true", help="render frames of a textured plane and run the KLT front-end on them")
+    ap.add_argument("--lens", default=None, metavar="k1,k2,p1,p2,k3",
+                    help="with --images: film through this Brown-Conrady lens (cfg's intrinsics) and rectify on the device")
     args = ap.parse_args()
     import torch  # noqa: F401  (HIP runtime first)
     cfg = abi.default_config()
+    world = None
+    if args.lens:
+        assert args.images, "--lens needs --images"
+        k = [float(x) for x in args.lens.split(",")]
+        assert len(k) == 5, "--lens k1,k2,p1,p2,k3"
+        world = ImageWorld(cfg, args.seed, lens=abi.make_lens(cfg.fx, cfg.fy, cfg.cx, cfg.cy, k))
+        print("lens %s: %d of %d rectified pixels look outside the raw frame (clamped)"
+              % (k, world.clamped, cfg.image_rows * cfg.image_cols))
     solver = pkg.backend.WindowSolver(cfg, max_batch=1)
     pre = lambda *a: pkg.backend.preintegrate(cfg, *a)
     tracker = pkg.frontend.FeatureTracker(cfg, n_seq=1) if args.images else None
     if args.python_loop:
-        loop = ClosedLoop(cfg, lambda w: solver.solve([w])[0], pre, seed=args.seed, init_noise=1.0, tracker=tracker)
+        loop = ClosedLoop(cfg, lambda w: solver.solve([w])[0], pre, seed=args.seed, init_noise=1.0, tracker=tracker, world=world)
     else:
-        loop = EstimatorLoop(cfg, seed=args.seed, init_noise=1.0, tracker=tracker, self_init=args.self_init)
+        loop = EstimatorLoop(cfg, seed=args.seed, init_noise=1.0, tracker=tracker, self_init=args.self_init, world=world)
     for _ in range(args.frames):
         loop.step()
     e = loop.errors()

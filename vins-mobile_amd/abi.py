@@ -102,6 +102,47 @@ def camera_fields(c):
     return c.fx, c.fy, c.cx, c.cy, np.array(c.tic[:]), np.array(c.ric[:]).reshape(3, 3)
 
 
+class VioLens(C.Structure):
+    """A Brown-Conrady lens of the image pre-step (vio_amd.h): raw intrinsics, k1 k2 p1 p2 k3, the rectified pinhole."""
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3",
+                                          "rect_fx", "rect_fy", "rect_cx", "rect_cy")]
+
+
+def make_lens(fx, fy, cx, cy, k=(0, 0, 0, 0, 0), rect=None):
+    """k = (k1, k2, p1, p2, k3); rect = (rect_fx, rect_fy, rect_cx, rect_cy), None: the raw intrinsics."""
+    r = (fx, fy, cx, cy) if rect is None else rect
+    return VioLens(fx, fy, cx, cy, *[float(x) for x in k], *[float(x) for x in r])
+
+
+def lens_distort_points(lens, xn):
+    """vio_lens_distort_points: normalized undistorted points [n, 2] -> raw pixels [n, 2] (not clamped)."""
+    xn = np.ascontiguousarray(xn, np.float64).reshape(-1, 2)
+    uv = np.zeros_like(xn)
+    rc = load_product().vio_lens_distort_points(C.byref(lens), _ptr(xn), len(xn), _ptr(uv))
+    if rc != VIO_OK:
+        raise RuntimeError("vio_lens_distort_points rc=%d" % rc)
+    return uv
+
+
+def lens_undistort_points(lens, uv):
+    """vio_lens_undistort_points: raw pixels [n, 2] -> (normalized points [n, 2], converged [n] uint8)."""
+    uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
+    xn, ok = np.zeros_like(uv), np.zeros(len(uv), np.uint8)
+    rc = load_product().vio_lens_undistort_points(C.byref(lens), _ptr(uv), len(uv), _ptr(xn), ok.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != VIO_OK:
+        raise RuntimeError("vio_lens_undistort_points rc=%d" % rc)
+    return xn, ok
+
+
+def lens_coverage(lens, rows, cols):
+    """vio_lens_coverage: the output pixels whose source lies outside the raw rows x cols image."""
+    n = C.c_int64()
+    rc = load_product().vio_lens_coverage(C.byref(lens), rows, cols, C.byref(n))
+    if rc != VIO_OK:
+        raise RuntimeError("vio_lens_coverage rc=%d" % rc)
+    return n.value
+
+
 class VioPreintegration(C.Structure):
     _fields_ = [
         ("sum_dt", C.c_double), ("delta_p", C.c_double * 3), ("delta_q", C.c_double * 4),
@@ -578,6 +619,12 @@ def load_product():
     lib.vio_preprocess_run_resident.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     lib.vio_preprocess_sync.argtypes = [vp]
     lib.vio_preprocess_kernel_ms.argtypes = [vp, _dp, _ip]
+    lensp = C.POINTER(VioLens)
+    lib.vio_preprocess_set_lenses.argtypes = [vp, C.c_int32, _ip, lensp]
+    lib.vio_preprocess_get_lens.argtypes = [vp, C.c_int32, lensp, _ip]
+    lib.vio_lens_distort_points.argtypes = [lensp, _dp, C.c_int32, _dp]
+    lib.vio_lens_undistort_points.argtypes = [lensp, _dp, C.c_int32, _dp, u8p]
+    lib.vio_lens_coverage.argtypes = [lensp, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     imup, kfp, i64 = C.POINTER(VioImuMsg), C.POINTER(VioKeyframeData), C.c_int64
     lib.vio_replay_read_imu.argtypes = [C.c_char_p, imup, C.c_int32, _ip]
     lib.vio_replay_write_imu.argtypes = [C.c_char_p, imup, C.c_int32]

@@ -19,6 +19,12 @@
 //   clahe_apply_kernel  one workgroup per band of 8 rows: the <= 3 tile rows of LUTs it needs staged in LDS as fp32
 //                       (aligned dword reads), 4 pixels per lane (one dword load, one dword store)
 // Algorithmic bytes per RGBA frame: 4*R*C (read) + R*C (gray out) + R*C (gray in) + R*C (equalized out) = 7*R*C.
+//
+// Lens rectification (VioLens, vio_preprocess_set_lenses) is fused into the gray pass: for a frame slot that holds a lens, the
+// pixel clahe_lut_kernel writes and counts is the rectified one (pre_rectify.h: ~70 fp64 instructions and four raw reads that
+// mostly hit the lines the neighbouring lanes read), so there is no map and no extra full-frame buffer. Lens or no lens is a
+// per-frame, wave-uniform branch outside the pixel loop of the <CH, true> instantiation; a context that holds no lens at
+// all launches <CH, false>, which is the kernel as it was before lenses existed.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -27,6 +33,9 @@
 
 #include <algorithm>
 
+#include <vector>
+
+#include "pre_rectify.h"
 #include "vio_amd.h"
 #include "vio_device.h"
 #include "vio_pool.h"
@@ -43,6 +52,11 @@ struct PreGeom {
   float lut_scale;
 };
 
+struct LensSlot {  // one per frame slot, in device memory
+  VioLens lens;
+  int32_t is_set, pad;
+};
+
 __device__ __forceinline__ int reflect101(int i, int n) { return i < n ? i : 2 * n - 2 - i; }
 
 __device__ __forceinline__ uint32_t rgba_gray(uint32_t px) {  // little endian: R in the low byte
@@ -50,10 +64,11 @@ __device__ __forceinline__ uint32_t rgba_gray(uint32_t px) {  // little endian: 
   return (r * 4899u + g * 9617u + b * 1868u + 8192u) >> 14;
 }
 
-template <int CH>
+template <int CH, bool LENS>
 __global__ __launch_bounds__(kThreads) void clahe_lut_kernel(const uint8_t *__restrict__ src, size_t frame_stride,
                                                               int row_stride, uint8_t *__restrict__ gray,
-                                                              uint8_t *__restrict__ lut, PreGeom G) {
+                                                              uint8_t *__restrict__ lut, PreGeom G,
+                                                              const LensSlot *__restrict__ lenses) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t scan[256];
   __shared__ uint32_t wsum[kThreads / 64];
@@ -64,17 +79,29 @@ __global__ __launch_bounds__(kThreads) void clahe_lut_kernel(const uint8_t *__re
   const uint8_t *img = src + (size_t)frame * frame_stride;
   uint8_t *gout = gray + (size_t)frame * G.rows * G.cols;
   const int area = G.tw * G.th;
-  for (int p = tid; p < area; p += kThreads) {
-    const int yy = p / G.tw, xx = p - yy * G.tw;
-    const int ey = ty * G.th + yy, ex = tx * G.tw + xx;
-    const int sy = reflect101(ey, G.rows), sx = reflect101(ex, G.cols);
-    uint32_t v;
-    if (CH == 4)
-      v = rgba_gray(*reinterpret_cast<const uint32_t *>(img + (size_t)sy * row_stride + 4 * sx));
-    else
-      v = img[(size_t)sy * row_stride + sx];
-    if (ey < G.rows && ex < G.cols) gout[(size_t)ey * G.cols + ex] = (uint8_t)v;  // every image pixel is in one tile
-    atomicAdd(&hist[v], 1u);
+  if (LENS && lenses[frame].is_set) {  // the frame's record: the same for every lane, read through the scalar cache
+    const VioLens L = lenses[frame].lens;
+    for (int p = tid; p < area; p += kThreads) {
+      const int yy = p / G.tw, xx = p - yy * G.tw;
+      const int ey = ty * G.th + yy, ex = tx * G.tw + xx;
+      const int sy = reflect101(ey, G.rows), sx = reflect101(ex, G.cols);  // the extension is one of OUTPUT coordinates
+      const uint32_t v = pre::rectify_px<CH>(img, (size_t)row_stride, G.rows, G.cols, L, sx, sy);
+      if (ey < G.rows && ex < G.cols) gout[(size_t)ey * G.cols + ex] = (uint8_t)v;
+      atomicAdd(&hist[v], 1u);
+    }
+  } else {
+    for (int p = tid; p < area; p += kThreads) {
+      const int yy = p / G.tw, xx = p - yy * G.tw;
+      const int ey = ty * G.th + yy, ex = tx * G.tw + xx;
+      const int sy = reflect101(ey, G.rows), sx = reflect101(ex, G.cols);
+      uint32_t v;
+      if (CH == 4)
+        v = rgba_gray(*reinterpret_cast<const uint32_t *>(img + (size_t)sy * row_stride + 4 * sx));
+      else
+        v = img[(size_t)sy * row_stride + sx];
+      if (ey < G.rows && ex < G.cols) gout[(size_t)ey * G.cols + ex] = (uint8_t)v;  // every image pixel is in one tile
+      atomicAdd(&hist[v], 1u);
+    }
   }
   __syncthreads();
   uint32_t h = hist[tid];
@@ -187,6 +214,9 @@ struct vio_preprocess {
   double clip_limit = 3.0;  // clahe->setClipLimit(3) ViewController.mm:436
   int tiles_x = 8, tiles_y = 8;  // cv::createCLAHE() default tileGridSize
   vio::DevBuf<uint8_t> d_src, d_gray, d_lut, d_out;
+  vio::DevBuf<LensSlot> d_lens;   // [max_frames]: written whole by every set_lenses, read by launches while n_lens > 0
+  std::vector<LensSlot> h_lens;   // the table as last set (zero: no lens)
+  int n_lens = 0;                 // slots that hold a lens: 0 launches the kernel without the lens branch
   vio::PinnedBuf<uint8_t> h_in, h_out;  // page-locked staging of the host-buffer entry point
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -225,10 +255,10 @@ int launch(vio_preprocess *p, const uint8_t *d_src, int channels, int n_frames, 
   const PreGeom G = geometry(p->rows, p->cols, p->tiles_x, p->tiles_y, p->clip_limit);
   const dim3 g1(G.tiles_x * G.tiles_y, n_frames), g2((G.rows + kBandRows - 1) / kBandRows, n_frames);
   (void)hipEventRecord(p->ev0, st);
-  if (channels == 4)
-    hipLaunchKernelGGL(clahe_lut_kernel<4>, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray.p, p->d_lut.p, G);
-  else
-    hipLaunchKernelGGL(clahe_lut_kernel<1>, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray.p, p->d_lut.p, G);
+  const LensSlot *ls = p->d_lens.p;
+  auto *lut_kernel = channels == 4 ? (p->n_lens ? clahe_lut_kernel<4, true> : clahe_lut_kernel<4, false>)
+                                   : (p->n_lens ? clahe_lut_kernel<1, true> : clahe_lut_kernel<1, false>);
+  hipLaunchKernelGGL(lut_kernel, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray.p, p->d_lut.p, G, ls);
   const bool vec4 = G.cols % 4 == 0 && out_row_stride % 4 == 0 && out_frame_stride % 4 == 0 &&
                     (reinterpret_cast<uintptr_t>(d_out) & 3) == 0;
   if (vec4)
@@ -260,8 +290,15 @@ int vio_preprocess_create(int32_t max_frames, int32_t rows, int32_t cols, vio_pr
   const size_t px = (size_t)rows * cols;
   if (p->d_src.ensure(px * 4 * max_frames) != VIO_OK || p->d_gray.ensure(px * max_frames) != VIO_OK ||
       p->d_out.ensure(px * max_frames) != VIO_OK || p->d_lut.ensure((size_t)kMaxTiles * kMaxTiles * 256 * max_frames) != VIO_OK ||
+      p->d_lens.ensure(max_frames) != VIO_OK ||
       hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess ||
       hipEventCreate(&p->ev1) != hipSuccess) {
+    delete p;
+    return VIO_ENOMEM;
+  }
+  try {
+    p->h_lens.assign((size_t)max_frames, LensSlot{});
+  } catch (const std::bad_alloc &) {
     delete p;
     return VIO_ENOMEM;
   }
@@ -285,6 +322,84 @@ int vio_preprocess_set_clahe(vio_preprocess_t *p, double clip_limit, int32_t til
   // a band of kBandRows rows must not span more than 3 tile rows; the reflected extension must stay inside the image
   if (G.th < kBandRows || G.tw < 1 || G.th * tiles_y - p->rows >= p->rows || G.tw * tiles_x - p->cols >= p->cols) return VIO_EINVAL;
   p->clip_limit = clip_limit, p->tiles_x = tiles_x, p->tiles_y = tiles_y;
+  return VIO_OK;
+}
+
+int vio_preprocess_set_lenses(vio_preprocess_t *p, int32_t n, const int32_t *slot, const VioLens *lens) {
+  if (!p || n < 0 || (n > 0 && !slot) || n > p->max_frames) return VIO_EINVAL;  // more than max_frames names a slot twice
+  std::vector<LensSlot> next;
+  std::vector<uint8_t> named;
+  try {
+    next = p->h_lens;
+    named.assign((size_t)p->max_frames, 0);
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+  for (int i = 0; i < n; i++) {
+    const int s = slot[i];
+    if (s < 0 || s >= p->max_frames || named[s]) return VIO_EINVAL;
+    if (lens && !pre::lens_valid(lens[i])) return VIO_EINVAL;
+    named[s] = 1;
+    next[s] = LensSlot{};
+    if (lens) next[s].lens = lens[i], next[s].is_set = 1;
+  }
+  if (n == 0) return VIO_OK;
+  VIO_ON_DEVICE_OF(p);
+  // launches of this context that are still in flight read the table: let the last one finish, then replace it, and
+  // return only when the new table is in device memory (a later launch on ANY stream then sees it)
+  if (hipEventSynchronize(p->ev1) != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpyAsync(p->d_lens.p, next.data(), sizeof(LensSlot) * next.size(), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
+      hipStreamSynchronize(p->stream) != hipSuccess)
+    return VIO_ENODEV;
+  p->h_lens.swap(next);
+  p->n_lens = 0;
+  for (const LensSlot &s : p->h_lens) p->n_lens += s.is_set;
+  return VIO_OK;
+}
+
+int vio_preprocess_get_lens(vio_preprocess_t *p, int32_t slot, VioLens *out, int32_t *is_set) {
+  if (!p || !out || !is_set || slot < 0 || slot >= p->max_frames) return VIO_EINVAL;
+  *out = p->h_lens[slot].lens, *is_set = p->h_lens[slot].is_set;
+  return VIO_OK;
+}
+
+int vio_lens_distort_points(const VioLens *lens, const double *xn, int32_t n, double *uv) {
+  if (!lens || n < 0 || (n > 0 && (!xn || !uv))) return VIO_EINVAL;
+  for (int i = 0; i < n; i++) pre::lens_project(*lens, xn[2 * i], xn[2 * i + 1], &uv[2 * i], &uv[2 * i + 1]);
+  return VIO_OK;
+}
+
+int vio_lens_undistort_points(const VioLens *lens, const double *uv, int32_t n, double *xn, uint8_t *converged) {
+  if (!lens || n < 0 || (n > 0 && (!uv || !xn)) || !(lens->fx > 0) || !(lens->fy > 0)) return VIO_EINVAL;
+  VioLens unit = *lens;  // the forward model in normalized coordinates: x_d = D(x)
+  unit.fx = unit.fy = 1.0, unit.cx = unit.cy = 0.0;
+  for (int i = 0; i < n; i++) {
+    const double xd = (uv[2 * i] - lens->cx) / lens->fx, yd = (uv[2 * i + 1] - lens->cy) / lens->fy;
+    double x = xd, y = yd;
+    uint8_t done = 0;
+    for (int round = 0; round < 50 && !done; round++) {  // x <- x + (x_d - D(x)): contracts while |1 - D'| < 1
+      double dx, dy;
+      pre::lens_project(unit, x, y, &dx, &dy);
+      const double sx = xd - dx, sy = yd - dy;
+      x += sx, y += sy;
+      done = fabs(sx) < 1e-12 && fabs(sy) < 1e-12;
+    }
+    xn[2 * i] = x, xn[2 * i + 1] = y;
+    if (converged) converged[i] = done;
+  }
+  return VIO_OK;
+}
+
+int vio_lens_coverage(const VioLens *lens, int32_t rows, int32_t cols, int64_t *n_outside) {
+  if (!lens || !n_outside || rows < 1 || cols < 1 || !pre::lens_valid(*lens)) return VIO_EINVAL;
+  int64_t n = 0;
+  for (int y = 0; y < rows; y++)
+    for (int x = 0; x < cols; x++) {
+      double u, v;
+      pre::lens_source(*lens, x, y, &u, &v);
+      n += pre::lens_outside(u, cols) || pre::lens_outside(v, rows);
+    }
+  *n_outside = n;
   return VIO_OK;
 }
 

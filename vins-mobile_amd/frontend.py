@@ -308,8 +308,27 @@ class Preprocessor:
         if rc != 0:
             raise RuntimeError("vio_preprocess_set_clahe failed: %d" % rc)
 
+    def set_lenses(self, slots, lenses=None):
+        """vio_preprocess_set_lenses: lenses[i] (abi.VioLens) rectifies the frame at position slots[i] of every later run;
+        lenses=None clears the named slots. -> the return code (VIO_EINVAL: nothing changed)."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        arr = None
+        if lenses is not None:
+            assert len(lenses) == len(slots)
+            arr = (abi.VioLens * max(len(slots), 1))(*lenses)
+        return self.lib.vio_preprocess_set_lenses(self._h, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int32)), arr)
+
+    def get_lens(self, slot):
+        """-> the slot's abi.VioLens, or None when it holds none."""
+        out, is_set = abi.VioLens(), C.c_int32()
+        rc = self.lib.vio_preprocess_get_lens(self._h, slot, C.byref(out), C.byref(is_set))
+        if rc != 0:
+            raise RuntimeError("vio_preprocess_get_lens failed: %d" % rc)
+        return out if is_set.value else None
+
     def run(self, frames):
-        """frames: [n, rows, cols] gray or [n, rows, cols, 4] RGBA (uint8) -> (gray [n, rows, cols], equalized)."""
+        """frames: [n, rows, cols] gray or [n, rows, cols, 4] RGBA (uint8) -> (gray [n, rows, cols], equalized); for a slot
+        that holds a lens both are of the rectified frame."""
         frames = np.ascontiguousarray(frames, np.uint8)
         ch = 4 if frames.ndim == 4 else 1
         n = frames.shape[0]
