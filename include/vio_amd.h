@@ -502,6 +502,72 @@ int vio_lens_undistort_points(const VioLens *lens, const double *uv /* [n][2] */
  * what a caller looks at when choosing rect_*.                                */
 int vio_lens_coverage(const VioLens *lens, int32_t rows, int32_t cols, int64_t *n_outside);
 
+/* Native-size source frames. A frame slot that holds a VioSource takes its
+ * frame as the camera or the decoder delivers it (size, row stride, pixel
+ * format, range) and the pre-step scales the crop rectangle to the context's
+ * rows x cols while it converts to gray; CLAHE and everything downstream see
+ * rows x cols as always. Exact integer arithmetic, the same bytes on the
+ * device and in csrc/pre_source.h on the host:
+ *   gray of a source pixel: RGBA / BGRA (R*4899 + G*9617 + B*1868 + 8192) >> 14;
+ *     GRAY8 / NV12 the byte Y, with range = 1 min(255, ((max(Y,16) - 16)*255 + 109) / 219)
+ *   no lens in the slot: the exact area average of the crop. gx = gcd(crop_cols, cols),
+ *     cw = crop_cols/gx, ow = cols/gx; source column j of the crop covers [j*ow, (j+1)*ow),
+ *     output column x covers [x*cw, (x+1)*cw), wx(x, j) = the length of their overlap
+ *     (sum over j = cw); rows likewise with ch, oh, wy. S = sum wy*wx*gray, D = cw*ch,
+ *     out = (S + D/2) / D: the nearest value, ties upward. A crop of rows x cols has D = 1.
+ *   a lens in the slot: VioLens.fx .. k3 refer to the whole delivered frame, rect_* to the
+ *     rows x cols output; the crop is not used and source coordinates are clamped to the
+ *     whole frame. s = min(4, max(ceil(src.cols/cols), ceil(src.rows/rows))); output pixel
+ *     (x, y) is the mean of s*s samples at (x + (2i+1-s)/(2s), y + (2j+1-s)/(2s)), i, j = 0..s-1,
+ *     each by the lens arithmetic above (gray / range at each neighbour),
+ *     out = (sum + s*s/2) / (s*s). s = 1 is the rectification above, byte for byte.
+ * The chroma plane of NV12 is never read.                                      */
+#define VIO_PIXEL_GRAY8 1   /* one byte per pixel                                   */
+#define VIO_PIXEL_RGBA8 4   /* R in byte 0 (what channels = 4 means)                */
+#define VIO_PIXEL_BGRA8 5   /* B in byte 0                                          */
+#define VIO_PIXEL_NV12  12  /* plane 0 = luma, rows x stride; the chroma plane is never read */
+typedef struct VioSource {
+  int32_t format, range;            /* range: 0 full, 1 video (16..235); 1 only with GRAY8 / NV12 */
+  int32_t rows, cols, stride;       /* the frame as delivered; stride = bytes per row of plane 0  */
+  int32_t crop_x, crop_y, crop_cols, crop_rows;  /* the part that becomes the output image        */
+} VioSource;
+/* Host only. VIO_EINVAL for: an unknown format; range not 0 / 1, or 1 with RGBA /
+ * BGRA; rows or cols outside 1..16384; stride below the bytes of a row, or no
+ * multiple of 4 for RGBA / BGRA; a crop that is not inside the frame; crop_cols <
+ * cols or crop_rows < rows (no upscaling); crop_cols > 8*cols or crop_rows > 8*rows;
+ * 255*cw*ch >= 2^32 (the sums stay in 32 bits; crop one pixel off to avoid it). */
+int vio_source_check(const VioSource *s, int32_t rows, int32_t cols);
+/* The pinhole of the rows x cols output of a slot without a lens, from the pinhole
+ * in[] = fx fy cx cy of the delivered frame: fx' = fx*cols/crop_cols,
+ * cx' = (cx - crop_x + 0.5)*cols/crop_cols - 0.5, fy' and cy' likewise with rows.
+ * This is what goes into that sequence's VioCamera, or into rect_* of a lens.  */
+int vio_source_camera(const VioSource *s, int32_t rows, int32_t cols, const double in[4], double out[4]);
+/* Slots as for vio_preprocess_set_lenses, and the same contract: src[i] goes to
+ * slot[i], src = NULL clears the named slots, a source stays until it is replaced
+ * or cleared; the call waits for the context's last launch and returns with the
+ * table in device memory. VIO_EINVAL, and nothing changed, for a slot out of range
+ * or named twice or an entry vio_source_check refuses.                           */
+int vio_preprocess_set_sources(vio_preprocess_t *p, int32_t n, const int32_t *slot /* [n] */, const VioSource *src /* [n] or NULL: clear */);
+int vio_preprocess_get_source(vio_preprocess_t *p, int32_t slot, VioSource *out, int32_t *is_set);
+/* Frame i of the call is slot i and lies at pixels[i] (the first byte of its plane
+ * 0), each frame where it is: sizes and formats may differ from slot to slot, with
+ * and without lenses, in one call and one launch of each of the two kernels. Every
+ * slot 0 .. n_frames-1 must hold a source (else VIO_ESTATE, nothing is launched).
+ * Outputs are laid out as those of vio_preprocess_run / _run_resident. The host
+ * form reads the crop's rows only (the whole plane 0 of a lensed slot). The resident
+ * form takes a HOST array of device pointers, which it copies before it returns
+ * (asynchronous like _run_resident; RGBA / BGRA pointers 4-byte aligned, else
+ * VIO_EINVAL). One-byte formats are read in aligned dwords where the stride is a
+ * multiple of 4: up to 3 bytes before the first and after the last pixel a row
+ * needs, inside the aligned dword that pixel lies in, are loaded and not used (no
+ * further: never another page, never the chroma plane's rows).
+ * vio_preprocess_run / _run_resident keep their meaning, frames of
+ * rows x cols with `channels`, whether or not sources are set.                   */
+int vio_preprocess_run_frames(vio_preprocess_t *p, const void *const *pixels /* [n_frames] host */, int32_t n_frames,
+                              uint8_t *gray_out /* may be NULL */, uint8_t *equalized_out);
+int vio_preprocess_run_frames_resident(vio_preprocess_t *p, const void *const *d_pixels /* host array of n_frames device pointers */,
+                                       int32_t n_frames, void *d_equalized, void *stream);
+
 /* Introspection of tracker state (cur_pts / ids / track_cnt,
  * feature_tracker.hpp:72-75) for parity tests.                               */
 int vio_frontend_get_state(vio_frontend_t *fe, int32_t seq, float *cur_pts /* [cap][2] */,

@@ -143,6 +143,35 @@ def lens_coverage(lens, rows, cols):
     return n.value
 
 
+VIO_PIXEL_GRAY8, VIO_PIXEL_RGBA8, VIO_PIXEL_BGRA8, VIO_PIXEL_NV12 = 1, 4, 5, 12
+
+
+class VioSource(C.Structure):
+    """The frame of one slot as delivered to the image pre-step (vio_amd.h): format, range, size, stride of plane 0, crop."""
+    _fields_ = [(k, C.c_int32) for k in ("format", "range", "rows", "cols", "stride", "crop_x", "crop_y", "crop_cols", "crop_rows")]
+
+
+def make_source(fmt, rows, cols, stride=None, crop=None, range=0):
+    """crop = (crop_x, crop_y, crop_cols, crop_rows), None: the whole frame; stride None: packed rows."""
+    bpp = 4 if fmt in (VIO_PIXEL_RGBA8, VIO_PIXEL_BGRA8) else 1
+    x, y, w, h = (0, 0, cols, rows) if crop is None else crop
+    return VioSource(fmt, range, rows, cols, cols * bpp if stride is None else stride, x, y, w, h)
+
+
+def source_check(src, rows, cols):
+    """vio_source_check -> the return code."""
+    return load_product().vio_source_check(C.byref(src), rows, cols)
+
+
+def source_camera(src, rows, cols, fx, fy, cx, cy):
+    """vio_source_camera: the pinhole (fx, fy, cx, cy) of the delivered frame -> that of the rows x cols output."""
+    a, out = (C.c_double * 4)(fx, fy, cx, cy), (C.c_double * 4)()
+    rc = load_product().vio_source_camera(C.byref(src), rows, cols, a, out)
+    if rc != VIO_OK:
+        raise RuntimeError("vio_source_camera rc=%d" % rc)
+    return tuple(out)
+
+
 class VioPreintegration(C.Structure):
     _fields_ = [
         ("sum_dt", C.c_double), ("delta_p", C.c_double * 3), ("delta_q", C.c_double * 4),
@@ -625,6 +654,13 @@ def load_product():
     lib.vio_lens_distort_points.argtypes = [lensp, _dp, C.c_int32, _dp]
     lib.vio_lens_undistort_points.argtypes = [lensp, _dp, C.c_int32, _dp, u8p]
     lib.vio_lens_coverage.argtypes = [lensp, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    srcp = C.POINTER(VioSource)
+    lib.vio_source_check.argtypes = [srcp, C.c_int32, C.c_int32]
+    lib.vio_source_camera.argtypes = [srcp, C.c_int32, C.c_int32, _dp, _dp]
+    lib.vio_preprocess_set_sources.argtypes = [vp, C.c_int32, _ip, srcp]
+    lib.vio_preprocess_get_source.argtypes = [vp, C.c_int32, srcp, _ip]
+    lib.vio_preprocess_run_frames.argtypes = [vp, C.POINTER(vp), C.c_int32, u8p, u8p]
+    lib.vio_preprocess_run_frames_resident.argtypes = [vp, C.POINTER(vp), C.c_int32, vp, vp]
     imup, kfp, i64 = C.POINTER(VioImuMsg), C.POINTER(VioKeyframeData), C.c_int64
     lib.vio_replay_read_imu.argtypes = [C.c_char_p, imup, C.c_int32, _ip]
     lib.vio_replay_write_imu.argtypes = [C.c_char_p, imup, C.c_int32]

@@ -25,6 +25,16 @@
 // mostly hit the lines the neighbouring lanes read), so there is no map and no extra full-frame buffer. Lens or no lens is a
 // per-frame, wave-uniform branch outside the pixel loop of the <CH, true> instantiation; a context that holds no lens at
 // all launches <CH, false>, which is the kernel as it was before lenses existed.
+//
+// Native-size source frames (VioSource, vio_preprocess_set_sources, vio_preprocess_run_frames*) go through
+// clahe_lut_frames_kernel, the same gray pass with a per-frame record (pre_source.h) and a per-frame base pointer: the tile's
+// gray pixels are the exact area average of the slot's crop, or the supersampled rectification of the whole frame for a lensed
+// slot. Format, identity / scaled / lensed are block-uniform branches outside the pixel loops, so one launch serves a batch that
+// mixes them. The area path is separable: lanes walk SOURCE rows, consecutive lanes reading consecutive dwords of a row (one
+// RGBA / BGRA pixel, or four one-byte pixels), and sum the rows of one output row with the vertical weights into LDS; then one
+// lane per output pixel takes the horizontal weighted sum from LDS and divides once. Algorithmic bytes of a scaled frame:
+// bpp * crop_rows * crop_cols (read once; a source row that two output rows share is read twice, from L2) + 3 * R * C,
+// e.g. 8.3 MB + 0.9 MB for 1080p RGBA to 640 x 480.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -36,6 +46,7 @@
 #include <vector>
 
 #include "pre_rectify.h"
+#include "pre_source.h"
 #include "vio_amd.h"
 #include "vio_device.h"
 #include "vio_pool.h"
@@ -62,6 +73,44 @@ __device__ __forceinline__ int reflect101(int i, int n) { return i < n ? i : 2 *
 __device__ __forceinline__ uint32_t rgba_gray(uint32_t px) {  // little endian: R in the low byte
   const uint32_t r = px & 0xff, g = (px >> 8) & 0xff, b = (px >> 16) & 0xff;
   return (r * 4899u + g * 9617u + b * 1868u + 8192u) >> 14;
+}
+
+// hist[256] of one tile (complete after the barrier below) -> its 256-byte LUT: clip, redistribution, scan, scale
+__device__ __forceinline__ void lut_of_histogram(uint32_t *hist, uint32_t *scan, uint32_t *wsum, const PreGeom &G, int tid,
+                                                 uint8_t *__restrict__ lut_out) {
+  __syncthreads();
+  uint32_t h = hist[tid];
+  if (G.clip > 0) {
+    uint32_t excess = h > (uint32_t)G.clip ? h - G.clip : 0;
+    if (excess) h = G.clip;
+    // block sum of the clipped mass
+    uint32_t s = excess;
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((tid & 63) == 0) wsum[tid >> 6] = s;
+    __syncthreads();
+    uint32_t clipped = 0;
+    for (int w = 0; w < kThreads / 64; w++) clipped += wsum[w];
+    const uint32_t batch = clipped / 256u;
+    uint32_t residual = clipped - batch * 256u;
+    h += batch;
+    if (residual != 0) {
+      const uint32_t step = 256u / residual > 1u ? 256u / residual : 1u;  // MAX(histSize / residual, 1)
+      if ((uint32_t)tid % step == 0 && (uint32_t)tid / step < residual) h += 1;
+    }
+  }
+  // inclusive scan over the 256 bins
+  scan[tid] = h;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const uint32_t add = tid >= o ? scan[tid - o] : 0;
+    __syncthreads();
+    scan[tid] += add;
+    __syncthreads();
+  }
+  const float f = (float)(int)scan[tid] * G.lut_scale;
+  int r = __float2int_rn(f);  // cvRound
+  r = r < 0 ? 0 : (r > 255 ? 255 : r);
+  lut_out[tid] = (uint8_t)r;
 }
 
 template <int CH, bool LENS>
@@ -103,39 +152,184 @@ __global__ __launch_bounds__(kThreads) void clahe_lut_kernel(const uint8_t *__re
       atomicAdd(&hist[v], 1u);
     }
   }
-  __syncthreads();
-  uint32_t h = hist[tid];
-  if (G.clip > 0) {
-    uint32_t excess = h > (uint32_t)G.clip ? h - G.clip : 0;
-    if (excess) h = G.clip;
-    // block sum of the clipped mass
-    uint32_t s = excess;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((tid & 63) == 0) wsum[tid >> 6] = s;
-    __syncthreads();
-    uint32_t clipped = 0;
-    for (int w = 0; w < kThreads / 64; w++) clipped += wsum[w];
-    const uint32_t batch = clipped / 256u;
-    uint32_t residual = clipped - batch * 256u;
-    h += batch;
-    if (residual != 0) {
-      const uint32_t step = 256u / residual > 1u ? 256u / residual : 1u;  // MAX(histSize / residual, 1)
-      if ((uint32_t)tid % step == 0 && (uint32_t)tid / step < residual) h += 1;
+  lut_of_histogram(hist, scan, wsum, G, tid, lut + ((size_t)frame * G.tiles_x * G.tiles_y + tile) * 256);
+}
+
+struct SourceSlot {  // one per frame slot, in device memory
+  pre::SourcePlan plan;
+  int32_t is_set, pad;
+};
+
+struct FrameRef {  // one per frame of a vio_preprocess_run_frames* call
+  const uint8_t *base;  // row `row0` of the frame's plane 0 (the host route stages only the rows the slot reads)
+  int32_t row0, pad;
+};
+
+constexpr int kAreaWords = 4096;  // LDS words of the area path's vertical sums
+constexpr int kRowBatch = 4;      // source rows a lane of the area path reads before it uses them: that many loads in flight
+
+// it / n for 0 <= it < kAreaWords, n >= 1, inv_n = 1.0f / n: (it + 0.5) / n is at least 0.5 / n away from an integer and the
+// two float roundings move it by less than (it + 0.5) * 2^-23, so the truncation is the exact quotient
+__device__ __forceinline__ int div_small(int it, float inv_n) { return (int)(((float)it + 0.5f) * inv_n); }
+
+// The gray pixels of one tile of a frame that holds a source, counted in hist: three routes, chosen per block.
+// (1) a lens in the slot: one lane per output pixel, the supersampled rectification of the whole delivered frame
+template <int BPP, bool VIDEO>
+__device__ __forceinline__ void lens_tile(const uint8_t *__restrict__ img, const pre::SourcePlan &P, const VioLens &L, const PreGeom &G, int tx,
+                                          int ty, uint8_t *__restrict__ gout, uint32_t *hist) {
+  for (int p = threadIdx.x; p < G.tw * G.th; p += kThreads) {
+    const int yy = p / G.tw, xx = p - yy * G.tw;
+    const int ey = ty * G.th + yy, ex = tx * G.tw + xx;
+    const int sy = reflect101(ey, G.rows), sx = reflect101(ex, G.cols);  // the extension is one of OUTPUT coordinates
+    const uint32_t v = pre::rectify_source_px<BPP, VIDEO>(img, P, L, sx, sy);
+    if (ey < G.rows && ex < G.cols) gout[(size_t)ey * G.cols + ex] = (uint8_t)v;
+    atomicAdd(&hist[v], 1u);
+  }
+}
+
+// (2) a crop of the output's size: one lane per pixel, clahe_lut_kernel's loop with the slot's origin, stride and format
+template <int BPP, bool VIDEO>
+__device__ __forceinline__ void direct_tile(const uint8_t *__restrict__ img, const pre::SourcePlan &P, const PreGeom &G, int tx, int ty,
+                                            uint8_t *__restrict__ gout, uint32_t *hist) {
+  const uint8_t *org = img + (size_t)P.crop_y * P.stride + (size_t)P.crop_x * BPP;
+  for (int p = threadIdx.x; p < G.tw * G.th; p += kThreads) {
+    const int yy = p / G.tw, xx = p - yy * G.tw;
+    const int ey = ty * G.th + yy, ex = tx * G.tw + xx;
+    const int sy = reflect101(ey, G.rows), sx = reflect101(ex, G.cols);
+    const uint32_t v = pre::source_gray<BPP, VIDEO>(org + (size_t)sy * P.stride, sx, P.c0, P.c2);
+    if (ey < G.rows && ex < G.cols) gout[(size_t)ey * G.cols + ex] = (uint8_t)v;
+    atomicAdd(&hist[v], 1u);
+  }
+}
+
+// (3) the area average, separable. Output columns go in chunks whose source span fits V; of each chunk, groups of `rg` output
+// rows: first one lane per (output row, SOURCE column) sums that column over the row's source rows with wy -- consecutive
+// lanes read consecutive dwords of a source row: one RGBA / BGRA pixel, or four one-byte pixels where the rows are dword
+// aligned -- then one lane per output pixel sums its span of V with wx and divides.
+template <int BPP, bool VIDEO>
+__device__ __forceinline__ void area_tile(const uint8_t *__restrict__ img, const pre::SourcePlan &P, const PreGeom &G, int tx, int ty,
+                                          uint8_t *__restrict__ gout, uint32_t *hist, uint32_t *V) {
+  const int tid = threadIdx.x;
+  const uint32_t D = (uint32_t)P.cw * (uint32_t)P.ch;
+  const int ex_end = tx * G.tw + G.tw, ey_end = ty * G.th + G.th;
+  const int xc = min(G.tw, (int)(((int64_t)(kAreaWords - 2) * P.ow) / P.cw));  // >= 511: cw <= 8 ow
+  const int span_max = (int)(((int64_t)xc * P.cw + P.ow - 1) / P.ow) + 1;      // <= kAreaWords
+  const int rg = min(G.th, kAreaWords / span_max);
+  for (int ex0 = tx * G.tw; ex0 < ex_end; ex0 += xc) {
+    const int ex1 = min(ex0 + xc, ex_end), nx = ex1 - ex0;
+    // the output columns this chunk reads, reflected ones included: [lo, hi), hi - lo <= nx
+    const int a = reflect101(ex0, G.cols), b = reflect101(ex1 - 1, G.cols);
+    const int lo = min(a, b), hi = (ex0 < G.cols && ex1 > G.cols) ? G.cols : max(a, b) + 1;
+    const int j0 = pre::area_first(lo, P.cw, P.ow), span = pre::area_end(hi - 1, P.cw, P.ow) - j0;
+    const uint8_t *col0 = img + (size_t)P.crop_y * P.stride + (size_t)(P.crop_x + j0) * BPP;  // source column j0 of crop row 0
+    // one-byte pixels, four to a lane: the dwords that hold columns j0 .. j0 + span - 1 of a row. Their first and last may
+    // reach up to 3 bytes beyond the row's pixels (never beyond the aligned dword a pixel of the frame lies in).
+    const bool quads = BPP == 1 && (P.stride & 3) == 0;
+    const int mis = quads ? (int)(reinterpret_cast<uintptr_t>(col0) & 3) : 0;
+    const int n1 = quads ? (mis + span + 3) >> 2 : span;                       // lanes of one output row in the first step
+    const float inv_n1 = 1.0f / (float)n1, inv_nx = 1.0f / (float)nx;
+    for (int ey0 = ty * G.th; ey0 < ey_end; ey0 += rg) {
+      const int nr = min(rg, ey_end - ey0);
+      for (int it = tid; it < nr * n1; it += kThreads) {
+        const int rr = div_small(it, inv_n1), g = it - rr * n1;
+        const int sy = reflect101(ey0 + rr, G.rows);
+        const int r0 = pre::area_first(sy, P.ch, P.oh), r1 = pre::area_end(sy, P.ch, P.oh);
+        if (quads) {
+          const int jj = 4 * g - mis;
+          const uint8_t *at = col0 + jj;
+          uint32_t acc[4] = {0, 0, 0, 0};
+          for (int r = r0; r < r1; r += kRowBatch) {
+            uint32_t w[kRowBatch], q[kRowBatch];
+#pragma unroll
+            for (int b = 0; b < kRowBatch; b++) {  // (a row past the last one: that one again, with weight 0)
+              const int rb = min(r + b, r1 - 1);
+              w[b] = r + b < r1 ? pre::area_weight(sy, rb, P.ch, P.oh) : 0u;
+              q[b] = *reinterpret_cast<const uint32_t *>(at + (size_t)rb * P.stride);
+            }
+#pragma unroll
+            for (int b = 0; b < kRowBatch; b++)
+#pragma unroll
+              for (int k = 0; k < 4; k++) {
+                const uint32_t y = (q[b] >> (8 * k)) & 0xff;
+                acc[k] += w[b] * (VIDEO ? pre::video_range(y) : y);
+              }
+          }
+#pragma unroll
+          for (int k = 0; k < 4; k++)
+            if (jj + k >= 0 && jj + k < span) V[rr * span + jj + k] = acc[k];
+        } else {
+          uint32_t acc = 0;
+          for (int r = r0; r < r1; r += kRowBatch) {
+            uint32_t w[kRowBatch], y[kRowBatch];
+#pragma unroll
+            for (int b = 0; b < kRowBatch; b++) {
+              const int rb = min(r + b, r1 - 1);
+              w[b] = r + b < r1 ? pre::area_weight(sy, rb, P.ch, P.oh) : 0u;
+              y[b] = pre::source_gray<BPP, VIDEO>(col0 + (size_t)rb * P.stride, g, P.c0, P.c2);
+            }
+#pragma unroll
+            for (int b = 0; b < kRowBatch; b++) acc += w[b] * y[b];
+          }
+          V[rr * span + g] = acc;
+        }
+      }
+      __syncthreads();
+      for (int it = tid; it < nr * nx; it += kThreads) {
+        const int rr = div_small(it, inv_nx), xx = it - rr * nx;
+        const int ey = ey0 + rr, ex = ex0 + xx;
+        const int sx = reflect101(ex, G.cols);
+        const int j1 = pre::area_end(sx, P.cw, P.ow);
+        const uint32_t *row = V + rr * span - j0;
+        uint32_t S = 0;
+        for (int j = pre::area_first(sx, P.cw, P.ow); j < j1; j++) S += pre::area_weight(sx, j, P.cw, P.ow) * row[j];
+        const uint32_t v = pre::area_round(S, D);
+        if (ey < G.rows && ex < G.cols) gout[(size_t)ey * G.cols + ex] = (uint8_t)v;
+        atomicAdd(&hist[v], 1u);
+      }
+      __syncthreads();
     }
   }
-  // inclusive scan over the 256 bins
-  scan[tid] = h;
+}
+
+template <int BPP, bool VIDEO>
+__device__ __forceinline__ void source_tile(const uint8_t *img, const pre::SourcePlan &P, const VioLens *lens, const PreGeom &G,
+                                            int tx, int ty, uint8_t *__restrict__ gout, uint32_t *hist, uint32_t *V) {
+  if (lens)
+    lens_tile<BPP, VIDEO>(img, P, *lens, G, tx, ty, gout, hist);
+  else if (P.cw == 1 && P.ch == 1)
+    direct_tile<BPP, VIDEO>(img, P, G, tx, ty, gout, hist);
+  else
+    area_tile<BPP, VIDEO>(img, P, G, tx, ty, gout, hist, V);
+}
+
+// clahe_lut_kernel for frames that lie where the caller has them, each described by its slot's record.
+// (7 waves per SIMD: left alone the allocator takes 81 registers for the area route's loads in flight, 5 waves, and the
+// one-pixel-per-lane routes, which live on occupancy, pay for it: identity frames 0.578 -> 0.554 ms per 512, 2 x RGBA 1.71 -> 1.65;
+// at 8 it spills to scratch)
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7))) void clahe_lut_frames_kernel(const FrameRef *__restrict__ frames,
+                                                                     const SourceSlot *__restrict__ sources,
+                                                                     uint8_t *__restrict__ gray, uint8_t *__restrict__ lut,
+                                                                     PreGeom G, const LensSlot *__restrict__ lenses) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t scan[256];
+  __shared__ uint32_t wsum[kThreads / 64];
+  __shared__ uint32_t V[kAreaWords];
+  const int tid = threadIdx.x, tile = blockIdx.x, frame = blockIdx.y;
+  const int tx = tile % G.tiles_x, ty = tile / G.tiles_x;
+  hist[tid] = 0;
   __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const uint32_t add = tid >= o ? scan[tid - o] : 0;
-    __syncthreads();
-    scan[tid] += add;
-    __syncthreads();
-  }
-  const float f = (float)(int)scan[tid] * G.lut_scale;
-  int r = __float2int_rn(f);  // cvRound
-  r = r < 0 ? 0 : (r > 255 ? 255 : r);
-  lut[((size_t)frame * G.tiles_x * G.tiles_y + tile) * 256 + tid] = (uint8_t)r;
+  // the frame's records: the same for every lane, read through the scalar cache
+  const pre::SourcePlan P = sources[frame].plan;
+  const uint8_t *img = frames[frame].base - (ptrdiff_t)frames[frame].row0 * P.stride;
+  const VioLens *lens = lenses && lenses[frame].is_set ? &lenses[frame].lens : nullptr;
+  uint8_t *gout = gray + (size_t)frame * G.rows * G.cols;
+  if (P.bpp == 4)
+    source_tile<4, false>(img, P, lens, G, tx, ty, gout, hist, V);
+  else if (P.video)
+    source_tile<1, true>(img, P, lens, G, tx, ty, gout, hist, V);
+  else
+    source_tile<1, false>(img, P, lens, G, tx, ty, gout, hist, V);
+  lut_of_histogram(hist, scan, wsum, G, tid, lut + ((size_t)frame * G.tiles_x * G.tiles_y + tile) * 256);
 }
 
 __device__ __forceinline__ uint32_t blend_px(const float *__restrict__ L1, const float *__restrict__ L2, int i1, int i2,
@@ -218,6 +412,20 @@ struct vio_preprocess {
   std::vector<LensSlot> h_lens;   // the table as last set (zero: no lens)
   int n_lens = 0;                 // slots that hold a lens: 0 launches the kernel without the lens branch
   vio::PinnedBuf<uint8_t> h_in, h_out;  // page-locked staging of the host-buffer entry point
+  // native-size source frames (vio_preprocess_run_frames*)
+  static constexpr int kRing = 8;
+  vio::DevBuf<SourceSlot> d_source;   // [max_frames]: written whole by every set_sources
+  std::vector<SourceSlot> h_source;   // the table as last set (zero: no source)
+  std::vector<VioSource> h_source_abi;  // what get_source returns
+  // the frame table of a call lives in one of kRing entries, page-locked on the host and in device memory, until the
+  // call's launch has run (ring_ev): a call returns before that, and the next calls take the next entries
+  vio::PinnedBuf<FrameRef> h_refs;
+  vio::DevBuf<FrameRef> d_refs;
+  hipEvent_t ring_ev[kRing] = {};
+  bool ring_used[kRing] = {};
+  int ring_next = 0;
+  vio::PinnedBuf<uint8_t> h_frames;   // staging of the host route: the rows each slot reads, grown on demand
+  vio::DevBuf<uint8_t> d_frames;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double ms_sum = 0;
@@ -225,6 +433,8 @@ struct vio_preprocess {
   ~vio_preprocess() {
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
+    for (hipEvent_t e : ring_ev)
+      if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -250,15 +460,15 @@ PreGeom geometry(int rows, int cols, int tiles_x, int tiles_y, double clip_limit
   return G;
 }
 
-int launch(vio_preprocess *p, const uint8_t *d_src, int channels, int n_frames, size_t frame_stride, int row_stride,
-           uint8_t *d_out, size_t out_frame_stride, int out_row_stride, hipStream_t st) {
-  const PreGeom G = geometry(p->rows, p->cols, p->tiles_x, p->tiles_y, p->clip_limit);
-  const dim3 g1(G.tiles_x * G.tiles_y, n_frames), g2((G.rows + kBandRows - 1) / kBandRows, n_frames);
-  (void)hipEventRecord(p->ev0, st);
-  const LensSlot *ls = p->d_lens.p;
-  auto *lut_kernel = channels == 4 ? (p->n_lens ? clahe_lut_kernel<4, true> : clahe_lut_kernel<4, false>)
-                                   : (p->n_lens ? clahe_lut_kernel<1, true> : clahe_lut_kernel<1, false>);
-  hipLaunchKernelGGL(lut_kernel, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray.p, p->d_lut.p, G, ls);
+void account(vio_preprocess *p) {
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, p->ev0, p->ev1) == hipSuccess) p->ms_sum += ms, p->launches++;
+}
+
+// the apply pass of a batch whose gray images and LUTs the gray pass has just been launched for; closes the timed interval
+int launch_apply(vio_preprocess *p, const PreGeom &G, int n_frames, uint8_t *d_out, size_t out_frame_stride, int out_row_stride,
+                 hipStream_t st) {
+  const dim3 g2((G.rows + kBandRows - 1) / kBandRows, n_frames);
   const bool vec4 = G.cols % 4 == 0 && out_row_stride % 4 == 0 && out_frame_stride % 4 == 0 &&
                     (reinterpret_cast<uintptr_t>(d_out) & 3) == 0;
   if (vec4)
@@ -271,9 +481,52 @@ int launch(vio_preprocess *p, const uint8_t *d_src, int channels, int n_frames, 
   return hipGetLastError() == hipSuccess ? VIO_OK : VIO_ENODEV;
 }
 
-void account(vio_preprocess *p) {
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, p->ev0, p->ev1) == hipSuccess) p->ms_sum += ms, p->launches++;
+int launch(vio_preprocess *p, const uint8_t *d_src, int channels, int n_frames, size_t frame_stride, int row_stride,
+           uint8_t *d_out, size_t out_frame_stride, int out_row_stride, hipStream_t st) {
+  const PreGeom G = geometry(p->rows, p->cols, p->tiles_x, p->tiles_y, p->clip_limit);
+  const dim3 g1(G.tiles_x * G.tiles_y, n_frames);
+  (void)hipEventRecord(p->ev0, st);
+  const LensSlot *ls = p->d_lens.p;
+  auto *lut_kernel = channels == 4 ? (p->n_lens ? clahe_lut_kernel<4, true> : clahe_lut_kernel<4, false>)
+                                   : (p->n_lens ? clahe_lut_kernel<1, true> : clahe_lut_kernel<1, false>);
+  hipLaunchKernelGGL(lut_kernel, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray.p, p->d_lut.p, G, ls);
+  return launch_apply(p, G, n_frames, d_out, out_frame_stride, out_row_stride, st);
+}
+
+// vio_preprocess_run_frames*: refs[f] is frame f of the call. The table goes to the device through the next ring entry, on
+// `st` ahead of the kernels, so the caller's array and this entry's host copy are free as soon as the call returns / the
+// launch has run.
+int launch_frames(vio_preprocess *p, const FrameRef *refs, int n_frames, uint8_t *d_out, hipStream_t st) {
+  const int k = p->ring_next;
+  if (p->ring_used[k] && hipEventSynchronize(p->ring_ev[k]) != hipSuccess) return VIO_ENODEV;  // kRing calls in flight
+  FrameRef *h = p->h_refs.p + (size_t)k * p->max_frames, *d = p->d_refs.p + (size_t)k * p->max_frames;
+  memcpy(h, refs, sizeof(FrameRef) * n_frames);
+  if (hipMemcpyAsync(d, h, sizeof(FrameRef) * n_frames, hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV;
+  const PreGeom G = geometry(p->rows, p->cols, p->tiles_x, p->tiles_y, p->clip_limit);
+  const dim3 g1(G.tiles_x * G.tiles_y, n_frames);
+  (void)hipEventRecord(p->ev0, st);
+  const LensSlot *ls = p->n_lens ? p->d_lens.p : nullptr;
+  hipLaunchKernelGGL(clahe_lut_frames_kernel, g1, dim3(kThreads), 0, st, (const FrameRef *)d, (const SourceSlot *)p->d_source.p,
+                     p->d_gray.p, p->d_lut.p, G, ls);
+  const int rc = launch_apply(p, G, n_frames, d_out, (size_t)p->rows * p->cols, p->cols, st);
+  (void)hipEventRecord(p->ring_ev[k], st);
+  p->ring_used[k] = true, p->ring_next = (k + 1) % vio_preprocess::kRing;
+  return rc;
+}
+
+// the batch's results to caller memory through the page-locked staging; waits for them
+int download(vio_preprocess *p, int n_frames, uint8_t *gray_out, uint8_t *equalized_out, hipStream_t st) {
+  const size_t px = (size_t)p->rows * p->cols, N = (size_t)n_frames;
+  if (hipMemcpyAsync(p->h_out.p, p->d_out.p, px * N, hipMemcpyDeviceToHost, st) != hipSuccess) return VIO_ENODEV;
+  if (gray_out && hipMemcpyAsync(p->h_out.p + (size_t)p->max_frames * px, p->d_gray.p, px * N, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return VIO_ENODEV;
+  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
+  vio::HostPool::get().parallel_for(n_frames, [&](int f) {
+    memcpy(equalized_out + (size_t)f * px, p->h_out.p + (size_t)f * px, px);
+    if (gray_out) memcpy(gray_out + (size_t)f * px, p->h_out.p + ((size_t)p->max_frames + f) * px, px);
+  });
+  account(p);
+  return VIO_OK;
 }
 
 }  // namespace
@@ -290,14 +543,23 @@ int vio_preprocess_create(int32_t max_frames, int32_t rows, int32_t cols, vio_pr
   const size_t px = (size_t)rows * cols;
   if (p->d_src.ensure(px * 4 * max_frames) != VIO_OK || p->d_gray.ensure(px * max_frames) != VIO_OK ||
       p->d_out.ensure(px * max_frames) != VIO_OK || p->d_lut.ensure((size_t)kMaxTiles * kMaxTiles * 256 * max_frames) != VIO_OK ||
-      p->d_lens.ensure(max_frames) != VIO_OK ||
+      p->d_lens.ensure(max_frames) != VIO_OK || p->d_source.ensure(max_frames) != VIO_OK ||
+      p->d_refs.ensure((size_t)vio_preprocess::kRing * max_frames) != VIO_OK ||
+      p->h_refs.ensure((size_t)vio_preprocess::kRing * max_frames) != VIO_OK ||
       hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess ||
       hipEventCreate(&p->ev1) != hipSuccess) {
     delete p;
     return VIO_ENOMEM;
   }
+  for (hipEvent_t &e : p->ring_ev)
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+      delete p;
+      return VIO_ENOMEM;
+    }
   try {
     p->h_lens.assign((size_t)max_frames, LensSlot{});
+    p->h_source.assign((size_t)max_frames, SourceSlot{});
+    p->h_source_abi.assign((size_t)max_frames, VioSource{});
   } catch (const std::bad_alloc &) {
     delete p;
     return VIO_ENOMEM;
@@ -430,16 +692,7 @@ int vio_preprocess_run(vio_preprocess_t *p, const uint8_t *pixels, int32_t chann
   }
   int rc = launch(p, p->d_src.p, channels, n_frames, fb, (int)row_bytes, p->d_out.p, px, p->cols, st);
   if (rc != VIO_OK) return rc;
-  if (hipMemcpyAsync(p->h_out.p, p->d_out.p, px * N, hipMemcpyDeviceToHost, st) != hipSuccess) return VIO_ENODEV;
-  if (gray_out && hipMemcpyAsync(p->h_out.p + (size_t)p->max_frames * px, p->d_gray.p, px * N, hipMemcpyDeviceToHost, st) != hipSuccess)
-    return VIO_ENODEV;
-  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
-  vio::HostPool::get().parallel_for(n_frames, [&](int f) {
-    memcpy(equalized_out + (size_t)f * px, p->h_out.p + (size_t)f * px, px);
-    if (gray_out) memcpy(gray_out + (size_t)f * px, p->h_out.p + ((size_t)p->max_frames + f) * px, px);
-  });
-  account(p);
-  return VIO_OK;
+  return download(p, n_frames, gray_out, equalized_out, st);
 }
 
 int vio_preprocess_run_resident(vio_preprocess_t *p, const void *d_pixels, int32_t channels, int32_t n_frames, int32_t stride,
@@ -452,6 +705,126 @@ int vio_preprocess_run_resident(vio_preprocess_t *p, const void *d_pixels, int32
   hipStream_t st = stream ? (hipStream_t)stream : p->stream;
   return launch(p, (const uint8_t *)d_pixels, channels, n_frames, (size_t)stride * p->rows, stride, (uint8_t *)d_equalized,
                 (size_t)p->rows * p->cols, p->cols, st);
+}
+
+int vio_source_check(const VioSource *s, int32_t rows, int32_t cols) {
+  return s && pre::source_valid(*s, rows, cols) ? VIO_OK : VIO_EINVAL;
+}
+
+int vio_source_camera(const VioSource *s, int32_t rows, int32_t cols, const double in[4], double out[4]) {
+  if (!s || !in || !out || !pre::source_valid(*s, rows, cols)) return VIO_EINVAL;
+  pre::source_camera(*s, rows, cols, in, out);
+  return VIO_OK;
+}
+
+int vio_preprocess_set_sources(vio_preprocess_t *p, int32_t n, const int32_t *slot, const VioSource *src) {
+  if (!p || n < 0 || (n > 0 && !slot) || n > p->max_frames) return VIO_EINVAL;  // more than max_frames names a slot twice
+  std::vector<SourceSlot> next;
+  std::vector<VioSource> next_abi;
+  std::vector<uint8_t> named;
+  try {
+    next = p->h_source, next_abi = p->h_source_abi;
+    named.assign((size_t)p->max_frames, 0);
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+  for (int i = 0; i < n; i++) {
+    const int s = slot[i];
+    if (s < 0 || s >= p->max_frames || named[s]) return VIO_EINVAL;
+    if (src && !pre::source_valid(src[i], p->rows, p->cols)) return VIO_EINVAL;
+    named[s] = 1;
+    next[s] = SourceSlot{}, next_abi[s] = VioSource{};
+    if (src) next[s].plan = pre::source_plan(src[i], p->rows, p->cols), next[s].is_set = 1, next_abi[s] = src[i];
+  }
+  if (n == 0) return VIO_OK;
+  VIO_ON_DEVICE_OF(p);
+  // as vio_preprocess_set_lenses: let the last launch finish, replace the table, return with it in device memory
+  if (hipEventSynchronize(p->ev1) != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpyAsync(p->d_source.p, next.data(), sizeof(SourceSlot) * next.size(), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
+      hipStreamSynchronize(p->stream) != hipSuccess)
+    return VIO_ENODEV;
+  p->h_source.swap(next), p->h_source_abi.swap(next_abi);
+  return VIO_OK;
+}
+
+int vio_preprocess_get_source(vio_preprocess_t *p, int32_t slot, VioSource *out, int32_t *is_set) {
+  if (!p || !out || !is_set || slot < 0 || slot >= p->max_frames) return VIO_EINVAL;
+  *out = p->h_source_abi[slot], *is_set = p->h_source[slot].is_set;
+  return VIO_OK;
+}
+
+int vio_preprocess_run_frames(vio_preprocess_t *p, const void *const *pixels, int32_t n_frames, uint8_t *gray_out,
+                              uint8_t *equalized_out) {
+  if (!p || !pixels || !equalized_out || n_frames < 1) return VIO_EINVAL;
+  if (n_frames > p->max_frames) return VIO_ECAP;
+  for (int f = 0; f < n_frames; f++) {
+    if (!pixels[f]) return VIO_EINVAL;
+    if (!p->h_source[f].is_set) return VIO_ESTATE;
+  }
+  VIO_ON_DEVICE_OF(p);
+  const size_t px = (size_t)p->rows * p->cols, N = (size_t)n_frames;
+  hipStream_t st = p->stream;
+  // per frame the rows its slot reads, each with the frame's own stride: the crop's rows, or all of plane 0 under a lens.
+  // The last row ends with its last pixel (a caller's plane need not be padded to the stride there).
+  struct Part {
+    size_t src_off, bytes, dst_off;
+    int32_t row0;
+  };
+  std::vector<Part> part;
+  std::vector<FrameRef> refs;
+  try {
+    part.resize(N), refs.resize(N);
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+  size_t total = 0;
+  for (size_t f = 0; f < N; f++) {
+    const pre::SourcePlan &S = p->h_source[f].plan;
+    const VioSource &A = p->h_source_abi[f];
+    const bool lens = p->h_lens[f].is_set != 0;
+    const int32_t row0 = lens ? 0 : A.crop_y, n_rows = lens ? A.rows : A.crop_rows;
+    part[f] = Part{(size_t)row0 * A.stride, (size_t)(n_rows - 1) * A.stride + (size_t)A.cols * S.bpp, total, row0};
+    total += (part[f].bytes + 15) & ~(size_t)15;
+  }
+  if (p->h_frames.ensure(total) != VIO_OK || p->d_frames.ensure(total) != VIO_OK ||
+      p->h_out.ensure((size_t)p->max_frames * px * 2) != VIO_OK)
+    return VIO_ENOMEM;
+  // the chunked gather of vio_preprocess_run: the DMA of one chunk overlaps the host copy of the next
+  const size_t n_chunks = N >= 16 ? 8 : 1, per = (N + n_chunks - 1) / n_chunks;
+  for (size_t c0 = 0; c0 < N; c0 += per) {
+    const size_t c1 = std::min(N, c0 + per);
+    vio::HostPool::get().parallel_for((int)(c1 - c0), [&](int i) {
+      const Part &q = part[c0 + i];
+      memcpy(p->h_frames.p + q.dst_off, (const uint8_t *)pixels[c0 + i] + q.src_off, q.bytes);
+    });
+    const size_t b0 = part[c0].dst_off, b1 = part[c1 - 1].dst_off + part[c1 - 1].bytes;
+    if (hipMemcpyAsync(p->d_frames.p + b0, p->h_frames.p + b0, b1 - b0, hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV;
+  }
+  for (size_t f = 0; f < N; f++) refs[f] = FrameRef{p->d_frames.p + part[f].dst_off, part[f].row0, 0};
+  const int rc = launch_frames(p, refs.data(), n_frames, p->d_out.p, st);
+  if (rc != VIO_OK) return rc;
+  return download(p, n_frames, gray_out, equalized_out, st);
+}
+
+int vio_preprocess_run_frames_resident(vio_preprocess_t *p, const void *const *d_pixels, int32_t n_frames, void *d_equalized,
+                                       void *stream) {
+  if (!p || !d_pixels || !d_equalized || n_frames < 1) return VIO_EINVAL;
+  if (n_frames > p->max_frames) return VIO_ECAP;
+  std::vector<FrameRef> refs;
+  try {
+    refs.resize((size_t)n_frames);
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+  for (int f = 0; f < n_frames; f++) {
+    if (!d_pixels[f]) return VIO_EINVAL;
+    if (!p->h_source[f].is_set) return VIO_ESTATE;
+    if (p->h_source[f].plan.bpp == 4 && (reinterpret_cast<uintptr_t>(d_pixels[f]) & 3)) return VIO_EINVAL;
+    refs[f] = FrameRef{(const uint8_t *)d_pixels[f], 0, 0};
+  }
+  VIO_ON_DEVICE_OF(p);
+  hipStream_t st = stream ? (hipStream_t)stream : p->stream;
+  return launch_frames(p, refs.data(), n_frames, (uint8_t *)d_equalized, st);
 }
 
 int vio_preprocess_sync(vio_preprocess_t *p) {

@@ -347,6 +347,42 @@ class Preprocessor:
         if rc != 0:
             raise RuntimeError("vio_preprocess_run_resident failed: %d" % rc)
 
+    def set_sources(self, slots, sources=None):
+        """vio_preprocess_set_sources: sources[i] (abi.VioSource) describes the frame at position slots[i] of every later
+        run_frames / run_frames_resident; sources=None clears the named slots. -> the return code (VIO_EINVAL: nothing changed)."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        arr = None
+        if sources is not None:
+            assert len(sources) == len(slots)
+            arr = (abi.VioSource * max(len(slots), 1))(*sources)
+        return self.lib.vio_preprocess_set_sources(self._h, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int32)), arr)
+
+    def get_source(self, slot):
+        """-> the slot's abi.VioSource, or None when it holds none."""
+        out, is_set = abi.VioSource(), C.c_int32()
+        rc = self.lib.vio_preprocess_get_source(self._h, slot, C.byref(out), C.byref(is_set))
+        if rc != 0:
+            raise RuntimeError("vio_preprocess_get_source failed: %d" % rc)
+        return out if is_set.value else None
+
+    def run_frames(self, frames, want_gray=True):
+        """frames[i]: a uint8 numpy array whose first byte is the first byte of plane 0 of slot i's frame, laid out as the
+        slot's source says -> (rc, gray [n, rows, cols] or None, equalized [n, rows, cols])."""
+        n = len(frames)
+        ptrs = (C.c_void_p * max(n, 1))(*[f.ctypes.data for f in frames])
+        gray = np.zeros((n, self.rows, self.cols), np.uint8) if want_gray else None
+        eq = np.zeros((n, self.rows, self.cols), np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        rc = self.lib.vio_preprocess_run_frames(self._h, ptrs, n, gray.ctypes.data_as(u8p) if want_gray else None,
+                                                eq.ctypes.data_as(u8p))
+        return rc, gray, eq
+
+    def run_frames_resident(self, d_pixels, d_equalized, stream=None):
+        """d_pixels: one device pointer per frame (slot i's frame at d_pixels[i]); asynchronous -> the return code."""
+        n = len(d_pixels)
+        ptrs = (C.c_void_p * max(n, 1))(*[int(x) for x in d_pixels])
+        return self.lib.vio_preprocess_run_frames_resident(self._h, ptrs, n, C.c_void_p(d_equalized), C.c_void_p(stream or 0))
+
     def sync(self):
         rc = self.lib.vio_preprocess_sync(self._h)
         if rc != 0:
