@@ -93,8 +93,10 @@ void vio_config_default(VioConfig *cfg);
  * Pinhole only. Lens distortion is NOT modelled, as in the reference, whose
  * rejectWithF works on raw pixels (feature_tracker.cpp:95,198); the frames of
  * a distorted lens are rectified to a pinhole by the image pre-step, on the
- * device (VioLens, vio_preprocess_set_lenses), and the intrinsics given here
- * are then those of the rectified image (VioLens.rect_*).                     */
+ * device (VioLens, vio_preprocess_set_lenses; VioLensModel,
+ * vio_preprocess_set_lens_models for a rational or a fisheye lens), and the
+ * intrinsics given here are then those of the rectified image (rect_* of
+ * either record).                                                             */
 typedef struct VioCamera {
   double fx, fy, cx, cy;   /* FOCUS_LENGTH_X/Y, PX, PY  global_param.cpp:24-131 */
   double tic[3], ric[9];   /* camera -> body, ric row-major (TIC_*, RIC_*)      */
@@ -501,6 +503,57 @@ int vio_lens_undistort_points(const VioLens *lens, const double *uv /* [n][2] */
  * (u outside [0, cols-1] or v outside [0, rows-1]; the kernel clamps these):
  * what a caller looks at when choosing rect_*.                                */
 int vio_lens_coverage(const VioLens *lens, int32_t rows, int32_t cols, int64_t *n_outside);
+
+/* Lens models. A slot's lens is one of three forward models; VioLensModel is
+ * VioLens with the model named and eight coefficients. Pixel -> (xn, yn), the
+ * clamp, rint(32 .), the integer blend and the supersampled form of a slot
+ * that also holds a VioSource are those of VioLens above, for every model; so
+ * are IEEE doubles, every operation rounded on its own, no contraction.
+ *   VIO_LENS_BROWN     the lines above with k1 k2 p1 p2 k3 = k[0..4]
+ *   VIO_LENS_RATIONAL  OpenCV's CALIB_RATIONAL_MODEL:
+ *     radial = (1 + r2*(k1 + r2*(k2 + r2*k3))) / (1 + r2*(k[5] + r2*(k[6] + r2*k[7])))
+ *     xd, yd, u, v as above. With k[5..7] = 0 the divisor is exactly 1: the
+ *     bytes of the same VioLens.
+ *   VIO_LENS_FISHEYE   cv::fisheye (equidistant, Kannala-Brandt over theta):
+ *     r = sqrt(r2), th = atan(r), t2 = th*th
+ *     thd = th*(1 + t2*(k[0] + t2*(k[1] + t2*(k[2] + t2*k[3]))))
+ *     s = r2 == 0 ? 1 : thd / r
+ *     u = fx*(xn*s) + cx, v = fy*(yn*s) + cy
+ *     sqrt is the correctly rounded IEEE one. atan is NOT a math library's
+ *     (those agree between host and device to an ulp, not to the bit) but the
+ *     fixed sequence of + - * / written out at the head of csrc/pre_rectify.h
+ *     (lens_atan: four breakpoints 7/16, 11/16, 19/16, 39/16, one division, an
+ *     odd polynomial of eleven terms; within 4 ulp of the true value), the
+ *     same bits on the host, on the device and in a restatement.              */
+#define VIO_LENS_BROWN    0  /* k = k1 k2 p1 p2 k3, k[5..7] = 0: VioLens, byte for byte            */
+#define VIO_LENS_RATIONAL 1  /* k = k1 k2 p1 p2 k3 k4 k5 k6, OpenCV's order                        */
+#define VIO_LENS_FISHEYE  2  /* k = k1 k2 k3 k4 of cv::fisheye over theta, k[4..7] = 0             */
+typedef struct VioLensModel {
+  int32_t model, reserved;                 /* reserved = 0 */
+  double fx, fy, cx, cy;                   /* raw image */
+  double k[8];
+  double rect_fx, rect_fy, rect_cx, rect_cy;
+} VioLensModel;
+/* The contract of vio_preprocess_set_lenses. VIO_EINVAL, and nothing changed,
+ * also for an unknown model, reserved != 0, or a coefficient the model does
+ * not use that is not 0. A slot holds ONE lens, whichever call set it:
+ * vio_preprocess_set_lenses stores its argument as VIO_LENS_BROWN, _get_lens_model
+ * reads any slot, and vio_preprocess_get_lens on a slot that holds another model
+ * returns VIO_ESTATE and leaves *out and *is_set alone.                        */
+int vio_preprocess_set_lens_models(vio_preprocess_t *p, int32_t n, const int32_t *slot /* [n] */, const VioLensModel *lens /* [n] or NULL: clear */);
+int vio_preprocess_get_lens_model(vio_preprocess_t *p, int32_t slot, VioLensModel *out, int32_t *is_set);
+/* Host only, as vio_lens_*. Undistort: Brown-Conrady and rational by the
+ * fixed-point iteration above with the same stopping rule; fisheye by
+ * thd = hypot(xd, yd), Newton on th*(1 + ...) = thd from th = thd, at most 50
+ * rounds, until a step is below 1e-12, xn = xd * tan(th)/thd (thd = 0: the
+ * centre); converged[i] = 0 when it does not settle or th >= pi/2 (such a ray
+ * has no pinhole image; xn, yn are then not meaningful). VIO_EINVAL for an
+ * unknown model or reserved != 0; undistort also for fx or fy <= 0, coverage
+ * for any record vio_preprocess_set_lens_models would refuse.                  */
+int vio_lens_model_distort_points(const VioLensModel *lens, const double *xn /* [n][2] */, int32_t n, double *uv /* [n][2] */);
+int vio_lens_model_undistort_points(const VioLensModel *lens, const double *uv /* [n][2] */, int32_t n, double *xn /* [n][2] */,
+                                    uint8_t *converged /* [n] or NULL */);
+int vio_lens_model_coverage(const VioLensModel *lens, int32_t rows, int32_t cols, int64_t *n_outside);
 
 /* Native-size source frames. A frame slot that holds a VioSource takes its
  * frame as the camera or the decoder delivers it (size, row stride, pixel

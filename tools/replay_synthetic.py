@@ -98,8 +98,10 @@ class SyntheticWorld:
 class ImageWorld(SyntheticWorld):
     """The same trajectory and IMU, but the camera films a textured plane: frames are rendered by intersecting every
     pixel's ray with the plane z = z0, and the observations come from the KLT front-end run on those frames.
-    lens (abi.VioLens whose rect_* are cfg's intrinsics): the camera films through that lens (raw pixel ->
-    vio_lens_undistort_points -> ray) and every frame is rectified on the device by the image pre-step before it is returned."""
+    lens (abi.VioLens or abi.VioLensModel whose rect_* are cfg's intrinsics): the camera films through that lens (raw pixel ->
+    vio_lens_undistort_points / vio_lens_model_undistort_points -> ray) and every frame is rectified on the device by the image
+    pre-step before it is returned. Raw pixels of a fisheye that have no ray in front of the camera (theta >= pi / 2), or one
+    more than 87 degrees off the axis, stay black; the rectified pinhole must not look there."""
 
     def __init__(self, cfg, seed, z0=-6.0, px_per_m=77.0, lens=None, **kw):
         super().__init__(cfg, seed, n_landmarks=1, **kw)
@@ -110,15 +112,31 @@ class ImageWorld(SyntheticWorld):
         rows, cols = cfg.image_rows, cfg.image_cols
         v, u = np.mgrid[0:rows, 0:cols].astype(np.float64)
         self.rays = np.stack([(u - cfg.cx) / cfg.fx, (v - cfg.cy) / cfg.fy, np.ones_like(u)], axis=-1)
-        self.pre = None
+        self.pre = self.blind = None
         if lens is not None:
             assert (lens.rect_fx, lens.rect_fy, lens.rect_cx, lens.rect_cy) == (cfg.fx, cfg.fy, cfg.cx, cfg.cy)
-            xn, ok = abi.lens_undistort_points(lens, np.stack([u.ravel(), v.ravel()], axis=1))
-            assert ok.all(), "the lens model does not invert over the raw image"
+            model = isinstance(lens, abi.VioLensModel)
+            undistort = abi.lens_model_undistort_points if model else abi.lens_undistort_points
+            xn, ok = undistort(lens, np.stack([u.ravel(), v.ravel()], axis=1))
+            if model and lens.model == abi.VIO_LENS_FISHEYE:
+                blind = (ok == 0) | ~(np.abs(xn).max(axis=1) < 20.0)
+                xn[blind] = 0.0
+                self.blind = blind.reshape(rows, cols)
+                # every raw pixel a rectified pixel blends must have been drawn
+                uv = abi.lens_model_distort_points(lens, self.rays[..., :2].reshape(-1, 2))
+                iu = np.clip(np.rint(uv[:, 0]), 0, cols - 1).astype(int)
+                iv = np.clip(np.rint(uv[:, 1]), 0, rows - 1).astype(int)
+                assert not self.blind[iv, iu].any(), "the rectified pinhole looks where the fisheye has no ray"
+            else:
+                assert ok.all(), "the lens model does not invert over the raw image"
             self.rays = np.concatenate([xn.reshape(rows, cols, 2), np.ones((rows, cols, 1))], axis=-1)
             self.pre = pkg.frontend.Preprocessor(rows, cols, max_frames=1)
-            assert self.pre.set_lenses([0], [lens]) == abi.VIO_OK
-            self.clamped = abi.lens_coverage(lens, rows, cols)
+            if model:
+                assert self.pre.set_lens_models([0], [lens]) == abi.VIO_OK
+                self.clamped = abi.lens_model_coverage(lens, rows, cols)
+            else:
+                assert self.pre.set_lenses([0], [lens]) == abi.VIO_OK
+                self.clamped = abi.lens_coverage(lens, rows, cols)
 
     def render(self, k):
         raw = self.render_raw(k)
@@ -132,6 +150,8 @@ class ImageWorld(SyntheticWorld):
         X, Y = Pc[0] + lam * d[..., 0], Pc[1] + lam * d[..., 1]
         img = synth._bilinear(self.tex, (X + self.tex_half) * self.s, (Y + self.tex_half) * self.s)
         img = img + self.rng.normal(0, 1.0, img.shape)
+        if self.blind is not None:
+            img[self.blind] = 0.0
         return np.clip(np.rint(img), 0, 255).astype(np.uint8)
 
 
@@ -343,10 +363,28 @@ def main():
     ap.add_argument("--images", action="store_true", help="render frames of a textured plane and run the KLT front-end on them")
     ap.add_argument("--lens", default=None, metavar="k1,k2,p1,p2,k3",
                     help="with --images: film through this Brown-Conrady lens (cfg's intrinsics) and rectify on the device")
+    ap.add_argument("--fisheye", default=None, metavar="f,k1,k2,k3,k4",
+                    help="with --images: film through this equidistant fisheye (focal length f pixels, cfg's centre) and rectify "
+                         "on the device to cfg's pinhole")
+    ap.add_argument("--rational", default=None, metavar="k1,k2,p1,p2,k3,k4,k5,k6",
+                    help="with --images: film through this rational lens (cfg's intrinsics) and rectify on the device")
     args = ap.parse_args()
     import torch  # noqa: F401  (HIP runtime first)
     cfg = abi.default_config()
     world = None
+    if args.fisheye or args.rational:
+        assert args.images and not args.lens and not (args.fisheye and args.rational), "one lens, and --images"
+        k = [float(x) for x in (args.fisheye or args.rational).split(",")]
+        rect = (cfg.fx, cfg.fy, cfg.cx, cfg.cy)
+        if args.fisheye:
+            assert len(k) == 5, "--fisheye f,k1,k2,k3,k4"
+            lens = abi.make_lens_model(abi.VIO_LENS_FISHEYE, k[0], k[0], cfg.cx, cfg.cy, k[1:], rect)
+        else:
+            assert len(k) == 8, "--rational k1,k2,p1,p2,k3,k4,k5,k6"
+            lens = abi.make_lens_model(abi.VIO_LENS_RATIONAL, cfg.fx, cfg.fy, cfg.cx, cfg.cy, k, rect)
+        world = ImageWorld(cfg, args.seed, lens=lens)
+        print("%s lens %s: %d of %d rectified pixels look outside the raw frame (clamped)"
+              % ("fisheye" if args.fisheye else "rational", k, world.clamped, cfg.image_rows * cfg.image_cols))
     if args.lens:
         assert args.images, "--lens needs --images"
         k = [float(x) for x in args.lens.split(",")]

@@ -143,6 +143,59 @@ def lens_coverage(lens, rows, cols):
     return n.value
 
 
+VIO_LENS_BROWN, VIO_LENS_RATIONAL, VIO_LENS_FISHEYE = 0, 1, 2
+
+
+class VioLensModel(C.Structure):
+    """A lens of the image pre-step with its model named (vio_amd.h): k = k1 k2 p1 p2 k3 (Brown-Conrady), k1 k2 p1 p2 k3 k4 k5 k6
+    (rational), k1 k2 k3 k4 over theta (fisheye); the coefficients a model does not use are 0."""
+    _fields_ = ([("model", C.c_int32), ("reserved", C.c_int32)] + [(k, C.c_double) for k in ("fx", "fy", "cx", "cy")] +
+                [("k", C.c_double * 8)] + [(k, C.c_double) for k in ("rect_fx", "rect_fy", "rect_cx", "rect_cy")])
+
+
+def make_lens_model(model, fx, fy, cx, cy, k=(), rect=None):
+    """k: the model's coefficients in its order (the rest 0); rect = (rect_fx, rect_fy, rect_cx, rect_cy), None: the raw intrinsics."""
+    r = (fx, fy, cx, cy) if rect is None else rect
+    kk = [float(x) for x in k] + [0.0] * (8 - len(k))
+    return VioLensModel(model, 0, fx, fy, cx, cy, (C.c_double * 8)(*kk), *[float(x) for x in r])
+
+
+def lens_model_of(lens):
+    """The VIO_LENS_BROWN record a VioLens stands for."""
+    return make_lens_model(VIO_LENS_BROWN, lens.fx, lens.fy, lens.cx, lens.cy, (lens.k1, lens.k2, lens.p1, lens.p2, lens.k3),
+                           (lens.rect_fx, lens.rect_fy, lens.rect_cx, lens.rect_cy))
+
+
+def lens_model_distort_points(lens, xn):
+    """vio_lens_model_distort_points: normalized undistorted points [n, 2] -> raw pixels [n, 2] (not clamped)."""
+    xn = np.ascontiguousarray(xn, np.float64).reshape(-1, 2)
+    uv = np.zeros_like(xn)
+    rc = load_product().vio_lens_model_distort_points(C.byref(lens), _ptr(xn), len(xn), _ptr(uv))
+    if rc != VIO_OK:
+        raise RuntimeError("vio_lens_model_distort_points rc=%d" % rc)
+    return uv
+
+
+def lens_model_undistort_points(lens, uv):
+    """vio_lens_model_undistort_points: raw pixels [n, 2] -> (normalized points [n, 2], converged [n] uint8)."""
+    uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
+    xn, ok = np.zeros_like(uv), np.zeros(len(uv), np.uint8)
+    rc = load_product().vio_lens_model_undistort_points(C.byref(lens), _ptr(uv), len(uv), _ptr(xn),
+                                                        ok.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != VIO_OK:
+        raise RuntimeError("vio_lens_model_undistort_points rc=%d" % rc)
+    return xn, ok
+
+
+def lens_model_coverage(lens, rows, cols):
+    """vio_lens_model_coverage: the output pixels whose source lies outside the raw rows x cols image."""
+    n = C.c_int64()
+    rc = load_product().vio_lens_model_coverage(C.byref(lens), rows, cols, C.byref(n))
+    if rc != VIO_OK:
+        raise RuntimeError("vio_lens_model_coverage rc=%d" % rc)
+    return n.value
+
+
 VIO_PIXEL_GRAY8, VIO_PIXEL_RGBA8, VIO_PIXEL_BGRA8, VIO_PIXEL_NV12 = 1, 4, 5, 12
 
 
@@ -654,6 +707,12 @@ def load_product():
     lib.vio_lens_distort_points.argtypes = [lensp, _dp, C.c_int32, _dp]
     lib.vio_lens_undistort_points.argtypes = [lensp, _dp, C.c_int32, _dp, u8p]
     lib.vio_lens_coverage.argtypes = [lensp, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    modelp = C.POINTER(VioLensModel)
+    lib.vio_preprocess_set_lens_models.argtypes = [vp, C.c_int32, _ip, modelp]
+    lib.vio_preprocess_get_lens_model.argtypes = [vp, C.c_int32, modelp, _ip]
+    lib.vio_lens_model_distort_points.argtypes = [modelp, _dp, C.c_int32, _dp]
+    lib.vio_lens_model_undistort_points.argtypes = [modelp, _dp, C.c_int32, _dp, u8p]
+    lib.vio_lens_model_coverage.argtypes = [modelp, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     srcp = C.POINTER(VioSource)
     lib.vio_source_check.argtypes = [srcp, C.c_int32, C.c_int32]
     lib.vio_source_camera.argtypes = [srcp, C.c_int32, C.c_int32, _dp, _dp]

@@ -13,7 +13,8 @@
 // 255 * D < 2^32 (vio_source_check) keeps S in 32 bits; the weights are separable and every partial sum is exact.
 // A lens: s = min(4, max(ceil(src.cols / cols), ceil(src.rows / rows))) samples per axis at (x + (2 i + 1 - s) / (2 s),
 // y + (2 j + 1 - s) / (2 s)), each through pre_rectify.h's arithmetic over the WHOLE delivered frame (the crop is not used),
-// out = (sum + s * s / 2) / (s * s). With s = 1 that is pre::rectify_px.
+// out = (sum + s * s / 2) / (s * s). With s = 1 that is pre::rectify_px. The lens is any of pre_rectify.h's (VioLens,
+// VioLensModel, LensAs<MODEL>).
 #pragma once
 #include "pre_rectify.h"
 
@@ -74,7 +75,8 @@ VIO_PRE_HD uint32_t area_px(const uint8_t *img, const SourcePlan &P, int x, int 
 }
 
 // pre::lens_source at a sample position that is no integer
-VIO_PRE_HD void lens_source_at(const VioLens &L, double xs, double ys, double *u, double *v) {
+template <class LENS>
+VIO_PRE_HD void lens_source_at(const LENS &L, double xs, double ys, double *u, double *v) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -85,8 +87,8 @@ VIO_PRE_HD void lens_source_at(const VioLens &L, double xs, double ys, double *u
 
 // The rectified gray of output pixel (x, y) from the whole delivered frame: the mean of s * s samples of pre::rectify_px's
 // arithmetic. Reads stay inside [0, P.rows) x [0, P.cols) by lens_fixed's clamp and the min, as there.
-template <int BPP, bool VIDEO>
-VIO_PRE_HD uint32_t rectify_source_px(const uint8_t *img, const SourcePlan &P, const VioLens &L, int x, int y) {
+template <int BPP, bool VIDEO, class LENS>
+VIO_PRE_HD uint32_t rectify_source_px(const uint8_t *img, const SourcePlan &P, const LENS &L, int x, int y) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif

@@ -25,6 +25,10 @@
 // mostly hit the lines the neighbouring lanes read), so there is no map and no extra full-frame buffer. Lens or no lens is a
 // per-frame, wave-uniform branch outside the pixel loop of the <CH, true> instantiation; a context that holds no lens at
 // all launches <CH, false>, which is the kernel as it was before lenses existed.
+// The lens MODEL (VioLensModel, vio_preprocess_set_lens_models: Brown-Conrady, rational, fisheye) is the frame's as well: each
+// model has a pixel loop of its own behind a second wave-uniform branch, so one launch serves a batch that mixes them. The
+// fisheye loop (sqrt, pre::lens_atan, two more divisions) needs registers that would cost every frame of the kernel a wave, so
+// it exists only in the FISHEYE instantiations, launched while some slot of the context holds a fisheye lens.
 //
 // Native-size source frames (VioSource, vio_preprocess_set_sources, vio_preprocess_run_frames*) go through
 // clahe_lut_frames_kernel, the same gray pass with a per-frame record (pre_source.h) and a per-frame base pointer: the tile's
@@ -64,7 +68,7 @@ struct PreGeom {
 };
 
 struct LensSlot {  // one per frame slot, in device memory
-  VioLens lens;
+  VioLensModel lens;  // vio_preprocess_set_lenses stores VIO_LENS_BROWN
   int32_t is_set, pad;
 };
 
@@ -113,7 +117,24 @@ __device__ __forceinline__ void lut_of_histogram(uint32_t *hist, uint32_t *scan,
   lut_out[tid] = (uint8_t)r;
 }
 
-template <int CH, bool LENS>
+// The rectified gray pixels of one tile of a frame whose slot holds a lens of model MODEL, counted in hist
+template <int CH, int MODEL>
+__device__ __forceinline__ void rect_tile(const uint8_t *__restrict__ img, int row_stride, const VioLensModel &lens, const PreGeom &G, int tx,
+                                          int ty, uint8_t *__restrict__ gout, uint32_t *hist) {
+  const pre::LensAs<MODEL> L(lens);
+  for (int p = threadIdx.x; p < G.tw * G.th; p += kThreads) {
+    const int yy = p / G.tw, xx = p - yy * G.tw;
+    const int ey = ty * G.th + yy, ex = tx * G.tw + xx;
+    const int sy = reflect101(ey, G.rows), sx = reflect101(ex, G.cols);  // the extension is one of OUTPUT coordinates
+    const uint32_t v = pre::rectify_px<CH>(img, (size_t)row_stride, G.rows, G.cols, L, sx, sy);
+    if (ey < G.rows && ex < G.cols) gout[(size_t)ey * G.cols + ex] = (uint8_t)v;
+    atomicAdd(&hist[v], 1u);
+  }
+}
+
+// FISHEYE: the instantiation a context launches while one of its slots holds a VIO_LENS_FISHEYE (its atan and square root take
+// registers that would cost the other models' frames a wave of occupancy); without it the fisheye route does not exist
+template <int CH, bool LENS, bool FISHEYE>
 __global__ __launch_bounds__(kThreads) void clahe_lut_kernel(const uint8_t *__restrict__ src, size_t frame_stride,
                                                               int row_stride, uint8_t *__restrict__ gray,
                                                               uint8_t *__restrict__ lut, PreGeom G,
@@ -129,15 +150,14 @@ __global__ __launch_bounds__(kThreads) void clahe_lut_kernel(const uint8_t *__re
   uint8_t *gout = gray + (size_t)frame * G.rows * G.cols;
   const int area = G.tw * G.th;
   if (LENS && lenses[frame].is_set) {  // the frame's record: the same for every lane, read through the scalar cache
-    const VioLens L = lenses[frame].lens;
-    for (int p = tid; p < area; p += kThreads) {
-      const int yy = p / G.tw, xx = p - yy * G.tw;
-      const int ey = ty * G.th + yy, ex = tx * G.tw + xx;
-      const int sy = reflect101(ey, G.rows), sx = reflect101(ex, G.cols);  // the extension is one of OUTPUT coordinates
-      const uint32_t v = pre::rectify_px<CH>(img, (size_t)row_stride, G.rows, G.cols, L, sx, sy);
-      if (ey < G.rows && ex < G.cols) gout[(size_t)ey * G.cols + ex] = (uint8_t)v;
-      atomicAdd(&hist[v], 1u);
-    }
+    const VioLensModel L = lenses[frame].lens;
+    // the model is the frame's too: each has a pixel loop of its own, so a Brown-Conrady frame runs the instructions it always ran
+    if (FISHEYE && L.model == VIO_LENS_FISHEYE)
+      rect_tile<CH, VIO_LENS_FISHEYE>(img, row_stride, L, G, tx, ty, gout, hist);
+    else if (L.model == VIO_LENS_RATIONAL)
+      rect_tile<CH, VIO_LENS_RATIONAL>(img, row_stride, L, G, tx, ty, gout, hist);
+    else
+      rect_tile<CH, VIO_LENS_BROWN>(img, row_stride, L, G, tx, ty, gout, hist);
   } else {
     for (int p = tid; p < area; p += kThreads) {
       const int yy = p / G.tw, xx = p - yy * G.tw;
@@ -174,9 +194,10 @@ __device__ __forceinline__ int div_small(int it, float inv_n) { return (int)(((f
 
 // The gray pixels of one tile of a frame that holds a source, counted in hist: three routes, chosen per block.
 // (1) a lens in the slot: one lane per output pixel, the supersampled rectification of the whole delivered frame
-template <int BPP, bool VIDEO>
-__device__ __forceinline__ void lens_tile(const uint8_t *__restrict__ img, const pre::SourcePlan &P, const VioLens &L, const PreGeom &G, int tx,
-                                          int ty, uint8_t *__restrict__ gout, uint32_t *hist) {
+template <int BPP, bool VIDEO, int MODEL>
+__device__ __forceinline__ void lens_tile(const uint8_t *__restrict__ img, const pre::SourcePlan &P, const VioLensModel &lens, const PreGeom &G,
+                                          int tx, int ty, uint8_t *__restrict__ gout, uint32_t *hist) {
+  const pre::LensAs<MODEL> L(lens);
   for (int p = threadIdx.x; p < G.tw * G.th; p += kThreads) {
     const int yy = p / G.tw, xx = p - yy * G.tw;
     const int ey = ty * G.th + yy, ex = tx * G.tw + xx;
@@ -291,11 +312,15 @@ __device__ __forceinline__ void area_tile(const uint8_t *__restrict__ img, const
   }
 }
 
-template <int BPP, bool VIDEO>
-__device__ __forceinline__ void source_tile(const uint8_t *img, const pre::SourcePlan &P, const VioLens *lens, const PreGeom &G,
+template <int BPP, bool VIDEO, bool FISHEYE>
+__device__ __forceinline__ void source_tile(const uint8_t *img, const pre::SourcePlan &P, const VioLensModel *lens, const PreGeom &G,
                                             int tx, int ty, uint8_t *__restrict__ gout, uint32_t *hist, uint32_t *V) {
-  if (lens)
-    lens_tile<BPP, VIDEO>(img, P, *lens, G, tx, ty, gout, hist);
+  if (FISHEYE && lens && lens->model == VIO_LENS_FISHEYE)
+    lens_tile<BPP, VIDEO, VIO_LENS_FISHEYE>(img, P, *lens, G, tx, ty, gout, hist);
+  else if (lens && lens->model == VIO_LENS_RATIONAL)
+    lens_tile<BPP, VIDEO, VIO_LENS_RATIONAL>(img, P, *lens, G, tx, ty, gout, hist);
+  else if (lens)
+    lens_tile<BPP, VIDEO, VIO_LENS_BROWN>(img, P, *lens, G, tx, ty, gout, hist);
   else if (P.cw == 1 && P.ch == 1)
     direct_tile<BPP, VIDEO>(img, P, G, tx, ty, gout, hist);
   else
@@ -306,7 +331,9 @@ __device__ __forceinline__ void source_tile(const uint8_t *img, const pre::Sourc
 // (7 waves per SIMD: left alone the allocator takes 81 registers for the area route's loads in flight, 5 waves, and the
 // one-pixel-per-lane routes, which live on occupancy, pay for it: identity frames 0.578 -> 0.554 ms per 512, 2 x RGBA 1.71 -> 1.65;
 // at 8 it spills to scratch)
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7))) void clahe_lut_frames_kernel(const FrameRef *__restrict__ frames,
+// FISHEYE as for clahe_lut_kernel: launched while a slot holds a fisheye lens, with one wave less so that its route does not spill
+template <bool FISHEYE>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(FISHEYE ? 6 : 7))) void clahe_lut_frames_kernel(const FrameRef *__restrict__ frames,
                                                                      const SourceSlot *__restrict__ sources,
                                                                      uint8_t *__restrict__ gray, uint8_t *__restrict__ lut,
                                                                      PreGeom G, const LensSlot *__restrict__ lenses) {
@@ -321,14 +348,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7))) v
   // the frame's records: the same for every lane, read through the scalar cache
   const pre::SourcePlan P = sources[frame].plan;
   const uint8_t *img = frames[frame].base - (ptrdiff_t)frames[frame].row0 * P.stride;
-  const VioLens *lens = lenses && lenses[frame].is_set ? &lenses[frame].lens : nullptr;
+  const VioLensModel *lens = lenses && lenses[frame].is_set ? &lenses[frame].lens : nullptr;
   uint8_t *gout = gray + (size_t)frame * G.rows * G.cols;
   if (P.bpp == 4)
-    source_tile<4, false>(img, P, lens, G, tx, ty, gout, hist, V);
+    source_tile<4, false, FISHEYE>(img, P, lens, G, tx, ty, gout, hist, V);
   else if (P.video)
-    source_tile<1, true>(img, P, lens, G, tx, ty, gout, hist, V);
+    source_tile<1, true, FISHEYE>(img, P, lens, G, tx, ty, gout, hist, V);
   else
-    source_tile<1, false>(img, P, lens, G, tx, ty, gout, hist, V);
+    source_tile<1, false, FISHEYE>(img, P, lens, G, tx, ty, gout, hist, V);
   lut_of_histogram(hist, scan, wsum, G, tid, lut + ((size_t)frame * G.tiles_x * G.tiles_y + tile) * 256);
 }
 
@@ -411,6 +438,7 @@ struct vio_preprocess {
   vio::DevBuf<LensSlot> d_lens;   // [max_frames]: written whole by every set_lenses, read by launches while n_lens > 0
   std::vector<LensSlot> h_lens;   // the table as last set (zero: no lens)
   int n_lens = 0;                 // slots that hold a lens: 0 launches the kernel without the lens branch
+  int n_fisheye = 0;              // ... a VIO_LENS_FISHEYE: 0 launches the kernels without the fisheye route
   vio::PinnedBuf<uint8_t> h_in, h_out;  // page-locked staging of the host-buffer entry point
   // native-size source frames (vio_preprocess_run_frames*)
   static constexpr int kRing = 8;
@@ -487,8 +515,8 @@ int launch(vio_preprocess *p, const uint8_t *d_src, int channels, int n_frames, 
   const dim3 g1(G.tiles_x * G.tiles_y, n_frames);
   (void)hipEventRecord(p->ev0, st);
   const LensSlot *ls = p->d_lens.p;
-  auto *lut_kernel = channels == 4 ? (p->n_lens ? clahe_lut_kernel<4, true> : clahe_lut_kernel<4, false>)
-                                   : (p->n_lens ? clahe_lut_kernel<1, true> : clahe_lut_kernel<1, false>);
+  auto *lut_kernel = channels == 4 ? (p->n_fisheye ? clahe_lut_kernel<4, true, true> : p->n_lens ? clahe_lut_kernel<4, true, false> : clahe_lut_kernel<4, false, false>)
+                                   : (p->n_fisheye ? clahe_lut_kernel<1, true, true> : p->n_lens ? clahe_lut_kernel<1, true, false> : clahe_lut_kernel<1, false, false>);
   hipLaunchKernelGGL(lut_kernel, g1, dim3(kThreads), 0, st, d_src, frame_stride, row_stride, p->d_gray.p, p->d_lut.p, G, ls);
   return launch_apply(p, G, n_frames, d_out, out_frame_stride, out_row_stride, st);
 }
@@ -506,7 +534,7 @@ int launch_frames(vio_preprocess *p, const FrameRef *refs, int n_frames, uint8_t
   const dim3 g1(G.tiles_x * G.tiles_y, n_frames);
   (void)hipEventRecord(p->ev0, st);
   const LensSlot *ls = p->n_lens ? p->d_lens.p : nullptr;
-  hipLaunchKernelGGL(clahe_lut_frames_kernel, g1, dim3(kThreads), 0, st, (const FrameRef *)d, (const SourceSlot *)p->d_source.p,
+  hipLaunchKernelGGL(p->n_fisheye ? clahe_lut_frames_kernel<true> : clahe_lut_frames_kernel<false>, g1, dim3(kThreads), 0, st, (const FrameRef *)d, (const SourceSlot *)p->d_source.p,
                      p->d_gray.p, p->d_lut.p, G, ls);
   const int rc = launch_apply(p, G, n_frames, d_out, (size_t)p->rows * p->cols, p->cols, st);
   (void)hipEventRecord(p->ring_ev[k], st);
@@ -526,6 +554,42 @@ int download(vio_preprocess *p, int n_frames, uint8_t *gray_out, uint8_t *equali
     if (gray_out) memcpy(gray_out + (size_t)f * px, p->h_out.p + ((size_t)p->max_frames + f) * px, px);
   });
   account(p);
+  return VIO_OK;
+}
+
+// vio_preprocess_set_lenses / _set_lens_models: lens(i) is entry i as a model record (nullptr: refused), clear: no entries
+template <class Entry>
+int set_lens_table(vio_preprocess_t *p, int32_t n, const int32_t *slot, bool clear, Entry lens) {
+  if (!p || n < 0 || (n > 0 && !slot) || n > p->max_frames) return VIO_EINVAL;  // more than max_frames names a slot twice
+  std::vector<LensSlot> next;
+  std::vector<uint8_t> named;
+  try {
+    next = p->h_lens;
+    named.assign((size_t)p->max_frames, 0);
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+  for (int i = 0; i < n; i++) {
+    const int s = slot[i];
+    if (s < 0 || s >= p->max_frames || named[s]) return VIO_EINVAL;
+    named[s] = 1;
+    next[s] = LensSlot{};
+    if (clear) continue;
+    VioLensModel m;
+    if (!lens(i, &m)) return VIO_EINVAL;
+    next[s].lens = m, next[s].is_set = 1;
+  }
+  if (n == 0) return VIO_OK;
+  VIO_ON_DEVICE_OF(p);
+  // launches of this context that are still in flight read the table: let the last one finish, then replace it, and
+  // return only when the new table is in device memory (a later launch on ANY stream then sees it)
+  if (hipEventSynchronize(p->ev1) != hipSuccess) return VIO_ENODEV;
+  if (hipMemcpyAsync(p->d_lens.p, next.data(), sizeof(LensSlot) * next.size(), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
+      hipStreamSynchronize(p->stream) != hipSuccess)
+    return VIO_ENODEV;
+  p->h_lens.swap(next);
+  p->n_lens = p->n_fisheye = 0;
+  for (const LensSlot &s : p->h_lens) p->n_lens += s.is_set, p->n_fisheye += s.is_set && s.lens.model == VIO_LENS_FISHEYE;
   return VIO_OK;
 }
 
@@ -588,38 +652,30 @@ int vio_preprocess_set_clahe(vio_preprocess_t *p, double clip_limit, int32_t til
 }
 
 int vio_preprocess_set_lenses(vio_preprocess_t *p, int32_t n, const int32_t *slot, const VioLens *lens) {
-  if (!p || n < 0 || (n > 0 && !slot) || n > p->max_frames) return VIO_EINVAL;  // more than max_frames names a slot twice
-  std::vector<LensSlot> next;
-  std::vector<uint8_t> named;
-  try {
-    next = p->h_lens;
-    named.assign((size_t)p->max_frames, 0);
-  } catch (const std::bad_alloc &) {
-    return VIO_ENOMEM;
-  }
-  for (int i = 0; i < n; i++) {
-    const int s = slot[i];
-    if (s < 0 || s >= p->max_frames || named[s]) return VIO_EINVAL;
-    if (lens && !pre::lens_valid(lens[i])) return VIO_EINVAL;
-    named[s] = 1;
-    next[s] = LensSlot{};
-    if (lens) next[s].lens = lens[i], next[s].is_set = 1;
-  }
-  if (n == 0) return VIO_OK;
-  VIO_ON_DEVICE_OF(p);
-  // launches of this context that are still in flight read the table: let the last one finish, then replace it, and
-  // return only when the new table is in device memory (a later launch on ANY stream then sees it)
-  if (hipEventSynchronize(p->ev1) != hipSuccess) return VIO_ENODEV;
-  if (hipMemcpyAsync(p->d_lens.p, next.data(), sizeof(LensSlot) * next.size(), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
-      hipStreamSynchronize(p->stream) != hipSuccess)
-    return VIO_ENODEV;
-  p->h_lens.swap(next);
-  p->n_lens = 0;
-  for (const LensSlot &s : p->h_lens) p->n_lens += s.is_set;
-  return VIO_OK;
+  return set_lens_table(p, n, slot, !lens, [&](int i, VioLensModel *m) {
+    if (!pre::lens_valid(lens[i])) return false;
+    *m = pre::lens_model_of(lens[i]);
+    return true;
+  });
+}
+
+int vio_preprocess_set_lens_models(vio_preprocess_t *p, int32_t n, const int32_t *slot, const VioLensModel *lens) {
+  return set_lens_table(p, n, slot, !lens, [&](int i, VioLensModel *m) {
+    if (!pre::lens_model_valid(lens[i])) return false;
+    *m = lens[i];
+    return true;
+  });
 }
 
 int vio_preprocess_get_lens(vio_preprocess_t *p, int32_t slot, VioLens *out, int32_t *is_set) {
+  if (!p || !out || !is_set || slot < 0 || slot >= p->max_frames) return VIO_EINVAL;
+  const LensSlot &s = p->h_lens[slot];
+  if (s.is_set && s.lens.model != VIO_LENS_BROWN) return VIO_ESTATE;  // no VioLens says what this slot holds
+  *out = pre::lens_of_model(s.lens), *is_set = s.is_set;
+  return VIO_OK;
+}
+
+int vio_preprocess_get_lens_model(vio_preprocess_t *p, int32_t slot, VioLensModel *out, int32_t *is_set) {
   if (!p || !out || !is_set || slot < 0 || slot >= p->max_frames) return VIO_EINVAL;
   *out = p->h_lens[slot].lens, *is_set = p->h_lens[slot].is_set;
   return VIO_OK;
@@ -654,6 +710,68 @@ int vio_lens_undistort_points(const VioLens *lens, const double *uv, int32_t n, 
 
 int vio_lens_coverage(const VioLens *lens, int32_t rows, int32_t cols, int64_t *n_outside) {
   if (!lens || !n_outside || rows < 1 || cols < 1 || !pre::lens_valid(*lens)) return VIO_EINVAL;
+  int64_t n = 0;
+  for (int y = 0; y < rows; y++)
+    for (int x = 0; x < cols; x++) {
+      double u, v;
+      pre::lens_source(*lens, x, y, &u, &v);
+      n += pre::lens_outside(u, cols) || pre::lens_outside(v, rows);
+    }
+  *n_outside = n;
+  return VIO_OK;
+}
+
+static bool lens_model_known(const VioLensModel *lens) {
+  return lens && lens->reserved == 0 && (lens->model == VIO_LENS_BROWN || lens->model == VIO_LENS_RATIONAL || lens->model == VIO_LENS_FISHEYE);
+}
+
+int vio_lens_model_distort_points(const VioLensModel *lens, const double *xn, int32_t n, double *uv) {
+  if (!lens_model_known(lens) || n < 0 || (n > 0 && (!xn || !uv))) return VIO_EINVAL;
+  for (int i = 0; i < n; i++) pre::lens_project(*lens, xn[2 * i], xn[2 * i + 1], &uv[2 * i], &uv[2 * i + 1]);
+  return VIO_OK;
+}
+
+int vio_lens_model_undistort_points(const VioLensModel *lens, const double *uv, int32_t n, double *xn, uint8_t *converged) {
+  if (!lens_model_known(lens) || n < 0 || (n > 0 && (!uv || !xn)) || !(lens->fx > 0) || !(lens->fy > 0)) return VIO_EINVAL;
+  VioLensModel unit = *lens;  // the forward model in normalized coordinates: x_d = D(x)
+  unit.fx = unit.fy = 1.0, unit.cx = unit.cy = 0.0;
+  const double *k = lens->k;
+  for (int i = 0; i < n; i++) {
+    const double xd = (uv[2 * i] - lens->cx) / lens->fx, yd = (uv[2 * i + 1] - lens->cy) / lens->fy;
+    double x = xd, y = yd;
+    uint8_t done = 0;
+    if (lens->model == VIO_LENS_FISHEYE) {
+      // th * (1 + k1 th^2 + k2 th^4 + k3 th^6 + k4 th^8) = thd by Newton from th = thd; the ray is (xd, yd) * tan(th) / thd
+      const double thd = hypot(xd, yd);
+      double th = thd;
+      for (int round = 0; round < 50 && !done; round++) {
+        const double t2 = th * th;
+        const double f = th * (1.0 + t2 * (k[0] + t2 * (k[1] + t2 * (k[2] + t2 * k[3])))) - thd;
+        const double df = 1.0 + t2 * (3.0 * k[0] + t2 * (5.0 * k[1] + t2 * (7.0 * k[2] + t2 * (9.0 * k[3]))));
+        const double step = f / df;
+        th -= step;
+        done = fabs(step) < 1e-12;
+      }
+      const double s = thd > 0.0 ? tan(th) / thd : 1.0;
+      x = xd * s, y = yd * s;
+      if (!(th >= 0.0 && th < 1.5707963267948966)) done = 0;  // at or behind the image plane's horizon (or a NaN)
+    } else {
+      for (int round = 0; round < 50 && !done; round++) {  // x <- x + (x_d - D(x)): contracts while |1 - D'| < 1
+        double dx, dy;
+        pre::lens_project(unit, x, y, &dx, &dy);
+        const double sx = xd - dx, sy = yd - dy;
+        x += sx, y += sy;
+        done = fabs(sx) < 1e-12 && fabs(sy) < 1e-12;
+      }
+    }
+    xn[2 * i] = x, xn[2 * i + 1] = y;
+    if (converged) converged[i] = done;
+  }
+  return VIO_OK;
+}
+
+int vio_lens_model_coverage(const VioLensModel *lens, int32_t rows, int32_t cols, int64_t *n_outside) {
+  if (!lens || !n_outside || rows < 1 || cols < 1 || !pre::lens_model_valid(*lens)) return VIO_EINVAL;
   int64_t n = 0;
   for (int y = 0; y < rows; y++)
     for (int x = 0; x < cols; x++) {

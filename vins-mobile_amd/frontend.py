@@ -319,11 +319,30 @@ class Preprocessor:
         return self.lib.vio_preprocess_set_lenses(self._h, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int32)), arr)
 
     def get_lens(self, slot):
-        """-> the slot's abi.VioLens, or None when it holds none."""
+        """-> the slot's abi.VioLens, or None when it holds none (a slot that holds a rational or a fisheye model: VIO_ESTATE,
+        raised)."""
         out, is_set = abi.VioLens(), C.c_int32()
         rc = self.lib.vio_preprocess_get_lens(self._h, slot, C.byref(out), C.byref(is_set))
         if rc != 0:
             raise RuntimeError("vio_preprocess_get_lens failed: %d" % rc)
+        return out if is_set.value else None
+
+    def set_lens_models(self, slots, lenses=None):
+        """vio_preprocess_set_lens_models: set_lenses with abi.VioLensModel records (Brown-Conrady, rational or fisheye);
+        both write the same table. -> the return code (VIO_EINVAL: nothing changed)."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        arr = None
+        if lenses is not None:
+            assert len(lenses) == len(slots)
+            arr = (abi.VioLensModel * max(len(slots), 1))(*lenses)
+        return self.lib.vio_preprocess_set_lens_models(self._h, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int32)), arr)
+
+    def get_lens_model(self, slot):
+        """-> the slot's lens as an abi.VioLensModel, whichever setter put it there, or None when it holds none."""
+        out, is_set = abi.VioLensModel(), C.c_int32()
+        rc = self.lib.vio_preprocess_get_lens_model(self._h, slot, C.byref(out), C.byref(is_set))
+        if rc != 0:
+            raise RuntimeError("vio_preprocess_get_lens_model failed: %d" % rc)
         return out if is_set.value else None
 
     def run(self, frames):
