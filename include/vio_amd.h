@@ -420,6 +420,32 @@ int vio_frontend_in_step(vio_frontend_t *fe, int32_t *in_step);
  * is changed then). Waits for the device. get_camera: tic = 0, ric = identity.          */
 int vio_frontend_set_cameras(vio_frontend_t *fe, int32_t n, const int32_t *seq /* [n] */, const VioCamera *cam /* [n] */);
 int vio_frontend_get_camera(vio_frontend_t *fe, int32_t seq, VioCamera *out);
+/* The region of interest of sequence seq[i]: what setMask starts from on a publish
+ * frame instead of an all-255 mask (feature_tracker.cpp:50-87; the static mask of the
+ * upstream family, FISHEYE_MASK in VINS-Mono's setMask). A tracked feature whose
+ * rounded position lies on a 0 pixel is not kept and paints no disc, and
+ * goodFeaturesToTrack receives the region minus the discs: its masked maximum and its
+ * candidates come from usable pixels only. Frames that do not publish, the list behind
+ * vio_frontend_get_pnp_points (it is ahead of setMask) and the rule that skips the
+ * detector when max_corners features survive are untouched; a sequence without a region
+ * computes what it always did. Uses: the valid region of a rectified wide lens
+ * (vio_preprocess_valid_regions_resident), a bonnet, a housing, a burnt-in overlay.
+ * masks: n images [rows][cols], nonzero = usable; NULL clears the named sequences.
+ * On the host, image i is the region of seq[i] (image mask_index[i] when mask_index is
+ * given). masks_on_device = 1: a packed [slots][rows][cols] device buffer (what
+ * vio_preprocess_valid_regions_resident writes), mask_index[i] names the slot of seq[i],
+ * NULL = slot i; the slots named must exist. The contract of vio_frontend_set_cameras:
+ * VIO_ESTATE between a submit and its collect; VIO_EINVAL, and nothing changed, for an
+ * entry of seq[] out of range or named twice or a negative mask_index; waits for the
+ * device (work queued on a caller's stream included); takes effect at the next publish
+ * frame; changes nothing of the tracker's pixel state; survives vio_frontend_reset; the
+ * caller's buffer is not referenced after the call returns.
+ * get_region: mask_out (may be NULL) receives 0 / 255, all 255 for a sequence without
+ * a region (*is_set = 0); *n_usable = the number of usable pixels.                    */
+int vio_frontend_set_regions(vio_frontend_t *fe, int32_t n, const int32_t *seq /* [n] */, const void *masks,
+                             int32_t masks_on_device, const int32_t *mask_index /* [n] or NULL */);
+int vio_frontend_get_region(vio_frontend_t *fe, int32_t seq, uint8_t *mask_out /* [rows][cols], may be NULL */,
+                            int32_t *is_set, int64_t *n_usable);
 
 /* Host frame buffers registered once (camera / decoder ring buffers, the cv::Mat
  * storage behind `_img` in FeatureTracker::readImage, feature_tracker.cpp:162):
@@ -620,6 +646,37 @@ int vio_preprocess_run_frames(vio_preprocess_t *p, const void *const *pixels /* 
                               uint8_t *gray_out /* may be NULL */, uint8_t *equalized_out);
 int vio_preprocess_run_frames_resident(vio_preprocess_t *p, const void *const *d_pixels /* host array of n_frames device pointers */,
                                        int32_t n_frames, void *d_equalized, void *stream);
+
+/* The valid region of a slot: where the rectified image is made of delivered
+ * pixels only, none of them the clamp's repeated border. Output pixel (x, y) is
+ * INSIDE
+ *   lens, no source:  when its un-clamped source (u, v) lies in the rows x cols
+ *     raw frame, u in [0, cols-1] and v in [0, rows-1] -- the complement of what
+ *     vio_lens_model_coverage counts; a NaN is outside;
+ *   lens and source:  when every one of the s*s sample positions lies in the
+ *     whole delivered frame (src.cols, src.rows), by the same test;
+ *   no lens:          always (a crop is inside its frame).
+ * mask[y][x] = 255 where (x, y) and every output pixel within `margin` of it
+ * (Chebyshev distance; neighbours outside the image do not count) is INSIDE,
+ * else 0. margin = 0 .. 32. Entry i of the call is the mask of slot[i], from the
+ * lens and source tables the context holds; one launch for all n slots of
+ * mixed models. A mask is static per lens: this is no per-frame call. VIO_EINVAL,
+ * and nothing written, for a slot out of range or named twice, a margin out of
+ * range or a null pointer. The resident form is asynchronous on `stream` (NULL =
+ * the context's own) and copies slot[] before it returns; the host form waits.
+ * vio_lens_model_valid_region is the same arithmetic on the host without a
+ * context (csrc/pre_source.h, the text the kernel compiles: the same bytes);
+ * src may be NULL (the frame has the output's size); VIO_EINVAL also for a lens
+ * or a source that the setters would refuse.
+ * Not covered: the polynomial models fold back far from the centre, and a
+ * folded pixel whose source lands inside the frame counts as inside, as it does
+ * in vio_lens_model_coverage.                                                   */
+int vio_preprocess_valid_regions(vio_preprocess_t *p, int32_t n, const int32_t *slot /* [n] */, int32_t margin,
+                                 uint8_t *masks_out /* host [n][rows][cols] */);
+int vio_preprocess_valid_regions_resident(vio_preprocess_t *p, int32_t n, const int32_t *slot /* [n] */, int32_t margin,
+                                          void *d_masks /* device [n][rows][cols] */, void *stream);
+int vio_lens_model_valid_region(const VioLensModel *lens, const VioSource *src /* may be NULL */, int32_t rows, int32_t cols,
+                                int32_t margin, uint8_t *mask /* [rows][cols] */);
 
 /* Introspection of tracker state (cur_pts / ids / track_cnt,
  * feature_tracker.hpp:72-75) for parity tests.                               */

@@ -225,6 +225,17 @@ def source_camera(src, rows, cols, fx, fy, cx, cy):
     return tuple(out)
 
 
+def lens_model_valid_region(lens, src, rows, cols, margin=0):
+    """vio_lens_model_valid_region: the 0 / 255 mask [rows, cols] of the output pixels made of delivered pixels only, eroded by
+    margin; src (a VioSource) may be None."""
+    mask = np.zeros((rows, cols), np.uint8)
+    rc = load_product().vio_lens_model_valid_region(C.byref(lens), None if src is None else C.byref(src), rows, cols, margin,
+                                                    mask.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != VIO_OK:
+        raise RuntimeError("vio_lens_model_valid_region rc=%d" % rc)
+    return mask
+
+
 class VioPreintegration(C.Structure):
     _fields_ = [
         ("sum_dt", C.c_double), ("delta_p", C.c_double * 3), ("delta_q", C.c_double * 4),
@@ -626,6 +637,8 @@ def load_product():
     lib.vio_backend_upload_cam.argtypes = [vp, C.POINTER(VioWindow), C.c_int32, _dp]
     lib.vio_frontend_set_cameras.argtypes = [vp, C.c_int32, _ip, camp]
     lib.vio_frontend_get_camera.argtypes = [vp, C.c_int32, camp]
+    lib.vio_frontend_set_regions.argtypes = [vp, C.c_int32, _ip, vp, C.c_int32, _ip]
+    lib.vio_frontend_get_region.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint8), _ip, C.POINTER(C.c_int64)]
     lib.vio_estimator_set_camera.argtypes = [vp, C.c_int32, camp]
     lib.vio_estimator_get_camera.argtypes = [vp, C.c_int32, camp]
     lib.vio_pnp_tracker_set_camera.argtypes = [vp, C.c_int32, camp]
@@ -720,6 +733,9 @@ def load_product():
     lib.vio_preprocess_get_source.argtypes = [vp, C.c_int32, srcp, _ip]
     lib.vio_preprocess_run_frames.argtypes = [vp, C.POINTER(vp), C.c_int32, u8p, u8p]
     lib.vio_preprocess_run_frames_resident.argtypes = [vp, C.POINTER(vp), C.c_int32, vp, vp]
+    lib.vio_preprocess_valid_regions.argtypes = [vp, C.c_int32, _ip, C.c_int32, u8p]
+    lib.vio_preprocess_valid_regions_resident.argtypes = [vp, C.c_int32, _ip, C.c_int32, vp, vp]
+    lib.vio_lens_model_valid_region.argtypes = [modelp, srcp, C.c_int32, C.c_int32, C.c_int32, u8p]
     imup, kfp, i64 = C.POINTER(VioImuMsg), C.POINTER(VioKeyframeData), C.c_int64
     lib.vio_replay_read_imu.argtypes = [C.c_char_p, imup, C.c_int32, _ip]
     lib.vio_replay_write_imu.argtypes = [C.c_char_p, imup, C.c_int32]

@@ -45,6 +45,26 @@ struct SubsetArgs {
 __device__ __forceinline__ int subset_at(const int *row, int i) { return __builtin_amdgcn_readfirstlane(row[i]); }
 __device__ __forceinline__ uint8_t *subset_bank(const SubsetArgs &M, int bank) { return bank ? M.pyr[1] : M.pyr[0]; }
 
+// The region of interest of every sequence (vio_frontend_set_regions): what setMask starts from instead of an all-255 mask, one
+// bit per pixel (1 = usable). Row y of sequence s is words[(s * rows + y) * wpr ..]: word 0 is padding (all 0), the bit of
+// column x is bit (x + 64) % 64 of word (x + 64) / 64, and one more word of padding ends the row, so the 64 columns from any
+// c >= -64 are a funnel shift of two words of the row. set[s] = 0: the sequence has no region (all usable), its rows are not read.
+// The REGION variants of the step's kernels take this as one more argument (a parameter pack that is empty in the kernels as
+// they always were: a context in which no sequence holds a region launches those, with the arguments they always had).
+struct RegionArgs {
+  const unsigned long long *words;
+  const int *set;  // [n_seq]
+  int wpr;         // words per row
+};
+__device__ __forceinline__ RegionArgs region_args() { return RegionArgs{nullptr, nullptr, 0}; }
+__device__ __forceinline__ RegionArgs region_args(const RegionArgs &g) { return g; }
+// the region bits of columns c0 .. c0 + 63 of one row (c0 >= -64; columns outside the image read 0)
+__device__ __forceinline__ unsigned long long region_window(const unsigned long long *row, int wpr, int c0) {
+  const int w = (c0 + 64) >> 6, sh = (c0 + 64) & 63;
+  const unsigned long long lo = w < wpr ? row[w] : 0ull, hi = w + 1 < wpr ? row[w + 1] : 0ull;
+  return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+}
+
 typedef short lk_s2 __attribute__((ext_vector_type(2)));
 typedef unsigned short lk_us2 __attribute__((ext_vector_type(2)));
 

@@ -67,11 +67,14 @@ __device__ __forceinline__ float sqrt_rn_normal(float x) {
 // to the strip's segment of the sequence's list, and a list that cannot take them all raises the sequence's flag in `ovf`.
 // FULL = true is the exact redo of a flagged sequence (corner_select_kernel's redo workgroups): every pixel of the tile writes
 // its key, or 0 when it is no candidate, to its own place y * cols + x of `full` -- no list, no counter, nothing to overflow.
-template <bool IMG_MASK, bool FULL, int NW>
+// REGION: the sequence's region of interest (RegionArgs, fe_common.h) is what the discs are painted on: one more item per
+// (wave, strip row) ORs the complement of the row's region bits under the wave's 64 columns into the same mask words.
+template <bool IMG_MASK, bool FULL, int NW, bool REGION = false>
 __device__ __forceinline__ void detect_tile(const uint8_t *img_base, size_t img_stride, const uint8_t *mask_base, size_t mask_stride,
                                             const int *kept_xy, const int *n_kept, int cap, const int *hw, int radius,
                                             unsigned *max_bits, int rows, int cols, unsigned long long *cand_base, int seg_cap,
-                                            int *n_cand, int *ovf, int epoch, unsigned long long *full, int seq, int bxi, int byi, int nseg) {
+                                            int *n_cand, int *ovf, int epoch, unsigned long long *full, int seq, int bxi, int byi, int nseg,
+                                            const RegionArgs G = RegionArgs{nullptr, nullptr, 0}) {
   // Equal eigenvalues (a plateau: a tiled pattern, upscaled or saturated content) make EVERY pixel of the plateau a candidate
   // -- `v == m` holds for all of them, as in the reference's val == dilated --, so no list shorter than the tile holds every
   // input. The lists are sized for what ordinary images produce (a strict 3x3 maximum occupies at most one pixel in four);
@@ -112,6 +115,12 @@ __device__ __forceinline__ void detect_tile(const uint8_t *img_base, size_t img_
       if (l0 > l1) continue;
       const unsigned long long bits = (l1 - l0 == 63 ? ~0ull : ((1ull << (l1 - l0 + 1)) - 1ull)) << l0;
       atomicOr(&s_mask[wv][r], bits);
+    }
+    if (REGION && G.set[seq]) {  // (uniform) the wave's window starts at column X0 - 2: a funnel shift of two region words
+      for (int it = tid; it < NW * kDetR; it += NW * 64) {
+        const int wv = it % NW, r = it / NW, y = Y0 + r;
+        if (y < rows) atomicOr(&s_mask[wv][r], ~region_window(G.words + ((size_t)seq * rows + y) * G.wpr, G.wpr, XB + wv * kDetW - 2));
+      }
     }
     __syncthreads();
   }
@@ -261,31 +270,52 @@ __device__ __forceinline__ void detect_tile(const uint8_t *img_base, size_t img_
   if (tid == 0 && (s_ncand > kCandLds || (nc && s_base + nc > seg_cap))) ovf[seq] = epoch;
 }
 
-template <bool IMG_MASK>
+template <bool IMG_MASK, class... REG>
 __global__ __launch_bounds__(256) void detect_kernel(const uint8_t *img_base, size_t img_stride, const uint8_t *mask_base,
                                                      size_t mask_stride, const int *kept_xy, const int *n_kept, int cap,
                                                      const int *hw, int radius, unsigned *max_bits, int rows, int cols,
                                                      unsigned long long *cand_base, int seg_cap, int *n_cand, int *ovf,
-                                                     int epoch, const int *n_have, int max_corners) {
+                                                     int epoch, const int *n_have, int max_corners, REG... region) {
   // n_max_cnt = MAX_CNT - forw_pts.size() <= 0: the reference does not call goodFeaturesToTrack at all (feature_tracker.cpp:256-266);
   // the sequence's candidate counters and maxima stay zero, which is "no corners" to the selection kernel
   if (n_have && n_have[blockIdx.z] >= max_corners) return;
-  detect_tile<IMG_MASK, false, kDetWaves>(img_base, img_stride, mask_base, mask_stride, kept_xy, n_kept, cap, hw, radius, max_bits, rows,
-                                          cols, cand_base, seg_cap, n_cand, ovf, epoch, (unsigned long long *)nullptr, blockIdx.z, blockIdx.x,
-                                          blockIdx.y, gridDim.y);
+  detect_tile<IMG_MASK, false, kDetWaves, sizeof...(REG) != 0>(img_base, img_stride, mask_base, mask_stride, kept_xy, n_kept, cap, hw, radius,
+                                                               max_bits, rows, cols, cand_base, seg_cap, n_cand, ovf, epoch,
+                                                               (unsigned long long *)nullptr, blockIdx.z, blockIdx.x, blockIdx.y, gridDim.y,
+                                                               region_args(region...));
 }
 
 // Subset instantiation (the step's form: setMask discs, no mask image): blockIdx.z counts the PUBLISHED sequences of the call;
 // the image is level 0 of the sequence's forw bank (M.pyr, img_stride apart).
+template <class... REG>
 __global__ __launch_bounds__(256) void detect_subset_kernel(SubsetArgs M, size_t img_stride, const int *kept_xy, const int *n_kept, int cap,
                                                             const int *hw, int radius, unsigned *max_bits, int rows, int cols,
                                                             unsigned long long *cand_base, int seg_cap, int *n_cand, int *ovf, int epoch,
-                                                            const int *n_have, int max_corners) {
+                                                            const int *n_have, int max_corners, REG... region) {
   const int i = subset_at(M.pub, blockIdx.z), seq = subset_at(M.seq, i);
   if (n_have && n_have[seq] >= max_corners) return;
-  detect_tile<false, false, kDetWaves>(subset_bank(M, subset_at(M.forw_bank, i)), img_stride, (const uint8_t *)nullptr, (size_t)0, kept_xy,
-                                       n_kept, cap, hw, radius, max_bits, rows, cols, cand_base, seg_cap, n_cand, ovf, epoch,
-                                       (unsigned long long *)nullptr, seq, blockIdx.x, blockIdx.y, gridDim.y);
+  detect_tile<false, false, kDetWaves, sizeof...(REG) != 0>(subset_bank(M, subset_at(M.forw_bank, i)), img_stride, (const uint8_t *)nullptr,
+                                                            (size_t)0, kept_xy, n_kept, cap, hw, radius, max_bits, rows, cols, cand_base, seg_cap,
+                                                            n_cand, ovf, epoch, (unsigned long long *)nullptr, seq, blockIdx.x, blockIdx.y, gridDim.y,
+                                                            region_args(region...));
+}
+
+// vio_frontend_set_regions: byte masks (nonzero = usable) -> the bit rows of RegionArgs (fe_common.h), padding words included.
+// Entry e of the call: image index[e] of `masks` (rows * cols bytes each) becomes the region of sequence seq[e]. One thread per
+// word of a row; not in the per-frame path.
+__global__ __launch_bounds__(256) void region_pack_kernel(const uint8_t *masks, const int *index, const int *seq, int rows, int cols, int wpr,
+                                                          unsigned long long *words) {
+  const int it = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
+  if (it >= rows * wpr) return;
+  const int y = it / wpr, w = it - y * wpr;
+  const uint8_t *row = masks + ((size_t)index[e] * rows + y) * cols;
+  unsigned long long bits = 0;
+  const int x0 = (w - 1) * 64;  // (word 0 is padding: x0 < 0 reads nothing)
+  for (int b = 0; b < 64; b++) {
+    const int x = x0 + b;
+    if (x >= 0 && x < cols && row[x] != 0) bits |= 1ull << b;
+  }
+  words[((size_t)seq[e] * rows + y) * wpr + w] = bits;
 }
 
 #undef LANE_LEFT

@@ -299,13 +299,14 @@ struct RedoParams {  // what a redo workgroup needs to run the detector again, a
 // any number of flagged sequences is served by n lists, no workgroup waits for another, and nothing depends on an order of
 // arrival. With no flag up -- every frame of an ordinary stream -- a redo workgroup reads its share of the flags and exits.
 // (Slow where it runs, one workgroup per frame: it is the exact answer for inputs the lists are not sized for, not a fast path.)
-template <bool IMG_MASK>
+// (REG: the region of interest, as for detect_kernel: the exact redo reads the same mask words)
+template <bool IMG_MASK, class... REG>
 __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned long long *cand_base, int seg_cap, int nseg,
                                                                     int *n_cand, unsigned *max_bits, RedoParams R,
                                                                     double quality, SelectParams P, float *forw_pts,
                                                                     float *cur_pts, float *pre_pts, int *ids, int *track_cnt,
                                                                     int *n_forw, int *n_pts, int *n_id, VioObs *obs,
-                                                                    int *n_obs, long long *prof) {
+                                                                    int *n_obs, long long *prof, REG... region) {
   const bool redo = (int)blockIdx.x >= R.n_seq;
   const int slot = (int)blockIdx.x - R.n_seq, n_slots = R.n_wg;
   if (redo) {
@@ -325,9 +326,9 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
       const int nbx = (P.cols + NW * kDetW - 1) / (NW * kDetW);
       for (int by = 0; by < nseg; by++)
         for (int bx = 0; bx < nbx; bx++) {
-          detect_tile<IMG_MASK, true, NW>(R.img_base, R.img_stride, R.mask_base, R.mask_stride, R.kept_xy, R.n_kept, P.cap, R.hw, R.radius,
-                                          (unsigned *)nullptr, P.rows, P.cols, (unsigned long long *)nullptr, 0, (int *)nullptr,
-                                          (int *)nullptr, 0, cand, seq, bx, by, nseg);
+          detect_tile<IMG_MASK, true, NW, sizeof...(REG) != 0>(R.img_base, R.img_stride, R.mask_base, R.mask_stride, R.kept_xy, R.n_kept, P.cap, R.hw,
+                                                               R.radius, (unsigned *)nullptr, P.rows, P.cols, (unsigned long long *)nullptr, 0,
+                                                               (int *)nullptr, (int *)nullptr, 0, cand, seq, bx, by, nseg, region_args(region...));
           __syncthreads();  // (the next tile clears the mask words this one reads; behind the last tile: the list is written)
         }
       if (threadIdx.x == 0) atomicAdd(R.n_redo, 1);
@@ -344,11 +345,13 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_kernel(unsigned lon
 // of a redo is level 0 of the sequence's forw bank (M.pyr, R.img_stride apart; R.img_base, R.mask_base and R.n_seq are not used).
 // select_sequence is the lock-step kernel's, untouched: image_msg lands in the sequence's own row of obs / n_obs, and
 // gather_obs_subset_kernel below packs the call's rows.
+template <class... REG>
 __global__ __launch_bounds__(kSelThreads) void corner_select_subset_kernel(SubsetArgs M, int n_pub, unsigned long long *cand_base,
                                                                            int seg_cap, int nseg, int *n_cand, unsigned *max_bits,
                                                                            RedoParams R, double quality, SelectParams P, float *forw_pts,
                                                                            float *cur_pts, float *pre_pts, int *ids, int *track_cnt,
-                                                                           int *n_forw, int *n_pts, int *n_id, VioObs *obs, int *n_obs) {
+                                                                           int *n_forw, int *n_pts, int *n_id, VioObs *obs, int *n_obs,
+                                                                           REG... region) {
   const bool redo = (int)blockIdx.x >= n_pub;
   const int slot = (int)blockIdx.x - n_pub, n_slots = R.n_wg;
   if (redo) {
@@ -369,9 +372,9 @@ __global__ __launch_bounds__(kSelThreads) void corner_select_subset_kernel(Subse
       const uint8_t *img = subset_bank(M, subset_at(M.forw_bank, i));
       for (int by = 0; by < nseg; by++)
         for (int bx = 0; bx < nbx; bx++) {
-          detect_tile<false, true, NW>(img, R.img_stride, (const uint8_t *)nullptr, (size_t)0, R.kept_xy, R.n_kept, P.cap, R.hw, R.radius,
-                                       (unsigned *)nullptr, P.rows, P.cols, (unsigned long long *)nullptr, 0, (int *)nullptr, (int *)nullptr, 0,
-                                       cand, seq, bx, by, nseg);
+          detect_tile<false, true, NW, sizeof...(REG) != 0>(img, R.img_stride, (const uint8_t *)nullptr, (size_t)0, R.kept_xy, R.n_kept, P.cap, R.hw,
+                                                            R.radius, (unsigned *)nullptr, P.rows, P.cols, (unsigned long long *)nullptr, 0, (int *)nullptr,
+                                                            (int *)nullptr, 0, cand, seq, bx, by, nseg, region_args(region...));
           __syncthreads();  // (the next tile clears the mask words this one reads; behind the last tile: the list is written)
         }
       if (threadIdx.x == 0) atomicAdd(R.n_redo, 1);

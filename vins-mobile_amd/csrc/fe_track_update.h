@@ -93,8 +93,11 @@ struct PackedPts {
 // One workgroup per sequence: everything between the LK call and goodFeaturesToTrack.
 // (two waves per SIMD: left to itself the compiler takes 289 registers per work-item for the double-precision 7-point code --
 // ONE wave per SIMD, one workgroup per CU, and the 512 sequences of the bench ran as two rounds of 256 workgroups)
-template <int CAP>
-__global__ __launch_bounds__(256, 2) void track_update_kernel(TrackerArrays A, int publish) {
+// (REG: the region of interest, RegionArgs of fe_common.h, or nothing: the kernel as it always was)
+template <int CAP, class... REG>
+__global__ __launch_bounds__(256, 2) void track_update_kernel(TrackerArrays A, int publish, REG... region) {
+  constexpr bool REGION = sizeof...(REG) != 0;
+  const RegionArgs G = region_args(region...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   TrackShared<CAP> &T = *reinterpret_cast<TrackShared<CAP> *>(smem_raw);
   RansacShared &R = *reinterpret_cast<RansacShared *>(smem_raw + ((sizeof(TrackShared<CAP>) + 15) & ~(size_t)15));
@@ -103,8 +106,10 @@ __global__ __launch_bounds__(256, 2) void track_update_kernel(TrackerArrays A, i
 }
 
 // Subset instantiation: one launch over the call's n sequences, workgroup i takes sequence seq[i] with publish[i].
-template <int CAP>
-__global__ __launch_bounds__(256, 2) void track_update_subset_kernel(TrackerArrays A, SubsetArgs M) {
+template <int CAP, class... REG>
+__global__ __launch_bounds__(256, 2) void track_update_subset_kernel(TrackerArrays A, SubsetArgs M, REG... region) {
+  constexpr bool REGION = sizeof...(REG) != 0;
+  const RegionArgs G = region_args(region...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   TrackShared<CAP> &T = *reinterpret_cast<TrackShared<CAP> *>(smem_raw);
   RansacShared &R = *reinterpret_cast<RansacShared *>(smem_raw + ((sizeof(TrackShared<CAP>) + 15) & ~(size_t)15));

@@ -63,6 +63,13 @@
       const int o = T.idx[i];
       T.ncnt[i] = T.cnt[o] + 1;  // for (auto &n : track_cnt) n++ :252-253
       T.ixy[i][0] = __float2int_rn(T.forw[o][0]), T.ixy[i][1] = __float2int_rn(T.forw[o][1]);
+      if (REGION) {
+        // the mask starts as the sequence's region: a position on a 0 pixel is never kept (and so never paints its disc). Its bit waits in
+        // pos[], which the greedy pass writes for kept positions only, each behind its own decision. (inBorder: the pixel is in the image)
+        int usable = 1;
+        if (G.set[seq]) usable = (int)(region_window(G.words + ((size_t)seq * A.rows + T.ixy[i][1]) * G.wpr, G.wpr, T.ixy[i][0]) & 1ull);
+        T.pos[i] = usable;
+      }
     }
     __syncthreads();
     // setMask :50-87 — stable order by track_cnt desc (i, j below are list positions)
@@ -119,6 +126,7 @@
       for (int r0 = 0; r0 < n; r0 += 64) {
         const int my_i = r0 + lane < n ? T.order[r0 + lane] : 0;
         const int cnt = n - r0 < 64 ? n - r0 : 64;
+        const unsigned long long usable = REGION ? __builtin_amdgcn_ballot_w64(r0 + lane < n && T.pos[my_i] != 0) : ~0ull;  // bit q: candidate r0 + q lies on a usable pixel
         unsigned long long kept = 0;  // bit q: candidate r0 + q is kept (uniform)
         for (int q0 = 0; q0 < cnt; q0 += 8) {  // the bit rows of eight candidates are fetched together, then decided in order
           int is[8];
@@ -131,7 +139,7 @@
 #pragma unroll
           for (int u = 0; u < 8; u++) {  // (no LDS traffic and no lane-0 branches inside the chain: the decisions go to a bit mask)
             const int i = is[u];
-            const bool keep_it = q0 + u < cnt && __builtin_amdgcn_ballot_w64((rows[u] & mine) != 0) == 0;
+            const bool keep_it = q0 + u < cnt && (!REGION || ((usable >> ((q0 + u) & 63)) & 1ull)) && __builtin_amdgcn_ballot_w64((rows[u] & mine) != 0) == 0;
             const unsigned long long bit = keep_it ? 1ULL << (i & 63) : 0ull;
             mine |= lane == (i >> 6) ? bit : 0ull;
             kept |= (unsigned long long)keep_it << ((q0 + u) & 63);

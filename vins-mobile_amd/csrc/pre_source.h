@@ -15,6 +15,9 @@
 // y + (2 j + 1 - s) / (2 s)), each through pre_rectify.h's arithmetic over the WHOLE delivered frame (the crop is not used),
 // out = (sum + s * s / 2) / (s * s). With s = 1 that is pre::rectify_px. The lens is any of pre_rectify.h's (VioLens,
 // VioLensModel, LensAs<MODEL>).
+// The valid region of a slot (which output pixels are made of delivered pixels only: lens_inside, lens_inside_source,
+// valid_region below) is this arithmetic without the clamp; valid_region_kernel, vio_lens_model_valid_region and
+// tests/emul/valid_region_main.cpp compile it.
 #pragma once
 #include "pre_rectify.h"
 
@@ -110,6 +113,65 @@ VIO_PRE_HD uint32_t rectify_source_px(const uint8_t *img, const SourcePlan &P, c
     }
   }
   return (sum + (uint32_t)(s * s) / 2u) / (uint32_t)(s * s);
+}
+
+// ---- the valid region of a slot (vio_preprocess_valid_regions*, vio_lens_model_valid_region) ----------------------------------
+// Output pixel (x, y) is INSIDE when nothing it is made of was clamped: without a source the un-clamped (u, v) of lens_source
+// lies in the rows x cols raw frame (the complement of what vio_lens_model_coverage counts; a NaN is outside); with a source
+// every one of the s * s sample positions of rectify_source_px lies in the whole delivered frame. The mask is the inside map
+// eroded by `margin` (Chebyshev distance; neighbours outside the image do not count). The polynomial models fold back far from
+// the centre: a folded pixel whose source lands inside the frame counts as inside, as it does in the coverage count.
+constexpr int kRegionMaxMargin = 32;
+
+template <class LENS>
+VIO_PRE_HD bool lens_inside(const LENS &L, int rows, int cols, int x, int y) {
+  double u, v;
+  lens_source(L, x, y, &u, &v);
+  return !(lens_outside(u, cols) || lens_outside(v, rows));
+}
+
+// s samples per axis over a src_rows x src_cols delivered frame: the positions of rectify_source_px
+template <class LENS>
+VIO_PRE_HD bool lens_inside_source(const LENS &L, int s, int src_rows, int src_cols, int x, int y) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  bool in = true;
+  for (int j = 0; j < s; j++) {
+    const double ys = (double)y + (double)(2 * j + 1 - s) / (double)(2 * s);
+    for (int i = 0; i < s; i++) {
+      const double xs = (double)x + (double)(2 * i + 1 - s) / (double)(2 * s);
+      double u, v;
+      lens_source_at(L, xs, ys, &u, &v);
+      in = in && !(lens_outside(u, src_cols) || lens_outside(v, src_rows));
+    }
+  }
+  return in;
+}
+
+// P: the slot's source plan, or null (the frame has the output's size)
+template <class LENS>
+VIO_PRE_HD bool region_inside(const LENS &L, const SourcePlan *P, int rows, int cols, int x, int y) {
+  return P ? lens_inside_source(L, P->s, P->rows, P->cols, x, y) : lens_inside(L, rows, cols, x, y);
+}
+
+// One axis of the erosion: is every entry of in[lo .. hi] (clipped to [0, n), `step` apart) nonzero?
+VIO_PRE_HD bool region_all(const uint8_t *in, int n, int step, int at, int margin) {
+  const int lo = at - margin > 0 ? at - margin : 0, hi = at + margin < n - 1 ? at + margin : n - 1;
+  bool all = true;
+  for (int k = lo; k <= hi; k++) all = all && in[(size_t)k * step] != 0;
+  return all;
+}
+
+// The whole mask on the host: lens null = a slot without a lens (all 255). tmp: rows * cols bytes of scratch.
+inline void valid_region(const VioLensModel *lens, const SourcePlan *P, int rows, int cols, int margin, uint8_t *mask, uint8_t *tmp) {
+  for (int y = 0; y < rows; y++)
+    for (int x = 0; x < cols; x++) mask[(size_t)y * cols + x] = !lens || region_inside(*lens, P, rows, cols, x, y) ? 255 : 0;
+  if (margin == 0 || !lens) return;
+  for (int y = 0; y < rows; y++)  // along the rows, then along the columns: the square window is separable
+    for (int x = 0; x < cols; x++) tmp[(size_t)y * cols + x] = region_all(mask + (size_t)y * cols, cols, 1, x, margin) ? 255 : 0;
+  for (int y = 0; y < rows; y++)
+    for (int x = 0; x < cols; x++) mask[(size_t)y * cols + x] = region_all(tmp + x, rows, cols, y, margin) ? 255 : 0;
 }
 
 inline int32_t source_gcd(int32_t a, int32_t b) {

@@ -109,10 +109,16 @@ struct vio_frontend {
   // the camera of every sequence (vio_frontend_set_cameras): cfg's until one is set; image_msg reads the device table
   DevBuf<double> cam;       // [n_seq][4] fx, fy, cx, cy
   std::vector<double> h_cam;  // the same on the host (vio_frontend_get_camera)
+  // the region of interest of every sequence (vio_frontend_set_regions; RegionArgs of fe_common.h): allocated with the first one.
+  // n_region = 0 launches the kernels as they always were, anything else their REGION variants for all sequences.
+  DevBuf<unsigned long long> region_words;  // [n_seq][rows][region_wpr]
+  DevBuf<int> region_set;                   // [n_seq]
+  std::vector<int> h_region_set;
+  int region_wpr = 0, n_region = 0;
   DevBuf<long long> d_prof;  // stage clock of track_update_kernel (VIO_AMD_TU_PROF=1)
   DevBuf<long long> d_cs_prof;  // stage clock of corner_select_kernel (VIO_AMD_CS_PROF=1, read at create)
   bool cs_prof = false;
-  bool attr_set = false;
+  bool attr_set = false, attr_set_region = false, attr_set_subset_region = false;
   bool detect_always = false;  // VIO_AMD_DETECT_ALWAYS=1 (measurement aid): detect_kernel also runs for sequences that need no new corner
   // resident frames (throughput runs)
   DevBuf<uint8_t> frames;
@@ -205,6 +211,8 @@ SelectParams select_params(const vio_frontend *fe) {
 }
 
 // feature_tracker.cpp:183-205 (+ :235-255, :50-87 on publish frames) for every sequence: one workgroup each
+RegionArgs region_of(const vio_frontend *fe) { return RegionArgs{fe->region_words.p, fe->region_set.p, fe->region_wpr}; }
+
 TrackerArrays tracker_arrays(vio_frontend *fe) {
   TrackerArrays A;
   A.cap = fe->cap, A.rows = fe->cfg.image_rows, A.cols = fe->cfg.image_cols;
@@ -230,8 +238,16 @@ int launch_track_update(vio_frontend *fe, int publish, hipStream_t st) {
     HIP_OK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     fe->attr_set = true;
   }
+  if (fe->n_region && !fe->attr_set_region) {
+    HIP_OK(hipFuncSetAttribute(small ? (const void *)track_update_kernel<256, RegionArgs> : (const void *)track_update_kernel<kMaxCap, RegionArgs>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    fe->attr_set_region = true;
+  }
   if (A.prof) (void)hipMemsetAsync(A.prof, 0, 32 * sizeof(long long), st);
-  if (small) hipLaunchKernelGGL(track_update_kernel<256>, dim3(fe->n_seq), dim3(256), shm, st, A, publish);
+  if (fe->n_region) {
+    if (small) hipLaunchKernelGGL((track_update_kernel<256, RegionArgs>), dim3(fe->n_seq), dim3(256), shm, st, A, publish, region_of(fe));
+    else hipLaunchKernelGGL((track_update_kernel<kMaxCap, RegionArgs>), dim3(fe->n_seq), dim3(256), shm, st, A, publish, region_of(fe));
+  } else if (small) hipLaunchKernelGGL(track_update_kernel<256>, dim3(fe->n_seq), dim3(256), shm, st, A, publish);
   else hipLaunchKernelGGL(track_update_kernel<kMaxCap>, dim3(fe->n_seq), dim3(256), shm, st, A, publish);
   if (A.prof) {  // (debug only: synchronises)
     long long h[32];
@@ -314,15 +330,27 @@ int fe_step(vio_frontend *fe, const uint8_t *d_frames /* [n_seq][rows*cols] on d
   if (rcu != VIO_OK) return rcu;
   if (publish) {
     dim3 tb(256), tg((cols + kDetWaves * kDetW - 1) / (kDetWaves * kDetW), fe->nseg, S);
-    hipLaunchKernelGGL(detect_kernel<false>, tg, tb, 0, st, alias0 ? d_frames : forw, alias0 ? img_bytes : fe->ld.pyr_bytes, (const uint8_t *)nullptr, (size_t)0,
-                       fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist, fe->max_bits.p, rows, cols, fe->cand.p,
-                       fe->seg_cap, fe->n_cand.p, fe->ovf.p, next_epoch(fe), fe->detect_always ? (const int *)nullptr : fe->n_forw.p,
-                       fe->cfg.max_corners);
+    const int epoch = next_epoch(fe);
+    const int *n_have = fe->detect_always ? (const int *)nullptr : fe->n_forw.p;
+    if (fe->n_region)
+      hipLaunchKernelGGL((detect_kernel<false, RegionArgs>), tg, tb, 0, st, alias0 ? d_frames : forw, alias0 ? img_bytes : fe->ld.pyr_bytes, (const uint8_t *)nullptr,
+                         (size_t)0, fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist, fe->max_bits.p, rows, cols, fe->cand.p,
+                         fe->seg_cap, fe->n_cand.p, fe->ovf.p, epoch, n_have, fe->cfg.max_corners, region_of(fe));
+    else
+      hipLaunchKernelGGL(detect_kernel<false>, tg, tb, 0, st, alias0 ? d_frames : forw, alias0 ? img_bytes : fe->ld.pyr_bytes, (const uint8_t *)nullptr, (size_t)0,
+                         fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist, fe->max_bits.p, rows, cols, fe->cand.p,
+                         fe->seg_cap, fe->n_cand.p, fe->ovf.p, epoch, n_have, fe->cfg.max_corners);
     const SelectParams SP = select_params(fe);
     const RedoParams RP = redo_params(fe, alias0 ? d_frames : forw, alias0 ? img_bytes : fe->ld.pyr_bytes, nullptr, 0, fe->cfg.min_dist);
-    hipLaunchKernelGGL(corner_select_kernel<false>, dim3(S + fe->n_redo_wg), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg,
-                       fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
-                       fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p, fe->cs_prof ? fe->d_cs_prof.p : nullptr);
+    if (fe->n_region)
+      hipLaunchKernelGGL((corner_select_kernel<false, RegionArgs>), dim3(S + fe->n_redo_wg), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg,
+                         fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
+                         fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p, fe->cs_prof ? fe->d_cs_prof.p : nullptr,
+                         region_of(fe));
+    else
+      hipLaunchKernelGGL(corner_select_kernel<false>, dim3(S + fe->n_redo_wg), dim3(kSelThreads), 0, st, fe->cand.p, fe->seg_cap, fe->nseg,
+                         fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
+                         fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p, fe->cs_prof ? fe->d_cs_prof.p : nullptr);
     if (fe->cs_prof) {  // (debug only: synchronises)
       long long h[5];
       if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h, fe->d_cs_prof.p, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
@@ -411,20 +439,39 @@ int fe_step_subset(vio_frontend *fe, const SubsetArgs &M, int n, int n_pub, cons
       HIP_OK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
       fe->attr_set_subset = true;
     }
-    if (small) hipLaunchKernelGGL(track_update_subset_kernel<256>, dim3(n), dim3(256), shm, st, A, M);
+    if (fe->n_region && !fe->attr_set_subset_region) {
+      HIP_OK(hipFuncSetAttribute(small ? (const void *)track_update_subset_kernel<256, RegionArgs> : (const void *)track_update_subset_kernel<kMaxCap, RegionArgs>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+      fe->attr_set_subset_region = true;
+    }
+    if (fe->n_region) {
+      if (small) hipLaunchKernelGGL((track_update_subset_kernel<256, RegionArgs>), dim3(n), dim3(256), shm, st, A, M, region_of(fe));
+      else hipLaunchKernelGGL((track_update_subset_kernel<kMaxCap, RegionArgs>), dim3(n), dim3(256), shm, st, A, M, region_of(fe));
+    } else if (small) hipLaunchKernelGGL(track_update_subset_kernel<256>, dim3(n), dim3(256), shm, st, A, M);
     else hipLaunchKernelGGL(track_update_subset_kernel<kMaxCap>, dim3(n), dim3(256), shm, st, A, M);
   }
   if (n_pub > 0) {
     dim3 tg((cols + kDetWaves * kDetW - 1) / (kDetWaves * kDetW), fe->nseg, n_pub);
-    hipLaunchKernelGGL(detect_subset_kernel, tg, dim3(256), 0, st, M, ld.pyr_bytes, fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist,
-                       fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, fe->ovf.p, next_epoch(fe),
-                       fe->detect_always ? (const int *)nullptr : fe->n_forw.p, fe->cfg.max_corners);
+    const int epoch = next_epoch(fe);
+    const int *n_have = fe->detect_always ? (const int *)nullptr : fe->n_forw.p;
+    if (fe->n_region)
+      hipLaunchKernelGGL(detect_subset_kernel<RegionArgs>, tg, dim3(256), 0, st, M, ld.pyr_bytes, fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist,
+                         fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, fe->ovf.p, epoch, n_have, fe->cfg.max_corners,
+                         region_of(fe));
+    else
+      hipLaunchKernelGGL(detect_subset_kernel<>, tg, dim3(256), 0, st, M, ld.pyr_bytes, fe->kept_xy.p, fe->n_kept.p, cap, fe->hw.p, fe->cfg.min_dist,
+                         fe->max_bits.p, rows, cols, fe->cand.p, fe->seg_cap, fe->n_cand.p, fe->ovf.p, epoch, n_have, fe->cfg.max_corners);
     const SelectParams SP = select_params(fe);
     RedoParams RP = redo_params(fe, nullptr, ld.pyr_bytes, nullptr, 0, fe->cfg.min_dist);
     RP.n_wg = std::min(fe->n_redo_wg, n_pub);
-    hipLaunchKernelGGL(corner_select_subset_kernel, dim3(n_pub + RP.n_wg), dim3(kSelThreads), 0, st, M, n_pub, fe->cand.p, fe->seg_cap, fe->nseg,
-                       fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
-                       fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p);
+    if (fe->n_region)
+      hipLaunchKernelGGL(corner_select_subset_kernel<RegionArgs>, dim3(n_pub + RP.n_wg), dim3(kSelThreads), 0, st, M, n_pub, fe->cand.p, fe->seg_cap,
+                         fe->nseg, fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
+                         fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p, region_of(fe));
+    else
+      hipLaunchKernelGGL(corner_select_subset_kernel<>, dim3(n_pub + RP.n_wg), dim3(kSelThreads), 0, st, M, n_pub, fe->cand.p, fe->seg_cap, fe->nseg,
+                         fe->n_cand.p, fe->max_bits.p, RP, fe->cfg.quality_level, SP, fe->forw_pts.p, fe->cur_pts.p, fe->pre_pts.p, fe->ids.p,
+                         fe->track_cnt.p, fe->n_forw.p, fe->n_pts.p, fe->n_id.p, fe->obs.p, fe->n_obs.p);
   }
   // image_msg in the call's order: only these rows travel back
   hipLaunchKernelGGL(gather_obs_subset_kernel, dim3(n), dim3(256), 0, st, M, cap, fe->obs.p, fe->n_obs.p, fe->obs_sub.p, fe->n_obs_sub.p);
@@ -919,6 +966,86 @@ int vio_frontend_get_camera(vio_frontend_t *fe, int32_t seq, VioCamera *out) {
   memset(out, 0, sizeof(*out));
   out->fx = row[0], out->fy = row[1], out->cx = row[2], out->cy = row[3];
   out->ric[0] = out->ric[4] = out->ric[8] = 1.0;  // (the front end has no use for the extrinsic)
+  return VIO_OK;
+}
+
+// The region of interest of a sequence is what setMask starts from on a publish frame (feature_tracker.cpp:50-87 with the
+// static mask of the upstream family in place of the all-255 one). Like the camera table it is rewritten between steps only.
+int vio_frontend_set_regions(vio_frontend_t *fe, int32_t n, const int32_t *seq, const void *masks, int32_t masks_on_device,
+                             const int32_t *mask_index) {
+  if (!fe || n < 0 || (n > 0 && !seq)) return VIO_EINVAL;
+  if (fe->pending) return VIO_ESTATE;
+  const int S = fe->n_seq, rows = fe->cfg.image_rows, cols = fe->cfg.image_cols;
+  std::vector<uint8_t> seen(S, 0);
+  if (!fe_subset::valid_list(S, n, seq, seen.data())) return VIO_EINVAL;
+  if (masks && mask_index)
+    for (int i = 0; i < n; i++)
+      if (mask_index[i] < 0) return VIO_EINVAL;
+  if (n == 0) return VIO_OK;
+  VIO_ON_DEVICE_OF(fe);
+  // a step that still runs reads the table, and a caller's device buffer may still be written on a stream of the caller's
+  HIP_OK(hipDeviceSynchronize());
+  fe->foreign_stream = false;
+  if (!fe->region_words.p) {
+    if (!masks) return VIO_OK;  // nothing was ever set
+    const int wpr = (cols + 63) / 64 + 2;
+    if (fe->region_words.ensure((size_t)S * rows * wpr) != VIO_OK || fe->region_set.ensure(S) != VIO_OK) {
+      fe->region_words.release();
+      return VIO_ENOMEM;
+    }
+    fe->region_wpr = wpr;
+    fe->h_region_set.assign(S, 0);
+    HIP_OK(hipMemset(fe->region_set.p, 0, sizeof(int) * S));
+  }
+  if (masks) {
+    const size_t px = (size_t)rows * cols;
+    DevBuf<uint8_t> d_masks;  // the host route's staging, gone when the call returns
+    DevBuf<int> d_list;       // mask index | sequence of every entry
+    std::vector<int> list(2 * (size_t)n);
+    for (int i = 0; i < n; i++) list[i] = masks_on_device && mask_index ? mask_index[i] : i, list[n + i] = seq[i];
+    if (d_list.ensure(2 * (size_t)n) != VIO_OK) return VIO_ENOMEM;
+    const uint8_t *src = static_cast<const uint8_t *>(masks);
+    if (!masks_on_device) {
+      if (d_masks.ensure((size_t)n * px) != VIO_OK) return VIO_ENOMEM;
+      for (int i = 0; i < n; i++)  // image mask_index[i] of the caller's array -> staging image i
+        HIP_OK(hipMemcpy(d_masks.p + (size_t)i * px, src + (size_t)(mask_index ? mask_index[i] : i) * px, px, hipMemcpyHostToDevice));
+      src = d_masks.p;
+    }
+    HIP_OK(hipMemcpy(d_list.p, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(region_pack_kernel, dim3((rows * fe->region_wpr + 255) / 256, n), dim3(256), 0, fe->stream, src, (const int *)d_list.p,
+                       (const int *)d_list.p + n, rows, cols, fe->region_wpr, fe->region_words.p);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(fe->stream));
+  }
+  for (int i = 0; i < n; i++) fe->h_region_set[seq[i]] = masks ? 1 : 0;
+  HIP_OK(hipMemcpy(fe->region_set.p, fe->h_region_set.data(), sizeof(int) * S, hipMemcpyHostToDevice));
+  fe->n_region = 0;
+  for (int s = 0; s < S; s++) fe->n_region += fe->h_region_set[s];
+  return VIO_OK;
+}
+
+int vio_frontend_get_region(vio_frontend_t *fe, int32_t seq, uint8_t *mask_out, int32_t *is_set, int64_t *n_usable) {
+  if (!fe || seq < 0 || seq >= fe->n_seq || !is_set || !n_usable) return VIO_EINVAL;
+  if (fe->pending) return VIO_ESTATE;
+  const int rows = fe->cfg.image_rows, cols = fe->cfg.image_cols;
+  const size_t px = (size_t)rows * cols;
+  if (!fe->region_words.p || !fe->h_region_set[seq]) {  // no region: every pixel is usable
+    *is_set = 0, *n_usable = (int64_t)px;
+    if (mask_out) memset(mask_out, 255, px);
+    return VIO_OK;
+  }
+  VIO_ON_DEVICE_OF(fe);
+  const int wpr = fe->region_wpr;
+  std::vector<unsigned long long> words((size_t)rows * wpr);
+  HIP_OK(hipMemcpy(words.data(), fe->region_words.p + (size_t)seq * rows * wpr, sizeof(unsigned long long) * words.size(), hipMemcpyDeviceToHost));
+  int64_t usable = 0;
+  for (int y = 0; y < rows; y++)
+    for (int x = 0; x < cols; x++) {
+      const int bit = (int)((words[(size_t)y * wpr + ((x + 64) >> 6)] >> ((x + 64) & 63)) & 1ull);
+      usable += bit;
+      if (mask_out) mask_out[(size_t)y * cols + x] = bit ? 255 : 0;
+    }
+  *is_set = 1, *n_usable = usable;
   return VIO_OK;
 }
 

@@ -359,6 +359,69 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(FISHEY
   lut_of_histogram(hist, scan, wsum, G, tid, lut + ((size_t)frame * G.tiles_x * G.tiles_y + tile) * 256);
 }
 
+// ---- the valid region of a slot: where the rectified image is made of delivered pixels only (pre_source.h) --------------------
+// One workgroup per tile of kRegTile x kRegTile output pixels of one entry of the call: one lane per pixel of the tile and its
+// halo of `margin` pixels evaluates the inside test into LDS (a position outside the image counts as inside: it is no
+// neighbour), then the erosion as two passes over LDS, along the rows and along the columns. Not in the per-frame path: a
+// mask is static per lens. The halo is evaluated again by the neighbouring tiles ((64 + 2 * 12)^2 / 64^2 = 1.9 at margin 12).
+constexpr int kRegTile = 64;
+constexpr int kRegSpan = kRegTile + 2 * pre::kRegionMaxMargin;
+
+template <int MODEL>
+__device__ __forceinline__ void region_tile(const VioLensModel &lens, const pre::SourcePlan *P, int rows, int cols, int x0, int y0,
+                                            int margin, uint8_t (*in)[kRegSpan]) {
+  const pre::LensAs<MODEL> L(lens);
+  const int span = kRegTile + 2 * margin;
+  for (int p = threadIdx.x; p < span * span; p += kThreads) {
+    const int yy = p / span, xx = p - yy * span;
+    const int y = y0 - margin + yy, x = x0 - margin + xx;
+    in[yy][xx] = y < 0 || y >= rows || x < 0 || x >= cols || pre::region_inside(L, P, rows, cols, x, y) ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void valid_region_kernel(const int32_t *__restrict__ slots, const LensSlot *__restrict__ lenses,
+                                                                const SourceSlot *__restrict__ sources, int rows, int cols, int margin,
+                                                                uint8_t *__restrict__ masks) {
+  __shared__ uint8_t in[kRegSpan][kRegSpan];
+  __shared__ uint8_t hz[kRegSpan][kRegTile];
+  const int tid = threadIdx.x, tiles_x = (cols + kRegTile - 1) / kRegTile;
+  const int x0 = (blockIdx.x % tiles_x) * kRegTile, y0 = (blockIdx.x / tiles_x) * kRegTile;
+  const int slot = slots[blockIdx.y];  // the entry's records: the same for every lane
+  uint8_t *out = masks + (size_t)blockIdx.y * rows * cols;
+  if (!(lenses && lenses[slot].is_set)) {  // a crop is always inside its frame
+    for (int p = tid; p < kRegTile * kRegTile; p += kThreads) {
+      const int y = y0 + p / kRegTile, x = x0 + p % kRegTile;
+      if (y < rows && x < cols) out[(size_t)y * cols + x] = 255;
+    }
+    return;
+  }
+  const VioLensModel L = lenses[slot].lens;
+  pre::SourcePlan plan;
+  const pre::SourcePlan *P = nullptr;
+  if (sources && sources[slot].is_set) plan = sources[slot].plan, P = &plan;
+  if (L.model == VIO_LENS_FISHEYE)
+    region_tile<VIO_LENS_FISHEYE>(L, P, rows, cols, x0, y0, margin, in);
+  else if (L.model == VIO_LENS_RATIONAL)
+    region_tile<VIO_LENS_RATIONAL>(L, P, rows, cols, x0, y0, margin, in);
+  else
+    region_tile<VIO_LENS_BROWN>(L, P, rows, cols, x0, y0, margin, in);
+  __syncthreads();
+  const int span = kRegTile + 2 * margin;
+  for (int p = tid; p < span * kRegTile; p += kThreads) {  // column xx of hz <-> columns xx .. xx + 2 margin of in
+    const int yy = p / kRegTile, xx = p % kRegTile;
+    uint32_t all = 1;
+    for (int k = 0; k <= 2 * margin; k++) all &= in[yy][xx + k];
+    hz[yy][xx] = (uint8_t)all;
+  }
+  __syncthreads();
+  for (int p = tid; p < kRegTile * kRegTile; p += kThreads) {
+    const int yy = p / kRegTile, xx = p % kRegTile, y = y0 + yy, x = x0 + xx;
+    uint32_t all = 1;
+    for (int k = 0; k <= 2 * margin; k++) all &= hz[yy + k][xx];
+    if (y < rows && x < cols) out[(size_t)y * cols + x] = all ? 255 : 0;
+  }
+}
+
 __device__ __forceinline__ uint32_t blend_px(const float *__restrict__ L1, const float *__restrict__ L2, int i1, int i2,
                                               uint32_t v, float xa, float xa1, float ya, float ya1) {
   const float res = (L1[i1 + v] * xa1 + L1[i2 + v] * xa) * ya1 + (L2[i1 + v] * xa1 + L2[i2 + v] * xa) * ya;
@@ -454,6 +517,11 @@ struct vio_preprocess {
   int ring_next = 0;
   vio::PinnedBuf<uint8_t> h_frames;   // staging of the host route: the rows each slot reads, grown on demand
   vio::DevBuf<uint8_t> d_frames;
+  // vio_preprocess_valid_regions*: the slot list of the call in flight (region_ev: its kernel has run)
+  vio::PinnedBuf<int32_t> h_region_slots;
+  vio::DevBuf<int32_t> d_region_slots;
+  hipEvent_t region_ev = nullptr;
+  bool region_used = false;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double ms_sum = 0;
@@ -461,6 +529,7 @@ struct vio_preprocess {
   ~vio_preprocess() {
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
+    if (region_ev) (void)hipEventDestroy(region_ev);
     for (hipEvent_t e : ring_ev)
       if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
@@ -491,6 +560,7 @@ PreGeom geometry(int rows, int cols, int tiles_x, int tiles_y, double clip_limit
 void account(vio_preprocess *p) {
   float ms = 0;
   if (hipEventElapsedTime(&ms, p->ev0, p->ev1) == hipSuccess) p->ms_sum += ms, p->launches++;
+  else (void)hipGetLastError();  // (no gray pass was launched yet, e.g. a sync behind valid_regions alone: not an error to keep)
 }
 
 // the apply pass of a batch whose gray images and LUTs the gray pass has just been launched for; closes the timed interval
@@ -583,13 +653,46 @@ int set_lens_table(vio_preprocess_t *p, int32_t n, const int32_t *slot, bool cle
   VIO_ON_DEVICE_OF(p);
   // launches of this context that are still in flight read the table: let the last one finish, then replace it, and
   // return only when the new table is in device memory (a later launch on ANY stream then sees it)
-  if (hipEventSynchronize(p->ev1) != hipSuccess) return VIO_ENODEV;
+  if (hipEventSynchronize(p->ev1) != hipSuccess || (p->region_used && hipEventSynchronize(p->region_ev) != hipSuccess)) return VIO_ENODEV;
   if (hipMemcpyAsync(p->d_lens.p, next.data(), sizeof(LensSlot) * next.size(), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
       hipStreamSynchronize(p->stream) != hipSuccess)
     return VIO_ENODEV;
   p->h_lens.swap(next);
   p->n_lens = p->n_fisheye = 0;
   for (const LensSlot &s : p->h_lens) p->n_lens += s.is_set, p->n_fisheye += s.is_set && s.lens.model == VIO_LENS_FISHEYE;
+  return VIO_OK;
+}
+
+// vio_preprocess_valid_regions*: the checked call's one launch on `st`, masks to d_masks [n][rows][cols]
+int launch_regions(vio_preprocess *p, int n, const int32_t *slot, int margin, uint8_t *d_masks, hipStream_t st) {
+  if (p->h_region_slots.ensure((size_t)p->max_frames) != VIO_OK || p->d_region_slots.ensure((size_t)p->max_frames) != VIO_OK) return VIO_ENOMEM;
+  // the slot list of the last call is read until its kernel has run
+  if (p->region_used && hipEventSynchronize(p->region_ev) != hipSuccess) return VIO_ENODEV;
+  memcpy(p->h_region_slots.p, slot, sizeof(int32_t) * n);
+  if (hipMemcpyAsync(p->d_region_slots.p, p->h_region_slots.p, sizeof(int32_t) * n, hipMemcpyHostToDevice, st) != hipSuccess) return VIO_ENODEV;
+  int n_source = 0;
+  for (const SourceSlot &s : p->h_source) n_source += s.is_set;
+  const int tiles = ((p->cols + kRegTile - 1) / kRegTile) * ((p->rows + kRegTile - 1) / kRegTile);
+  hipLaunchKernelGGL(valid_region_kernel, dim3(tiles, n), dim3(kThreads), 0, st, (const int32_t *)p->d_region_slots.p,
+                     p->n_lens ? (const LensSlot *)p->d_lens.p : nullptr, n_source ? (const SourceSlot *)p->d_source.p : nullptr, p->rows,
+                     p->cols, margin, d_masks);
+  (void)hipEventRecord(p->region_ev, st);
+  p->region_used = true;
+  return hipGetLastError() == hipSuccess ? VIO_OK : VIO_ENODEV;
+}
+
+int regions_check(vio_preprocess *p, int32_t n, const int32_t *slot, int32_t margin, const void *out) {
+  if (!p || !slot || !out || n < 0 || n > p->max_frames || margin < 0 || margin > pre::kRegionMaxMargin) return VIO_EINVAL;
+  std::vector<uint8_t> named;
+  try {
+    named.assign((size_t)p->max_frames, 0);
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+  for (int i = 0; i < n; i++) {
+    if (slot[i] < 0 || slot[i] >= p->max_frames || named[slot[i]]) return VIO_EINVAL;
+    named[slot[i]] = 1;
+  }
   return VIO_OK;
 }
 
@@ -611,7 +714,7 @@ int vio_preprocess_create(int32_t max_frames, int32_t rows, int32_t cols, vio_pr
       p->d_refs.ensure((size_t)vio_preprocess::kRing * max_frames) != VIO_OK ||
       p->h_refs.ensure((size_t)vio_preprocess::kRing * max_frames) != VIO_OK ||
       hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess ||
-      hipEventCreate(&p->ev1) != hipSuccess) {
+      hipEventCreate(&p->ev1) != hipSuccess || hipEventCreateWithFlags(&p->region_ev, hipEventDisableTiming) != hipSuccess) {
     delete p;
     return VIO_ENOMEM;
   }
@@ -783,6 +886,46 @@ int vio_lens_model_coverage(const VioLensModel *lens, int32_t rows, int32_t cols
   return VIO_OK;
 }
 
+int vio_lens_model_valid_region(const VioLensModel *lens, const VioSource *src, int32_t rows, int32_t cols, int32_t margin,
+                                uint8_t *mask) {
+  if (!lens || !mask || rows < 1 || cols < 1 || rows > 16384 || cols > 16384 || margin < 0 || margin > pre::kRegionMaxMargin ||
+      !pre::lens_model_valid(*lens) || (src && !pre::source_valid(*src, rows, cols)))
+    return VIO_EINVAL;
+  std::vector<uint8_t> tmp;
+  try {
+    tmp.resize((size_t)rows * cols);
+  } catch (const std::bad_alloc &) {
+    return VIO_ENOMEM;
+  }
+  pre::SourcePlan plan;
+  if (src) plan = pre::source_plan(*src, rows, cols);
+  pre::valid_region(lens, src ? &plan : nullptr, rows, cols, margin, mask, tmp.data());
+  return VIO_OK;
+}
+
+int vio_preprocess_valid_regions_resident(vio_preprocess_t *p, int32_t n, const int32_t *slot, int32_t margin, void *d_masks,
+                                          void *stream) {
+  const int rc = regions_check(p, n, slot, margin, d_masks);
+  if (rc != VIO_OK || n == 0) return rc;
+  VIO_ON_DEVICE_OF(p);
+  return launch_regions(p, n, slot, margin, (uint8_t *)d_masks, stream ? (hipStream_t)stream : p->stream);
+}
+
+int vio_preprocess_valid_regions(vio_preprocess_t *p, int32_t n, const int32_t *slot, int32_t margin, uint8_t *masks_out) {
+  int rc = regions_check(p, n, slot, margin, masks_out);
+  if (rc != VIO_OK || n == 0) return rc;
+  VIO_ON_DEVICE_OF(p);
+  const size_t bytes = (size_t)p->rows * p->cols * n;
+  if (p->h_out.ensure((size_t)p->max_frames * p->rows * p->cols * 2) != VIO_OK) return VIO_ENOMEM;
+  // d_out and the staging are the host routes' own, used in the order of the context's stream
+  if ((rc = launch_regions(p, n, slot, margin, p->d_out.p, p->stream)) != VIO_OK) return rc;
+  if (hipMemcpyAsync(p->h_out.p, p->d_out.p, bytes, hipMemcpyDeviceToHost, p->stream) != hipSuccess ||
+      hipStreamSynchronize(p->stream) != hipSuccess || hipGetLastError() != hipSuccess)
+    return VIO_ENODEV;
+  memcpy(masks_out, p->h_out.p, bytes);
+  return VIO_OK;
+}
+
 int vio_preprocess_run(vio_preprocess_t *p, const uint8_t *pixels, int32_t channels, int32_t n_frames, int32_t stride,
                        uint8_t *gray_out, uint8_t *equalized_out) {
   if (!p || !pixels || !equalized_out || !(channels == 1 || channels == 4) || n_frames < 1 || stride < channels * p->cols)
@@ -857,7 +1000,7 @@ int vio_preprocess_set_sources(vio_preprocess_t *p, int32_t n, const int32_t *sl
   if (n == 0) return VIO_OK;
   VIO_ON_DEVICE_OF(p);
   // as vio_preprocess_set_lenses: let the last launch finish, replace the table, return with it in device memory
-  if (hipEventSynchronize(p->ev1) != hipSuccess) return VIO_ENODEV;
+  if (hipEventSynchronize(p->ev1) != hipSuccess || (p->region_used && hipEventSynchronize(p->region_ev) != hipSuccess)) return VIO_ENODEV;
   if (hipMemcpyAsync(p->d_source.p, next.data(), sizeof(SourceSlot) * next.size(), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
       hipStreamSynchronize(p->stream) != hipSuccess)
     return VIO_ENODEV;
@@ -948,6 +1091,7 @@ int vio_preprocess_run_frames_resident(vio_preprocess_t *p, const void *const *d
 int vio_preprocess_sync(vio_preprocess_t *p) {
   if (!p) return VIO_EINVAL;
   VIO_ON_DEVICE_OF(p);
+  if (p->region_used && hipEventSynchronize(p->region_ev) != hipSuccess) return VIO_ENODEV;
   if (hipEventSynchronize(p->ev1) != hipSuccess || hipGetLastError() != hipSuccess) return VIO_ENODEV;
   account(p);
   return VIO_OK;

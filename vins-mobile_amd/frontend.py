@@ -187,6 +187,29 @@ class FeatureTracker:
         self._check(self.lib.vio_frontend_get_camera(self._h, seq, C.byref(out)), "get_camera")
         return out
 
+    def set_regions(self, seqs, masks=None, mask_index=None):
+        """vio_frontend_set_regions: setMask of sequence seqs[i] starts from masks[i] (uint8 [n, rows, cols] on the host,
+        nonzero = usable) from its next published frame on; masks an int: a device pointer to packed [slots, rows, cols] masks,
+        mask_index naming the slots; masks None clears the named sequences. -> rc."""
+        seqs = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        mi = None if mask_index is None else np.ascontiguousarray(mask_index, np.int32).reshape(-1)
+        assert mi is None or len(mi) == len(seqs)
+        mip = mi.ctypes.data_as(_ip) if mi is not None else None
+        if masks is None or isinstance(masks, int):
+            return self.lib.vio_frontend_set_regions(self._h, len(seqs), seqs.ctypes.data_as(_ip), C.c_void_p(masks or 0),
+                                                     0 if masks is None else 1, mip)
+        masks = np.ascontiguousarray(masks, np.uint8)
+        assert masks.ndim == 3 and masks.shape[1:] == (self.cfg.image_rows, self.cfg.image_cols), masks.shape
+        assert len(masks) > (int(mi.max()) if mi is not None and len(mi) else len(seqs) - 1)
+        return self.lib.vio_frontend_set_regions(self._h, len(seqs), seqs.ctypes.data_as(_ip), C.c_void_p(masks.ctypes.data), 0, mip)
+
+    def region(self, seq=0):
+        """vio_frontend_get_region -> (mask uint8 [rows, cols] of 0 / 255, is_set, n_usable)."""
+        mask = np.zeros((self.cfg.image_rows, self.cfg.image_cols), np.uint8)
+        is_set, n = C.c_int32(), C.c_int64()
+        self._check(self.lib.vio_frontend_get_region(self._h, seq, mask.ctypes.data_as(_u8p), C.byref(is_set), C.byref(n)), "get_region")
+        return mask, bool(is_set.value), n.value
+
     def in_step(self):
         """True while every sequence is in the same phase, i.e. while the lock-step calls (read_images, submit, step) are allowed."""
         v = C.c_int32()
@@ -401,6 +424,21 @@ class Preprocessor:
         n = len(d_pixels)
         ptrs = (C.c_void_p * max(n, 1))(*[int(x) for x in d_pixels])
         return self.lib.vio_preprocess_run_frames_resident(self._h, ptrs, n, C.c_void_p(d_equalized), C.c_void_p(stream or 0))
+
+    def valid_regions(self, slots, margin=0):
+        """vio_preprocess_valid_regions -> (rc, masks [n, rows, cols] of 0 / 255): where slot slots[i]'s rectified image is made
+        of delivered pixels only, eroded by margin (VIO_EINVAL: nothing written)."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        masks = np.zeros((len(slots), self.rows, self.cols), np.uint8)
+        rc = self.lib.vio_preprocess_valid_regions(self._h, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int32)), margin,
+                                                   masks.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return rc, masks
+
+    def valid_regions_resident(self, slots, margin, d_masks, stream=None):
+        """The same into the device buffer d_masks [n][rows][cols], asynchronous on stream -> the return code."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        return self.lib.vio_preprocess_valid_regions_resident(self._h, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int32)), margin,
+                                                              C.c_void_p(d_masks), C.c_void_p(stream or 0))
 
     def sync(self):
         rc = self.lib.vio_preprocess_sync(self._h)
